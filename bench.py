@@ -6,7 +6,13 @@ lights, 5 reduced bloom levels + luminance + tonemap), run through the RenderGra
 headless platform runs frames (application_headless.cpp:581-612: warm-up, then timed frames).  Inputs are resident in HBM
 before the timed region.  Prints ONE JSON line (rank 0).
 
-  python bench.py --gpus 1 --steps 200 --warmup 20
+A plain run does what the headline needs: set-up, W warm-up frames, the clock settle, K timed frames, the line.  --full adds the rest
+(per-kernel hipEvent brackets and the roofline with its HBM probe, the sustained run, the CPU baselines and the parity check against
+the oracle, at N > 1 the band check and the config5_8k sub-record).  --dump-outputs DIR writes what the last timed frame delivered
+(dump_outputs below); the inputs are seeded and the number of frames in front of the dump is fixed, so two builds compare output
+for output.
+
+  python bench.py --gpus 1 --steps 200 --warmup 20 [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -56,6 +62,11 @@ VALU_SIMDS, VALU_CLOCK_HZ, VALU_CYCLES_PER_INST = 1024, 2.4e9, 2.0  # 256 CUs x 
 BRACKET_EVERY = 8  # the dominant kernel keeps its hipEvent bracket on every 8th launch of the timed region (short runs: >= 16 brackets, or all)
 MIN_BRACKETS = 16
 SETTLE_MS = float(os.environ.get("GRANITE_BENCH_SETTLE_MS", "40"))  # of untimed, un-bracketed load immediately in front of the timed region
+# Recorded pace of each workload (current numbers): turns SETTLE_MS into a FIXED frame count, so that the frame the timed
+# region ends on -- exposure adaptation and bloom feedback carry state from frame to frame -- is the same in every run.
+PACE_MS_PER_FRAME = {"config1_256_post_only": 0.027, "config2_1080p_256lights": 0.056, "config3_4k_4096lights": 0.21,
+                     "config3_4k_4096lights_b10g11r11": 0.22, "config4_4k_smaa_taa": 0.55, "config5_8k": 0.73}
+DUMP_SAMPLE_PIXELS = 1 << 20  # --dump-outputs: larger images are written as this many pixels, a fixed seeded sample (16 MiB per image)
 
 
 def parse_args():
@@ -64,10 +75,16 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="config3_4k_4096lights", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: per-kernel brackets, roofline and HBM probe, the sustained run, "
+                         "the CPU baselines and the parity check; at N > 1 the band check and the config5_8k sub-record")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed frame delivered as DIR/<name>.npy (float32; images larger than "
+                         f"{DUMP_SAMPLE_PIXELS} pixels as a fixed seeded sample of pixels)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baselines and the parity check")
     ap.add_argument("--sustain-seconds", type=float, default=6.0,
-                    help="length of the unbracketed run after the timed region (0 = off); 6 s by default so that a 5 s utilisation sampler sees the GPU busy")
-    ap.add_argument("--cpu-sample-rows", type=int, default=0, help="rows of the frame the CPU baseline renders (0 = auto)")
+                    help="--full: length of the unbracketed run after the timed region (0 = off); 6 s by default so that a 5 s utilisation sampler sees the GPU busy")
+    ap.add_argument("--cpu-sample-rows", type=int, default=0, help="--full: rows of the frame the CPU baseline renders (0 = auto)")
     ap.add_argument("--scene", default="default", choices=["default", "depth_split", "hot_spot"],
                     help="synthetic scene (granite_amd/synth.py): default = the scene every headline number is quoted on; depth_split = a third of the "
                          "lighting tiles straddles a 1-7 / 30 unit depth discontinuity; hot_spot = 128 lights on 5 %% of the screen (64-94 in range per pixel)")
@@ -217,6 +234,53 @@ def parity_check(cam, gbuf, descs, device, reference):
         a.close()
     return hdr_bad == 0 and tm_bad == 0, {"hdr_channels_beyond_2ulp": hdr_bad, "backbuffer_bytes_beyond_1lsb": tm_bad,
                                           "frames": reference["frames"]}
+
+
+def unpack_b10g11r11(words: np.ndarray) -> np.ndarray:
+    """B10G11R11_UFLOAT_PACK32 words (...) -> float32 RGBA (..., 4), exact, alpha 1: R and G are 5-bit exponent + 6-bit mantissa, B 5 + 5,
+    exponent bias 15, exponent 0 denormal, exponent 31 inf / NaN."""
+    w = np.asarray(words, np.uint32)
+
+    def channel(bits, mbits):
+        e = (bits >> mbits).astype(np.int32)
+        m = (bits & ((1 << mbits) - 1)).astype(np.float64) / (1 << mbits)
+        v = np.where(e == 0, m * 2.0 ** -14, (1.0 + m) * np.exp2(e - 15.0))
+        return np.where(e == 31, np.where(m == 0, np.inf, np.nan), v).astype(np.float32)
+
+    return np.stack([channel(w & 0x7FF, 6), channel((w >> 11) & 0x7FF, 6), channel(w >> 22, 5), np.ones(w.shape, np.float32)], axis=-1)
+
+
+def dump_outputs(app, out_dir):
+    """What the last timed frame delivered, as float32 .npy files in out_dir: `backbuffer` (the tonemapped RGBA8 target, byte values
+    0-255), `hdr_main` (the HDR target the post chain read, RGBA decoded from fp16 or B10G11R11) and `average_luminance` (the exposure
+    buffer the tonemap used; at N > 1 rank 0's, whose backbuffer is the assembled frame).  An image of more than DUMP_SAMPLE_PIXELS
+    pixels is written as (DUMP_SAMPLE_PIXELS, 4): the pixels at a sorted sample of raster indices drawn with seed synth.SEED, the
+    same sample for both images, taken before any conversion.  At most 2 x 16 MiB in all."""
+    from granite_amd import capi, synth
+    app.sync()
+    backbuffer = app.read_backbuffer()
+    info = app.resource("HDR-main")
+    hdr = app.read("HDR-main")
+    if info.format == capi.FORMAT_B10G11R11_UFLOAT_PACK32:
+        decode = unpack_b10g11r11
+    elif info.format == capi.FORMAT_R16G16B16A16_SFLOAT:
+        def decode(bits):
+            return bits.view(np.float16).astype(np.float32)
+    else:
+        raise SystemExit(f"--dump-outputs: HDR-main has format {info.format}, neither RGBA16F nor B10G11R11")
+    h, w = backbuffer.shape[:2]
+    images = {"backbuffer": (backbuffer, lambda b: b.astype(np.float32))}
+    if hdr.shape[:2] == (h, w):  # row bands (N > 1): a rank holds its own band of the HDR target only
+        images["hdr_main"] = (hdr, decode)
+    sample = None
+    if h * w > DUMP_SAMPLE_PIXELS:
+        sample = np.sort(np.random.default_rng(synth.SEED).choice(h * w, DUMP_SAMPLE_PIXELS, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, (raw, convert) in images.items():
+        if sample is not None:
+            raw = raw.reshape((h * w,) + raw.shape[2:])[sample]
+        np.save(os.path.join(out_dir, name + ".npy"), convert(raw))
+    np.save(os.path.join(out_dir, "average_luminance.npy"), app.read("average-luminance").view(np.float32).copy())
 
 
 def main():
@@ -411,7 +475,7 @@ def main():
         dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         return {"min": 1000.0 * float(lo.item()) / steps, "max": 1000.0 * float(hi.item()) / steps}, float(hi.item())
 
-    bands_checked = check_bands(application, cam, gbuf, descs, width, height) if bands else None
+    bands_checked = check_bands(application, cam, gbuf, descs, width, height) if bands and args.full else None
 
     def barrier():
         torch.cuda.synchronize()
@@ -427,52 +491,41 @@ def main():
         except Exception:  # noqa: BLE001 - e.g. not enough free HBM beside an 8K frame: the spec peak stands alone
             return None, None
 
-    copy_gbs, triad_gbs = hbm_probe()
+    copy_gbs, triad_gbs = hbm_probe() if args.full else (None, None)
 
-    # ---- warm-up (also finds the dominant kernel with every launcher bracketed) ----
+    # ---- warm-up (--full: also finds the dominant kernel with every launcher bracketed) ----
     kctx.timing_set_sampling(1)
-    kctx.timing_enable(True)
+    kctx.timing_enable(args.full)
     kctx.timing_set_filter(None)
     kctx.timing_reset()
-    t_warm = time.perf_counter()
     application.render_frames(max(args.warmup, 1), sync=True)
-    warm_ms_per_frame = 1000.0 * (time.perf_counter() - t_warm) / max(args.warmup, 1)
-    per_kernel = kctx.timing_query()
+    per_kernel = kctx.timing_query() if args.full else {}
     # the dominant kernel = the longest single-launch kernel among those whose algorithmic bytes SURVEY 8d states
     known = {k: v for k, v in per_kernel.items() if k in ALGO_BYTES_PER_PX and k != "chain" and v[0]}
     dominant = max(known.items(), key=lambda kv: kv[1][1] / kv[1][0])[0] if known else "lighting"
     warm_breakdown = {k: {"launches": c, "avg_us": 1000.0 * ms / max(c, 1)} for k, (c, ms) in per_kernel.items()}
     gather_us = gather_brackets(per_kernel, kctx)
 
-    # ---- timed region: only the dominant kernel keeps its hipEvent bracket, on every BRACKET_EVERY-th launch.  (An event
+    # ---- timed region (--full): only the dominant kernel keeps its hipEvent bracket, on every BRACKET_EVERY-th launch.  (An event
     # pair around a kernel stops the command processor from overlapping it with its neighbours on the stream: bracketing
-    # every launch costs the frame ~8 %; the launch duration is still measured live, inside the timed frames.) ----
+    # every launch costs the frame ~8 %; the launch duration is still measured live, inside the timed frames.)  A plain run brackets nothing. ----
     kctx.timing_set_filter(dominant)
     kctx.timing_set_sampling(max(1, min(BRACKET_EVERY, args.steps // MIN_BRACKETS)))
     kctx.timing_reset()
     # ---- clock settle: the device reaches its sustained clocks only after tens of milliseconds of uninterrupted load, and the host-side
-    # pause above (the warm-up's per-kernel read-out) is enough to lose them again: a timed region that starts cold runs its first ~30
+    # pause above (the warm-up's read-out) is enough to lose them again: a timed region that starts cold runs its first ~30
     # frames 7 % slower (profiles/r03_launch_gap_experiments.txt: 20 frames at 0.260 ms cold, 0.248 after 40 frames of load, 0.242 after
     # 160).  So the SAME frames run, un-bracketed and untimed, for about SETTLE_MS right up to the barrier that opens the timed region.
     # They are warm-up beyond the W the command line asks for and are reported as such ("clock_settle"); GRANITE_BENCH_SETTLE_MS=0 = off.
+    # The count is fixed (SETTLE_MS at the workload's recorded pace, in blocks of 16): every run, and every rank, renders the same frames.
     settle_frames = 0
     if SETTLE_MS > 0:
         kctx.timing_enable(False)
-        if dist is None:
-            # the host runs at most two frames ahead of the device (Device::next_frame_context), so its clock follows the device's load
-            t_settle = time.perf_counter()
-            while 1000.0 * (time.perf_counter() - t_settle) < SETTLE_MS and settle_frames < 8000:
-                application.render_frames(16, sync=False)
-                settle_frames += 16
-        else:
-            # the ranks render the same number of frames (a frame is a collective): a count agreed on beforehand
-            settle_frames = int(min(4000, max(100, -(-SETTLE_MS // max(warm_ms_per_frame, 1e-3)))))
-            t = torch.tensor([settle_frames], dtype=torch.int64)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            settle_frames = int(t.item())
-            application.render_frames(settle_frames, sync=False)
+        settle_frames = int(min(8000, 16 * -(-SETTLE_MS // (16 * PACE_MS_PER_FRAME[args.workload]))))
+        # the host runs at most two frames ahead of the device (Device::next_frame_context), so its clock follows the device's load
+        application.render_frames(settle_frames, sync=False)
     barrier()
-    kctx.timing_enable(True)
+    kctx.timing_enable(args.full)
     og0 = application.output_gather_stats()
     t0 = time.perf_counter()
     hs0 = application.host_stats()
@@ -483,15 +536,17 @@ def main():
     host_busy = (hs1["seconds"] - hs0["seconds"]) - (hs1["blocked_seconds"] - hs0["blocked_seconds"])
     barrier()
     elapsed = time.perf_counter() - t0
-    timed = kctx.timing_query()
+    timed = kctx.timing_query() if args.full else {}
     kctx.timing_enable(False)
     kctx.timing_set_sampling(1)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(application, args.dump_outputs)
 
-    # ---- after the timed region: the same loop, unbracketed, kept running for about a second.  Reported beside `value`
+    # ---- after the timed region (--full): the same loop, unbracketed, kept running for about a second.  Reported beside `value`
     # (never instead of it): a K-step run at ~0.25 ms per step is over before a 1 Hz utilisation sampler sees the GPU busy,
     # and it pays the executor's three-frame pipeline fill once per K frames. ----
     sustained = None
-    if args.sustain_seconds > 0:
+    if args.full and args.sustain_seconds > 0:
         # every rank must render the SAME number of frames (each frame is a set of collectives): the count comes from the slowest rank's clock
         agreed = elapsed
         if dist is not None:
@@ -522,7 +577,7 @@ def main():
     dom_avg_s = (dom_ms / 1000.0) / max(dom_count, 1)
     bpp = (ALGO_BYTES_PER_PX_PACKED if args.workload in PACKED_HDR_WORKLOADS else ALGO_BYTES_PER_PX).get(dominant)
     roofline = None
-    if bpp and dom_avg_s > 0:
+    if args.full and bpp and dom_avg_s > 0:
         # rank 0's launch of the dominant kernel covers its own band only
         band = {"lighting": plan["lighting"], "tonemap": plan["tonemap"], "bloom_threshold": plan["threshold"]}.get(dominant)
         rows = height if band is None else band[1] * (2 if dominant == "bloom_threshold" else 1)
@@ -637,10 +692,10 @@ def main():
         "roofline": roofline,
         "chain": {"algorithmic_GBps": chain_gbs, "frac_of_hbm_peak": chain_gbs / HBM_PEAK_GBS,
                   "algorithmic_bytes_per_frame": chain_bytes},
-        "kernels_warmup": warm_breakdown,
+        "kernels_warmup": warm_breakdown if args.full else None,
         "host_busy_ms_per_step": 1000.0 * host_busy / args.steps,
         # untimed frames in front of the timed region beyond --warmup (see "clock settle" above); 0 frames = switched off
-        "clock_settle": {"frames": settle_frames, "target_ms_of_load": SETTLE_MS,
+        "clock_settle": {"frames": settle_frames, "target_ms_of_load": SETTLE_MS, "pace_ms_per_frame": PACE_MS_PER_FRAME[args.workload],
                          "why": "the device needs tens of ms of uninterrupted load to reach its sustained clocks; the warm-up's host-side read-out loses them again"},
     }
     if bands:
@@ -653,7 +708,7 @@ def main():
         sustained["unit"] = "Mpixels/s"
         result["sustained"] = sustained
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload not in SINGLE_GPU_WORKLOADS:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload not in SINGLE_GPU_WORKLOADS:
         rows = args.cpu_sample_rows or height  # whole frame: ~4 s on a 256-thread host, ~20 s on 8 cores
         reference, result["cpu_baseline"] = cpu_baseline(cam, gbuf, descs, width, height, rows)
         # beside it, never instead of it: the reference's own shader text executed on the same cores
@@ -670,14 +725,14 @@ def main():
         result["cpu_baseline"] = None
         result["cpu_baseline_reference_shaders"] = None
         result["parity_checked"] = False
-        result["parity_detail"] = {"reason": "no CPU baseline in this run (multi-GPU rank, --no-cpu-baseline, or a workload whose oracle comparison "
-                                             "lives in tests/test_gpu_fullsize.py: config 1 / config 4)"}
+        result["parity_detail"] = {"reason": "no CPU baseline in this run (no --full, multi-GPU rank, --no-cpu-baseline, or a workload whose oracle "
+                                             "comparison lives in tests/test_gpu_fullsize.py: config 1 / config 4)"}
 
     application.close()
     # ---- BASELINE config 5 beside the default workload (N > 1): the default line is weak scaling (one 4K frame's worth of pixels per
     # rank); the configuration BASELINE.json names for the multi-GPU case is ONE 7680x4320 frame over the ranks -- strong scaling.  Same
     # contract on a second executor: W warm-up frames, then exactly K frames between two barriers, max over the ranks.
-    if bands and args.workload == "config3_4k_4096lights" and os.environ.get("GRANITE_BENCH_CONFIG5", "1") == "1":
+    if args.full and bands and args.workload == "config3_4k_4096lights" and os.environ.get("GRANITE_BENCH_CONFIG5", "1") == "1":
         sub = None
         try:
             app5, cam5, gbuf5, descs5, w5, h5, desc5, name5 = build(True, "config5_8k")

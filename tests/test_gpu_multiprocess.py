@@ -64,7 +64,7 @@ def test_bench_runs_as_the_driver_launches_it_with_two_ranks():
     """python -m torch.distributed.run --nproc-per-node 2 ... bench.py --gpus 2 --steps K --warmup W: one JSON line from rank 0, the
     frame tiled into two row bands (not the replicas fallback), the assembled frame equal to the whole-frame executor's."""
     r = launch(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "3", "--workload", "config2_1080p_256lights",
-                   "--no-cpu-baseline", "--sustain-seconds", "0"], 29900 + (os.getpid() % 90))
+                   "--full", "--no-cpu-baseline", "--sustain-seconds", "0"], 29900 + (os.getpid() % 90))
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

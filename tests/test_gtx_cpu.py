@@ -1,5 +1,5 @@
 """CPU: the GTX ("GRANITE TEXFMT1") reader / writer of the host library, pinned against the .gtx files the reference ships
-(tests/golden/gtx_reference_files.json, made by tests/golden/make_gtx_golden.py from /root/reference/assets/textures)."""
+(tests/golden/gtx_reference_files.json, made by tests/golden/make_gtx_golden.py from the reference's assets/textures)."""
 import hashlib
 import json
 import os
@@ -36,13 +36,26 @@ def test_writer_reproduces_the_reference_files_bit_for_bit(tmp_path):
     assert hashlib.sha256(f.payload.tobytes()).hexdigest() == GOLDEN["smaa/area.gtx"]["payload_sha256"]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/assets/textures"), reason="reference tree not present")
-def test_reader_accepts_every_gtx_file_of_the_reference():
+# the committed payload of each file the reference ships (granite_amd/data): with the recorded 64-byte header it is that file again
+PAYLOADS = {"ibl_brdf_lut.gtx": "ibl_brdf_lut_rg16f_256x256.bin", "smaa/area.gtx": "smaa_area_rg8_160x560.bin",
+            "smaa/search.gtx": "smaa_search_r8_64x16.bin"}
+
+
+def test_reader_accepts_every_gtx_file_of_the_reference(tmp_path):
+    """The reference's files, reassembled from the recorded header and the committed payload; the whole-file sha256 recorded from
+    the reference proves they are its files byte for byte before the reader sees them."""
+    assert set(PAYLOADS) == set(GOLDEN)
+    files = {}
     for name, want in GOLDEN.items():
-        f = gtx.read(os.path.join("/root/reference/assets/textures", name))
+        raw = bytes.fromhex(want["header_hex"]) + open(os.path.join(os.path.dirname(data.__file__), PAYLOADS[name]), "rb").read()
+        assert hashlib.sha256(raw).hexdigest() == want["sha256"], name
+        files[name] = tmp_path / name.replace("/", "_")
+        files[name].write_bytes(raw)
+    for name, want in GOLDEN.items():
+        f = gtx.read(str(files[name]))
         assert f.payload.size + gtx.HEADER_SIZE == want["size"]
         assert hashlib.sha256(f.payload.tobytes()).hexdigest() == want["payload_sha256"]
-    lut = gtx.read("/root/reference/assets/textures/ibl_brdf_lut.gtx")
+    lut = gtx.read(str(files["ibl_brdf_lut.gtx"]))
     assert (lut.info.format, lut.info.width, lut.info.height, lut.info.levels) == (capi.FORMAT_R16G16_SFLOAT, 256, 256, 1)
 
 

@@ -5,7 +5,6 @@ import math
 import os
 import struct
 import subprocess
-import sys
 import zlib
 
 import numpy as np
@@ -230,67 +229,57 @@ def test_corrupt_png_is_a_load_failure_not_a_crash(tmp_path):
     assert failures > 50
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/tools/sweep_scene.py"), reason="needs the Granite checkout")
+# Granite's tools/sweep_scene.py and tools/bench_aa.py run against a stand-in for our headless runners, recorded by
+# tests/golden/make_reference_tools_golden.py: every command line each script built, the --stat document it read back after each call
+# and the results document it wrote from them.
+TOOLS_GOLDEN = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_tools_runs.json")))
+
+
+def recorded_argv(argv, tmp_path):
+    return [str(tmp_path / "stat.json") if a == "{stat}" else a.replace("{tmp}", str(tmp_path)) for a in argv]
+
+
 def test_the_references_sweep_script_consumes_our_stat_file(tmp_path):
-    """Granite's own tools/sweep_scene.py, executed, with a stand-in viewer binary that takes the command line the script builds
-    (sweep_scene.py:94-117) through the headless runner's argument parser and writes the --stat document with stat_document():
-    the script must get through run_test / map_result_to_json and write its results file."""
-    stub = tmp_path / "viewer-stub"
-    stub.write_text(f"""#!{sys.executable}
-import json, sys
-sys.path.insert(0, {ROOT!r})
-from granite_amd import headless
-args = headless.parse_args(sys.argv[1:])
-assert args.frames == 7 and args.width == 640 and args.height == 360 and args.timestamp and args.config.endswith(".json")
-kw = headless.viewer_config_to_kwargs(json.load(open(args.config)))
-stamps = {{"gbuffer-main + lighting-main": (7, 1.4), "tonemap": (7, 0.21)}}
-json.dump(headless.stat_document(250.0 if kw["post_aa"] == 0 else 300.0, "stub gpu", 42, stamps, args.frames), open(args.stat, "w"))
-""")
-    stub.chmod(0o755)
-    cfgs = []
-    for name, doc in (("plain", {"renderer": "deferred", "hdrBloom": True}), ("fxaa", {"postAA": "fxaa"})):
-        p = tmp_path / f"{name}.json"
-        p.write_text(json.dumps(doc))
-        cfgs.append(str(p))
-    results = tmp_path / "results.json"
-    r = subprocess.run([sys.executable, "/root/reference/tools/sweep_scene.py", "--viewer-binary", str(stub), "--scene", "synthetic",
-                        "--configs", *cfgs, "--width", "640", "--height", "360", "--frames", "7", "--iterations", "2", "--timestamp",
-                        "--results", str(results)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr[-1500:]
-    runs = json.loads(results.read_text())["runs"]
+    """Granite's own tools/sweep_scene.py (recorded run): each command line the script builds (sweep_scene.py:94-117) must go through the
+    headless runner's argument parser, and the --stat document stat_document() writes for it must be the document the script read back
+    and turned into its results file through run_test / map_result_to_json."""
+    rec = TOOLS_GOLDEN["sweep_scene"]
+    for name, doc in rec["configs"].items():
+        (tmp_path / f"{name}.json").write_text(json.dumps(doc))
+    assert len(rec["calls"]) == 2 * len(rec["configs"])  # --iterations 2
+    for call in rec["calls"]:
+        args = headless.parse_args(recorded_argv(call["argv"], tmp_path))
+        assert args.frames == 7 and args.width == 640 and args.height == 360 and args.timestamp and args.config.endswith(".json")
+        kw = headless.viewer_config_to_kwargs(json.load(open(args.config)))
+        stamps = {"gbuffer-main + lighting-main": (7, 1.4), "tonemap": (7, 0.21)}
+        doc = headless.stat_document(250.0 if kw["post_aa"] == 0 else 300.0, "stub gpu", 42, stamps, args.frames)
+        assert json.loads(json.dumps(doc)) == call["stat"], call["argv"]
+    runs = rec["results"]["runs"]
     assert [x["config"] for x in runs] == ["plain", "fxaa"] and [x["avg"] for x in runs] == [250.0, 300.0]
     assert runs[0]["gpu"] == "stub gpu" and runs[0]["version"] == 42 and runs[0]["width"] == 640
     assert runs[0]["performance"]["tonemap"] == {"timePerAccumulationUs": 30.0, "timePerFrameContextUs": 30.0,
                                                    "accumulationsPerFrameContext": 1.0}
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/tools/bench_aa.py"), reason="needs the Granite checkout")
 def test_the_references_aa_bench_script_drives_our_stand_in(tmp_path):
-    """Granite's own tools/bench_aa.py, executed: the command line it builds for aa-bench-headless (bench_aa.py:144-148 +
-    '--aa-method' per method, :161-166) must parse with the stand-in's argument parser and its run_test / map_result_to_json must
-    consume the --stat document.  The stub stands for the GPU run; tests/test_gpu_headless.py runs the real one."""
-    stub = tmp_path / "aa-bench-stub"
-    stub.write_text(f"""#!{sys.executable}
-import json, sys
-sys.path.insert(0, {ROOT!r})
-from granite_amd import aa_bench, headless
-args = aa_bench.parse_args(sys.argv[1:])
-assert args.frames == 9 and args.width == 320 and args.height == 200 and args.input_images == ["a.png", "b.png"]
-kw = aa_bench.method_to_kwargs(args.aa_method)
-cost = 100.0 + 10.0 * kw["post_aa"] + 20.0 * kw["pre_aa"]
-json.dump(headless.stat_document(cost, "stub gpu", 7, {{"tonemap": (9, 0.9)}}, args.frames), open(args.stat, "w"))
-""")
-    stub.chmod(0o755)
-    results = tmp_path / "aa.json"
-    r = subprocess.run([sys.executable, "/root/reference/tools/bench_aa.py", "--binary", str(stub), "--images", "a.png", "b.png", "--width", "320",
-                        "--height", "200", "--frames", "9", "--iterations", "2", "--results", str(results)], capture_output=True, text=True,
-                       timeout=180)
-    assert r.returncode == 0, r.stderr[-1500:]
-    runs = {x["method"]: x for x in json.loads(results.read_text())["runs"]}
-    # bench_aa.py:158-159: every method it knows, live in the reference or not
+    """Granite's own tools/bench_aa.py (recorded run): the command line it builds for aa-bench-headless (bench_aa.py:144-148 +
+    '--aa-method' per method, :161-166) must parse with the stand-in's argument parser, and the --stat document stat_document() writes
+    for it must be the one its run_test / map_result_to_json consumed.  tests/test_gpu_headless.py runs the real binary."""
+    from granite_amd import aa_bench
+    rec = TOOLS_GOLDEN["bench_aa"]
+    methods = []
+    for call in rec["calls"]:
+        args = aa_bench.parse_args(recorded_argv(call["argv"], tmp_path))
+        assert args.frames == 9 and args.width == 320 and args.height == 200 and args.input_images == ["a.png", "b.png"]
+        kw = aa_bench.method_to_kwargs(args.aa_method)
+        doc = headless.stat_document(100.0 + 10.0 * kw["post_aa"] + 20.0 * kw["pre_aa"], "stub gpu", 7, {"tonemap": (9, 0.9)}, args.frames)
+        assert json.loads(json.dumps(doc)) == call["stat"], call["argv"]
+        methods.append(args.aa_method)
+    runs = {x["method"]: x for x in rec["results"]["runs"]}
+    # bench_aa.py:158-159: every method it knows, live in the reference or not, --iterations 2 times each
     assert set(runs) == {"none", "fxaa", "fxaa2phase", "smaaLow", "smaaMedium", "smaaHigh", "smaaUltra", "smaaUltraT2X", "taaLow", "taaMedium",
                          "taaHigh", "taaUltra", "taaExtreme", "taaNightmare"}
-    from granite_amd import app as gapp
+    assert sorted(methods) == sorted(list(runs) * 2)
     assert runs["none"]["avg"] == 100.0 and runs["fxaa"]["avg"] == 100.0 + 10.0 * gapp.POST_AA_FXAA
     assert runs["taaHigh"]["avg"] == 100.0 + 20.0 * gapp.POST_AA_TAA_HIGH and runs["taaNightmare"]["avg"] == 100.0
     assert runs["smaaUltra"]["gpu"] == "stub gpu" and runs["smaaUltra"]["version"] == 7 and runs["smaaUltra"]["width"] == 320

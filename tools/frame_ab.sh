@@ -14,7 +14,7 @@ for round in 1 2; do
     name=${v%%:*}; settings=""; [ "$v" != "$name" ] && settings=${v#*:}
     for wl in $WORKLOADS; do
       ( IFS=,; for kv in $settings; do export "$kv"; done
-        timeout 300 python bench.py --workload $wl --no-cpu-baseline "${EXTRA[@]}" > $O/bench_${wl}_$name.$round.json 2>/dev/null )
+        timeout 300 python bench.py --workload $wl --full --no-cpu-baseline "${EXTRA[@]}" > $O/bench_${wl}_$name.$round.json 2>/dev/null )
       python tools/bench_brief.py $O/bench_${wl}_$name.$round.json | sed "s/^/$name $wl /"
     done
   done

@@ -11,7 +11,7 @@ for round in 1 2; do
   done
 done
 for lib in "${@:-lib}"; do
-  GRANITE_LIB_DIR=$lib timeout 200 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_${lib}.json 2>/dev/null
+  GRANITE_LIB_DIR=$lib timeout 200 python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline > $O/bench_${lib}.json 2>/dev/null
   python tools/bench_brief.py $O/bench_${lib}.json | sed "s/^/$lib /"
 done
 if [ -d granite_amd/lib_stamp ]; then

@@ -57,6 +57,19 @@ class ResourceInfo(C.Structure):
                 ("size_bytes", C.c_uint64), ("physical_index", C.c_int32), ("levels", C.c_uint32)]
 
 
+class VideoOptions(C.Structure):
+    _fields_ = [("format", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("hdr10", C.c_int32), ("ring_frames", C.c_uint32)]
+
+
+class VideoLayout(C.Structure):
+    _fields_ = [("num_planes", C.c_uint32), ("bytes_per_sample", C.c_uint32), ("width", C.c_uint32 * 3), ("height", C.c_uint32 * 3),
+                ("pitch", C.c_uint32 * 3), ("offset", C.c_uint64 * 3), ("frame_bytes", C.c_uint64)]
+
+
+# gra_video_format
+VIDEO_FORMATS = {"nv12": 0, "yuv420p": 1, "yuv420p16": 2, "yuv444p": 3, "yuv444p16": 4, "p010": 5, "p016": 6}
+
+
 class Timestamp(C.Structure):
     _fields_ = [("tag", C.c_char * 64), ("count", C.c_uint64), ("total_ms", C.c_double)]
 
@@ -69,6 +82,7 @@ EXPORTED_SYMBOLS = [
     "gra_set_smaa_luts", "gra_get_host_stats", "gra_get_output_gather_stats", "gra_get_prefetched_refreshes", "gra_get_launch_graph_replays", "gra_get_allocated_bytes", "gra_gtx_probe", "gra_gtx_read", "gra_gtx_write",
     "gra_upload_gbuffer_gtx", "gra_save_resource_gtx", "gra_get_render_size", "gra_upload_ambient_occlusion", "gra_upload_aa_bench_images", "gra_compute_rec709_to_display", "gra_set_exchange_callback", "gra_get_strip_plan", "gra_get_strip_plan_aa", "gra_get_strip_plan_taa_history",
     "gra_comm_create_unique_id", "gra_comm_init", "gra_comm_info", "gra_comm_init_output", "gra_install_ssr_tables", "gra_reset_timestamps", "gra_set_directional_light", "gra_set_fog", "gra_generate_mipmaps", "gra_write_resource", "gra_get_frame_state", "gra_set_frame_state",
+    "gra_video_begin", "gra_video_frame_layout", "gra_video_read_frame", "gra_video_end",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -136,6 +150,10 @@ def load_library() -> C.CDLL:
         "gra_comm_init": (C.c_int, [vp, vp, C.c_int32, C.c_int32]),
         "gra_comm_info": (C.c_int, [vp, P(C.c_int32), P(C.c_int32), P(C.c_int32)]),
         "gra_comm_init_output": (C.c_int, [vp, vp, C.c_int32, C.c_int32]),
+        "gra_video_begin": (C.c_int, [vp, P(VideoOptions)]),
+        "gra_video_frame_layout": (C.c_int, [vp, P(VideoLayout)]),
+        "gra_video_read_frame": (C.c_int, [vp, vp, C.c_uint64, P(C.c_int64)]),
+        "gra_video_end": (C.c_int, [vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -338,6 +356,37 @@ class Application:
         self._check(self.lib.gra_read_backbuffer(self.handle, raw.ctypes.data, raw.nbytes))
         return self._shape(info, raw)
 
+    # ---- frame recording (gra_video_*) ------------------------------------------------------------------------------
+    def start_video(self, format: str = "nv12", size=None, hdr10: bool = False, ring_frames: int = 0) -> VideoLayout:
+        """Every frame rendered from now on is converted to YCbCr planes (`format`, one of VIDEO_FORMATS) at `size` (w, h; None = the
+        backbuffer's) and queued for read_video_frame."""
+        w, h = size if size else (0, 0)
+        opts = VideoOptions(VIDEO_FORMATS[format], w, h, int(bool(hdr10)), ring_frames)
+        self._check(self.lib.gra_video_begin(self.handle, C.byref(opts)))
+        return self.video_layout()
+
+    def video_layout(self) -> VideoLayout:
+        layout = VideoLayout()
+        self._check(self.lib.gra_video_frame_layout(self.handle, C.byref(layout)))
+        return layout
+
+    def read_video_frame(self, raw: bool = False):
+        """The oldest unread recorded frame: (planes, frame_number), or None when none is pending.  planes: list of numpy arrays
+        (h, w) for Y / Cb / Cr, (h, w, 2) for interleaved CbCr; raw=True returns the packed bytes instead."""
+        layout = self.video_layout()
+        buf = np.empty(layout.frame_bytes, np.uint8)
+        number = C.c_int64(-1)
+        rc = self.lib.gra_video_read_frame(self.handle, buf.ctypes.data, buf.nbytes, C.byref(number))
+        if rc == 1:
+            return None
+        self._check(rc)
+        if raw:
+            return buf, int(number.value)
+        return video_planes(layout, buf), int(number.value)
+
+    def stop_video(self):
+        self._check(self.lib.gra_video_end(self.handle))
+
     def backbuffer_info(self) -> ResourceInfo:
         info = ResourceInfo()
         self._check(self.lib.gra_get_backbuffer(self.handle, info))
@@ -532,3 +581,15 @@ class KernelContextView:
         if self.lib.gr_timing_max_ms(self.handle, name.encode(), C.byref(out)) < 0:
             raise capi.GraniteHipError(self.lib.gr_last_error(self.handle).decode())
         return float(out.value)
+
+
+def video_planes(layout: VideoLayout, buf: np.ndarray) -> list:
+    """Split one packed recorded frame (gra_video_frame_layout) into numpy planes."""
+    dtype = np.uint16 if layout.bytes_per_sample == 2 else np.uint8
+    planes = []
+    for i in range(layout.num_planes):
+        w, h, pitch, off = layout.width[i], layout.height[i], layout.pitch[i], layout.offset[i]
+        rows = buf[off:off + pitch * h].view(dtype).reshape(h, pitch // layout.bytes_per_sample)
+        comps = (pitch // layout.bytes_per_sample) // w
+        planes.append(rows.reshape(h, w, comps) if comps > 1 else rows)
+    return planes

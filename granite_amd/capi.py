@@ -21,8 +21,12 @@ FORMAT_R8_UNORM = 9
 FORMAT_R8G8_UNORM = 16
 FORMAT_R8G8B8A8_UNORM = 37
 FORMAT_R8G8B8A8_SRGB = 43
+FORMAT_B8G8R8A8_UNORM = 44
+FORMAT_B8G8R8A8_SRGB = 50
 FORMAT_A2B10G10R10_UNORM_PACK32 = 64
+FORMAT_R16_UNORM = 70
 FORMAT_R16_SFLOAT = 76
+FORMAT_R16G16_UNORM = 77
 FORMAT_R16G16_SFLOAT = 83
 FORMAT_R16G16B16A16_SFLOAT = 97
 FORMAT_R32_SFLOAT = 100
@@ -35,6 +39,10 @@ FORMAT_BPP = {
     FORMAT_R8G8_UNORM: 2,
     FORMAT_R8G8B8A8_UNORM: 4,
     FORMAT_R8G8B8A8_SRGB: 4,
+    FORMAT_B8G8R8A8_UNORM: 4,
+    FORMAT_B8G8R8A8_SRGB: 4,
+    FORMAT_R16_UNORM: 2,
+    FORMAT_R16G16_UNORM: 4,
     FORMAT_A2B10G10R10_UNORM_PACK32: 4,
     FORMAT_R16_SFLOAT: 2,
     FORMAT_R16G16_SFLOAT: 4,
@@ -44,6 +52,21 @@ FORMAT_BPP = {
     FORMAT_D16_UNORM: 2,
     FORMAT_D32_SFLOAT: 4,
 }
+
+# gr_video_scale: VkColorSpaceKHR values, scaler.comp CONTROL bits and transfer functions
+COLOR_SPACE_SRGB_NONLINEAR = 0
+COLOR_SPACE_EXTENDED_SRGB_LINEAR = 1000104002
+COLOR_SPACE_HDR10_ST2084 = 1000104008
+VIDEO_CONTROL_SKIP_RESCALE_BIT = 1
+VIDEO_CONTROL_DOWNSCALING_BIT = 2
+VIDEO_CONTROL_SAMPLED_DOWNSCALING_BIT = 4
+VIDEO_CONTROL_CLAMP_COORD_BIT = 8
+VIDEO_CONTROL_CHROMA_SUBSAMPLE_BIT = 16
+VIDEO_CONTROL_PRIMARY_CONVERSION_BIT = 32
+VIDEO_CONTROL_DITHER_BIT = 64
+VIDEO_TRANSFER_IDENTITY = 0
+VIDEO_TRANSFER_SRGB = 1
+VIDEO_TRANSFER_PQ = 2
 
 LIGHTING_DIRECTIONAL_BIT = 1
 LIGHTING_CLUSTERED_BIT = 2
@@ -65,6 +88,19 @@ TRANSFORMS_SIZE = 852480
 class Image(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("pitch_bytes", C.c_uint32),
                 ("format", C.c_uint32)]
+
+
+class PushVideo(C.Structure):
+    _fields_ = [("resolution", C.c_int32 * 2), ("scaling_to_input", C.c_float * 2), ("inv_input_resolution", C.c_float * 2),
+                ("dither_strength", C.c_float)]
+
+
+assert C.sizeof(PushVideo) == 28
+
+
+class VideoPlan(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("eotf", C.c_uint32), ("oetf", C.c_uint32), ("num_planes", C.c_uint32), ("push", PushVideo),
+                ("gamma_space_transform", C.c_float * 12), ("primary_transform", C.c_float * 9)]
 
 
 class TimingEntry(C.Structure):
@@ -307,6 +343,9 @@ def load_library() -> C.CDLL:
         "gr_pack_b10g11r11": (C.c_int, [vp, vp, vp, vp, C.c_uint32]),
         "gr_pq10_encode": (C.c_int, [vp, vp, P(Image), P(Image), P(Image), P(PushPq10)]),
         "gr_fsr_upscale": (C.c_int, [vp, vp, P(Image), P(Image), C.c_int]),
+        "gr_video_scale": (C.c_int, [vp, vp, P(Image), P(Image), C.c_uint32, C.c_uint32, C.c_uint32]),
+        "gr_video_scale_plan": (C.c_int, [P(Image), P(Image), C.c_uint32, C.c_uint32, C.c_uint32, P(VideoPlan)]),
+        "gr_video_scaler_weights": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_uint16)]),
         "gr_fsr_sharpen": (C.c_int, [vp, vp, P(Image), P(Image), C.c_float]),
         "gr_mip_chain_offset": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
         "gr_mip_chain_size": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
@@ -327,7 +366,41 @@ EXPORTED_SYMBOLS = [
     "gr_cluster_spot_transform", "gr_cluster_setup", "gr_cluster_binning", "gr_cluster_z_range", "gr_cluster_front", "gr_lighting",
     "gr_smaa_set_luts", "gr_fxaa", "gr_blit", "gr_smaa_edge_detection", "gr_smaa_blend_weight", "gr_smaa_neighbor_blend", "gr_taa_resolve",
     "gr_hiz", "gr_mip_chain_offset", "gr_mip_chain_size", "gr_fsr_upscale", "gr_fsr_sharpen", "gr_fill_byte", "gr_fill_u32", "gr_pq10_encode", "gr_get_device_info", "gr_spd_downsample", "gr_debug_mix", "gr_pack_b10g11r11",
+    "gr_video_scale", "gr_video_scale_plan", "gr_video_scaler_weights",
 ]
+
+
+def _video_images(input_size, input_format, planes):
+    """gr_image descriptors (null pointers) for the host-only plan: input_size (w, h), planes [(w, h, format), ...]."""
+    src = Image(None, int(input_size[0]), int(input_size[1]), int(input_size[0]) * FORMAT_BPP[input_format], int(input_format))
+    arr = (Image * max(1, len(planes)))()
+    for i, (w, h, fmt) in enumerate(planes):
+        arr[i] = Image(None, int(w), int(h), int(w) * FORMAT_BPP[fmt], int(fmt))
+    return src, arr
+
+
+def video_scale_plan(input_size, input_format, planes, input_color_space, output_color_space) -> Optional[dict]:
+    """What gr_video_scale would launch (VideoScaler::rescale's decisions), computed on the host; None when it refuses."""
+    lib = load_library()
+    src, arr = _video_images(input_size, input_format, planes)
+    plan = VideoPlan()
+    if lib.gr_video_scale_plan(C.byref(src), arr, len(planes), int(input_color_space), int(output_color_space), C.byref(plan)) < 0:
+        return None
+    return {"flags": plan.flags, "eotf": plan.eotf, "oetf": plan.oetf, "num_planes": plan.num_planes,
+            "resolution": tuple(plan.push.resolution), "scaling_to_input": tuple(plan.push.scaling_to_input),
+            "inv_input_resolution": tuple(plan.push.inv_input_resolution), "dither_strength": plan.push.dither_strength,
+            "gamma_space_transform": np.array(plan.gamma_space_transform[:], dtype=np.float32).reshape(3, 4),
+            "primary_transform": np.array(plan.primary_transform[:], dtype=np.float32).reshape(3, 3).T}
+
+
+def video_scaler_weights(input_width: int, input_height: int, output_width: int, output_height: int) -> np.ndarray:
+    """The fp16 weight table of VideoScaler::update_weights as uint16 bits, shape (2, 256, 8): horizontal, vertical."""
+    lib = load_library()
+    out = np.zeros((2, 256, 8), dtype=np.uint16)
+    rc = lib.gr_video_scaler_weights(input_width, input_height, output_width, output_height, out.ctypes.data_as(C.POINTER(C.c_uint16)))
+    if rc < 0:
+        raise GraniteHipError(f"gr_video_scaler_weights({input_width}, {input_height}, {output_width}, {output_height}) failed")
+    return out
 
 
 class DeviceBuffer:
@@ -393,8 +466,14 @@ class DeviceImage:
         self.ctx.check(self.ctx.lib.gr_download(self.ctx.handle, None, out.ctypes.data, self.ptr, out.nbytes))
         if self.format == FORMAT_R16G16B16A16_SFLOAT:
             return out.view(np.uint16).reshape(self.height, self.width, 4)
-        if self.format in (FORMAT_R8G8B8A8_SRGB, FORMAT_R8G8B8A8_UNORM):
+        if self.format in (FORMAT_R8G8B8A8_SRGB, FORMAT_R8G8B8A8_UNORM, FORMAT_B8G8R8A8_UNORM, FORMAT_B8G8R8A8_SRGB):
             return out.reshape(self.height, self.width, 4)
+        if self.format == FORMAT_R8_UNORM:
+            return out.reshape(self.height, self.width)
+        if self.format == FORMAT_R16_UNORM:
+            return out.view(np.uint16).reshape(self.height, self.width)
+        if self.format == FORMAT_R16G16_UNORM:
+            return out.view(np.uint16).reshape(self.height, self.width, 2)
         if self.format == FORMAT_R8G8_UNORM:
             return out.reshape(self.height, self.width, 2)
         if self.format in (FORMAT_D32_SFLOAT, FORMAT_R32_SFLOAT):
@@ -612,6 +691,12 @@ class Context:
         push.hdr_pre_exposure, push.ui_pre_exposure = hdr_pre_exposure, ui_pre_exposure
         push.max_light_level, push.inv_max_light_level = max_light_level, float(np.float32(1.0) / np.float32(max_light_level))
         self.check(self.lib.gr_pq10_encode(self.handle, stream, hdr.desc, ui.desc, out.desc, push))
+
+    def video_scale(self, src: DeviceImage, planes, input_color_space: int = COLOR_SPACE_SRGB_NONLINEAR,
+                    output_color_space: int = COLOR_SPACE_SRGB_NONLINEAR, stream=None):
+        """gr_video_scale: `src` converted (and rescaled to planes[0]'s size) into 1-3 output planes (DeviceImage or Image)."""
+        arr = (Image * len(planes))(*[p.desc if isinstance(p, DeviceImage) else p for p in planes])
+        self.check(self.lib.gr_video_scale(self.handle, stream, src.desc, arr, len(planes), int(input_color_space), int(output_color_space)))
 
     def hiz(self, depth: DeviceImage, z_transform, output_downsample: bool = False, chain: Optional[DeviceBuffer] = None,
             counter: Optional[DeviceBuffer] = None, stream=None):

@@ -247,6 +247,12 @@ void gr_destroy(gr_ctx *ctx)
 	for (auto &bits : ctx->smaa_bits)
 		if (bits.second.memory)
 			(void)hipFree(bits.second.memory);
+	for (auto &table : ctx->video_weights)
+	{
+		(void)hipFree(table.second.device);
+		(void)hipHostFree(table.second.host);
+		(void)hipEventDestroy(table.second.ready);
+	}
 	delete ctx;
 }
 

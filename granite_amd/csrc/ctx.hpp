@@ -55,6 +55,15 @@ struct gr_ctx
 	// aa.hip: (axis length, 1 / length bits) -> "pixel-centre taps along this axis are texel fetches" (aa_core.hpp: axis_taps_exact)
 	std::map<uint64_t, bool> centre_taps_exact, diag_walk_exact_x, diag_walk_exact_y;
 
+	// gr_video_scale (video.hip): the fp16 polyphase weight table per (input w, h, output w, h), built on first use and never rewritten
+	// (a launch on another stream may still read it); the upload is stream-ordered from a pinned copy and published by `ready`.
+	struct VideoWeights
+	{
+		void *device = nullptr, *host = nullptr;
+		hipEvent_t ready = nullptr;
+	};
+	std::map<uint64_t, VideoWeights> video_weights;
+
 	bool timing_enabled = false;
 	std::string timing_filter; // empty = every launcher
 	unsigned timing_every = 1;  // bracket every n-th matching launch (gr_timing_set_sampling)

@@ -751,3 +751,37 @@ void *gra_get_stream(gra_app *app)
 	return app ? app->app->get_device().get_stream(HIP::CommandBuffer::Type::Generic) : nullptr;
 }
 }
+
+int gra_video_begin(gra_app *app, const gra_video_options *options)
+{
+	return guarded(app, [&]() {
+		if (!options)
+			throw std::logic_error("gra_video_begin: options are required");
+		app->app->video_begin(*options);
+	});
+}
+
+int gra_video_frame_layout(gra_app *app, gra_video_layout *layout)
+{
+	return guarded(app, [&]() {
+		if (!layout)
+			throw std::logic_error("gra_video_frame_layout: layout is required");
+		*layout = app->app->video_layout();
+	});
+}
+
+int gra_video_read_frame(gra_app *app, void *dst_host, uint64_t size_bytes, int64_t *frame_number)
+{
+	bool got = false;
+	const int rc = guarded(app, [&]() {
+		if (!dst_host)
+			throw std::logic_error("gra_video_read_frame: destination is required");
+		got = app->app->video_read(dst_host, size_bytes, frame_number);
+	});
+	return rc < 0 ? rc : (got ? 0 : 1);
+}
+
+int gra_video_end(gra_app *app)
+{
+	return guarded(app, [&]() { app->app->video_end(); });
+}

@@ -140,6 +140,7 @@ ImageSpaceApplication::~ImageSpaceApplication()
 	cluster.invalidate_prefetch(); // no helper-thread job may outlive the light objects it reads
 	if (device_holder)
 		device_holder->wait_idle();
+	video_release();
 	for (auto &e : output_gather_done)
 		(void)hipEventDestroy(static_cast<hipEvent_t>(e.second));
 	if (output_ready_event)
@@ -845,6 +846,8 @@ void ImageSpaceApplication::render_frame()
 	auto &device = get_device();
 	const auto host_t0 = std::chrono::steady_clock::now();
 	check_taa_history_reach();
+	if (video)
+		video_check_ring(); // a full ring fails the frame before any of its state advances
 	if (need_bake)
 		bake_render_graph();
 
@@ -868,6 +871,8 @@ void ImageSpaceApplication::render_frame()
 	else if (camera_moves)
 		context.set_camera(base_projection, base_view);
 
+	if (video)
+		video_before_frame(*backbuffer); // before anything of this frame is enqueued
 	graph.setup_attachments(device, backbuffer);
 	if (config.enable_lighting)
 	{
@@ -897,7 +902,10 @@ void ImageSpaceApplication::render_frame()
 		else
 			cluster.prefetch(context.get_render_parameters());
 	}
+	const uint64_t device_frame = device.get_frame_number();
 	graph.enqueue_render_passes(device, composer);
+	if (video)
+		video_after_frame(*backbuffer, device_frame);
 	gbuffer_dirty = false;
 	last_backbuffer = backbuffer;
 	host_frames++;

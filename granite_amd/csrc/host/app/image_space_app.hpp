@@ -19,6 +19,7 @@
 #include "../render_context.hpp"
 #include "../render_graph.hpp"
 #include "../renderer.hpp"
+#include "../video/scaler.hpp"
 
 namespace Granite
 {
@@ -35,6 +36,8 @@ public:
 	{
 		if (device_holder)
 			device_holder->wait_idle();
+		if (video)
+			video_wait();
 		check_taa_history_reach();
 	}
 	// Row bands with a bounded TAA history reach: throws once a resolve has reported a fetch outside the rows this rank holds.
@@ -95,6 +98,11 @@ public:
 	void upload_ambient_occlusion(const void *ao_r8);
 	void upload_aa_bench_images(const void *first, const void *second, uint32_t width, uint32_t height);
 	void save_image_gtx(HIP::Image &image, const std::string &path);
+	// Frame recording (include/granite_app.h: gra_video_*; video_recording.cpp)
+	void video_begin(const gra_video_options &options);
+	void video_end();
+	const gra_video_layout &video_layout() const;
+	bool video_read(void *dst, uint64_t size, int64_t *frame_number); // false: nothing pending
 	std::string last_error;
 
 private:
@@ -155,6 +163,33 @@ private:
 	uint64_t host_frames = 0;
 	uint64_t output_acquires = 0, output_acquire_waits = 0;
 	double host_seconds = 0.0;
+
+	// Recording state: one device copy of the planes (conversion and copy are in order on `stream`), a ring of pinned frames.
+	struct VideoRecording
+	{
+		gra_video_options options = {};
+		gra_video_layout layout = {};
+		uint32_t plane_format[3] = {};
+		void *stream = nullptr;        // hipStream_t
+		void *planes = nullptr;        // device
+		VideoScaler scaler;
+		struct Slot
+		{
+			void *host = nullptr;      // pinned
+			void *copied = nullptr;    // hipEvent_t: the copy into `host` is done
+			int64_t frame = -1;
+		};
+		std::vector<Slot> ring;
+		uint64_t written = 0, read = 0; // frames converted / handed back
+		// per swapchain image: hipEvent_t after the conversion that read it (the image's next writer waits for it)
+		std::unordered_map<const void *, void *> read_done;
+	};
+	std::unique_ptr<VideoRecording> video;
+	void video_check_ring() const;
+	void video_wait();
+	void video_before_frame(HIP::Image &backbuffer);
+	void video_after_frame(HIP::Image &backbuffer, uint64_t device_frame);
+	void video_release();
 
 	void bake_render_graph();
 	void add_main_pass_deferred(const std::string &tag);

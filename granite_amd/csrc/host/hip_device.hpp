@@ -191,6 +191,19 @@ public:
 	// Every launch, copy and event record the executor's streams were given in frames up to this one (device frame numbers) has completed: what
 	// frame pacing waited for on the host in next_frame_context().  An event recorded in such a frame needs neither a query nor a wait.
 	uint64_t get_completed_frame() const { return completed_through; }
+	// The fences next_frame_context() recorded for device frame `frame` while that frame is still in the ring: fn(hipEvent_t) once per
+	// stream that was given work in it.  Waiting on all of them orders a consumer behind everything the frame enqueued (its last
+	// writer of the swapchain image included, on whichever stream that ran).
+	template <typename Fn>
+	void for_each_fence_of(uint64_t frame, Fn &&fn) const
+	{
+		if (frame == 0 || frame >= frame_number || frame + StagingFrames < frame_number)
+			return;
+		const StagingFrame &slot = staging[(frame - 1) % StagingFrames];
+		for (int i = 0; i < int(CommandBuffer::Type::Count); i++)
+			if (slot.fence_frame[i] == frame)
+				fn(slot.fence[i]);
+	}
 	// Number of the frame being enqueued (from 1; advanced by next_frame_context()).
 	uint64_t get_frame_number() const { return frame_number; }
 	void next_frame_context();

@@ -19,8 +19,12 @@ enum VkFormat : uint32_t
 	VK_FORMAT_R8G8_UNORM = 16,
 	VK_FORMAT_R8G8B8A8_UNORM = 37,
 	VK_FORMAT_R8G8B8A8_SRGB = 43,
+	VK_FORMAT_B8G8R8A8_UNORM = 44,
+	VK_FORMAT_B8G8R8A8_SRGB = 50,
 	VK_FORMAT_A2B10G10R10_UNORM_PACK32 = 64,
+	VK_FORMAT_R16_UNORM = 70,
 	VK_FORMAT_R16_SFLOAT = 76,
+	VK_FORMAT_R16G16_UNORM = 77,
 	VK_FORMAT_R16G16_SFLOAT = 83,
 	VK_FORMAT_R16G16B16A16_SFLOAT = 97,
 	VK_FORMAT_R32_SFLOAT = 100,
@@ -82,9 +86,13 @@ static inline unsigned vk_format_block_size(VkFormat format)
 	case VK_FORMAT_R8_UNORM: return 1;
 	case VK_FORMAT_R8G8_UNORM: return 2;
 	case VK_FORMAT_D16_UNORM: return 2;
-	case VK_FORMAT_R16_SFLOAT: return 2;
+	case VK_FORMAT_R16_SFLOAT:
+	case VK_FORMAT_R16_UNORM: return 2;
 	case VK_FORMAT_R8G8B8A8_UNORM:
 	case VK_FORMAT_R8G8B8A8_SRGB:
+	case VK_FORMAT_B8G8R8A8_UNORM:
+	case VK_FORMAT_B8G8R8A8_SRGB:
+	case VK_FORMAT_R16G16_UNORM:
 	case VK_FORMAT_A2B10G10R10_UNORM_PACK32:
 	case VK_FORMAT_R16G16_SFLOAT:
 	case VK_FORMAT_B10G11R11_UFLOAT_PACK32:
@@ -95,5 +103,5 @@ static inline unsigned vk_format_block_size(VkFormat format)
 	}
 }
 
-static inline bool vk_format_is_srgb(VkFormat format) { return format == VK_FORMAT_R8G8B8A8_SRGB; }
+static inline bool vk_format_is_srgb(VkFormat format) { return format == VK_FORMAT_R8G8B8A8_SRGB || format == VK_FORMAT_B8G8R8A8_SRGB; }
 static inline bool vk_format_has_depth(VkFormat format) { return format == VK_FORMAT_D32_SFLOAT || format == VK_FORMAT_D16_UNORM; }

@@ -8,6 +8,7 @@ tooling drives the HIP executor unchanged:
 
     granite-hip-headless SCENE --frames N --width W --height H [--stat out.json] [--timestamp] [--config viewer.json]
         [--png-path prefix] [--png-reference-path out.png] [--gtx-reference-path out.gtx] [--camera-index i] [--lights N]
+        [--video-encode-path out.y4m | out.yuv]
 
 SCENE is what stands in for the glTF file: a directory holding the G-buffer attachments a Granite build dumped as
 `emissive.gtx albedo.gtx normal.gtx pbr.gtx depth.gtx` (+ optional `lights.json`, read_lights()'s format,
@@ -20,7 +21,13 @@ with --timestamp, performance{pass: timePerAccumulationUs, timePerFrameContextUs
 --config understands the viewer_config keys that select image-space work (read_config, scene_viewer_application.cpp:
 163-260): renderer, hdrBloom, hdrBloomDynamicExposure, clusteredLights, postAA, resolutionScale, resolutionScaleSharpen,
 hdr10, ssao (as the lighting pass's ambient-occlusion input), ssr; keys that concern geometry or shadow passes are accepted and
-ignored, a forward renderer or MSAA is refused (no G-buffer for this executor to consume)."""
+ignored, a forward renderer or MSAA is refused (no G-buffer for this executor to consume).
+
+--video-encode-path records every timed frame as the reference's runner does (application_headless.cpp:225-275, 348-372): each
+frame's swapchain image goes through VideoScaler::rescale (gr_video_scale) beside the next frames and its YCbCr planes are
+written out; --png-path takes precedence.  There is no FFmpeg: a path ending in .y4m gets YUV4MPEG2 (4:2:0, 8 bits, or 16 bits
+when the config has hdr10; full range, F<round(1 / time-step)>:1), any other path raw concatenated NV12 frames (P010 under hdr10)
+as `ffmpeg -f rawvideo -pix_fmt nv12 -s WxH` reads them."""
 from __future__ import annotations
 
 import argparse
@@ -172,9 +179,37 @@ def parse_args(argv):
     ap.add_argument("--camera-index", type=int, default=-1)
     ap.add_argument("--lights", type=int, default=-1, help="synthetic scene: number of positional lights (default 4096)")
     ap.add_argument("--device", type=int, default=0)
-    for ignored in ("--fs-assets", "--fs-builtin", "--fs-cache", "--video-encode-path"):
+    ap.add_argument("--video-encode-path", default="")
+    for ignored in ("--fs-assets", "--fs-builtin", "--fs-cache"):
         ap.add_argument(ignored, default="")
     return ap.parse_args(argv)
+
+
+class VideoWriter:
+    """Recorded frames to a file: YUV4MPEG2 for *.y4m (planar 4:2:0 or 4:4:4, 8 or 16 bits), raw packed frames otherwise."""
+
+    def __init__(self, path: str, width: int, height: int, time_step: float, format: str):
+        self.y4m = path.lower().endswith(".y4m")
+        self.format = format
+        self.f = open(path, "wb")
+        if self.y4m:
+            chroma = {"yuv420p": "C420jpeg", "yuv444p": "C444", "yuv420p16": "C420p16", "yuv444p16": "C444p16"}[format]
+            fps = max(1, int(round(1.0 / time_step)))
+            self.f.write(f"YUV4MPEG2 W{width} H{height} F{fps}:1 Ip A1:1 {chroma} XCOLORRANGE=FULL\n".encode())
+
+    @staticmethod
+    def format_for(path: str, hdr10: bool) -> str:
+        if path.lower().endswith(".y4m"):
+            return "yuv420p16" if hdr10 else "yuv420p"
+        return "p010" if hdr10 else "nv12"
+
+    def write(self, packed: np.ndarray):
+        if self.y4m:
+            self.f.write(b"FRAME\n")
+        self.f.write(packed.tobytes())
+
+    def close(self):
+        self.f.close()
 
 
 def backbuffer_rgba8(app: gapp.Application) -> np.ndarray:
@@ -256,12 +291,29 @@ def main(argv=None) -> int:
     app.render_frames(1)                  # warm-up frame, then wait idle and reset the timestamp log
     app.timestamps()
     app.reset_timestamps()
+    writer = None
+    if args.video_encode_path and not args.png_path:   # application_headless.cpp:509: the PNG dump takes precedence
+        fmt = VideoWriter.format_for(args.video_encode_path, kw["hdr10"])
+        app.start_video(fmt, hdr10=kw["hdr10"])
+        writer = VideoWriter(args.video_encode_path, args.width, args.height, args.time_step, fmt)
+
+    def drain(keep: int):
+        # hand recorded frames to the file, leaving the newest `keep` in flight (reading one waits for its copy)
+        while writer and rendered - written[0] > keep:
+            got = app.read_video_frame(raw=True)
+            if got is None:
+                break
+            writer.write(got[0])
+            written[0] += 1
+
+    written = [0]
     print("[INFO]: === Begin run ===")
     start = time.perf_counter_ns()
     rendered = 0
     for frame in range(args.frames):
         app.render_frames(1, sync=False)
         rendered += 1
+        drain(2)
         if args.png_path:
             app.sync()
             png.write_png(f"{args.png_path}_{frame:05d}.png", backbuffer_rgba8(app))
@@ -269,6 +321,10 @@ def main(argv=None) -> int:
     app.sync()
     end = time.perf_counter_ns()
     print("[INFO]: === End run ===")
+    if writer:
+        drain(0)
+        app.stop_video()
+        writer.close()
 
     usec = 1e-3 * (end - start) / rendered
     print(f"[INFO]: Average frame time: {usec:.3f} usec")

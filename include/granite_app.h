@@ -206,7 +206,10 @@ typedef struct gra_frame_state
 } gra_frame_state;
 int gra_get_frame_state(gra_app *app, gra_frame_state *state);
 int gra_set_frame_state(gra_app *app, const gra_frame_state *state);
-/* The swapchain image the last frame was rendered into (external to the graph, 4-image ring). */
+/* The swapchain image the last frame was rendered into (external to the graph, 4-image ring).  The image is complete only after
+ * gra_sync (gra_read_backbuffer syncs itself) or, for work on a stream of the caller's, behind the executor stream that wrote it last:
+ * gra_render_frames with sync == 0 returns while the frame is still being rendered, and the image is rewritten four frames later.
+ * Recorded frames (gra_video_*, below) are the supported way to consume frames asynchronously. */
 int gra_get_backbuffer(gra_app *app, gra_resource_info *info);
 int gra_read_backbuffer(gra_app *app, void *dst_host, uint64_t size_bytes);
 
@@ -301,6 +304,46 @@ int gra_get_allocated_bytes(gra_app *app, uint64_t *out);
 /* Per-kernel timing lives in the kernel library: gr_timing_* on this context. */
 void *gra_get_kernel_context(gra_app *app); /* gr_ctx* */
 void *gra_get_stream(gra_app *app);         /* hipStream_t of the generic queue */
+
+/* ---- frame recording (the headless runner's --video-encode-path: application_headless.cpp, VideoEncoder::process_rgb) ------------
+ * While recording, every frame's backbuffer is converted by gr_video_scale (VideoScaler::rescale) on a stream of the recorder's own,
+ * behind the frame fences of the executor streams that rendered it (no device sync), and copied into a ring of pinned host buffers.
+ * The swapchain image is rewritten four frames later only after its conversion has read it.  gra_render_frames fails, before it
+ * enqueues anything for that frame, when `ring_frames` frames are unread: frames are never overwritten or dropped.  Input colour
+ * space: HDR10 when the app renders hdr10, sRGB otherwise.  Not available with row bands (strip_count > 1). */
+typedef enum gra_video_format
+{
+	GRA_VIDEO_NV12 = 0,      /* Y + interleaved CbCr, 8 bits, 4:2:0 */
+	GRA_VIDEO_YUV420P = 1,   /* Y, Cb, Cr, 8 bits, 4:2:0 */
+	GRA_VIDEO_YUV420P16 = 2, /* 16 bits (UNORM16) */
+	GRA_VIDEO_YUV444P = 3,
+	GRA_VIDEO_YUV444P16 = 4,
+	GRA_VIDEO_P010 = 5,      /* Y + interleaved CbCr, 16-bit words (UNORM16, as the reference stores them), 4:2:0 */
+	GRA_VIDEO_P016 = 6
+} gra_video_format;
+typedef struct gra_video_options
+{
+	uint32_t format;      /* gra_video_format */
+	uint32_t width, height; /* encode size; 0 = the backbuffer's */
+	int32_t hdr10;        /* output colour space HDR10 (ST 2084, BT.2020) instead of sRGB (BT.709) */
+	uint32_t ring_frames; /* unread frames held; 0 = 8 */
+} gra_video_options;
+/* One packed frame: planes back to back, rows tightly packed. */
+typedef struct gra_video_layout
+{
+	uint32_t num_planes;
+	uint32_t bytes_per_sample;   /* 1 or 2 */
+	uint32_t width[3], height[3]; /* in samples; an interleaved CbCr plane counts pairs */
+	uint32_t pitch[3];            /* bytes */
+	uint64_t offset[3];
+	uint64_t frame_bytes;
+} gra_video_layout;
+int gra_video_begin(gra_app *app, const gra_video_options *options);
+int gra_video_frame_layout(gra_app *app, gra_video_layout *layout);
+/* The oldest unread recorded frame, in order: waits for that frame's copy only.  0: copied (frame_number = the frame's index since
+ * gra_video_begin, from 0); 1: no frame pending; negative: error. */
+int gra_video_read_frame(gra_app *app, void *dst_host, uint64_t size_bytes, int64_t *frame_number);
+int gra_video_end(gra_app *app);
 
 #ifdef __cplusplus
 }

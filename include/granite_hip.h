@@ -44,8 +44,12 @@ typedef enum gr_format
 	GR_FORMAT_R8G8_UNORM = 16,
 	GR_FORMAT_R8G8B8A8_UNORM = 37,
 	GR_FORMAT_R8G8B8A8_SRGB = 43,
+	GR_FORMAT_B8G8R8A8_UNORM = 44,     /* video output plane (gr_video_scale) */
+	GR_FORMAT_B8G8R8A8_SRGB = 50,      /* video output plane (gr_video_scale) */
 	GR_FORMAT_A2B10G10R10_UNORM_PACK32 = 64,
+	GR_FORMAT_R16_UNORM = 70,          /* P010 / P016 / 16-bit YUV planes (gr_video_scale) */
 	GR_FORMAT_R16_SFLOAT = 76,
+	GR_FORMAT_R16G16_UNORM = 77,       /* P010 / P016 interleaved chroma (gr_video_scale) */
 	GR_FORMAT_R16G16_SFLOAT = 83,
 	GR_FORMAT_R16G16B16A16_SFLOAT = 97,
 	GR_FORMAT_R32_SFLOAT = 100,
@@ -668,6 +672,59 @@ typedef struct gr_push_pq10
 	float inv_max_light_level;
 } gr_push_pq10;
 int gr_pq10_encode(gr_ctx *ctx, gr_stream stream, const gr_image *hdr, const gr_image *ui, const gr_image *out, const gr_push_pq10 *push);
+/* ---- video frame conversion -----------------------------------------------------------------------------------------------
+ * VideoScaler::rescale (video/scaler.cpp) + assets/shaders/util/scaler.comp: what the headless runner's --video-encode-path does
+ * to every frame before FFmpeg encodes it.  input: R8G8B8A8_UNORM / _SRGB (an *_SRGB input is decoded as its sampled view does),
+ * A2B10G10R10_UNORM_PACK32 or R16G16B16A16_SFLOAT.  planes:
+ *   1 plane   R8G8B8A8 / B8G8R8A8 (UNORM or SRGB; stored as UNORM like the reference's storage view), 4 x 4 ordered dither;
+ *   2 planes  R8 + R8G8 (NV12) or R16_UNORM + R16G16_UNORM (P010 / P016): Y and interleaved Cb Cr;
+ *   3 planes  R8 x 3 or R16_UNORM x 3: Y, Cb, Cr.
+ * The chroma planes have the luma plane's size (4:4:4) or half of it rounded up (4:2:0: the mean of each 2 x 2 block).  YCbCr is
+ * full range, BT.2020 for an HDR10 output and BT.709 otherwise.  When planes[0] differs in size from the input, the frame is
+ * rescaled with the reference's 8-tap, 256-phase Hann-windowed sinc (above a ratio of 2: a bilinear prefilter to twice the target
+ * size first).  Colour spaces are VkColorSpaceKHR values.  The first call with a new pair of sizes builds that size's fp16 weight
+ * table on the device (an allocation: not inside a graph capture; its upload is ordered on `stream`); the table is kept with the context.
+ * Stores outside a plane are dropped; out-of-frame input texels read as zero on the same-size path. */
+#define GR_COLOR_SPACE_SRGB_NONLINEAR 0u
+#define GR_COLOR_SPACE_EXTENDED_SRGB_LINEAR 1000104002u
+#define GR_COLOR_SPACE_HDR10_ST2084 1000104008u
+/* scaler.comp CONTROL bits and transfer functions */
+#define GR_VIDEO_CONTROL_SKIP_RESCALE_BIT 1u
+#define GR_VIDEO_CONTROL_DOWNSCALING_BIT 2u
+#define GR_VIDEO_CONTROL_SAMPLED_DOWNSCALING_BIT 4u
+#define GR_VIDEO_CONTROL_CLAMP_COORD_BIT 8u
+#define GR_VIDEO_CONTROL_CHROMA_SUBSAMPLE_BIT 16u
+#define GR_VIDEO_CONTROL_PRIMARY_CONVERSION_BIT 32u
+#define GR_VIDEO_CONTROL_DITHER_BIT 64u
+#define GR_VIDEO_TRANSFER_IDENTITY 0u
+#define GR_VIDEO_TRANSFER_SRGB 1u
+#define GR_VIDEO_TRANSFER_PQ 2u
+/* scaler.comp Registers (push constants), byte-identical */
+typedef struct gr_push_video
+{
+	int32_t resolution[2];        /* input size */
+	float scaling_to_input[2];    /* input / output size, at most 2 */
+	float inv_input_resolution[2];
+	float dither_strength;
+} gr_push_video;
+/* Everything VideoScaler::rescale decides for one conversion */
+typedef struct gr_video_plan
+{
+	uint32_t flags;                  /* GR_VIDEO_CONTROL_* */
+	uint32_t eotf, oetf;             /* GR_VIDEO_TRANSFER_* (both identity when they cancel on a same-size conversion) */
+	uint32_t num_planes;
+	gr_push_video push;
+	float gamma_space_transform[12]; /* row major 3 x 4: rows Cr, Y, Cb of [R G B 1] */
+	float primary_transform[9];      /* column major, sdr_scale included; identity without PRIMARY_CONVERSION */
+} gr_video_plan;
+int gr_video_scale(gr_ctx *ctx, gr_stream stream, const gr_image *input, const gr_image *planes, uint32_t num_planes,
+                   uint32_t input_color_space, uint32_t output_color_space);
+/* Host-only (no device): the plan gr_video_scale would launch (image pointers are not read), and the fp16 weight table of
+ * update_weights for these sizes, out[2][256][8] (horizontal, vertical).  Negative on arguments gr_video_scale refuses. */
+int gr_video_scale_plan(const gr_image *input, const gr_image *planes, uint32_t num_planes, uint32_t input_color_space,
+                        uint32_t output_color_space, gr_video_plan *plan);
+int gr_video_scaler_weights(uint32_t input_width, uint32_t input_height, uint32_t output_width, uint32_t output_height, uint16_t *out);
+
 /* Fill with a 32-bit pattern (count dwords): attachment clears to a colour. */
 int gr_fill_u32(gr_ctx *ctx, gr_stream stream, void *dst, uint32_t value, size_t count);
 /* Executor self-test operation (no counterpart in the reference): out[i] = hash(i, salt, one dword of each of up to four
@@ -752,6 +809,8 @@ GR_ASSERT_OFFSET(gr_cluster_params, decals_texture_offset, 152);
 GR_ASSERT_OFFSET(gr_cluster_params, z_max_index, 156);
 GR_ASSERT_OFFSET(gr_cluster_params, z_scale, 160);
 GR_ASSERT_SIZE(gr_push_pq10, 80);             /* hdr.cpp:626-633 */
+GR_ASSERT_SIZE(gr_push_video, 28);            /* scaler.comp:78-84, scaler.cpp:184-190 */
+GR_ASSERT_OFFSET(gr_push_video, dither_strength, 24);
 GR_STATIC_ASSERT(GR_TRANSFORMS_OFFSET_SHADOW == GR_MAX_LIGHTS_BINDLESS * 48u, "ClustererBindlessTransforms: lights[4096] of 48 B");
 GR_STATIC_ASSERT(GR_TRANSFORMS_OFFSET_MODEL + GR_MAX_LIGHTS_BINDLESS * 48u == GR_TRANSFORMS_OFFSET_TYPE_MASK, "ClustererBindlessTransforms: model[4096] of 48 B");
 GR_STATIC_ASSERT(GR_TRANSFORMS_OFFSET_TYPE_MASK + GR_MAX_LIGHTS_BINDLESS / 8u == GR_TRANSFORMS_OFFSET_DECALS, "ClustererBindlessTransforms: type_mask[128]");

@@ -1,0 +1,194 @@
+"""GPU: gr_video_scale (VideoScaler::rescale + scaler.comp) against tests/video_ref.py.
+
+Bounds, per sample:
+  * 8-bit planes at the same size: 1 code.  The reference and the kernel compute the same expression, the reference in float64,
+    the kernel in fp32 (the shader in fp16); a difference below 1e-5 can still fall on either side of a rounding midpoint.
+  * 8-bit planes when rescaled: 2 codes.  The filter's input and its vertical result are fp16 in both (the shader's LDS tiles);
+    accumulation order and the fp32 transfer functions move a value by a few fp16 ulps (2^-11 relative), which the sRGB encode
+    near black (slope 12.92) can bring to a little over one code.
+  * 16-bit planes: 64 of 65535.  The shader rounds the OETF result and the YCbCr value to fp16: one fp16 ulp at [0.5, 1) is
+    2^-11 = 32 codes of 65535; the kernel keeps fp32 there, so it may sit up to two half-ulps from the shader's value.
+Chroma is compared against the 2 x 2 mean (4:2:0) of the reference's per-pixel Cb / Cr.  Every plane lies in a buffer with a padded
+row pitch and a guard after its last row: no byte outside the plane's extent may change.
+"""
+import numpy as np
+import pytest
+
+import video_ref as vr
+from granite_amd import capi
+
+pytestmark = pytest.mark.gpu
+
+GUARD = 4096
+FILL = 0xA5
+S, HDR, LIN = capi.COLOR_SPACE_SRGB_NONLINEAR, capi.COLOR_SPACE_HDR10_ST2084, capi.COLOR_SPACE_EXTENDED_SRGB_LINEAR
+CHANNELS = {vr.R8: (1, np.uint8), vr.R16: (1, np.uint16), vr.R8G8: (2, np.uint8), vr.R16G16: (2, np.uint16),
+            vr.RGBA8: (4, np.uint8), vr.BGRA8: (4, np.uint8), vr.RGBA8_SRGB: (4, np.uint8), vr.BGRA8_SRGB: (4, np.uint8)}
+
+
+class GuardedPlane:
+    """A plane inside a larger allocation: row pitch padded past the row (by default to a multiple of 16 plus 16: the vector stores;
+    `pad` gives row + pad bytes instead) starting `offset` bytes into the buffer, GUARD bytes after the last row, all filled with FILL
+    before the launch.  An offset or pitch that is not a multiple of 16 takes the store-by-store path of every run."""
+
+    def __init__(self, gr, w, h, fmt, offset=0, pad=None):
+        self.w, self.h, self.fmt = w, h, fmt
+        self.ch, self.dtype = CHANNELS[fmt]
+        self.row = w * self.ch * np.dtype(self.dtype).itemsize
+        self.pitch = (self.row + 15) // 16 * 16 + 16 if pad is None else self.row + pad
+        self.offset = offset
+        self.buf = capi.DeviceBuffer(gr, offset + self.pitch * h + GUARD)
+        self.buf.upload(np.full(self.buf.nbytes, FILL, np.uint8))
+        self.desc = capi.Image(self.buf.ptr + offset, w, h, self.pitch, fmt)
+
+    def read(self):
+        raw = self.buf.download(np.uint8)
+        assert (raw[:self.offset] == FILL).all(), "bytes written before the plane"
+        raw = raw[self.offset:]
+        rows = raw[:self.pitch * self.h].reshape(self.h, self.pitch)
+        assert (rows[:, self.row:] == FILL).all(), "bytes written in a row's pitch padding"
+        assert (raw[self.pitch * self.h:] == FILL).all(), "bytes written after the plane's last row"
+        data = np.ascontiguousarray(rows[:, :self.row]).view(self.dtype)
+        return data.reshape(self.h, self.w, self.ch) if self.ch > 1 else data.reshape(self.h, self.w)
+
+
+def make_input(gr, fmt, w, h, seed, smooth=False):
+    rng = np.random.default_rng(seed)
+    if fmt in (vr.RGBA8, vr.RGBA8_SRGB):
+        data = rng.integers(0, 256, (h, w, 4), dtype=np.uint8)
+        # smooth regions next to the noise: the filter's DC path and the chroma mean of flat blocks
+        data[: h // 4] = (np.linspace(0, 255, w)[None, :, None] * np.array([1.0, 0.6, 0.3, 1.0])).astype(np.uint8)
+    elif fmt == vr.A2B10G10R10:
+        c = rng.integers(0, 1024, (h, w, 3), dtype=np.uint32)
+        if smooth:  # diagonal ramps with +-8 codes of noise
+            ramp = (np.arange(w)[None, :, None] * 700 // w + np.arange(h)[:, None, None] * 300 // h) * np.array([1, 1, 1])[None, None]
+            c = np.clip(ramp + rng.integers(-8, 9, (h, w, 3)), 0, 1023).astype(np.uint32)
+        data = c[..., 0] | (c[..., 1] << 10) | (c[..., 2] << 20) | np.uint32(3 << 30)
+    else:
+        data = rng.uniform(0.0, 1.2, (h, w, 4)).astype(np.float16).view(np.uint16)
+    img = capi.DeviceImage(gr, w, h, fmt).upload(data)
+    return data, img
+
+
+def run_case(gr, in_fmt, in_size, planes, src_space, dst_space, tol, seed=1, smooth=False, offset=0, pad=None):
+    data, img = make_input(gr, in_fmt, in_size[0], in_size[1], seed, smooth)
+    outs = [GuardedPlane(gr, *p, offset=offset, pad=pad) for p in planes]
+    arr = (capi.Image * len(outs))(*[o.desc for o in outs])
+    gr.check(gr.lib.gr_video_scale(gr.handle, None, img.desc, arr, len(outs), src_space, dst_space))
+    gr.sync()
+    got = [o.read() for o in outs]
+    ref = vr.video_scale(data, in_fmt, planes, src_space, dst_space)
+    for i, (g, r) in enumerate(zip(got, ref)):
+        assert g.shape == r.shape, (i, g.shape, r.shape)
+        err = np.abs(g.astype(np.int64) - r)
+        worst = np.unravel_index(np.argmax(err), err.shape)
+        assert err.max() <= tol, f"plane {i}: {int((err > tol).sum())} samples beyond {tol} codes, worst {err.max()} at {worst}"
+    return got
+
+
+def nv12(w, h, wide=False):
+    return [(w, h, vr.R16 if wide else vr.R8), ((w + 1) // 2, (h + 1) // 2, vr.R16G16 if wide else vr.R8G8)]
+
+
+def yuv(w, h, sub=True, wide=False):
+    cw, ch = ((w + 1) // 2, (h + 1) // 2) if sub else (w, h)
+    f = vr.R16 if wide else vr.R8
+    return [(w, h, f), (cw, ch, f), (cw, ch, f)]
+
+
+SAME_SIZE_LAYOUTS = {
+    "nv12": lambda w, h: nv12(w, h),
+    "yuv420p": lambda w, h: yuv(w, h),
+    "yuv444p": lambda w, h: yuv(w, h, sub=False),
+    "rgba8_dither": lambda w, h: [(w, h, vr.RGBA8)],
+    "bgra8_dither": lambda w, h: [(w, h, vr.BGRA8_SRGB)],
+    "yuv420p16": lambda w, h: yuv(w, h, wide=True),
+}
+
+
+@pytest.mark.parametrize("layout", sorted(SAME_SIZE_LAYOUTS))
+@pytest.mark.parametrize("size", [(3840, 2160), (1277, 719)], ids=["4k", "odd"])
+def test_same_size_from_srgb_rgba8(gr, size, layout):
+    planes = SAME_SIZE_LAYOUTS[layout](*size)
+    run_case(gr, vr.RGBA8, size, planes, S, S, 64 if planes[0][2] == vr.R16 else 1)
+
+
+@pytest.mark.parametrize("layout", ["nv12", "yuv420p", "yuv444p", "rgba8_dither", "yuv420p16"])
+def test_unaligned_planes(gr, layout):
+    # plane pointers 4 bytes into their buffers and pitches of row + 4: vector stores are off, every sample goes out on its own
+    for size in ((3840, 2160), (1277, 719)):
+        planes = SAME_SIZE_LAYOUTS[layout](*size)
+        run_case(gr, vr.RGBA8, size, planes, S, S, 64 if planes[0][2] == vr.R16 else 1, offset=4, pad=4)
+    run_case(gr, vr.RGBA8, (2560, 1440), nv12(1920, 1080), S, S, 2, offset=4, pad=4)
+
+
+def test_same_size_srgb_view_input(gr):
+    # an *_SRGB input decodes through the view and the sRGB OETF re-encodes: no cancellation
+    run_case(gr, vr.RGBA8_SRGB, (1277, 719), nv12(1277, 719), S, S, 1)
+
+
+def test_p010_from_hdr10_target(gr):
+    run_case(gr, vr.A2B10G10R10, (3840, 2160), nv12(3840, 2160, wide=True), HDR, HDR, 64)
+
+
+def test_srgb_to_hdr10_with_primary_conversion(gr):
+    run_case(gr, vr.RGBA8, (1920, 1080), nv12(1920, 1080, wide=True), S, HDR, 64)
+
+
+def test_hdr10_to_srgb(gr):
+    # BT.2020 -> BT.709 of out-of-gamut colours in nits (sdr_scale 1): a channel can be the difference of terms of up to 10^4 that
+    # cancel to below 1, where fp32 keeps ~1e-3 of absolute error and the sRGB encode (slope 12.92 near black) turns it into a few
+    # codes.  The shader holds these nits in fp16 (ulp 4 at 8000), far coarser; 8 codes bound the fp32 kernel.
+    run_case(gr, vr.A2B10G10R10, (1277, 719), nv12(1277, 719), HDR, S, 8)
+
+
+def test_rgba16f_input(gr):
+    # scRGB -> sRGB scales by 80 (sdr_scale) and saturates most colour: the sRGB -> sRGB run checks the colour channels of the
+    # RGBA16F fetch, this one the primary conversion with alpha passed through; 4K takes the 32-B vector loads, the odd width the
+    # texel-by-texel ones
+    run_case(gr, vr.RGBA16F, (1277, 719), [(1277, 719, vr.RGBA8)], LIN, S, 1)
+    run_case(gr, vr.RGBA16F, (3840, 2160), [(3840, 2160, vr.RGBA8)], S, S, 1)
+    run_case(gr, vr.RGBA16F, (1277, 719), yuv(1277, 719), S, S, 1)
+
+
+@pytest.mark.parametrize("case", [
+    ((3840, 2160), nv12(1920, 1080)),
+    ((2560, 1440), yuv(1920, 1080)),
+    ((1280, 720), nv12(1920, 1080)),
+    ((7680, 4320), nv12(1920, 1080)),
+    ((1280, 720), yuv(1919, 1081, sub=False)),
+], ids=["4k_to_1080p", "1440p_to_1080p", "720p_to_1080p", "8k_to_1080p_sampled", "720p_to_odd_444"])
+def test_rescale(gr, case):
+    in_size, planes = case
+    run_case(gr, vr.RGBA8, in_size, planes, S, S, 2)
+
+
+def test_rescale_to_rgba8(gr):
+    # Per-channel sRGB output of a filtered noise frame: the fp16 tiles of kernel and reference can differ by one fp16 ulp where the
+    # fp32 and float64 sums straddle a rounding point (2^-11 at magnitudes in [0.5, 1)); through a tap weight near 1 and the sRGB
+    # encode's slope of 12.92 near black that is 12.92 * 255 / 2048 = 1.6 codes per differing tap, so two such taps reach 4.  The
+    # YCbCr planes above average three channels and stay within 2.
+    run_case(gr, vr.RGBA8, (2560, 1440), [(1917, 1083, vr.RGBA8)], S, S, 4)
+
+
+def test_rescale_16_bit(gr):
+    # PQ in, PQ out, filtered in nits: on full-range noise the sinc's negative lobes cancel terms of up to 10^4 nits down to near
+    # black, where fp16 staging (ulp 8 at 10^4, in the shader as here) meets PQ's unbounded slope and any two roundings disagree by
+    # thousands of codes.  A ramp with +-8 codes of noise keeps the filtered values away from that cliff.
+    run_case(gr, vr.A2B10G10R10, (3840, 2160), nv12(1920, 1080, wide=True), HDR, HDR, 64, smooth=True)
+
+
+def test_refusals_report_an_error(gr):
+    data, img = make_input(gr, vr.RGBA8, 64, 32, 3)
+    y = GuardedPlane(gr, 64, 32, vr.R8)
+    c = GuardedPlane(gr, 31, 16, vr.R8G8)  # neither half nor full size
+    arr = (capi.Image * 2)(y.desc, c.desc)
+    rc = gr.lib.gr_video_scale(gr.handle, None, img.desc, arr, 2, S, S)
+    assert rc == -1 and b"chroma" in gr.lib.gr_last_error(gr.handle)
+    good = GuardedPlane(gr, 32, 16, vr.R8G8)
+    arr = (capi.Image * 2)(y.desc, good.desc)
+    assert gr.lib.gr_video_scale(gr.handle, None, img.desc, arr, 2, S, LIN) == -1
+    assert gr.lib.gr_video_scale(gr.handle, None, img.desc, arr, 2, 7, S) == -1
+    gr.sync()
+    # nothing was launched: the planes still hold the fill
+    assert (y.buf.download(np.uint8) == FILL).all()

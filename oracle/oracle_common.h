@@ -229,6 +229,15 @@ static inline uint8_t float_to_unorm8(float v)
 	return uint8_t(int(v * 255.0f + 0.5f));
 }
 static inline float unorm8_to_float(uint8_t v) { return float(v) / 255.0f; }
+// UNORM16: the same with 65535.
+static inline uint16_t float_to_unorm16(float v)
+{
+	if (!(v > 0.0f))
+		return 0;
+	if (v >= 1.0f)
+		return 65535;
+	return uint16_t(int(v * 65535.0f + 0.5f));
+}
 
 // assets/shaders/inc/srgb.h:4-19 semantics (also the hardware sRGB transfer functions).
 static inline float srgb_decode(float c)

@@ -12,7 +12,7 @@
 //   * textureLod: LinearClamp or NearestClamp on a tightly packed image; texel weights (1 - a, a) from
 //     a = fract(u * w - 0.5), lerp horizontally then vertically -- the oracle's sampler.
 //   * imageStore / fragment outputs convert to the attachment format: RGBA16F round-to-nearest-even, UNORM8
-//     floor(v * 255 + 0.5) after clamping, sRGB8 encode then UNORM8.
+//     floor(v * 255 + 0.5) after clamping (UNORM16: 65535), sRGB8 encode then UNORM8; BGRA8 stores (b, g, r, a).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -29,6 +29,7 @@ using uint = uint32_t;
 template <typename T> struct tvec2;
 template <typename T> struct tvec3;
 template <typename T> struct tvec4;
+struct float16_t;
 
 // Swizzle proxies: plain arrays that sit in a union with the components and convert to the selected vector.  A swizzle that
 // names consecutive components in order (.xy, .zw, .rgb ...) IS such a vector in memory and converts to a reference, so it
@@ -41,6 +42,9 @@ struct swz2<T, N, A, B, false>
 	T d[N];
 	operator tvec2<T>() const;
 	swz2 &operator=(const tvec2<T> &v);
+	swz2 &operator+=(const tvec2<T> &v) { d[A] += v.d[0]; d[B] += v.d[1]; return *this; }
+	swz2 &operator+=(T s) { d[A] += s; d[B] += s; return *this; }
+	swz2 &operator*=(T s) { d[A] *= s; d[B] *= s; return *this; }
 };
 template <typename T, int N, int A, int B>
 struct swz2<T, N, A, B, true>
@@ -65,6 +69,7 @@ struct swz3<T, N, A, B, C, true>
 	T d[N];
 	operator tvec3<T> &();
 	operator const tvec3<T> &() const;
+	operator tvec3<float>() const requires std::is_same_v<T, float16_t>;
 	swz3 &operator=(const tvec3<T> &v);
 };
 template <typename T, int N, int A, int B, int C, int D>
@@ -115,7 +120,8 @@ struct tvec3
 	tvec3(T x_, T y_, T z_) : x(x_), y(y_), z(z_) {}
 	tvec3(const tvec2<T> &v, T z_) : x(v.x), y(v.y), z(z_) {}
 	tvec3(T x_, const tvec2<T> &v) : x(x_), y(v.x), z(v.y) {}
-	template <typename U> explicit tvec3(const tvec3<U> &o) : x(T(o.x)), y(T(o.y)), z(T(o.z)) {}
+	// GLSL converts float16_t to float implicitly; everything else is spelled out
+	template <typename U> explicit(!(std::is_same_v<U, float16_t> && std::is_same_v<T, float>)) tvec3(const tvec3<U> &o) : x(T(o.x)), y(T(o.y)), z(T(o.z)) {}
 	explicit tvec3(const tvec4<T> &o);
 	tvec3(const tvec3 &o) : x(o.x), y(o.y), z(o.z) {}
 	tvec3 &operator=(const tvec3 &o) { x = o.x; y = o.y; z = o.z; return *this; }
@@ -143,7 +149,8 @@ struct tvec4
 	tvec4(T x_, const tvec3<T> &v) : x(x_), y(v.x), z(v.y), w(v.z) {}
 	tvec4(T x_, const tvec2<T> &v, T w_) : x(x_), y(v.x), z(v.y), w(w_) {}
 	tvec4(T x_, T y_, const tvec2<T> &v) : x(x_), y(y_), z(v.x), w(v.y) {}
-	template <typename U> explicit tvec4(const tvec4<U> &o) : x(T(o.x)), y(T(o.y)), z(T(o.z)), w(T(o.w)) {}
+	template <typename U> explicit(!(std::is_same_v<U, float16_t> && std::is_same_v<T, float>)) tvec4(const tvec4<U> &o) : x(T(o.x)), y(T(o.y)), z(T(o.z)), w(T(o.w)) {}
+	template <typename U> explicit tvec4(const tvec3<U> &v, T w_) requires(!std::is_same_v<U, T>) : x(T(v.x)), y(T(v.y)), z(T(v.z)), w(w_) {}
 	// GLSL's implicit conversion int -> uint, component-wise (an ivec4 passed where a uvec4 parameter is declared)
 	operator tvec4<uint32_t>() const requires std::is_same_v<T, int> { return tvec4<uint32_t>(uint32_t(x), uint32_t(y), uint32_t(z), uint32_t(w)); }
 	tvec4(const tvec4 &o) : x(o.x), y(o.y), z(o.z), w(o.w) {}
@@ -164,6 +171,7 @@ template <typename T, int N, int A, int B, int C> swz3<T, N, A, B, C, false> &sw
 template <typename T, int N, int A, int B, int C> swz3<T, N, A, B, C, true>::operator tvec3<T> &() { return *reinterpret_cast<tvec3<T> *>(&d[A]); }
 template <typename T, int N, int A, int B, int C> swz3<T, N, A, B, C, true>::operator const tvec3<T> &() const { return *reinterpret_cast<const tvec3<T> *>(&d[A]); }
 template <typename T, int N, int A, int B, int C> swz3<T, N, A, B, C, true> &swz3<T, N, A, B, C, true>::operator=(const tvec3<T> &v) { d[A] = v.x; d[B] = v.y; d[C] = v.z; return *this; }
+template <typename T, int N, int A, int B, int C> swz3<T, N, A, B, C, true>::operator tvec3<float>() const requires std::is_same_v<T, float16_t> { return tvec3<float>(float(d[A]), float(d[B]), float(d[C])); }
 template <typename T, int N, int A, int B, int C, int D> swz4<T, N, A, B, C, D>::operator tvec4<T>() const { return tvec4<T>(d[A], d[B], d[C], d[D]); }
 template <typename T, int N, int A, int B, int C, int D> swz4<T, N, A, B, C, D> &swz4<T, N, A, B, C, D>::operator=(const tvec4<T> &v)
 {
@@ -355,6 +363,7 @@ inline f16vec4 uint16BitsToHalf(const u16vec4 &a) { return f16vec4(uint16BitsToH
 	inline bool operator!=(const V &a, const V &b) { return !(a == b); }                                                          \
 	inline V operator>>(const V &a, int s) { V r; for (int i = 0; i < N; i++) r.d[i] = a.d[i] >> s; return r; }                   \
 	inline V operator<<(const V &a, int s) { V r; for (int i = 0; i < N; i++) r.d[i] = a.d[i] << s; return r; }                   \
+	inline V &operator>>=(V &a, int s) { for (int i = 0; i < N; i++) a.d[i] >>= s; return a; }                                    \
 	inline V operator&(const V &a, const V &b) { V r; for (int i = 0; i < N; i++) r.d[i] = a.d[i] & b.d[i]; return r; }          \
 	inline V operator|(const V &a, const V &b) { V r; for (int i = 0; i < N; i++) r.d[i] = a.d[i] | b.d[i]; return r; }          \
 	inline V operator&(const V &a, V::scalar s) { V r; for (int i = 0; i < N; i++) r.d[i] = a.d[i] & s; return r; }               \
@@ -517,6 +526,16 @@ struct mat3
 };
 inline vec3 operator*(const mat3 &m, const vec3 &v) { return m.c[0] * v.x + m.c[1] * v.y + m.c[2] * v.z; }
 
+// mat4x3: 4 columns of 3 components
+struct mat4x3
+{
+	vec3 c[4];
+	mat4x3() {}
+	vec3 &operator[](int i) { return c[i]; }
+	const vec3 &operator[](int i) const { return c[i]; }
+};
+inline vec3 operator*(const mat4x3 &m, const vec4 &v) { return m.c[0] * v.x + m.c[1] * v.y + m.c[2] * v.z + m.c[3] * v.w; }
+
 // mat3x4: 3 columns of 4 components; vec4 * mat3x4 = the three column dot products.
 struct mat3x4
 {
@@ -559,8 +578,13 @@ template <typename T> inline T subgroupBroadcastFirst(const T &v) { return v; }
 template <typename T> inline const T &nonuniformEXT(const T &v) { return v; }
 
 // ---- resources ------------------------------------------------------------------------------------------------------------
-enum class Format { RGBA16F, RGBA8_UNORM, RGBA8_SRGB, R32F, RG16F, RG8_UNORM, R8_UNORM, A2B10G10R10_UNORM, R16F, B10G11R11_UFLOAT };
+enum class Format { RGBA16F, RGBA8_UNORM, RGBA8_SRGB, R32F, RG16F, RG8_UNORM, R8_UNORM, A2B10G10R10_UNORM, R16F, B10G11R11_UFLOAT,
+                    R16_UNORM, RG16_UNORM, BGRA8_UNORM };
 enum class Filter { Linear, Nearest };
+struct sampler
+{
+	Filter filter = Filter::Linear;
+};
 
 struct Texture
 {
@@ -568,6 +592,7 @@ struct Texture
 	int w = 0, h = 0;
 	Format format = Format::RGBA16F;
 	Filter filter = Filter::Linear;
+	bool fetch_zero_outside = false; // texelFetch outside the image reads zero (robust image access) instead of clamping
 
 	vec4 texel(int x, int y) const
 	{
@@ -642,7 +667,19 @@ using subpassInput = Texture; // an input attachment: the texel under the fragme
 inline vec4 textureLod(const Texture &t, const vec2 &uv, float) { return t.sample(uv); }
 inline vec4 texture(const Texture &t, const vec2 &uv) { return t.sample(uv); }
 inline vec4 textureLodOffset(const Texture &t, const vec2 &uv, float, const ivec2 &o) { return t.sample(uv, o.x, o.y); }
-inline vec4 texelFetch(const Texture &t, const ivec2 &p, int) { return t.texel(p.x, p.y); }
+inline vec4 texelFetch(const Texture &t, const ivec2 &p, int)
+{
+	if (t.fetch_zero_outside && (p.x < 0 || p.y < 0 || p.x >= t.w || p.y >= t.h))
+		return vec4(0.0f);
+	return t.texel(p.x, p.y);
+}
+// sampler2D(texture, sampler): the texture filtered as the sampler says
+inline Texture combined_sampler(const Texture &t, const sampler &s)
+{
+	Texture r = t;
+	r.filter = s.filter;
+	return r;
+}
 // textureGather: the 2 x 2 footprint a bilinear fetch at uv would read, one component: (x, y, z, w) = texels
 // (i0, j0 + 1), (i0 + 1, j0 + 1), (i0 + 1, j0), (i0, j0) with (i0, j0) = floor(uv * size - 0.5); coordinates clamp per texel.
 inline vec4 textureGatherOffset(const Texture &t, const vec2 &uv, const ivec2 &o, int comp = 0)
@@ -702,6 +739,26 @@ inline void imageStore(Image &img, const ivec2 &p, const vec4 &v)
 	case Format::R8_UNORM:
 		static_cast<uint8_t *>(img.data)[i] = orc::float_to_unorm8(v.x);
 		break;
+	case Format::RG8_UNORM:
+		static_cast<uint8_t *>(img.data)[2 * i] = orc::float_to_unorm8(v.x);
+		static_cast<uint8_t *>(img.data)[2 * i + 1] = orc::float_to_unorm8(v.y);
+		break;
+	case Format::R16_UNORM:
+		static_cast<uint16_t *>(img.data)[i] = orc::float_to_unorm16(v.x);
+		break;
+	case Format::RG16_UNORM:
+		static_cast<uint16_t *>(img.data)[2 * i] = orc::float_to_unorm16(v.x);
+		static_cast<uint16_t *>(img.data)[2 * i + 1] = orc::float_to_unorm16(v.y);
+		break;
+	case Format::BGRA8_UNORM:
+	{
+		uint8_t *o = static_cast<uint8_t *>(img.data) + i * 4;
+		o[0] = orc::float_to_unorm8(v.z);
+		o[1] = orc::float_to_unorm8(v.y);
+		o[2] = orc::float_to_unorm8(v.x);
+		o[3] = orc::float_to_unorm8(v.w);
+		break;
+	}
 	default:
 		break;
 	}

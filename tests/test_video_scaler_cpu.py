@@ -113,8 +113,9 @@ def test_plan_primary_matrices_are_the_known_conversions():
     (K4, vr.RGBA8, [(3840, 2160, vr.R8)], S, S),                        # one plane must be RGBA8 / BGRA8
     (K4, vr.R8, nv12(*K4), S, S),                                        # input format
     (K4, vr.RGBA8, [], S, S),
+    ((1, 2), vr.RGBA8, nv12(1, 2), S, S),                               # one pixel wide: 4:2:0 chroma is as wide as the luma
 ], ids=["space_in", "space_out", "nv12_linear", "yuv_linear", "chroma_size", "chroma_depth", "plane3_size", "luma_alone",
-        "input_format", "no_planes"])
+        "input_format", "no_planes", "one_wide_420"])
 def test_plan_refuses_invalid_conversions(args):
     in_size, in_fmt, planes, src_space, dst_space = args
     assert capi.video_scale_plan(in_size, in_fmt, planes, src_space, dst_space) is None

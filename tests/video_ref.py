@@ -6,6 +6,9 @@ evaluates in float64 with the shader's fp16 weights, its fixed-point sample posi
 its vertical result (the two LDS tiles); the kernel evaluates in fp32 around the same fp16 points.  Out-of-frame input texels read as
 zero on the same-size path and are clamped to the edge when rescaling (CLAMP_COORD, or the LinearClamp sampler of the prefilter).
 """
+import ctypes as C
+import os
+
 import numpy as np
 
 PHASES, TAPS = 256, 8
@@ -250,15 +253,30 @@ def _dither(x, y):
     return DITHER_TABLE[y[:, None] & 3, x[None, :] & 3]
 
 
+def dither_probe():
+    """64 x 16 RGBA16F frame (scRGB, same size: no transfer, no conversion) whose every channel in column block j = x / 4 and row
+    block k = y / 4 holds (10 + k + (j + 0.5) / 16) / 255.  The one-plane store adds (n / 16 - 0.5) / 255, n the table entry at
+    (x & 3, y & 3), so the code is 10 + k + 1 exactly when n + j >= 16: 1/32 of a code from any midpoint, far beyond the fp16
+    input (2^-16 * 255 here) and every rounding after it.  Returns (data, expected codes (h, w, 4))."""
+    h, w = 16, 64
+    y, x = np.mgrid[0:h, 0:w]
+    j, k = x // 4, y // 4
+    v = (10 + k + (j + 0.5) / 16) / 255
+    data = np.repeat(v[..., None], 4, axis=-1).astype(np.float16).view(np.uint16)
+    codes = 10 + k + ((DITHER_TABLE[y & 3, x & 3] + 0.5) * 16 + j >= 16)
+    return data, np.repeat(codes[..., None], 4, axis=-1)
+
+
 def _codes(v, bits):
     scale = 255.0 if bits == 8 else 65535.0
     return np.floor(np.clip(v, 0.0, 1.0) * scale + 0.5).astype(np.int64)
 
 
-def video_scale(data, in_format, planes, in_space, out_space):
+def video_scale(data, in_format, planes, in_space, out_space, weights=None):
     """Expected output planes (integer codes) of gr_video_scale.  data: stored input texels (h, w, 4) uint8 / (h, w) uint32 /
-    (h, w, 4) fp16 bits; planes: [(w, h, format), ...].  Returns a list of arrays: (h, w) for Y / Cb / Cr, (h, w, 2) for
-    interleaved chroma, (h, w, 4) for RGBA/BGRA."""
+    (h, w, 4) fp16 bits; planes: [(w, h, format), ...]; weights: the filter's (2, 256, 8) fp16 table, by default
+    scaler_weights' for these sizes.  Returns a list of arrays: (h, w) for Y / Cb / Cr, (h, w, 2) for interleaved chroma, (h, w, 4)
+    for RGBA/BGRA."""
     rgba = decode_input(data, in_format)
     in_h, in_w = rgba.shape[:2]
     p = plan((in_w, in_h), in_format, planes, in_space, out_space)
@@ -269,7 +287,8 @@ def video_scale(data, in_format, planes, in_space, out_space):
         pad[:out_h, :out_w] = rgba
         px = _finish(p, _eotf(p, pad))
     else:
-        px = _finish(p, _rescaled(rgba, p, out_w, out_h, scaler_weights(in_w, in_h, out_w, out_h)))
+        weights = scaler_weights(in_w, in_h, out_w, out_h) if weights is None else weights
+        px = _finish(p, _rescaled(rgba, p, out_w, out_h, weights))
     ys, xs = np.arange(px.shape[0]), np.arange(px.shape[1])
     d = _dither(xs, ys) * float(p["dither_strength"])
     if len(planes) == 1:
@@ -296,3 +315,52 @@ def video_scale(data, in_format, planes, in_space, out_space):
     if len(planes) == 2:
         return [y, np.stack([cb, cr], axis=-1)]
     return [y, cb, cr]
+
+
+# ---- the reference's own shader, executed on the CPU -----------------------------------------------------------------------------
+REF_LIB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "libref_video.so")
+_ref_lib = None
+
+
+def shader_lib():
+    """oracle/_ref/libref_video.so (oracle/ref_build: scaler.comp run on the CPU by ref_video.cpp); skips the calling test when
+    it was not built, which needs the reference's sources."""
+    global _ref_lib
+    if _ref_lib is None:
+        if not os.path.exists(REF_LIB):
+            import pytest
+            pytest.skip("oracle/_ref/libref_video.so not built (needs the reference's sources)")
+        lib = C.CDLL(REF_LIB)
+        P = C.c_void_p
+        lib.ref_video_scale.restype = C.c_int
+        lib.ref_video_scale.argtypes = [P, C.c_int, C.c_int, C.c_int, C.c_int, P, P, P, P, C.c_int, C.c_int, C.c_int, P, P, P, P, P,
+                                        C.c_float, P]
+        _ref_lib = lib
+    return _ref_lib
+
+
+def shader_scale(data, in_format, planes, p, weights):
+    """Output planes of scaler.comp, executed, in video_scale's layout.  p: a plan (gr_video_scale_plan's, or plan() above);
+    weights: the (2, 256, 8) fp16 bits of the table the launch would use."""
+    lib = shader_lib()
+    data = np.ascontiguousarray(data)
+    in_h, in_w = data.shape[:2]
+    outs = []
+    for w, h, fmt in planes:
+        ch = 4 if fmt in (RGBA8, BGRA8, RGBA8_SRGB, BGRA8_SRGB) else 2 if fmt in (R8G8, R16G16) else 1
+        outs.append(np.zeros((h, w, ch) if ch > 1 else (h, w), np.uint16 if fmt in (R16, R16G16) else np.uint8))
+    n = len(planes)
+    ptrs = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+    ints = lambda v: np.ascontiguousarray(v, np.int32)
+    floats = lambda v: np.ascontiguousarray(v, np.float32)
+    pw, ph, pf = ints([q[0] for q in planes]), ints([q[1] for q in planes]), ints([q[2] for q in planes])
+    gst = floats(np.asarray(p["gamma_space_transform"], np.float32).reshape(3, 4))
+    prim = floats(np.asarray(p["primary_transform"], np.float32).T)  # column major
+    res, sti, inv = ints(p["resolution"]), floats(p["scaling_to_input"]), floats(p["inv_input_resolution"])
+    table = np.ascontiguousarray(weights, np.uint16)
+    ptr = lambda a: a.ctypes.data
+    rc = lib.ref_video_scale(ptr(data), in_w, in_h, in_format, n, C.cast(ptrs, C.c_void_p), ptr(pw), ptr(ph), ptr(pf), int(p["flags"]),
+                             int(p["eotf"]), int(p["oetf"]), ptr(gst), ptr(prim), ptr(res), ptr(sti), ptr(inv),
+                             float(p["dither_strength"]), ptr(table))
+    assert rc == 0, f"scaler.comp not built for CONTROL {p['flags']}, EOTF {p['eotf']}, OETF {p['oetf']}, {n} planes (VIDEO_VARIANTS)"
+    return [o.astype(np.int64) for o in outs]

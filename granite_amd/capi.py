@@ -131,6 +131,39 @@ class BloomPyramidArgs(C.Structure):
                 ("push_u2", PushBloomUpsample), ("push_u1", PushBloomUpsample), ("push_u0", PushBloomUpsample), ("push_luminance", PushLuminance)]
 
 
+# The push blocks of the bloom chain, filled as host/post/hdr.cpp fills them; `out` / `src` / `d3`: anything with a width and a height
+# (a DeviceImage, an Image descriptor).
+def threshold_push(out) -> PushBloomThreshold:
+    return PushBloomThreshold((out.width, out.height), (1.0 / out.width, 1.0 / out.height))
+
+
+def downsample_push(out, src, lerp: float = 0.0) -> PushBloomDownsample:
+    return PushBloomDownsample((out.width, out.height), (1.0 / out.width, 1.0 / out.height), (1.0 / src.width, 1.0 / src.height), lerp)
+
+
+def upsample_push(out, src) -> PushBloomUpsample:
+    return PushBloomUpsample((out.width, out.height), (1.0 / out.width, 1.0 / out.height), (1.0 / src.width, 1.0 / src.height))
+
+
+def luminance_push(d3, lerp: float, min_loglum: float = -3.0, max_loglum: float = 2.0) -> PushLuminance:
+    return PushLuminance((d3.width // 2, d3.height // 2), lerp, min_loglum, max_loglum)
+
+
+def pyramid_args(hdr: Image, levels: dict, history: Image, feedback_lerp: float, lum_ptr=None, lum_lerp: float = 0.0) -> BloomPyramidArgs:
+    """gr_bloom_pyramid's argument block from the Image descriptors of the frame (levels: threshold, d0..d3, u2..u0 by name)."""
+    l, a = levels, BloomPyramidArgs()
+    a.hdr, a.history, a.lum = hdr, history, lum_ptr
+    for name in ("threshold", "d0", "d1", "d2", "d3", "u2", "u1", "u0"):
+        setattr(a, name, l[name])
+    a.push_threshold = threshold_push(l["threshold"])
+    a.push_d0, a.push_d1 = downsample_push(l["d0"], l["threshold"]), downsample_push(l["d1"], l["d0"])
+    a.push_d2, a.push_d3 = downsample_push(l["d2"], l["d1"], feedback_lerp), downsample_push(l["d3"], l["d2"], feedback_lerp)
+    a.push_u2, a.push_u1, a.push_u0 = upsample_push(l["u2"], l["d3"]), upsample_push(l["u1"], l["u2"]), upsample_push(l["u0"], l["u1"])
+    if lum_ptr is not None:
+        a.push_luminance = luminance_push(l["d3"], lum_lerp)
+    return a
+
+
 class PushTonemap(C.Structure):
     _fields_ = [("dynamic_exposure", C.c_float)]
 
@@ -533,43 +566,32 @@ class Context:
         return None if rows is None else C.byref(Rows(int(rows[0]), int(rows[1])))
 
     def bloom_threshold(self, hdr: DeviceImage, out: DeviceImage, lum_ptr=None, stream=None, rows=None):
-        push = PushBloomThreshold((out.width, out.height), (1.0 / out.width, 1.0 / out.height))
-        self.check(self.lib.gr_bloom_threshold_rows(self.handle, stream, hdr.desc, out.desc, lum_ptr, push, self._rows(rows)))
+        self.check(self.lib.gr_bloom_threshold_rows(self.handle, stream, hdr.desc, out.desc, lum_ptr, threshold_push(out), self._rows(rows)))
 
     def bloom_downsample(self, src: DeviceImage, out: DeviceImage, history: Optional[DeviceImage] = None, lerp: float = 0.0,
                          stream=None, rows=None):
-        push = PushBloomDownsample((out.width, out.height), (1.0 / out.width, 1.0 / out.height),
-                                   (1.0 / src.width, 1.0 / src.height), lerp)
         self.check(self.lib.gr_bloom_downsample_rows(self.handle, stream, src.desc, out.desc,
-                                                     history.desc if history is not None else None, push, self._rows(rows)))
+                                                     history.desc if history is not None else None, downsample_push(out, src, lerp), self._rows(rows)))
 
     def bloom_upsample(self, src: DeviceImage, out: DeviceImage, stream=None, rows=None):
-        push = PushBloomUpsample((out.width, out.height), (1.0 / out.width, 1.0 / out.height),
-                                 (1.0 / src.width, 1.0 / src.height))
-        self.check(self.lib.gr_bloom_upsample_rows(self.handle, stream, src.desc, out.desc, push, self._rows(rows)))
+        self.check(self.lib.gr_bloom_upsample_rows(self.handle, stream, src.desc, out.desc, upsample_push(out, src), self._rows(rows)))
 
     def bloom_tail(self, d1: DeviceImage, d2: DeviceImage, d3: DeviceImage, history: DeviceImage, u2: DeviceImage, u1: DeviceImage,
                    feedback_lerp: float, lum_ptr=None, lum_lerp: float = 0.0, stream=None) -> bool:
         """downsample-2, downsample-3 (+ feedback), luminance, upsample-2, upsample-1 as the two fused launches; False (nothing
         launched) when the pyramid does not qualify."""
-        def down(out, src):
-            return PushBloomDownsample((out.width, out.height), (1.0 / out.width, 1.0 / out.height), (1.0 / src.width, 1.0 / src.height), feedback_lerp)
-
-        def up(out, src):
-            return PushBloomUpsample((out.width, out.height), (1.0 / out.width, 1.0 / out.height), (1.0 / src.width, 1.0 / src.height))
-        p_d2, p_d3, p_u2, p_u1 = down(d2, d1), down(d3, d2), up(u2, d3), up(u1, u2)
+        p_d2, p_d3 = downsample_push(d2, d1, feedback_lerp), downsample_push(d3, d2, feedback_lerp)
+        p_u2, p_u1 = upsample_push(u2, d3), upsample_push(u1, u2)
         if not self.lib.gr_bloom_tail_supported(d1.desc, d2.desc, d3.desc, u2.desc, u1.desc, p_d2, p_d3, p_u2, p_u1):
             return False
         self.check(self.lib.gr_bloom_down_tail(self.handle, stream, d1.desc, d2.desc, d3.desc, history.desc, p_d2, p_d3))
-        p_lum = PushLuminance((d3.width // 2, d3.height // 2), lum_lerp, -3.0, 2.0) if lum_ptr is not None else None
+        p_lum = luminance_push(d3, lum_lerp) if lum_ptr is not None else None
         self.check(self.lib.gr_bloom_up_tail(self.handle, stream, d3.desc, u2.desc, u1.desc, lum_ptr, p_u2, p_u1, p_lum))
         return True
 
     def bloom_down_mid(self, threshold: DeviceImage, d0: DeviceImage, d1: DeviceImage, stream=None, rows=None) -> bool:
         """downsample-0 and downsample-1 as one launch (rows restricts downsample-1); False (nothing launched) when the levels do not qualify."""
-        def down(out, src):
-            return PushBloomDownsample((out.width, out.height), (1.0 / out.width, 1.0 / out.height), (1.0 / src.width, 1.0 / src.height), 0.0)
-        p_d0, p_d1 = down(d0, threshold), down(d1, d0)
+        p_d0, p_d1 = downsample_push(d0, threshold), downsample_push(d1, d0)
         if not self.lib.gr_bloom_down_mid_supported(threshold.desc, d0.desc, d1.desc, p_d0, p_d1):
             return False
         self.check(self.lib.gr_bloom_down_mid(self.handle, stream, threshold.desc, d0.desc, d1.desc, p_d0, p_d1, self._rows(rows)))
@@ -578,12 +600,10 @@ class Context:
     def bloom_up_all(self, d3: DeviceImage, u2: DeviceImage, u1: DeviceImage, u0: DeviceImage, lum_ptr=None, lum_lerp: float = 0.0, stream=None,
                      busy_frame: bool = False) -> bool:
         """luminance, upsample-2, upsample-1 and upsample-0 as one launch; False (nothing launched) when the frame does not qualify."""
-        def up(out, src):
-            return PushBloomUpsample((out.width, out.height), (1.0 / out.width, 1.0 / out.height), (1.0 / src.width, 1.0 / src.height))
-        p_u2, p_u1, p_u0 = up(u2, d3), up(u1, u2), up(u0, u1)
+        p_u2, p_u1, p_u0 = upsample_push(u2, d3), upsample_push(u1, u2), upsample_push(u0, u1)
         if not self.lib.gr_bloom_up_all_supported(d3.desc, u2.desc, u1.desc, u0.desc, p_u2, p_u1, p_u0):
             return False
-        p_lum = PushLuminance((d3.width // 2, d3.height // 2), lum_lerp, -3.0, 2.0) if lum_ptr is not None else None
+        p_lum = luminance_push(d3, lum_lerp) if lum_ptr is not None else None
         self.check(self.lib.gr_bloom_up_all(self.handle, stream, d3.desc, u2.desc, u1.desc, u0.desc, lum_ptr, p_u2, p_u1, p_u0, p_lum, 1 if busy_frame else 0))
         return True
 
@@ -591,23 +611,7 @@ class Context:
                       any_size: bool = False) -> bool:
         """The whole bloom pass as ONE launch (levels: threshold, d0..d3, u2..u0 by name); False (nothing launched) when the frame does not qualify.
         any_size: launch without asking gr_bloom_pyramid_supported (which offers the launch up to 640 x 384 frames; the launcher checks the rest itself)."""
-        def down(out, src, lerp=0.0):
-            return PushBloomDownsample((out.width, out.height), (1.0 / out.width, 1.0 / out.height), (1.0 / src.width, 1.0 / src.height), lerp)
-
-        def up(out, src):
-            return PushBloomUpsample((out.width, out.height), (1.0 / out.width, 1.0 / out.height), (1.0 / src.width, 1.0 / src.height))
-        l = levels
-        a = BloomPyramidArgs()
-        a.hdr, a.history = hdr.desc, history.desc
-        for name in ("threshold", "d0", "d1", "d2", "d3", "u2", "u1", "u0"):
-            setattr(a, name, l[name].desc)
-        a.lum = lum_ptr
-        a.push_threshold = PushBloomThreshold((l["threshold"].width, l["threshold"].height), (1.0 / l["threshold"].width, 1.0 / l["threshold"].height))
-        a.push_d0, a.push_d1 = down(l["d0"], l["threshold"]), down(l["d1"], l["d0"])
-        a.push_d2, a.push_d3 = down(l["d2"], l["d1"], feedback_lerp), down(l["d3"], l["d2"], feedback_lerp)
-        a.push_u2, a.push_u1, a.push_u0 = up(l["u2"], l["d3"]), up(l["u1"], l["u2"]), up(l["u0"], l["u1"])
-        if lum_ptr is not None:
-            a.push_luminance = PushLuminance((l["d3"].width // 2, l["d3"].height // 2), lum_lerp, -3.0, 2.0)
+        a = pyramid_args(hdr.desc, {name: image.desc for name, image in levels.items()}, history.desc, feedback_lerp, lum_ptr, lum_lerp)
         if not any_size and not self.lib.gr_bloom_pyramid_supported(a):
             return False
         self.check(self.lib.gr_bloom_pyramid(self.handle, stream, a))
@@ -620,18 +624,14 @@ class Context:
 
     def bloom_down_head(self, hdr: DeviceImage, threshold: DeviceImage, d0: DeviceImage, d1: DeviceImage, lum_ptr=None, stream=None) -> bool:
         """threshold, downsample-0 and downsample-1 as one launch; False (nothing launched) when the frame does not qualify."""
-        def down(out, src):
-            return PushBloomDownsample((out.width, out.height), (1.0 / out.width, 1.0 / out.height), (1.0 / src.width, 1.0 / src.height), 0.0)
-        p_t = PushBloomThreshold((threshold.width, threshold.height), (1.0 / threshold.width, 1.0 / threshold.height))
-        p_d0, p_d1 = down(d0, threshold), down(d1, d0)
+        p_t, p_d0, p_d1 = threshold_push(threshold), downsample_push(d0, threshold), downsample_push(d1, d0)
         if not self.lib.gr_bloom_down_head_supported(hdr.desc, threshold.desc, d0.desc, d1.desc, p_t, p_d0, p_d1):
             return False
         self.check(self.lib.gr_bloom_down_head(self.handle, stream, hdr.desc, threshold.desc, d0.desc, d1.desc, lum_ptr, p_t, p_d0, p_d1))
         return True
 
     def luminance(self, d3: DeviceImage, lum_ptr, lerp: float, min_loglum: float = -3.0, max_loglum: float = 2.0, stream=None):
-        push = PushLuminance((d3.width // 2, d3.height // 2), lerp, min_loglum, max_loglum)
-        self.check(self.lib.gr_luminance(self.handle, stream, d3.desc, lum_ptr, push))
+        self.check(self.lib.gr_luminance(self.handle, stream, d3.desc, lum_ptr, luminance_push(d3, lerp, min_loglum, max_loglum)))
 
     def tonemap(self, hdr: DeviceImage, bloom: DeviceImage, out: DeviceImage, lum_ptr=None, dynamic_exposure: float = 1.0,
                 stream=None, rows=None):

@@ -10,9 +10,52 @@ namespace Granite
 {
 namespace
 {
-const gr_luminance_data *luminance_ptr(RenderGraph &graph, const RenderBufferResource *res)
+gr_luminance_data *luminance_ptr(RenderGraph &graph, const RenderBufferResource *res)
 {
-	return res ? static_cast<const gr_luminance_data *>(graph.get_physical_buffer_resource(*res).get_device_pointer()) : nullptr;
+	return res ? static_cast<gr_luminance_data *>(graph.get_physical_buffer_resource(*res).get_device_pointer()) : nullptr;
+}
+
+// The push blocks of the chain, each filled here and nowhere else.  The kernel library picks the constant-weight stencils where these
+// floats equal the reciprocals of the sizes to the bit (downsample_is_exact / upsample_is_exact, post.hip): the expressions are part of that.
+template <typename Push> Push output_push(HIP::ImageView &output)
+{
+	Push push = {};
+	push.threads[0] = output.get_width();
+	push.threads[1] = output.get_height();
+	push.inv_output_size[0] = 1.0f / float(push.threads[0]);
+	push.inv_output_size[1] = 1.0f / float(push.threads[1]);
+	return push;
+}
+
+gr_push_bloom_threshold threshold_push(HIP::ImageView &output) { return output_push<gr_push_bloom_threshold>(output); }
+
+gr_push_bloom_upsample upsample_push(HIP::ImageView &output, HIP::ImageView &input)
+{
+	auto push = output_push<gr_push_bloom_upsample>(output);
+	push.inv_input_size[0] = 1.0f / float(input.get_width());
+	push.inv_input_size[1] = 1.0f / float(input.get_height());
+	return push;
+}
+
+gr_push_bloom_downsample downsample_push(const FrameParameters &frame, HIP::ImageView &output, HIP::ImageView &input)
+{
+	auto push = output_push<gr_push_bloom_downsample>(output);
+	push.inv_input_size[0] = 1.0f / float(input.get_width());
+	push.inv_input_size[1] = 1.0f / float(input.get_height());
+	push.lerp = float(1.0 - std::pow(0.001, frame.frame_time)); // the temporal feedback of downsample-3 (read only where a history is bound)
+	return push;
+}
+
+// the reduction walks downsample-3 in 2 x 2 boxes; the exposure follows the scene with a half-life of a second, log-luminance held to [-3, 2]
+gr_push_luminance luminance_push(const FrameParameters &frame, HIP::ImageView &d3)
+{
+	gr_push_luminance push = {};
+	push.size[0] = d3.get_width() / 2;
+	push.size[1] = d3.get_height() / 2;
+	push.lerp = float(1.0 - std::pow(0.5, frame.frame_time));
+	push.min_loglum = -3.0f;
+	push.max_loglum = 2.0f;
+	return push;
 }
 
 // luminance_build_compute / luminance_build_render_pass (hdr.cpp:35-98)
@@ -20,16 +63,8 @@ void record_luminance(HIP::CommandBuffer &cmd, const FrameParameters &frame, Ren
                       const RenderTextureResource &d3)
 {
 	auto &input = graph.get_physical_texture_resource(d3);
-	auto &output = graph.get_physical_buffer_resource(lum);
-	gr_push_luminance push = {};
-	push.size[0] = input.get_width() / 2;
-	push.size[1] = input.get_height() / 2;
-	push.lerp = float(1.0 - std::pow(0.5, frame.frame_time));
-	push.min_loglum = -3.0f;
-	push.max_loglum = 2.0f;
-	cmd.check(gr_luminance(cmd.get_context(), cmd.get_stream(), &input.get_view(),
-	                       static_cast<gr_luminance_data *>(output.get_device_pointer()), &push),
-	          "luminance");
+	const gr_push_luminance push = luminance_push(frame, input);
+	cmd.check(gr_luminance(cmd.get_context(), cmd.get_stream(), &input.get_view(), luminance_ptr(graph, &lum), &push), "luminance");
 }
 
 // bloom_threshold_build_compute / _render_pass (hdr.cpp:100-144)
@@ -41,11 +76,7 @@ void record_threshold(HIP::CommandBuffer &cmd, RenderGraph &graph, const RenderT
 		return;
 	auto &output = graph.get_physical_texture_resource(threshold);
 	auto &input = graph.get_physical_texture_resource(hdr);
-	gr_push_bloom_threshold push = {};
-	push.threads[0] = output.get_width();
-	push.threads[1] = output.get_height();
-	push.inv_output_size[0] = 1.0f / float(push.threads[0]);
-	push.inv_output_size[1] = 1.0f / float(push.threads[1]);
+	const gr_push_bloom_threshold push = threshold_push(output);
 	cmd.check(gr_bloom_threshold_rows(cmd.get_context(), cmd.get_stream(), &input.get_view(), &output.get_view(), luminance_ptr(graph, ubo),
 	                                  &push, &rows),
 	          "bloom_threshold");
@@ -61,15 +92,7 @@ void record_downsample(HIP::CommandBuffer &cmd, const FrameParameters &frame, Re
 	auto &output = graph.get_physical_texture_resource(output_res);
 	auto &input = graph.get_physical_texture_resource(input_res);
 	HIP::ImageView *history = feedback ? graph.get_physical_history_texture_resource(*feedback) : nullptr; // null on frame 0
-
-	gr_push_bloom_downsample push = {};
-	push.threads[0] = output.get_width();
-	push.threads[1] = output.get_height();
-	push.inv_output_size[0] = 1.0f / float(push.threads[0]);
-	push.inv_output_size[1] = 1.0f / float(push.threads[1]);
-	push.inv_input_size[0] = 1.0f / float(input.get_width());
-	push.inv_input_size[1] = 1.0f / float(input.get_height());
-	push.lerp = float(1.0 - std::pow(0.001, frame.frame_time));
+	const gr_push_bloom_downsample push = downsample_push(frame, output, input);
 	cmd.check(gr_bloom_downsample_rows(cmd.get_context(), cmd.get_stream(), &input.get_view(), &output.get_view(),
 	                                   history ? &history->get_view() : nullptr, &push, &rows),
 	          "bloom_downsample");
@@ -84,184 +107,102 @@ void record_upsample(HIP::CommandBuffer &cmd, RenderGraph &graph, const RenderTe
 		return;
 	auto &output = graph.get_physical_texture_resource(output_res);
 	auto &input = graph.get_physical_texture_resource(input_res);
-	gr_push_bloom_upsample push = {};
-	push.threads[0] = output.get_width();
-	push.threads[1] = output.get_height();
-	push.inv_output_size[0] = 1.0f / float(push.threads[0]);
-	push.inv_output_size[1] = 1.0f / float(push.threads[1]);
-	push.inv_input_size[0] = 1.0f / float(input.get_width());
-	push.inv_input_size[1] = 1.0f / float(input.get_height());
+	const gr_push_bloom_upsample push = upsample_push(output, input);
 	cmd.check(gr_bloom_upsample_rows(cmd.get_context(), cmd.get_stream(), &input.get_view(), &output.get_view(), &push, &rows),
 	          "bloom_upsample");
 }
 
-gr_push_bloom_downsample downsample_push(const FrameParameters &frame, HIP::ImageView &output, HIP::ImageView &input)
+// What the fused launches of the bloom-compute pass work on: the frame, the eight levels, last frame's downsample-3 (null on frame 0) and the
+// exposure buffer (null without dynamic exposure).
+struct BloomImages
 {
-	gr_push_bloom_downsample push = {};
-	push.threads[0] = output.get_width();
-	push.threads[1] = output.get_height();
-	push.inv_output_size[0] = 1.0f / float(push.threads[0]);
-	push.inv_output_size[1] = 1.0f / float(push.threads[1]);
-	push.inv_input_size[0] = 1.0f / float(input.get_width());
-	push.inv_input_size[1] = 1.0f / float(input.get_height());
-	push.lerp = float(1.0 - std::pow(0.001, frame.frame_time));
-	return push;
-}
-
-gr_push_bloom_upsample upsample_push(HIP::ImageView &output, HIP::ImageView &input)
-{
-	gr_push_bloom_upsample push = {};
-	push.threads[0] = output.get_width();
-	push.threads[1] = output.get_height();
-	push.inv_output_size[0] = 1.0f / float(push.threads[0]);
-	push.inv_output_size[1] = 1.0f / float(push.threads[1]);
-	push.inv_input_size[0] = 1.0f / float(input.get_width());
-	push.inv_input_size[1] = 1.0f / float(input.get_height());
-	return push;
-}
+	HIP::ImageView &hdr, &t, &d0, &d1, &d2, &d3, &u2, &u1, &u0;
+	HIP::ImageView *history;
+	gr_luminance_data *lum;
+};
 
 // The dispatches hdr.cpp:364-377 records for downsample-2, downsample-3, the luminance reduction, upsample-2 and upsample-1,
 // as the two fused launches of the C ABI when the pyramid qualifies (gr_bloom_tail_supported); returns false otherwise and
 // records nothing.  Same values in every level either way.
-// u0_res (whole-image frames only): upsample-0 joins the second launch when the frame qualifies (gr_bloom_up_all_supported); *u0_done says
+// with_u0 (whole-image frames only): upsample-0 joins the second launch when the frame qualifies (gr_bloom_up_all_supported); u0_done says
 // whether it did.
-bool record_pyramid_tail(HIP::CommandBuffer &cmd, const FrameParameters &frame, RenderGraph &graph, const RenderTextureResource &d1_res,
-                         const RenderTextureResource &d2_res, const RenderTextureResource &d3_res, const RenderTextureResource &u2_res,
-                         const RenderTextureResource &u1_res, const RenderBufferResource *lum_res, const RenderTextureResource *u0_res = nullptr,
-                         bool *u0_done = nullptr, bool busy_frame = false)
+bool record_pyramid_tail(HIP::CommandBuffer &cmd, const FrameParameters &frame, const BloomImages &im, bool with_u0, bool &u0_done, bool busy_frame)
 {
-	if (u0_done)
-		*u0_done = false;
-	auto &d1 = graph.get_physical_texture_resource(d1_res);
-	auto &d2 = graph.get_physical_texture_resource(d2_res);
-	auto &d3 = graph.get_physical_texture_resource(d3_res);
-	auto &u2 = graph.get_physical_texture_resource(u2_res);
-	auto &u1 = graph.get_physical_texture_resource(u1_res);
-	HIP::ImageView *history = graph.get_physical_history_texture_resource(d3_res); // null on frame 0
-	if (!history)
+	u0_done = false;
+	if (!im.history)
 		return false;
-	const gr_push_bloom_downsample push_d2 = downsample_push(frame, d2, d1), push_d3 = downsample_push(frame, d3, d2);
-	const gr_push_bloom_upsample push_u2 = upsample_push(u2, d3), push_u1 = upsample_push(u1, u2);
-	if (!gr_bloom_tail_supported(&d1.get_view(), &d2.get_view(), &d3.get_view(), &u2.get_view(), &u1.get_view(), &push_d2, &push_d3, &push_u2, &push_u1))
+	const gr_push_bloom_downsample push_d2 = downsample_push(frame, im.d2, im.d1), push_d3 = downsample_push(frame, im.d3, im.d2);
+	const gr_push_bloom_upsample push_u2 = upsample_push(im.u2, im.d3), push_u1 = upsample_push(im.u1, im.u2);
+	const gr_image *d1 = &im.d1.get_view(), *d2 = &im.d2.get_view(), *d3 = &im.d3.get_view(), *u2 = &im.u2.get_view(), *u1 = &im.u1.get_view();
+	if (!gr_bloom_tail_supported(d1, d2, d3, u2, u1, &push_d2, &push_d3, &push_u2, &push_u1))
 		return false;
-	cmd.check(gr_bloom_down_tail(cmd.get_context(), cmd.get_stream(), &d1.get_view(), &d2.get_view(), &d3.get_view(), &history->get_view(), &push_d2,
-	                             &push_d3),
-	          "bloom_down_tail");
+	cmd.check(gr_bloom_down_tail(cmd.get_context(), cmd.get_stream(), d1, d2, d3, &im.history->get_view(), &push_d2, &push_d3), "bloom_down_tail");
 	cmd.barrier(VK_PIPELINE_STAGE_COMPUTE_SHADER_BIT, VK_ACCESS_2_SHADER_STORAGE_WRITE_BIT, VK_PIPELINE_STAGE_COMPUTE_SHADER_BIT,
 	            VK_ACCESS_2_SHADER_SAMPLED_READ_BIT);
-	gr_push_luminance push_lum = {};
-	gr_luminance_data *lum = nullptr;
-	if (lum_res)
+	const gr_push_luminance push_lum = luminance_push(frame, im.d3);
+	if (with_u0)
 	{
-		push_lum.size[0] = d3.get_width() / 2;
-		push_lum.size[1] = d3.get_height() / 2;
-		push_lum.lerp = float(1.0 - std::pow(0.5, frame.frame_time));
-		push_lum.min_loglum = -3.0f;
-		push_lum.max_loglum = 2.0f;
-		lum = static_cast<gr_luminance_data *>(graph.get_physical_buffer_resource(*lum_res).get_device_pointer());
-	}
-	if (u0_res)
-	{
-		auto &u0 = graph.get_physical_texture_resource(*u0_res);
-		const gr_push_bloom_upsample push_u0 = upsample_push(u0, u1);
-		if (gr_bloom_up_all_supported(&d3.get_view(), &u2.get_view(), &u1.get_view(), &u0.get_view(), &push_u2, &push_u1, &push_u0))
+		const gr_push_bloom_upsample push_u0 = upsample_push(im.u0, im.u1);
+		if (gr_bloom_up_all_supported(d3, u2, u1, &im.u0.get_view(), &push_u2, &push_u1, &push_u0))
 		{
-			cmd.check(gr_bloom_up_all(cmd.get_context(), cmd.get_stream(), &d3.get_view(), &u2.get_view(), &u1.get_view(), &u0.get_view(), lum, &push_u2,
-			                          &push_u1, &push_u0, lum ? &push_lum : nullptr, busy_frame ? GR_BLOOM_BUSY_FRAME_BIT : 0u),
+			cmd.check(gr_bloom_up_all(cmd.get_context(), cmd.get_stream(), d3, u2, u1, &im.u0.get_view(), im.lum, &push_u2, &push_u1, &push_u0,
+			                          im.lum ? &push_lum : nullptr, busy_frame ? GR_BLOOM_BUSY_FRAME_BIT : 0u),
 			          "bloom_up_all");
-			if (u0_done)
-				*u0_done = true;
+			u0_done = true;
 			return true;
 		}
 	}
-	cmd.check(gr_bloom_up_tail(cmd.get_context(), cmd.get_stream(), &d3.get_view(), &u2.get_view(), &u1.get_view(), lum, &push_u2, &push_u1,
-	                           lum ? &push_lum : nullptr),
+	cmd.check(gr_bloom_up_tail(cmd.get_context(), cmd.get_stream(), d3, u2, u1, im.lum, &push_u2, &push_u1, im.lum ? &push_lum : nullptr),
 	          "bloom_up_tail");
 	return true;
 }
 
-// The dispatches of downsample-0 and downsample-1 (hdr.cpp:358-362) as one fused launch of the C ABI when the levels qualify; returns
-// false otherwise and records nothing.  Under row bands the launch is restricted to this rank's rows of downsample-1; downsample-0
-// is written under their taps (StripPlan::d0 is that footprint).
-bool record_pyramid_middle(HIP::CommandBuffer &cmd, const FrameParameters &frame, RenderGraph &graph, const RenderTextureResource &t_res,
-                           const RenderTextureResource &d0_res, const RenderTextureResource &d1_res, const RowRange *rows_d1)
+// The dispatches of downsample-0 and downsample-1 (hdr.cpp:358-362) as one fused launch of the C ABI when the levels qualify
+// (gr_bloom_down_mid_supported); returns false otherwise and records nothing.  Under row bands the launch is restricted to this rank's rows
+// of downsample-1; downsample-0 is written under their taps (StripPlan::d0 is that footprint).
+bool record_pyramid_middle(HIP::CommandBuffer &cmd, const FrameParameters &frame, const BloomImages &im, const RowRange *rows_d1)
 {
-	auto &t = graph.get_physical_texture_resource(t_res);
-	auto &d0 = graph.get_physical_texture_resource(d0_res);
-	auto &d1 = graph.get_physical_texture_resource(d1_res);
-	const gr_push_bloom_downsample push_d0 = downsample_push(frame, d0, t), push_d1 = downsample_push(frame, d1, d0);
-	if (!gr_bloom_down_mid_supported(&t.get_view(), &d0.get_view(), &d1.get_view(), &push_d0, &push_d1))
+	const gr_push_bloom_downsample push_d0 = downsample_push(frame, im.d0, im.t), push_d1 = downsample_push(frame, im.d1, im.d0);
+	if (!gr_bloom_down_mid_supported(&im.t.get_view(), &im.d0.get_view(), &im.d1.get_view(), &push_d0, &push_d1))
 		return false;
 	gr_rows rows;
 	if (to_rows(rows_d1, rows))
-		cmd.check(gr_bloom_down_mid(cmd.get_context(), cmd.get_stream(), &t.get_view(), &d0.get_view(), &d1.get_view(), &push_d0, &push_d1, &rows),
+		cmd.check(gr_bloom_down_mid(cmd.get_context(), cmd.get_stream(), &im.t.get_view(), &im.d0.get_view(), &im.d1.get_view(), &push_d0, &push_d1, &rows),
 		          "bloom_down_mid");
 	return true;
 }
 
 // The threshold dispatch and the dispatches of downsample-0 and downsample-1 (hdr.cpp:354-362) as ONE fused launch of the C ABI when the
-// frame qualifies (gr_bloom_down_head_supported: every level exactly half of its input, up to 1440p); returns false otherwise and
-// records nothing.  Whole images only: row bands keep the band-limited launches.
-bool record_pyramid_head(HIP::CommandBuffer &cmd, const FrameParameters &frame, RenderGraph &graph, const RenderTextureResource &hdr_res,
-                         const RenderTextureResource &t_res, const RenderTextureResource &d0_res, const RenderTextureResource &d1_res,
-                         const RenderBufferResource *ubo)
+// frame qualifies (gr_bloom_down_head_supported); returns false otherwise and records nothing.  Whole images only: row bands keep the
+// band-limited launches.
+bool record_pyramid_head(HIP::CommandBuffer &cmd, const FrameParameters &frame, const BloomImages &im)
 {
-	auto &hdr = graph.get_physical_texture_resource(hdr_res);
-	auto &t = graph.get_physical_texture_resource(t_res);
-	auto &d0 = graph.get_physical_texture_resource(d0_res);
-	auto &d1 = graph.get_physical_texture_resource(d1_res);
-	gr_push_bloom_threshold push_t = {};
-	push_t.threads[0] = t.get_width();
-	push_t.threads[1] = t.get_height();
-	push_t.inv_output_size[0] = 1.0f / float(push_t.threads[0]);
-	push_t.inv_output_size[1] = 1.0f / float(push_t.threads[1]);
-	const gr_push_bloom_downsample push_d0 = downsample_push(frame, d0, t), push_d1 = downsample_push(frame, d1, d0);
-	if (!gr_bloom_down_head_supported(&hdr.get_view(), &t.get_view(), &d0.get_view(), &d1.get_view(), &push_t, &push_d0, &push_d1))
+	const gr_push_bloom_threshold push_t = threshold_push(im.t);
+	const gr_push_bloom_downsample push_d0 = downsample_push(frame, im.d0, im.t), push_d1 = downsample_push(frame, im.d1, im.d0);
+	if (!gr_bloom_down_head_supported(&im.hdr.get_view(), &im.t.get_view(), &im.d0.get_view(), &im.d1.get_view(), &push_t, &push_d0, &push_d1))
 		return false;
-	cmd.check(gr_bloom_down_head(cmd.get_context(), cmd.get_stream(), &hdr.get_view(), &t.get_view(), &d0.get_view(), &d1.get_view(),
-	                             luminance_ptr(graph, ubo), &push_t, &push_d0, &push_d1),
+	cmd.check(gr_bloom_down_head(cmd.get_context(), cmd.get_stream(), &im.hdr.get_view(), &im.t.get_view(), &im.d0.get_view(), &im.d1.get_view(), im.lum,
+	                             &push_t, &push_d0, &push_d1),
 	          "bloom_down_head");
 	return true;
 }
 
-// Every dispatch of the pass (hdr.cpp:354-379) as ONE launch of the C ABI when the frame qualifies (gr_bloom_pyramid_supported: what the fused
-// head, tail and upsample launches require, up to a 640 x 384 frame); returns false otherwise and records nothing.  Whole images only.
-bool record_pyramid_whole(HIP::CommandBuffer &cmd, const FrameParameters &frame, RenderGraph &graph, const RenderTextureResource &hdr_res,
-                          const RenderTextureResource &t_res, const RenderTextureResource &d0_res, const RenderTextureResource &d1_res,
-                          const RenderTextureResource &d2_res, const RenderTextureResource &d3_res, const RenderTextureResource &u2_res,
-                          const RenderTextureResource &u1_res, const RenderTextureResource &u0_res, const RenderBufferResource *lum_res)
+// Every dispatch of the pass (hdr.cpp:354-379) as ONE launch of the C ABI when the frame qualifies (gr_bloom_pyramid_supported); returns
+// false otherwise and records nothing.  Whole images only.
+bool record_pyramid_whole(HIP::CommandBuffer &cmd, const FrameParameters &frame, const BloomImages &im)
 {
-	HIP::ImageView *history = graph.get_physical_history_texture_resource(d3_res); // null on frame 0
-	if (!history)
+	if (!im.history)
 		return false;
-	auto &hdr = graph.get_physical_texture_resource(hdr_res);
-	auto &t = graph.get_physical_texture_resource(t_res);
-	auto &d0 = graph.get_physical_texture_resource(d0_res);
-	auto &d1 = graph.get_physical_texture_resource(d1_res);
-	auto &d2 = graph.get_physical_texture_resource(d2_res);
-	auto &d3 = graph.get_physical_texture_resource(d3_res);
-	auto &u2 = graph.get_physical_texture_resource(u2_res);
-	auto &u1 = graph.get_physical_texture_resource(u1_res);
-	auto &u0 = graph.get_physical_texture_resource(u0_res);
 	gr_bloom_pyramid_args a = {};
-	a.hdr = hdr.get_view(), a.threshold = t.get_view(), a.d0 = d0.get_view(), a.d1 = d1.get_view(), a.d2 = d2.get_view(), a.d3 = d3.get_view();
-	a.history = history->get_view(), a.u2 = u2.get_view(), a.u1 = u1.get_view(), a.u0 = u0.get_view();
-	a.push_threshold.threads[0] = t.get_width();
-	a.push_threshold.threads[1] = t.get_height();
-	a.push_threshold.inv_output_size[0] = 1.0f / float(a.push_threshold.threads[0]);
-	a.push_threshold.inv_output_size[1] = 1.0f / float(a.push_threshold.threads[1]);
-	a.push_d0 = downsample_push(frame, d0, t), a.push_d1 = downsample_push(frame, d1, d0);
-	a.push_d2 = downsample_push(frame, d2, d1), a.push_d3 = downsample_push(frame, d3, d2);
-	a.push_u2 = upsample_push(u2, d3), a.push_u1 = upsample_push(u1, u2), a.push_u0 = upsample_push(u0, u1);
-	if (lum_res)
-	{
-		a.lum = static_cast<gr_luminance_data *>(graph.get_physical_buffer_resource(*lum_res).get_device_pointer());
-		a.push_luminance.size[0] = d3.get_width() / 2;
-		a.push_luminance.size[1] = d3.get_height() / 2;
-		a.push_luminance.lerp = float(1.0 - std::pow(0.5, frame.frame_time));
-		a.push_luminance.min_loglum = -3.0f;
-		a.push_luminance.max_loglum = 2.0f;
-	}
+	a.hdr = im.hdr.get_view(), a.threshold = im.t.get_view(), a.d0 = im.d0.get_view(), a.d1 = im.d1.get_view(), a.d2 = im.d2.get_view();
+	a.d3 = im.d3.get_view(), a.history = im.history->get_view(), a.u2 = im.u2.get_view(), a.u1 = im.u1.get_view(), a.u0 = im.u0.get_view();
+	a.push_threshold = threshold_push(im.t);
+	a.push_d0 = downsample_push(frame, im.d0, im.t), a.push_d1 = downsample_push(frame, im.d1, im.d0);
+	a.push_d2 = downsample_push(frame, im.d2, im.d1), a.push_d3 = downsample_push(frame, im.d3, im.d2);
+	a.push_u2 = upsample_push(im.u2, im.d3), a.push_u1 = upsample_push(im.u1, im.u2), a.push_u0 = upsample_push(im.u0, im.u1);
+	a.lum = im.lum;
+	if (im.lum)
+		a.push_luminance = luminance_push(frame, im.d3);
 	if (!gr_bloom_pyramid_supported(&a))
 		return false;
 	cmd.check(gr_bloom_pyramid(cmd.get_context(), cmd.get_stream(), &a), "bloom_pyramid");
@@ -345,13 +286,16 @@ void setup_hdr_postprocess_compute(RenderGraph &graph, const FrameParameters &fr
 				cmd.barrier(VK_PIPELINE_STAGE_COMPUTE_SHADER_BIT, VK_ACCESS_2_SHADER_STORAGE_WRITE_BIT, VK_PIPELINE_STAGE_COMPUTE_SHADER_BIT,
 				            VK_ACCESS_2_SHADER_SAMPLED_READ_BIT);
 			};
-			if (!strip && record_pyramid_whole(cmd, frame, graph, hdr, t, d0, d1, d2, d3, u2, u1, u0, ubo))
+			const auto image = [&graph](const RenderTextureResource &res) -> HIP::ImageView & { return graph.get_physical_texture_resource(res); };
+			const BloomImages im = {image(hdr), image(t), image(d0), image(d1), image(d2), image(d3), image(u2), image(u1), image(u0),
+			                        graph.get_physical_history_texture_resource(d3), luminance_ptr(graph, ubo)};
+			if (!strip && record_pyramid_whole(cmd, frame, im))
 				return;
-			if (strip || !record_pyramid_head(cmd, frame, graph, hdr, t, d0, d1, ubo))
+			if (strip || !record_pyramid_head(cmd, frame, im))
 			{
 				record_threshold(cmd, graph, t, hdr, ubo, strip ? &strip->threshold : nullptr);
 				compute_to_compute();
-				if (!record_pyramid_middle(cmd, frame, graph, t, d0, d1, strip ? &strip->d1 : nullptr))
+				if (!record_pyramid_middle(cmd, frame, im, strip ? &strip->d1 : nullptr))
 				{
 					record_downsample(cmd, frame, graph, d0, t, nullptr, strip ? &strip->d0 : nullptr);
 					compute_to_compute();
@@ -362,7 +306,7 @@ void setup_hdr_postprocess_compute(RenderGraph &graph, const FrameParameters &fr
 				strip->exchange(cmd, graph.get_physical_texture_resource(d1), strip->d1_chunk_rows, "downsample-1");
 			compute_to_compute();
 			bool u0_done = false;
-			if (!record_pyramid_tail(cmd, frame, graph, d1, d2, d3, u2, u1, ubo, strip ? nullptr : &u0, &u0_done, busy_frame))
+			if (!record_pyramid_tail(cmd, frame, im, !strip, u0_done, busy_frame))
 			{
 				record_downsample(cmd, frame, graph, d2, d1, nullptr);
 				compute_to_compute();

@@ -1143,6 +1143,24 @@ __global__ __launch_bounds__(TONEMAP_BLOCK_X *TONEMAP_BLOCK_Y) void k_tonemap(De
 }
 
 
+// ---- launchers ----------------------------------------------------------------------------------------------------------------------------
+// Each rule about what a kernel can be launched on is stated once below, as a named predicate with the reason for it; the gr_bloom_*_supported
+// queries and the entry points are composed from them.
+
+// Measurement switches that more than one function of this file reads (A/B runs only; unset = product behaviour).
+static bool allow_stencil() { static const bool allow = gr_measurement_switch("GR_NO_STENCIL") == nullptr; return allow; }
+static bool allow_tail_fusion() { static const bool allow = gr_measurement_switch("GR_NO_TAIL_FUSION") == nullptr; return allow; }
+
+// Runtime flags to template arguments: f(std::bool_constant<flags>...), one instantiation of f per combination.
+template <typename F> static void with_flags(F &&f) { f(); }
+template <typename F, typename... Rest> static void with_flags(F &&f, bool flag, Rest... rest)
+{
+	if (flag)
+		with_flags([&](auto... constants) { f(std::true_type{}, constants...); }, rest...);
+	else
+		with_flags([&](auto... constants) { f(std::false_type{}, constants...); }, rest...);
+}
+
 static bool is_rgba16f(const gr_image *img)
 {
 	return img && img->ptr && img->format == GR_FORMAT_R16G16B16A16_SFLOAT && img->width && img->height &&
@@ -1155,21 +1173,115 @@ static bool is_b10g11r11(const gr_image *img)
 }
 // an HDR colour target as the passes that only read it take it: RGBA16F, or the reference's default B10G11R11_UFLOAT_PACK32
 static bool is_hdr_target(const gr_image *img) { return is_rgba16f(img) || is_b10g11r11(img); }
+// rows that 16-byte loads can walk
+static bool is_aligned16(const gr_image *img) { return (img->pitch_bytes & 15u) == 0 && (reinterpret_cast<uintptr_t>(img->ptr) & 15u) == 0; }
+static bool same_size(const gr_image *a, const gr_image *b) { return a->width == b->width && a->height == b->height; }
+// a fused kernel writes whole levels: its push block names every texel of the image
+static bool covers(const uint32_t threads[2], const gr_image *img) { return threads[0] == img->width && threads[1] == img->height; }
+// a push block's reciprocals are what its sizes say, to the bit: the constant-weight stencils take the place of the sampler only then
+static bool is_reciprocal_of(const float inv[2], uint32_t width, uint32_t height) { return inv[0] == 1.0f / float(width) && inv[1] == 1.0f / float(height); }
+static bool is_half_of(const gr_image *out, const gr_image *in) { return in->width == 2u * out->width && in->height == 2u * out->height; }
+// The patch of `fine` under an 8 x 8 tile of the level `coarse` below it fits the down_pair kernel's LDS patch (TAIL_PATCH = 24 rows / columns:
+// 2.3 x 8 + the taps' margin), whatever rounding made the coarse level's size.
+static bool down_patch_fits(const gr_image *fine, const gr_image *coarse)
+{
+	return float(fine->width) <= 2.3f * float(coarse->width) && float(fine->height) <= 2.3f * float(coarse->height);
+}
+// `fine` at most twice `coarse` (+ 1: a level is ceil(half) of the one above), or the patch of `coarse` under a tile of `fine` would not fit the
+// kernels' LDS (UP_PATCH of k_bloom_up_tail, UPALL_P1 / UPALL_P2 of k_bloom_up_all)
+static bool up_patch_fits(const gr_image *fine, const gr_image *coarse)
+{
+	return fine->width <= 2 * coarse->width && fine->height <= 2 * coarse->height && 2 * coarse->width <= fine->width + 1 && 2 * coarse->height <= fine->height + 1;
+}
+static bool has_texels(const gr_push_luminance *push) { return push->size[0] != 0 && push->size[1] != 0; }
+
 // What gr_bloom_downsample / gr_bloom_upsample pick for a level: the constant-weight stencil when it is exactly 2:1 / 1:2.
 static bool downsample_is_exact(const gr_image *in, const gr_push_bloom_downsample *push)
 {
-	static const bool allow_stencil = gr_measurement_switch("GR_NO_STENCIL") == nullptr;
-	return allow_stencil && in->width == 2u * push->threads[0] && in->height == 2u * push->threads[1] && (in->pitch_bytes & 15u) == 0 &&
-	       (reinterpret_cast<uintptr_t>(in->ptr) & 15u) == 0 && push->inv_output_size[0] == 1.0f / float(push->threads[0]) &&
-	       push->inv_output_size[1] == 1.0f / float(push->threads[1]) && push->inv_input_size[0] == 1.0f / float(in->width) &&
-	       push->inv_input_size[1] == 1.0f / float(in->height);
+	return allow_stencil() && in->width == 2u * push->threads[0] && in->height == 2u * push->threads[1] && is_aligned16(in) &&
+	       is_reciprocal_of(push->inv_output_size, push->threads[0], push->threads[1]) && is_reciprocal_of(push->inv_input_size, in->width, in->height);
 }
 static bool upsample_is_exact(const gr_image *in, const gr_push_bloom_upsample *push)
 {
-	static const bool allow_stencil = gr_measurement_switch("GR_NO_STENCIL") == nullptr;
-	return allow_stencil && push->threads[0] == 2u * in->width && push->threads[1] == 2u * in->height &&
-	       push->inv_output_size[0] == 1.0f / float(push->threads[0]) && push->inv_output_size[1] == 1.0f / float(push->threads[1]) &&
-	       push->inv_input_size[0] == 1.0f / float(in->width) && push->inv_input_size[1] == 1.0f / float(in->height);
+	return allow_stencil() && push->threads[0] == 2u * in->width && push->threads[1] == 2u * in->height &&
+	       is_reciprocal_of(push->inv_output_size, push->threads[0], push->threads[1]) && is_reciprocal_of(push->inv_input_size, in->width, in->height);
+}
+// The threshold level in its 2:1 form (two outputs per thread from one 16-byte-aligned box of the frame)
+static bool threshold_is_exact(const gr_image *hdr, const gr_image *out, const gr_push_bloom_threshold *push)
+{
+	return allow_stencil() && hdr->width == 2u * push->threads[0] && hdr->height == 2u * push->threads[1] && (push->threads[0] & 1u) == 0 &&
+	       out->width == push->threads[0] && is_aligned16(hdr) && is_aligned16(out) && is_reciprocal_of(push->inv_output_size, push->threads[0], push->threads[1]);
+}
+
+// "Do these arguments fit this kernel", one function per fused launch: nullptr when they do, else the rule they break, which an entry point
+// reports (GR_CHECK_FIT) and a _supported query turns into 0.  What is not a matter of correctness -- measurement switches, the size limits
+// with their measurements -- is the queries' alone.
+#define GR_RULE(cond) do { if (!(cond)) return #cond; } while (0)
+#define GR_CHECK_FIT(ctx, fit) do { if (const char *rule__ = (fit)) return (ctx)->fail(GR_ERR_INVALID_ARGUMENT, "%s: invalid argument: %s", __func__, rule__); } while (0)
+
+// k_bloom_down_pair: downsample-0 + downsample-1 (gr_bloom_down_mid), downsample-2 + downsample-3 (gr_bloom_down_tail)
+static const char *down_pair_fits(const gr_image *in, const gr_image *fine, const gr_image *coarse, const gr_push_bloom_downsample *push_fine,
+                                  const gr_push_bloom_downsample *push_coarse)
+{
+	GR_RULE(push_fine != nullptr && push_coarse != nullptr);
+	GR_RULE(is_rgba16f(in) && is_rgba16f(fine) && is_rgba16f(coarse));
+	GR_RULE(covers(push_fine->threads, fine) && covers(push_coarse->threads, coarse));
+	GR_RULE(down_patch_fits(fine, coarse));
+	return nullptr;
+}
+
+// k_bloom_down_head: every level exactly half of its input on the 2:1 stencils, which is what HEAD_T_PATCH / HEAD_D0_PATCH hold under an 8 x 8
+// tile of downsample-1; the frame read with 16-byte loads.  (push_d0 / push_d1 are not handed to the kernel: their rows follow from the rest.)
+static const char *down_head_fits(const gr_image *hdr, const gr_image *threshold, const gr_image *d0, const gr_image *d1, const gr_push_bloom_threshold *push_t,
+                                  const gr_push_bloom_downsample *push_d0, const gr_push_bloom_downsample *push_d1)
+{
+	GR_RULE(hdr && threshold && d0 && d1 && push_t && push_d0 && push_d1);
+	GR_RULE(is_hdr_target(hdr) && is_rgba16f(threshold) && is_rgba16f(d0) && is_rgba16f(d1));
+	GR_RULE(is_half_of(threshold, hdr) && is_half_of(d0, threshold) && is_half_of(d1, d0));
+	GR_RULE(covers(push_t->threads, threshold) && push_d0->threads[0] == d0->width && push_d1->threads[0] == d1->width);
+	GR_RULE(downsample_is_exact(threshold, push_d0) && downsample_is_exact(d0, push_d1));
+	GR_RULE(is_aligned16(hdr));
+	return nullptr;
+}
+
+// k_bloom_up_tail: upsample-2 + upsample-1
+static const char *up_tail_fits(const gr_image *d3, const gr_image *u2, const gr_image *u1, const gr_push_bloom_upsample *push_u2,
+                                const gr_push_bloom_upsample *push_u1)
+{
+	GR_RULE(push_u2 != nullptr && push_u1 != nullptr);
+	GR_RULE(is_rgba16f(d3) && is_rgba16f(u2) && is_rgba16f(u1));
+	GR_RULE(covers(push_u2->threads, u2) && covers(push_u1->threads, u1));
+	GR_RULE(up_patch_fits(u1, u2));
+	return nullptr;
+}
+
+// k_bloom_up_all: what k_bloom_up_tail takes, and upsample-0 on the 1:2 stencil
+static const char *up_all_fits(const gr_image *d3, const gr_image *u2, const gr_image *u1, const gr_image *u0, const gr_push_bloom_upsample *push_u2,
+                               const gr_push_bloom_upsample *push_u1, const gr_push_bloom_upsample *push_u0)
+{
+	GR_RULE(d3 && u2 && u1 && u0 && push_u0 != nullptr);
+	if (const char *rule = up_tail_fits(d3, u2, u1, push_u2, push_u1))
+		return rule;
+	GR_RULE(is_rgba16f(u0) && covers(push_u0->threads, u0) && upsample_is_exact(u1, push_u0));
+	return nullptr;
+}
+
+// the optional luminance reduction of the upsample launches: its output and its push block come together, over at least one texel
+static const char *luminance_fits(const gr_luminance_data *lum, const gr_push_luminance *push_lum)
+{
+	GR_RULE((lum == nullptr) == (push_lum == nullptr));
+	GR_RULE(!push_lum || has_texels(push_lum));
+	return nullptr;
+}
+
+// k_bloom_pyramid beyond the three launches it stands for: upsample-2 the size of downsample-2 (as gr_bloom_tail_supported asks, where
+// gr_bloom_down_tail and gr_bloom_up_all each see one of the two), a feedback history the size of downsample-3, a luminance size
+static const char *pyramid_own_fits(const gr_bloom_pyramid_args *a)
+{
+	GR_RULE(same_size(&a->u2, &a->d2));
+	GR_RULE(is_rgba16f(&a->history) && same_size(&a->history, &a->d3) && a->history.ptr != a->d3.ptr);
+	GR_RULE(!a->lum || has_texels(&a->push_luminance));
+	return nullptr;
 }
 
 } // namespace
@@ -1196,29 +1308,21 @@ int gr_bloom_threshold_rows(gr_ctx *ctx, gr_stream stream, const gr_image *hdr, 
 	const RowSpan span = resolve_rows(rows, push->threads[1]);
 	if (span.count() == 0)
 		return GR_OK;
+	const bool exact = threshold_is_exact(hdr, out, push);
+	const uint32_t pairs = push->threads[0] / 2u;
 	dim3 block(POST_BLOCK_X, POST_BLOCK_Y);
-	dim3 grid(gr_div_up(push->threads[0], POST_BLOCK_X), gr_div_up(span.count(), POST_BLOCK_Y));
+	dim3 grid(gr_div_up(exact ? pairs : push->threads[0], POST_BLOCK_X), gr_div_up(span.count(), POST_BLOCK_Y));
 	gr_scoped_timing timing{ctx, gr_to_stream(stream), "bloom_threshold"};
-	static const bool allow_stencil = gr_measurement_switch("GR_NO_STENCIL") == nullptr; // A/B switch for measurements
-	const bool exact = allow_stencil && hdr->width == 2u * push->threads[0] && hdr->height == 2u * push->threads[1] && (push->threads[0] & 1u) == 0 &&
-	                   out->width == push->threads[0] && (hdr->pitch_bytes & 15u) == 0 && (out->pitch_bytes & 15u) == 0 &&
-	                   (reinterpret_cast<uintptr_t>(hdr->ptr) & 15u) == 0 && (reinterpret_cast<uintptr_t>(out->ptr) & 15u) == 0 &&
-	                   push->inv_output_size[0] == 1.0f / float(push->threads[0]) && push->inv_output_size[1] == 1.0f / float(push->threads[1]);
-	if (exact)
-	{
-		const uint32_t pairs = push->threads[0] / 2u;
-		dim3 grid2(gr_div_up(pairs, POST_BLOCK_X), gr_div_up(span.count(), POST_BLOCK_Y));
-		if (lum)
-			hipLaunchKernelGGL(k_bloom_threshold_2to1<true>, grid2, block, 0, gr_to_stream(stream), to_dev(hdr), to_dev_rw(out), lum, pairs, push->inv_output_size[0], push->inv_output_size[1], span.first, span.end, b10);
-		else
-			hipLaunchKernelGGL(k_bloom_threshold_2to1<false>, grid2, block, 0, gr_to_stream(stream), to_dev(hdr), to_dev_rw(out), lum, pairs, push->inv_output_size[0], push->inv_output_size[1], span.first, span.end, b10);
-	}
-	else if (lum)
-		hipLaunchKernelGGL(k_bloom_threshold<true>, grid, block, 0, gr_to_stream(stream), to_dev(hdr), to_dev_rw(out), lum, *push,
-		                   span.first, span.end, b10);
-	else
-		hipLaunchKernelGGL(k_bloom_threshold<false>, grid, block, 0, gr_to_stream(stream), to_dev(hdr), to_dev_rw(out), lum, *push,
-		                   span.first, span.end, b10);
+	with_flags(
+	    [&](auto dynamic) {
+		    if (exact)
+			    hipLaunchKernelGGL(k_bloom_threshold_2to1<dynamic.value>, grid, block, 0, gr_to_stream(stream), to_dev(hdr), to_dev_rw(out), lum, pairs,
+			                       push->inv_output_size[0], push->inv_output_size[1], span.first, span.end, b10);
+		    else
+			    hipLaunchKernelGGL(k_bloom_threshold<dynamic.value>, grid, block, 0, gr_to_stream(stream), to_dev(hdr), to_dev_rw(out), lum, *push, span.first,
+			                       span.end, b10);
+	    },
+	    lum != nullptr);
 	GR_CHECK_LAUNCH(ctx);
 	return GR_OK;
 }
@@ -1243,27 +1347,22 @@ int gr_bloom_downsample_rows(gr_ctx *ctx, gr_stream stream, const gr_image *in, 
 	const RowSpan span = resolve_rows(rows, push->threads[1]);
 	if (span.count() == 0)
 		return GR_OK;
-	dim3 block(POST_BLOCK_X, POST_BLOCK_Y);
-	dim3 grid(gr_div_up(push->threads[0], POST_BLOCK_X), gr_div_up(span.count(), POST_BLOCK_Y));
-	gr_scoped_timing timing{ctx, gr_to_stream(stream), "bloom_downsample"};
-	// Exact 2:1 level (and push constants that say so): constant-weight stencil, two outputs per thread.
+	// Exact 2:1 level (and push constants that say so): constant-weight stencil, two outputs (two rows) per thread.
 	const bool exact = downsample_is_exact(in, push);
-	if (exact)
-	{
-		grid.y = gr_div_up(gr_div_up(span.count(), 2u), POST_BLOCK_Y); // two output rows per thread
-		if (history)
-			hipLaunchKernelGGL(k_bloom_downsample_2to1<true>, grid, block, 0, gr_to_stream(stream), to_dev(in), to_dev_rw(out),
-			                   to_dev(history), *push, span.first, span.end);
-		else
-			hipLaunchKernelGGL(k_bloom_downsample_2to1<false>, grid, block, 0, gr_to_stream(stream), to_dev(in), to_dev_rw(out),
-			                   DevImage{}, *push, span.first, span.end);
-	}
-	else if (history)
-		hipLaunchKernelGGL(k_bloom_downsample<true>, grid, block, 0, gr_to_stream(stream), to_dev(in), to_dev_rw(out),
-		                   to_dev(history), *push, span.first, span.end);
-	else
-		hipLaunchKernelGGL(k_bloom_downsample<false>, grid, block, 0, gr_to_stream(stream), to_dev(in), to_dev_rw(out),
-		                   DevImage{}, *push, span.first, span.end);
+	dim3 block(POST_BLOCK_X, POST_BLOCK_Y);
+	dim3 grid(gr_div_up(push->threads[0], POST_BLOCK_X), gr_div_up(exact ? gr_div_up(span.count(), 2u) : span.count(), POST_BLOCK_Y));
+	gr_scoped_timing timing{ctx, gr_to_stream(stream), "bloom_downsample"};
+	const DevImage previous = history ? to_dev(history) : DevImage{};
+	with_flags(
+	    [&](auto feedback) {
+		    if (exact)
+			    hipLaunchKernelGGL(k_bloom_downsample_2to1<feedback.value>, grid, block, 0, gr_to_stream(stream), to_dev(in), to_dev_rw(out), previous, *push,
+			                       span.first, span.end);
+		    else
+			    hipLaunchKernelGGL(k_bloom_downsample<feedback.value>, grid, block, 0, gr_to_stream(stream), to_dev(in), to_dev_rw(out), previous, *push,
+			                       span.first, span.end);
+	    },
+	    history != nullptr);
 	GR_CHECK_LAUNCH(ctx);
 	return GR_OK;
 }
@@ -1289,8 +1388,7 @@ int gr_bloom_upsample_rows(gr_ctx *ctx, gr_stream stream, const gr_image *in, co
 	dim3 block(POST_BLOCK_X, POST_BLOCK_Y);
 	dim3 grid(gr_div_up(push->threads[0], POST_BLOCK_X), gr_div_up(span.count(), POST_BLOCK_Y));
 	gr_scoped_timing timing{ctx, gr_to_stream(stream), "bloom_upsample"};
-	const bool exact = upsample_is_exact(in, push);
-	if (exact)
+	if (upsample_is_exact(in, push))
 		hipLaunchKernelGGL(k_bloom_upsample_1to2, grid, block, 0, gr_to_stream(stream), to_dev(in), to_dev_rw(out), *push, span.first,
 		                   span.end);
 	else
@@ -1303,12 +1401,7 @@ int gr_bloom_down_mid_supported(const gr_image *threshold, const gr_image *d0, c
                                 const gr_push_bloom_downsample *push_d1)
 {
 	static const bool allow_fusion = gr_measurement_switch("GR_NO_MID_FUSION") == nullptr; // A/B switch for measurements
-	if (!allow_fusion || !threshold || !d0 || !d1 || !push_d0 || !push_d1 || !is_rgba16f(threshold) || !is_rgba16f(d0) || !is_rgba16f(d1))
-		return 0;
-	if (push_d0->threads[0] != d0->width || push_d0->threads[1] != d0->height || push_d1->threads[0] != d1->width || push_d1->threads[1] != d1->height)
-		return 0;
-	// the patch of downsample-0 under an 8 x 8 tile of downsample-1 must fit the kernel's LDS patch
-	if (d1->width == 0 || d1->height == 0 || float(d0->width) > 2.3f * float(d1->width) || float(d0->height) > 2.3f * float(d1->height))
+	if (!allow_fusion || down_pair_fits(threshold, d0, d1, push_d0, push_d1))
 		return 0;
 	// Worth it only where the chain of launches, not the arithmetic, sets the pace: the fused form recomputes 56 % of downsample-0
 	// (overlapping patches).  Measured on one box: 1080p frame 0.0748 -> 0.0725 ms, 256 x 256 post chain 0.0622 -> 0.0587 ms, but the
@@ -1324,25 +1417,19 @@ int gr_bloom_down_mid(gr_ctx *ctx, gr_stream stream, const gr_image *threshold, 
 {
 	if (!ctx)
 		return GR_ERR_INVALID_ARGUMENT;
-	GR_CHECK_ARG(ctx, threshold && d0 && d1 && push_d0 && push_d1);
-	GR_CHECK_ARG(ctx, is_rgba16f(threshold) && is_rgba16f(d0) && is_rgba16f(d1) && d0->ptr != d1->ptr && threshold->ptr != d0->ptr);
-	GR_CHECK_ARG(ctx, push_d0->threads[0] == d0->width && push_d0->threads[1] == d0->height);
-	GR_CHECK_ARG(ctx, push_d1->threads[0] == d1->width && push_d1->threads[1] == d1->height);
-	GR_CHECK_ARG(ctx, float(d0->width) <= 2.3f * float(d1->width) && float(d0->height) <= 2.3f * float(d1->height));
+	GR_CHECK_FIT(ctx, down_pair_fits(threshold, d0, d1, push_d0, push_d1));
+	GR_CHECK_ARG(ctx, d0->ptr != d1->ptr && threshold->ptr != d0->ptr); // the entry point's own: the query does not look at the pointers
 	const RowSpan span = resolve_rows(rows_d1, d1->height);
-	if (span.count() == 0 || d1->width == 0)
+	if (span.count() == 0)
 		return GR_OK;
 	dim3 grid(gr_div_up(d1->width, TAIL_TILE), gr_div_up(span.count(), TAIL_TILE));
 	gr_scoped_timing timing{ctx, gr_to_stream(stream), "bloom_down_mid"};
-	auto launch = [&](auto kernel) {
-		hipLaunchKernelGGL(kernel, grid, dim3(256), 0, gr_to_stream(stream), to_dev(threshold), to_dev_rw(d0), to_dev_rw(d1), DevImage{}, *push_d0, *push_d1,
-		                   span.first, span.end);
-	};
-	const bool d0_exact = downsample_is_exact(threshold, push_d0), d1_exact = downsample_is_exact(d0, push_d1);
-	if (d0_exact && d1_exact) launch(k_bloom_down_pair<true, true, false>);
-	else if (d0_exact) launch(k_bloom_down_pair<true, false, false>);
-	else if (d1_exact) launch(k_bloom_down_pair<false, true, false>);
-	else launch(k_bloom_down_pair<false, false, false>);
+	with_flags(
+	    [&](auto d0_exact, auto d1_exact) {
+		    hipLaunchKernelGGL((k_bloom_down_pair<d0_exact.value, d1_exact.value, false>), grid, dim3(256), 0, gr_to_stream(stream), to_dev(threshold),
+		                       to_dev_rw(d0), to_dev_rw(d1), DevImage{}, *push_d0, *push_d1, span.first, span.end);
+	    },
+	    downsample_is_exact(threshold, push_d0), downsample_is_exact(d0, push_d1));
 	GR_CHECK_LAUNCH(ctx);
 	return GR_OK;
 }
@@ -1351,14 +1438,14 @@ int gr_bloom_down_head_supported(const gr_image *hdr, const gr_image *threshold,
                                  const gr_push_bloom_threshold *push_t, const gr_push_bloom_downsample *push_d0, const gr_push_bloom_downsample *push_d1)
 {
 	static const bool allow_fusion = gr_measurement_switch("GR_NO_HEAD_FUSION") == nullptr; // A/B switch for measurements
+	// offered where the fused middle is (its switch, its size limit; both rows of push_d0 / push_d1, of which the kernel needs one)
 	if (!allow_fusion || !hdr || !push_t || !gr_bloom_down_mid_supported(threshold, d0, d1, push_d0, push_d1))
 		return 0;
-	if (!is_hdr_target(hdr) || !downsample_is_exact(threshold, push_d0) || !downsample_is_exact(d0, push_d1))
+	if (down_head_fits(hdr, threshold, d0, d1, push_t, push_d0, push_d1))
 		return 0;
-	// the threshold level as the 2:1 form of gr_bloom_threshold takes it
-	return hdr->width == 2u * push_t->threads[0] && hdr->height == 2u * push_t->threads[1] && threshold->width == push_t->threads[0] &&
-	       threshold->height == push_t->threads[1] && (hdr->pitch_bytes & 15u) == 0 && (reinterpret_cast<uintptr_t>(hdr->ptr) & 15u) == 0 &&
-	       push_t->inv_output_size[0] == 1.0f / float(push_t->threads[0]) && push_t->inv_output_size[1] == 1.0f / float(push_t->threads[1]);
+	// the query's own: the threshold level as the 2:1 form of gr_bloom_threshold takes it, its reciprocals included (the entry point takes
+	// inv_output_size as given)
+	return threshold_is_exact(hdr, threshold, push_t);
 }
 
 int gr_bloom_down_head(gr_ctx *ctx, gr_stream stream, const gr_image *hdr, const gr_image *threshold, const gr_image *d0, const gr_image *d1,
@@ -1367,26 +1454,17 @@ int gr_bloom_down_head(gr_ctx *ctx, gr_stream stream, const gr_image *hdr, const
 {
 	if (!ctx)
 		return GR_ERR_INVALID_ARGUMENT;
-	GR_CHECK_ARG(ctx, hdr && threshold && d0 && d1 && push_t && push_d0 && push_d1);
-	GR_CHECK_ARG(ctx, is_hdr_target(hdr) && is_rgba16f(threshold) && is_rgba16f(d0) && is_rgba16f(d1));
-	GR_CHECK_ARG(ctx, hdr->ptr != threshold->ptr && threshold->ptr != d0->ptr && d0->ptr != d1->ptr);
-	// every level exactly half of its input (what gr_bloom_down_head_supported answers, whatever the size)
-	GR_CHECK_ARG(ctx, hdr->width == 2u * threshold->width && hdr->height == 2u * threshold->height && threshold->width == 2u * d0->width &&
-	                      threshold->height == 2u * d0->height && d0->width == 2u * d1->width && d0->height == 2u * d1->height);
-	GR_CHECK_ARG(ctx, push_t->threads[0] == threshold->width && push_t->threads[1] == threshold->height && downsample_is_exact(threshold, push_d0) &&
-	                      downsample_is_exact(d0, push_d1) && push_d0->threads[0] == d0->width && push_d1->threads[0] == d1->width);
-	GR_CHECK_ARG(ctx, (hdr->pitch_bytes & 15u) == 0 && (reinterpret_cast<uintptr_t>(hdr->ptr) & 15u) == 0);
-	if (d1->width == 0 || d1->height == 0)
-		return GR_OK;
+	GR_CHECK_FIT(ctx, down_head_fits(hdr, threshold, d0, d1, push_t, push_d0, push_d1));
+	GR_CHECK_ARG(ctx, hdr->ptr != threshold->ptr && threshold->ptr != d0->ptr && d0->ptr != d1->ptr); // the entry point's own, as above
 	const dim3 grid(gr_div_up(d1->width, TAIL_TILE), gr_div_up(d1->height, TAIL_TILE));
 	const bool b10 = hdr->format == GR_FORMAT_B10G11R11_UFLOAT_PACK32;
 	gr_scoped_timing timing{ctx, gr_to_stream(stream), "bloom_down_head"};
-	if (lum)
-		hipLaunchKernelGGL(k_bloom_down_head<true>, grid, dim3(256), 0, gr_to_stream(stream), to_dev(hdr), to_dev_rw(threshold), to_dev_rw(d0), to_dev_rw(d1), lum,
-		                   push_t->inv_output_size[0], push_t->inv_output_size[1], b10);
-	else
-		hipLaunchKernelGGL(k_bloom_down_head<false>, grid, dim3(256), 0, gr_to_stream(stream), to_dev(hdr), to_dev_rw(threshold), to_dev_rw(d0), to_dev_rw(d1), lum,
-		                   push_t->inv_output_size[0], push_t->inv_output_size[1], b10);
+	with_flags(
+	    [&](auto dynamic) {
+		    hipLaunchKernelGGL(k_bloom_down_head<dynamic.value>, grid, dim3(256), 0, gr_to_stream(stream), to_dev(hdr), to_dev_rw(threshold), to_dev_rw(d0),
+		                       to_dev_rw(d1), lum, push_t->inv_output_size[0], push_t->inv_output_size[1], b10);
+	    },
+	    lum != nullptr);
 	GR_CHECK_LAUNCH(ctx);
 	return GR_OK;
 }
@@ -1395,24 +1473,9 @@ int gr_bloom_tail_supported(const gr_image *d1, const gr_image *d2, const gr_ima
                             const gr_push_bloom_downsample *push_d2, const gr_push_bloom_downsample *push_d3,
                             const gr_push_bloom_upsample *push_u2, const gr_push_bloom_upsample *push_u1)
 {
-	static const bool allow_fusion = gr_measurement_switch("GR_NO_TAIL_FUSION") == nullptr; // A/B switch for measurements
-	if (!allow_fusion || !is_rgba16f(d1) || !is_rgba16f(d2) || !is_rgba16f(d3) || !is_rgba16f(u2) || !is_rgba16f(u1))
-		return 0;
-	if (!push_d2 || !push_d3 || !push_u2 || !push_u1)
-		return 0;
-	// whole levels only, upsample-2 the size of downsample-2 (the 2:1 / 1:2 stencils where a level is exactly half / twice its input, the nine taps else)
-	if (push_d2->threads[0] != d2->width || push_d2->threads[1] != d2->height || push_d3->threads[0] != d3->width || push_d3->threads[1] != d3->height ||
-	    push_u2->threads[0] != u2->width || push_u2->threads[1] != u2->height || push_u1->threads[0] != u1->width || push_u1->threads[1] != u1->height)
-		return 0;
-	if (u2->width != d2->width || u2->height != d2->height)
-		return 0;
-	// upsample-1 at most twice upsample-2 (+ 1: a level is ceil(half) of the one above), or its patch would not fit the kernel's LDS
-	if (u1->width > 2 * u2->width || u1->height > 2 * u2->height || 2 * u2->width > u1->width + 1 || 2 * u2->height > u1->height + 1)
-		return 0;
-	// the patch of downsample-2 under an 8 x 8 tile of downsample-3 must fit the kernel's LDS patch
-	if (d3->width == 0 || d3->height == 0 || float(d2->width) > 2.3f * float(d3->width) || float(d2->height) > 2.3f * float(d3->height))
-		return 0;
-	return 1;
+	// the two launches (gr_bloom_down_tail, gr_bloom_up_tail) on whole levels -- the 2:1 / 1:2 stencils where a level is exactly half / twice
+	// its input, the nine taps else -- and, the query's own, upsample-2 the size of downsample-2
+	return allow_tail_fusion() && !down_pair_fits(d1, d2, d3, push_d2, push_d3) && !up_tail_fits(d3, u2, u1, push_u2, push_u1) && same_size(u2, d2);
 }
 
 int gr_bloom_down_tail(gr_ctx *ctx, gr_stream stream, const gr_image *d1, const gr_image *d2, const gr_image *d3, const gr_image *history,
@@ -1420,24 +1483,17 @@ int gr_bloom_down_tail(gr_ctx *ctx, gr_stream stream, const gr_image *d1, const 
 {
 	if (!ctx)
 		return GR_ERR_INVALID_ARGUMENT;
-	GR_CHECK_ARG(ctx, push_d2 != nullptr && push_d3 != nullptr);
-	GR_CHECK_ARG(ctx, is_rgba16f(d1) && is_rgba16f(d2) && is_rgba16f(d3));
-	GR_CHECK_ARG(ctx, !history || (is_rgba16f(history) && history->ptr != d3->ptr));
-	GR_CHECK_ARG(ctx, push_d2->threads[0] == d2->width && push_d2->threads[1] == d2->height);
-	GR_CHECK_ARG(ctx, push_d3->threads[0] == d3->width && push_d3->threads[1] == d3->height);
-	GR_CHECK_ARG(ctx, float(d2->width) <= 2.3f * float(d3->width) && float(d2->height) <= 2.3f * float(d3->height));
-	GR_CHECK_ARG(ctx, history != nullptr); // the last level of the pyramid always carries the temporal feedback (hdr.cpp:366)
+	GR_CHECK_FIT(ctx, down_pair_fits(d1, d2, d3, push_d2, push_d3));
+	// the entry point's own (the query does not see the history): the last level of the pyramid always carries the temporal feedback (hdr.cpp)
+	GR_CHECK_ARG(ctx, is_rgba16f(history) && history->ptr != d3->ptr);
 	dim3 grid(gr_div_up(d3->width, TAIL_TILE), gr_div_up(d3->height, TAIL_TILE));
 	gr_scoped_timing timing{ctx, gr_to_stream(stream), "bloom_down_tail"};
-	auto launch = [&](auto kernel) {
-		hipLaunchKernelGGL(kernel, grid, dim3(256), 0, gr_to_stream(stream), to_dev(d1), to_dev_rw(d2), to_dev_rw(d3), to_dev(history), *push_d2, *push_d3, 0u,
-		                   d3->height);
-	};
-	const bool d2_exact = downsample_is_exact(d1, push_d2), d3_exact = downsample_is_exact(d2, push_d3);
-	if (d2_exact && d3_exact) launch(k_bloom_down_pair<true, true, true>);
-	else if (d2_exact) launch(k_bloom_down_pair<true, false, true>);
-	else if (d3_exact) launch(k_bloom_down_pair<false, true, true>);
-	else launch(k_bloom_down_pair<false, false, true>);
+	with_flags(
+	    [&](auto d2_exact, auto d3_exact) {
+		    hipLaunchKernelGGL((k_bloom_down_pair<d2_exact.value, d3_exact.value, true>), grid, dim3(256), 0, gr_to_stream(stream), to_dev(d1), to_dev_rw(d2),
+		                       to_dev_rw(d3), to_dev(history), *push_d2, *push_d3, 0u, d3->height);
+	    },
+	    downsample_is_exact(d1, push_d2), downsample_is_exact(d2, push_d3));
 	GR_CHECK_LAUNCH(ctx);
 	return GR_OK;
 }
@@ -1447,31 +1503,17 @@ int gr_bloom_up_tail(gr_ctx *ctx, gr_stream stream, const gr_image *d3, const gr
 {
 	if (!ctx)
 		return GR_ERR_INVALID_ARGUMENT;
-	GR_CHECK_ARG(ctx, push_u2 != nullptr && push_u1 != nullptr && (lum == nullptr) == (push_lum == nullptr));
-	GR_CHECK_ARG(ctx, is_rgba16f(d3) && is_rgba16f(u2) && is_rgba16f(u1));
-	GR_CHECK_ARG(ctx, push_u1->threads[0] == u1->width && push_u1->threads[1] == u1->height);
-	GR_CHECK_ARG(ctx, push_u2->threads[0] == u2->width && push_u2->threads[1] == u2->height);
-	GR_CHECK_ARG(ctx, u1->width <= 2 * u2->width && u1->height <= 2 * u2->height && 2 * u2->width <= u1->width + 1 && 2 * u2->height <= u1->height + 1);
-	GR_CHECK_ARG(ctx, !push_lum || (push_lum->size[0] != 0 && push_lum->size[1] != 0));
+	GR_CHECK_FIT(ctx, up_tail_fits(d3, u2, u1, push_u2, push_u1));
+	GR_CHECK_FIT(ctx, luminance_fits(lum, push_lum));
 	dim3 grid(gr_div_up(u1->width, UP_TILE), gr_div_up(u1->height, UP_TILE));
 	gr_scoped_timing timing{ctx, gr_to_stream(stream), "bloom_up_tail"};
 	const gr_push_luminance no_lum = {};
-	const bool u2_exact = upsample_is_exact(d3, push_u2), u1_exact = upsample_is_exact(u2, push_u1);
-	auto launch = [&](auto kernel) {
-		hipLaunchKernelGGL(kernel, grid, dim3(LUM_THREADS), 0, gr_to_stream(stream), to_dev(d3), to_dev_rw(u2), to_dev_rw(u1), lum, *push_u2, *push_u1,
-		                   push_lum ? *push_lum : no_lum);
-	};
-	auto pick = [&](auto u2e, auto u1e) {
-		constexpr bool A = decltype(u2e)::value, B = decltype(u1e)::value;
-		if (lum) launch(k_bloom_up_tail<A, B, true>);
-		else launch(k_bloom_up_tail<A, B, false>);
-	};
-	using T = std::true_type;
-	using F = std::false_type;
-	if (u2_exact && u1_exact) pick(T{}, T{});
-	else if (u2_exact) pick(T{}, F{});
-	else if (u1_exact) pick(F{}, T{});
-	else pick(F{}, F{});
+	with_flags(
+	    [&](auto u2_exact, auto u1_exact, auto luminance) {
+		    hipLaunchKernelGGL((k_bloom_up_tail<u2_exact.value, u1_exact.value, luminance.value>), grid, dim3(LUM_THREADS), 0, gr_to_stream(stream), to_dev(d3),
+		                       to_dev_rw(u2), to_dev_rw(u1), lum, *push_u2, *push_u1, push_lum ? *push_lum : no_lum);
+	    },
+	    upsample_is_exact(d3, push_u2), upsample_is_exact(u2, push_u1), lum != nullptr);
 	GR_CHECK_LAUNCH(ctx);
 	return GR_OK;
 }
@@ -1479,18 +1521,8 @@ int gr_bloom_up_tail(gr_ctx *ctx, gr_stream stream, const gr_image *d3, const gr
 int gr_bloom_up_all_supported(const gr_image *d3, const gr_image *u2, const gr_image *u1, const gr_image *u0, const gr_push_bloom_upsample *push_u2,
                               const gr_push_bloom_upsample *push_u1, const gr_push_bloom_upsample *push_u0)
 {
-	static const bool allow_fusion = gr_measurement_switch("GR_NO_UP_FUSION") == nullptr && gr_measurement_switch("GR_NO_TAIL_FUSION") == nullptr;
-	if (!allow_fusion || !d3 || !u2 || !u1 || !u0 || !push_u2 || !push_u1 || !push_u0)
-		return 0;
-	if (!is_rgba16f(d3) || !is_rgba16f(u2) || !is_rgba16f(u1) || !is_rgba16f(u0))
-		return 0;
-	if (push_u2->threads[0] != u2->width || push_u2->threads[1] != u2->height || push_u1->threads[0] != u1->width || push_u1->threads[1] != u1->height ||
-	    push_u0->threads[0] != u0->width || push_u0->threads[1] != u0->height)
-		return 0;
-	// upsample-1 at most twice upsample-2 (+ 1: a level is ceil(half) of the one above), as for gr_bloom_up_tail; upsample-0 on the 1:2 stencil
-	if (u1->width > 2 * u2->width || u1->height > 2 * u2->height || 2 * u2->width > u1->width + 1 || 2 * u2->height > u1->height + 1)
-		return 0;
-	if (!upsample_is_exact(u1, push_u0) || u1->width == 0 || u1->height == 0)
+	static const bool allow_fusion = gr_measurement_switch("GR_NO_UP_FUSION") == nullptr; // A/B switch for measurements
+	if (!allow_fusion || !allow_tail_fusion() || up_all_fits(d3, u2, u1, u0, push_u2, push_u1, push_u0))
 		return 0;
 	// Up to the quarter level of a 4K frame.  The levels involved are a quarter of the frame and coarser, but a 32 x 32 tile of upsample-0
 	// recomputes its patches of the two levels under it (upsample-2 five times over all tiles): 3.05 M wave instructions at 4K against
@@ -1508,46 +1540,22 @@ int gr_bloom_up_all(gr_ctx *ctx, gr_stream stream, const gr_image *d3, const gr_
 {
 	if (!ctx)
 		return GR_ERR_INVALID_ARGUMENT;
-	GR_CHECK_ARG(ctx, d3 && u2 && u1 && u0 && push_u2 && push_u1 && push_u0 && (lum == nullptr) == (push_lum == nullptr));
-	GR_CHECK_ARG(ctx, is_rgba16f(d3) && is_rgba16f(u2) && is_rgba16f(u1) && is_rgba16f(u0));
-	GR_CHECK_ARG(ctx, push_u0->threads[0] == u0->width && push_u0->threads[1] == u0->height && upsample_is_exact(u1, push_u0));
-	GR_CHECK_ARG(ctx, push_u1->threads[0] == u1->width && push_u1->threads[1] == u1->height);
-	GR_CHECK_ARG(ctx, push_u2->threads[0] == u2->width && push_u2->threads[1] == u2->height);
-	GR_CHECK_ARG(ctx, u1->width <= 2 * u2->width && u1->height <= 2 * u2->height && 2 * u2->width <= u1->width + 1 && 2 * u2->height <= u1->height + 1);
-	GR_CHECK_ARG(ctx, u0->ptr != u1->ptr && u1->ptr != u2->ptr && u2->ptr != d3->ptr);
-	GR_CHECK_ARG(ctx, !push_lum || (push_lum->size[0] != 0 && push_lum->size[1] != 0));
-	if (u0->width == 0 || u0->height == 0)
-		return GR_OK;
+	GR_CHECK_FIT(ctx, up_all_fits(d3, u2, u1, u0, push_u2, push_u1, push_u0));
+	GR_CHECK_ARG(ctx, u0->ptr != u1->ptr && u1->ptr != u2->ptr && u2->ptr != d3->ptr); // the entry point's own: the query does not look at the pointers
+	GR_CHECK_FIT(ctx, luminance_fits(lum, push_lum));
 	dim3 grid(gr_div_up(u0->width, UPALL_TILE), gr_div_up(u0->height, UPALL_TILE));
 	gr_scoped_timing timing{ctx, gr_to_stream(stream), "bloom_up_all"};
 	const gr_push_luminance no_lum = {};
-	const bool u2_exact = upsample_is_exact(d3, push_u2), u1_exact = upsample_is_exact(u2, push_u1);
 	// measurement switch: GR_UP_ALL_THREADS=256 / 1024 whatever the caller's hint
 	static const int forced = []() { const char *env = gr_measurement_switch("GR_UP_ALL_THREADS"); return env ? atoi(env) : 0; }();
 	const int threads = forced == 256 || forced == 1024 ? forced : ((flags & GR_BLOOM_BUSY_FRAME_BIT) ? 256 : 1024);
-	auto launch = [&](auto kernel, int nt) {
-		hipLaunchKernelGGL(kernel, grid, dim3(nt), 0, gr_to_stream(stream), to_dev(d3), to_dev_rw(u2), to_dev_rw(u1), to_dev_rw(u0), lum, *push_u2, *push_u1,
-		                   push_lum ? *push_lum : no_lum);
-	};
-	auto pick = [&](auto u2e, auto u1e) {
-		constexpr bool A = decltype(u2e)::value, B = decltype(u1e)::value;
-		if (threads == 1024)
-		{
-			if (lum) launch(k_bloom_up_all<A, B, true, LUM_THREADS>, LUM_THREADS);
-			else launch(k_bloom_up_all<A, B, false, LUM_THREADS>, LUM_THREADS);
-		}
-		else
-		{
-			if (lum) launch(k_bloom_up_all<A, B, true, 256>, 256);
-			else launch(k_bloom_up_all<A, B, false, 256>, 256);
-		}
-	};
-	using T = std::true_type;
-	using F = std::false_type;
-	if (u2_exact && u1_exact) pick(T{}, T{});
-	else if (u2_exact) pick(T{}, F{});
-	else if (u1_exact) pick(F{}, T{});
-	else pick(F{}, F{});
+	with_flags(
+	    [&](auto u2_exact, auto u1_exact, auto luminance, auto wide) {
+		    constexpr int NT = wide.value ? LUM_THREADS : 256;
+		    hipLaunchKernelGGL((k_bloom_up_all<u2_exact.value, u1_exact.value, luminance.value, NT>), grid, dim3(NT), 0, gr_to_stream(stream), to_dev(d3),
+		                       to_dev_rw(u2), to_dev_rw(u1), to_dev_rw(u0), lum, *push_u2, *push_u1, push_lum ? *push_lum : no_lum);
+	    },
+	    upsample_is_exact(d3, push_u2), upsample_is_exact(u2, push_u1), lum != nullptr, threads == 1024);
 	GR_CHECK_LAUNCH(ctx);
 	return GR_OK;
 }
@@ -1555,15 +1563,12 @@ int gr_bloom_up_all(gr_ctx *ctx, gr_stream stream, const gr_image *d3, const gr_
 int gr_bloom_pyramid_supported(const gr_bloom_pyramid_args *a)
 {
 	static const bool allow_fusion = gr_measurement_switch("GR_NO_PYRAMID_FUSION") == nullptr; // A/B switch for measurements
-	if (!allow_fusion || !a || !a->history.ptr)
+	if (!allow_fusion || !a)
 		return 0;
+	// offered where the three launches it stands for are (their switches and size limits included)
 	if (!gr_bloom_down_head_supported(&a->hdr, &a->threshold, &a->d0, &a->d1, &a->push_threshold, &a->push_d0, &a->push_d1) ||
 	    !gr_bloom_tail_supported(&a->d1, &a->d2, &a->d3, &a->u2, &a->u1, &a->push_d2, &a->push_d3, &a->push_u2, &a->push_u1) ||
-	    !gr_bloom_up_all_supported(&a->d3, &a->u2, &a->u1, &a->u0, &a->push_u2, &a->push_u1, &a->push_u0))
-		return 0;
-	if (!is_rgba16f(&a->history) || a->history.width != a->d3.width || a->history.height != a->d3.height || a->history.ptr == a->d3.ptr)
-		return 0;
-	if (a->lum && (a->push_luminance.size[0] == 0 || a->push_luminance.size[1] == 0))
+	    !gr_bloom_up_all_supported(&a->d3, &a->u2, &a->u1, &a->u0, &a->push_u2, &a->push_u1, &a->push_u0) || pyramid_own_fits(a))
 		return 0;
 	// Up to a 640 x 384 frame.  A hand-over between two phases costs what agent-scope release / acquire cost on eight XCDs with an L2 each (an L2
 	// write-back per publishing workgroup, an invalidate per waiting one): measured 22 us for the 21 workgroups of a 256 x 256 frame against 8.7 +
@@ -1579,33 +1584,18 @@ int gr_bloom_pyramid(gr_ctx *ctx, gr_stream stream, const gr_bloom_pyramid_args 
 	if (!ctx)
 		return GR_ERR_INVALID_ARGUMENT;
 	GR_CHECK_ARG(ctx, a != nullptr);
-	// what the three launches this one stands for check (gr_bloom_down_head, gr_bloom_down_tail, gr_bloom_up_all)
-	GR_CHECK_ARG(ctx, is_hdr_target(&a->hdr) && is_rgba16f(&a->threshold) && is_rgba16f(&a->d0) && is_rgba16f(&a->d1) && is_rgba16f(&a->d2) && is_rgba16f(&a->d3) &&
-	                      is_rgba16f(&a->u2) && is_rgba16f(&a->u1) && is_rgba16f(&a->u0) && is_rgba16f(&a->history));
-	GR_CHECK_ARG(ctx, a->hdr.width == 2u * a->threshold.width && a->hdr.height == 2u * a->threshold.height && a->threshold.width == 2u * a->d0.width &&
-	                      a->threshold.height == 2u * a->d0.height && a->d0.width == 2u * a->d1.width && a->d0.height == 2u * a->d1.height);
-	GR_CHECK_ARG(ctx, a->push_threshold.threads[0] == a->threshold.width && a->push_threshold.threads[1] == a->threshold.height &&
-	                      downsample_is_exact(&a->threshold, &a->push_d0) && downsample_is_exact(&a->d0, &a->push_d1) && a->push_d0.threads[0] == a->d0.width &&
-	                      a->push_d1.threads[0] == a->d1.width);
-	GR_CHECK_ARG(ctx, (a->hdr.pitch_bytes & 15u) == 0 && (reinterpret_cast<uintptr_t>(a->hdr.ptr) & 15u) == 0);
-	GR_CHECK_ARG(ctx, a->push_d2.threads[0] == a->d2.width && a->push_d2.threads[1] == a->d2.height && a->push_d3.threads[0] == a->d3.width &&
-	                      a->push_d3.threads[1] == a->d3.height);
-	GR_CHECK_ARG(ctx, float(a->d2.width) <= 2.3f * float(a->d3.width) && float(a->d2.height) <= 2.3f * float(a->d3.height));
-	GR_CHECK_ARG(ctx, a->history.ptr != a->d3.ptr && a->history.width == a->d3.width && a->history.height == a->d3.height);
-	GR_CHECK_ARG(ctx, a->push_u0.threads[0] == a->u0.width && a->push_u0.threads[1] == a->u0.height && upsample_is_exact(&a->u1, &a->push_u0));
-	GR_CHECK_ARG(ctx, a->push_u1.threads[0] == a->u1.width && a->push_u1.threads[1] == a->u1.height && a->push_u2.threads[0] == a->u2.width &&
-	                      a->push_u2.threads[1] == a->u2.height && a->u2.width == a->d2.width && a->u2.height == a->d2.height);
-	GR_CHECK_ARG(ctx, a->u1.width <= 2 * a->u2.width && a->u1.height <= 2 * a->u2.height && 2 * a->u2.width <= a->u1.width + 1 &&
-	                      2 * a->u2.height <= a->u1.height + 1);
+	// the three launches this one stands for (gr_bloom_down_head, gr_bloom_down_tail, gr_bloom_up_all), then its own
+	GR_CHECK_FIT(ctx, down_head_fits(&a->hdr, &a->threshold, &a->d0, &a->d1, &a->push_threshold, &a->push_d0, &a->push_d1));
+	GR_CHECK_FIT(ctx, down_pair_fits(&a->d1, &a->d2, &a->d3, &a->push_d2, &a->push_d3));
+	GR_CHECK_FIT(ctx, up_all_fits(&a->d3, &a->u2, &a->u1, &a->u0, &a->push_u2, &a->push_u1, &a->push_u0));
+	GR_CHECK_FIT(ctx, pyramid_own_fits(a));
 	{
+		// the entry point's own (the queries do not look at the pointers, but for history / downsample-3): one launch, so no two images may alias
 		const void *levels[] = {a->hdr.ptr, a->threshold.ptr, a->d0.ptr, a->d1.ptr, a->d2.ptr, a->d3.ptr, a->u2.ptr, a->u1.ptr, a->u0.ptr, a->history.ptr};
 		for (size_t i = 0; i < sizeof(levels) / sizeof(levels[0]); i++)
 			for (size_t j = i + 1; j < sizeof(levels) / sizeof(levels[0]); j++)
 				GR_CHECK_ARG(ctx, levels[i] != levels[j]);
 	}
-	GR_CHECK_ARG(ctx, !a->lum || (a->push_luminance.size[0] != 0 && a->push_luminance.size[1] != 0));
-	if (a->d3.width == 0 || a->d3.height == 0)
-		return GR_OK;
 	PyramidArgs k{};
 	k.hdr = to_dev(&a->hdr), k.history = to_dev(&a->history);
 	k.thr = to_dev_rw(&a->threshold), k.d0 = to_dev_rw(&a->d0), k.d1 = to_dev_rw(&a->d1), k.d2 = to_dev_rw(&a->d2), k.d3 = to_dev_rw(&a->d3);
@@ -1623,22 +1613,13 @@ int gr_bloom_pyramid(gr_ctx *ctx, gr_stream stream, const gr_bloom_pyramid_args 
 	k.hdr_b10 = a->hdr.format == GR_FORMAT_B10G11R11_UFLOAT_PACK32;
 	const dim3 grid(k.n0 + k.n1 + k.n2);
 	gr_scoped_timing timing{ctx, gr_to_stream(stream), "bloom_pyramid"};
-	const bool d2e = downsample_is_exact(&a->d1, &a->push_d2), d3e = downsample_is_exact(&a->d2, &a->push_d3);
-	const bool u2e = upsample_is_exact(&a->d3, &a->push_u2), u1e = upsample_is_exact(&a->u2, &a->push_u1);
-	const unsigned variant = (a->lum ? 16u : 0u) | (d2e ? 8u : 0u) | (d3e ? 4u : 0u) | (u2e ? 2u : 0u) | (u1e ? 1u : 0u);
-	switch (variant)
-	{
-#define GR_PYRAMID_CASE(V)                                                                                                                     \
-	case V:                                                                                                                                    \
-		hipLaunchKernelGGL((k_bloom_pyramid<((V) & 16) != 0, ((V) & 8) != 0, ((V) & 4) != 0, ((V) & 2) != 0, ((V) & 1) != 0>), grid, dim3(PYRAMID_THREADS), 0, \
-		                   gr_to_stream(stream), k);                                                                                           \
-		break;
-		GR_PYRAMID_CASE(0) GR_PYRAMID_CASE(1) GR_PYRAMID_CASE(2) GR_PYRAMID_CASE(3) GR_PYRAMID_CASE(4) GR_PYRAMID_CASE(5) GR_PYRAMID_CASE(6) GR_PYRAMID_CASE(7)
-		GR_PYRAMID_CASE(8) GR_PYRAMID_CASE(9) GR_PYRAMID_CASE(10) GR_PYRAMID_CASE(11) GR_PYRAMID_CASE(12) GR_PYRAMID_CASE(13) GR_PYRAMID_CASE(14) GR_PYRAMID_CASE(15)
-		GR_PYRAMID_CASE(16) GR_PYRAMID_CASE(17) GR_PYRAMID_CASE(18) GR_PYRAMID_CASE(19) GR_PYRAMID_CASE(20) GR_PYRAMID_CASE(21) GR_PYRAMID_CASE(22) GR_PYRAMID_CASE(23)
-		GR_PYRAMID_CASE(24) GR_PYRAMID_CASE(25) GR_PYRAMID_CASE(26) GR_PYRAMID_CASE(27) GR_PYRAMID_CASE(28) GR_PYRAMID_CASE(29) GR_PYRAMID_CASE(30) GR_PYRAMID_CASE(31)
-#undef GR_PYRAMID_CASE
-	}
+	with_flags(
+	    [&](auto dynamic, auto d2_exact, auto d3_exact, auto u2_exact, auto u1_exact) {
+		    hipLaunchKernelGGL((k_bloom_pyramid<dynamic.value, d2_exact.value, d3_exact.value, u2_exact.value, u1_exact.value>), grid, dim3(PYRAMID_THREADS), 0,
+		                       gr_to_stream(stream), k);
+	    },
+	    a->lum != nullptr, downsample_is_exact(&a->d1, &a->push_d2), downsample_is_exact(&a->d2, &a->push_d3), upsample_is_exact(&a->d3, &a->push_u2),
+	    upsample_is_exact(&a->u2, &a->push_u1));
 	GR_CHECK_LAUNCH(ctx);
 	return GR_OK;
 }
@@ -1663,7 +1644,7 @@ int gr_luminance(gr_ctx *ctx, gr_stream stream, const gr_image *in, gr_luminance
 		return GR_ERR_INVALID_ARGUMENT;
 	GR_CHECK_ARG(ctx, push != nullptr && lum != nullptr);
 	GR_CHECK_ARG(ctx, is_rgba16f(in));
-	GR_CHECK_ARG(ctx, push->size[0] != 0 && push->size[1] != 0);
+	GR_CHECK_ARG(ctx, has_texels(push));
 	gr_scoped_timing timing{ctx, gr_to_stream(stream), "luminance"};
 	hipLaunchKernelGGL(k_luminance, dim3(1), dim3(LUM_THREADS), 0, gr_to_stream(stream), to_dev(in), lum, *push);
 	GR_CHECK_LAUNCH(ctx);
@@ -1698,26 +1679,13 @@ int gr_tonemap_rows(gr_ctx *ctx, gr_stream stream, const gr_image *hdr, const gr
 	const int row_groups = columns * gr_div_up(span.count(), TONEMAP_BLOCK_Y * TONEMAP_ROW_GROUPS) < 64u ? 1 : TONEMAP_ROW_GROUPS;
 	dim3 grid(columns, gr_div_up(span.count(), unsigned(TONEMAP_BLOCK_Y * row_groups)));
 	gr_scoped_timing timing{ctx, gr_to_stream(stream), "tonemap"};
-	hipStream_t s = gr_to_stream(stream);
-	const bool quarter = hdr->width == 4u * bloom->width && hdr->height == 4u * bloom->height;
-	auto launch = [&](auto kernel) {
-		hipLaunchKernelGGL(kernel, grid, block, 0, s, to_dev(hdr), to_dev(bloom), to_dev_rw(out), lum, ctx->tonemap_srgb8_lut, *push, span.first, span.end,
-		                   hdr->format == GR_FORMAT_B10G11R11_UFLOAT_PACK32, row_groups);
-	};
-	if (quarter)
-	{
-		if (lum && srgb) launch(k_tonemap<true, true, true>);
-		else if (lum) launch(k_tonemap<true, false, true>);
-		else if (srgb) launch(k_tonemap<false, true, true>);
-		else launch(k_tonemap<false, false, true>);
-	}
-	else
-	{
-		if (lum && srgb) launch(k_tonemap<true, true, false>);
-		else if (lum) launch(k_tonemap<true, false, false>);
-		else if (srgb) launch(k_tonemap<false, true, false>);
-		else launch(k_tonemap<false, false, false>);
-	}
+	with_flags(
+	    [&](auto dynamic, auto srgb8, auto quarter_bloom) {
+		    hipLaunchKernelGGL((k_tonemap<dynamic.value, srgb8.value, quarter_bloom.value>), grid, block, 0, gr_to_stream(stream), to_dev(hdr), to_dev(bloom),
+		                       to_dev_rw(out), lum, ctx->tonemap_srgb8_lut, *push, span.first, span.end, hdr->format == GR_FORMAT_B10G11R11_UFLOAT_PACK32,
+		                       row_groups);
+	    },
+	    lum != nullptr, srgb, hdr->width == 4u * bloom->width && hdr->height == 4u * bloom->height);
 	GR_CHECK_LAUNCH(ctx);
 	return GR_OK;
 }

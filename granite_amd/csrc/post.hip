@@ -172,7 +172,9 @@ __device__ __forceinline__ float4 apply_feedback(float4 value, const DevImage &h
 	const int hx = clampi(int(floorf(u * float(history.w))), 0, history.w - 1);
 	const int hy = clampi(int(floorf(v * float(history.h))), 0, history.h - 1);
 	const float4 h = load_rgba16f(history, hx, hy);
-	return make_float4(h.x * (1.0f - l) + value.x * l, h.y * (1.0f - l) + value.y * l, h.z * (1.0f - l) + value.z * l, value.w);
+	// alpha: mix(h.w, value.w, 1.0) = h.w * 0 + value.w, the product kept -- an infinite (overflowed) alpha in the history makes it NaN, as the
+	// shader's mix does
+	return make_float4(h.x * (1.0f - l) + value.x * l, h.y * (1.0f - l) + value.y * l, h.z * (1.0f - l) + value.z * l, h.w * 0.0f + value.w);
 }
 
 template <bool FEEDBACK>

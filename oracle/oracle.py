@@ -126,12 +126,14 @@ def luminance(d3: np.ndarray, lum3: np.ndarray, lerp: float, lo: float = -3.0, h
     return out
 
 
-def tonemap(hdr: np.ndarray, bloom: np.ndarray, lum3=None, dynamic_exposure: float = 1.0) -> np.ndarray:
+def tonemap(hdr: np.ndarray, bloom: np.ndarray, lum3=None, dynamic_exposure: float = 1.0, out_format: str = "rgba8_srgb") -> np.ndarray:
+    """tonemap.frag into an R8G8B8A8_SRGB target (the default) or, out_format="rgba8_unorm", the same linear RGB into an R8G8B8A8_UNORM one."""
+    assert out_format in ("rgba8_srgb", "rgba8_unorm")
     w, h = _img16(hdr)
     bw, bh = _img16(bloom)
     out = np.zeros((h, w, 4), np.uint8)
     l = None if lum3 is None else np.ascontiguousarray(lum3, np.float32)
-    lib().orc_tonemap(_p(hdr), w, h, _p(bloom), bw, bh, _p(l), C.c_float(dynamic_exposure), _p(out))
+    lib().orc_tonemap_to(_p(hdr), w, h, _p(bloom), bw, bh, _p(l), C.c_float(dynamic_exposure), _p(out), BLIT_FORMATS[out_format])
     return out
 
 
@@ -291,6 +293,7 @@ def cluster_build(rp, prm, lights, model, type_mask, num_lights: int, res_z: int
 def pack_b10g11r11(rgba16f: np.ndarray) -> np.ndarray:
     """RGBA16F bits (h, w, 4) -> B10G11R11_UFLOAT_PACK32 words (h, w): the attachment store conversion (round to the closest finite
     value, ties to even; negatives -> 0)."""
+    assert np.shape(rgba16f)[-1] == 4, "four halves per texel: the packer reads eight bytes per texel"
     src = np.ascontiguousarray(rgba16f, np.uint16)
     out = np.zeros(src.shape[:-1], np.uint32)
     lib().orc_pack_b10g11r11_from_rgba16f(_p(src), _p(out), C.c_uint64(out.size))

@@ -23,14 +23,18 @@ void orc_bloom_threshold(const uint16_t *hdr, int iw, int ih, uint16_t *out, int
 			vec2 uv = (V2(float(x), float(y)) + V2(0.5f, 0.5f)) * inv_output_size;
 			vec4 t = tex.sample_linear(uv);
 			vec3 color = V3(t.x, t.y, t.z);
-			float luminance = std::max(std::max(color.x, color.y), color.z) + 0.0001f;
+			// GLSL max / clamp as the executed shaders have them (oracle/ref_build: fmaxf / fminf, which drop a NaN operand), here and below
+			float luminance = fmaxf(fmaxf(color.x, color.y), color.z) + 0.0001f;
 			float loglum = log2f(luminance);
 			color = color / luminance;
 			if (lum3)
 				luminance -= 8.0f * lum3[1];
 			else
 				luminance -= 8.0f;
-			vec3 thres = max3(color * luminance, V3(0.0f));
+			// max(NaN, 0) = 0 (an infinite texel makes inf / inf above): what the shader gives when executed (oracle/ref_build: GLSL max is
+			// fmaxf) and what the GPU's maximum instruction gives; std::max would keep the NaN
+			const vec3 scaled = color * luminance;
+			vec3 thres = V3(fmaxf(scaled.x, 0.0f), fmaxf(scaled.y, 0.0f), fmaxf(scaled.z, 0.0f));
 			store_rgba16f(out, ow, x, y, V4(thres, loglum));
 		}
 	}
@@ -123,7 +127,7 @@ void orc_luminance(const uint16_t *d3, int w, int h, float *lum3, float lerp, fl
 			shared_loglum[i] += shared_loglum[i + step];
 	float loglum = shared_loglum[0] + shared_loglum[1];
 	loglum *= inv_size.x * inv_size.y;
-	loglum = clampf(loglum, min_loglum, max_loglum);
+	loglum = fminf(fmaxf(loglum, min_loglum), max_loglum); // a NaN sum (a NaN alpha in downsample-3) clamps to min_loglum, as the shader's clamp does
 	float new_log_luma = mixf(lum3[0], loglum, lerp);
 	lum3[0] = new_log_luma;
 	lum3[1] = exp2f(new_log_luma);
@@ -139,9 +143,11 @@ static inline float uncharted2(float x)
 // tonemap.frag:30-66 + hdr.cpp:283-306.  Output is the RGBA8_SRGB backbuffer (headless swapchain format,
 // application_headless.cpp:207-229): the shader writes linear RGB, the attachment store encodes sRGB.
 // The shader's output is vec3, alpha is written as 1.0 (undefined in the reference; fixed here).
-void orc_tonemap(const uint16_t *hdr, int w, int h, const uint16_t *bloom, int bw, int bh, const float *lum3,
-                 float dynamic_exposure, uint8_t *out_srgb8)
+// out_format (as orc_blit's): 2 = R8G8B8A8_SRGB, 1 = R8G8B8A8_UNORM -- the same linear RGB, stored without the encode.
+void orc_tonemap_to(const uint16_t *hdr, int w, int h, const uint16_t *bloom, int bw, int bh, const float *lum3,
+                    float dynamic_exposure, uint8_t *out_rgba8, int out_format)
 {
+	const bool srgb = out_format == 2;
 	Tex16F thdr{hdr, w, h};
 	Tex16F tbloom{bloom, bw, bh};
 	vec2 inv = V2(1.0f / float(w), 1.0f / float(h));
@@ -159,13 +165,18 @@ void orc_tonemap(const uint16_t *hdr, int w, int h, const uint16_t *bloom, int b
 			vec3 color = V3(c.x + b.x, c.y + b.y, c.z + b.z) * scale;
 			vec3 r = V3(uncharted2(color.x) * white_scale, uncharted2(color.y) * white_scale,
 			            uncharted2(color.z) * white_scale);
-			uint8_t *p = out_srgb8 + (size_t(y) * w + x) * 4;
-			p[0] = float_to_srgb8(r.x);
-			p[1] = float_to_srgb8(r.y);
-			p[2] = float_to_srgb8(r.z);
+			uint8_t *p = out_rgba8 + (size_t(y) * w + x) * 4;
+			p[0] = srgb ? float_to_srgb8(r.x) : float_to_unorm8(r.x);
+			p[1] = srgb ? float_to_srgb8(r.y) : float_to_unorm8(r.y);
+			p[2] = srgb ? float_to_srgb8(r.z) : float_to_unorm8(r.z);
 			p[3] = 255;
 		}
 	}
+}
+void orc_tonemap(const uint16_t *hdr, int w, int h, const uint16_t *bloom, int bw, int bh, const float *lum3,
+                 float dynamic_exposure, uint8_t *out_srgb8)
+{
+	orc_tonemap_to(hdr, w, h, bloom, bw, bh, lum3, dynamic_exposure, out_srgb8, 2);
 }
 
 // ---- format helpers exported for the tests ---------------------------------------------------

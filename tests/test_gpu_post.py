@@ -75,6 +75,29 @@ def test_chain_levels_match_oracle(gr, w, h):
         assert_rgba8_close(got["tonemapped"], ref["tonemapped"], 1, what=f"{w}x{h} frame {frame} tonemapped")
 
 
+@pytest.mark.parametrize("w,h,use_lum", [(256, 256, True), (256, 256, False), (250, 130, True), (250, 130, False)])
+def test_chain_into_a_unorm_target_matches_oracle(gr, w, h, use_lum):
+    """gr_tonemap into an R8G8B8A8_UNORM target (k_tonemap<*, SRGB = false, *>: the formula and a plain UNORM store, no encode table) at the end
+    of the chain: 256 x 256 (the 4 x bloom form) and 250 x 130 (bloom by the bilinear fetch), dynamic and static exposure.  Within 1 LSB, the
+    file's tolerance for RGBA8, and not tighter: the store itself is round-to-nearest of the same float, but the float is not the oracle's --
+    the kernel divides the filmic curve by a reciprocal approximation (1 ulp) and contracts its polynomials, so a value next to a rounding
+    boundary of the store may land on the other side of it.  The bytes that differ must be few."""
+    hdr = synth.make_hdr(w, h)
+    ostate, gstate = {}, {}
+    for frame in range(2):
+        ref = orc.hdr_chain(hdr, ostate, use_lum=use_lum)
+        got = run_chain_gpu(gr, hdr, gstate, use_lum=use_lum, fmt=capi.FORMAT_R8G8B8A8_UNORM)
+        assert_rgba16f_close(got["u0"], ref["u0"], what=f"{w}x{h} frame {frame} u0")
+        # the oracle's store on the GPU's own bloom level and exposure: nothing but the tonemap pass between the two
+        lum = got["lum"] if use_lum else None
+        want = orc.tonemap(hdr, got["u0"], lum, 1.0, "rgba8_unorm")
+        assert_rgba8_close(got["tonemapped"], want, 1, what=f"{w}x{h} frame {frame} tonemapped (UNORM)")
+        assert (got["tonemapped"] != want).mean() < 1e-3
+        assert (got["tonemapped"][..., 3] == 255).all()
+        # ... and it is not the sRGB image
+        assert (got["tonemapped"] != ref["tonemapped"]).mean() > 0.25
+
+
 @pytest.mark.parametrize("w,h", TINY_SIZES)
 def test_chain_tiny_sizes_without_exposure(gr, w, h):
     hdr = synth.make_hdr(w, h)
@@ -122,12 +145,12 @@ def test_kernels_stagewise_on_identical_inputs(gr):
     gr.bloom_upsample(dd, du)
     assert_rgba16f_close(du.download(), orc.bloom_upsample(ref_d, tw, th), what="upsample")
 
-    for fmt, check in ((capi.FORMAT_R8G8B8A8_SRGB, True),):
+    for fmt, store in ((capi.FORMAT_R8G8B8A8_SRGB, "rgba8_srgb"), (capi.FORMAT_R8G8B8A8_UNORM, "rgba8_unorm")):
         dout = capi.DeviceImage(gr, w, h, fmt)
         gr.tonemap(dhdr, dd, dout, lumbuf.ptr, 1.3)
-        assert_rgba8_close(dout.download(), orc.tonemap(hdr, ref_d, lum3, 1.3), 1, what="tonemap(dynamic)")
+        assert_rgba8_close(dout.download(), orc.tonemap(hdr, ref_d, lum3, 1.3, store), 1, what=f"tonemap(dynamic, {store})")
         gr.tonemap(dhdr, dd, dout, None, 0.7)
-        assert_rgba8_close(dout.download(), orc.tonemap(hdr, ref_d, None, 0.7), 1, what="tonemap(static)")
+        assert_rgba8_close(dout.download(), orc.tonemap(hdr, ref_d, None, 0.7, store), 1, what=f"tonemap(static, {store})")
 
 
 def test_constant_image_known_answers(gr):
@@ -237,7 +260,7 @@ def test_fused_pyramid_head_equals_threshold_and_the_two_downsamples(gr, w, h, p
     rng = np.random.default_rng(w * 31 + h)
     hdr_f = np.exp2(rng.uniform(-6, 6, (h, w, 4))).astype(np.float32)
     if packed:
-        hdr = capi.DeviceImage(gr, w, h, capi.FORMAT_B10G11R11_UFLOAT_PACK32).upload(orc.pack_b10g11r11(hdr_f[..., :3]))
+        hdr = capi.DeviceImage(gr, w, h, capi.FORMAT_B10G11R11_UFLOAT_PACK32).upload(orc.pack_b10g11r11(hdr_f.astype(np.float16).view(np.uint16)))
     else:
         hdr = capi.DeviceImage(gr, w, h, F16).upload(hdr_f.astype(np.float16).view(np.uint16))
     lum = capi.DeviceBuffer(gr, 12).upload(np.array([0.3, 1.7, 1.0 / 1.7], np.float32)) if dynamic else None  # (kept alive: .ptr alone would free it)
@@ -299,7 +322,7 @@ def test_whole_pyramid_in_one_launch_equals_the_separate_launches(gr, w, h, pack
     rng = np.random.default_rng(w * 7 + h)
     hdr_f = np.exp2(rng.uniform(-6, 6, (h, w, 4))).astype(np.float32)
     if packed:
-        hdr = capi.DeviceImage(gr, w, h, capi.FORMAT_B10G11R11_UFLOAT_PACK32).upload(orc.pack_b10g11r11(hdr_f[..., :3]))
+        hdr = capi.DeviceImage(gr, w, h, capi.FORMAT_B10G11R11_UFLOAT_PACK32).upload(orc.pack_b10g11r11(hdr_f.astype(np.float16).view(np.uint16)))
     else:
         hdr = capi.DeviceImage(gr, w, h, F16).upload(hdr_f.astype(np.float16).view(np.uint16))
     d3_size = orc.level_size(w, h, scales["d3"])

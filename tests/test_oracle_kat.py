@@ -138,6 +138,34 @@ def test_tonemap_white_point_and_black():
     assert abs(int(run(1.0)[0]) - round(srgb * 255)) <= 1
 
 
+def test_tonemap_unorm_target_differs_from_the_srgb_one_exactly_by_the_encode():
+    """orc.tonemap(out_format="rgba8_unorm") stores the linear RGB that the default (an *_SRGB target) encodes first.  Every finite non-negative
+    half as the HDR value (bloom 0, exposure 1, so the exposed colour is that half exactly): the curve restated in float32 numpy (the oracle
+    is built without contraction, so this is its arithmetic to the bit) gives r; the UNORM bytes are round-to-nearest of clamp(r) * 255, the
+    sRGB bytes are orc.float_to_srgb8(r) -- the two stores differ by the encode and by nothing else."""
+    halves = np.arange(0, 0x7c00, dtype=np.uint16)
+    hdr = np.zeros((124, 256, 4), np.uint16)
+    hdr[..., 0] = hdr[..., 1] = hdr[..., 2] = halves.reshape(124, 256)
+    hdr[..., 3] = 0x3c00
+    bloom = np.zeros((1, 1, 4), np.uint16)
+    srgb, unorm = orc.tonemap(hdr, bloom), orc.tonemap(hdr, bloom, out_format="rgba8_unorm")
+    np.testing.assert_array_equal(srgb, orc.tonemap(hdr, bloom, out_format="rgba8_srgb"))  # the default is the sRGB target
+    x = halves.view(np.float16).astype(np.float32).reshape(124, 256)
+    A, B, C_, D, E, F, W = (np.float32(v) for v in (0.15, 0.50, 0.10, 0.20, 0.02, 0.30, 11.2))
+    u2 = lambda v: ((v * (A * v + C_ * B) + D * E) / (v * (A * v + B) + D * F)) - E / F
+    r = (u2(x) * (np.float32(1.0) / u2(W))).astype(np.float32)
+    want_unorm = np.where(r > 0, np.where(r >= 1, 255, (np.minimum(r, np.float32(1.0)) * np.float32(255.0) + np.float32(0.5)).astype(np.int32)), 0)
+    for c in range(3):
+        np.testing.assert_array_equal(unorm[..., c], want_unorm.astype(np.uint8))
+        np.testing.assert_array_equal(srgb[..., c], orc.float_to_srgb8(r))
+    assert (unorm[..., 3] == 255).all() and (srgb[..., 3] == 255).all()
+    # encode(c) > c for 0 < c < 1, by more than a byte's width while the UNORM byte is 1 .. 250 (the gap closes towards 1): a larger byte there
+    inside = (unorm[..., 0] >= 1) & (unorm[..., 0] <= 250)
+    assert (srgb[..., 0] >= unorm[..., 0]).all() and (srgb[..., 0][inside] > unorm[..., 0][inside]).all() and inside.sum() > 1000
+    assert tuple(unorm[0, 0]) == (0, 0, 0, 255) and tuple(unorm[-1, -1]) == (255, 255, 255, 255)
+    assert len(np.unique(unorm[..., 0])) == 256
+
+
 # ---- lights ------------------------------------------------------------------------------------------------------------
 def one_light_scene(light_type, color=(10.0, 10.0, 10.0), light_pos_view=(0.0, 0.0, -3.0), w=64, h=36):
     cam = synth.Camera(w, h)

@@ -93,6 +93,59 @@ def test_post_chain_shaders_bit_for_bit(ref, w, h):
             np.testing.assert_array_equal(got, want, err_msg="tonemap")
 
 
+def test_post_chain_shaders_bit_for_bit_on_special_values(ref):
+    """+0, the smallest denormal, 65504 and +inf planted in each pass's input (tests/post_sweep.py plant_specials: corners, last column, tile
+    corner, interior): the oracle is the statement the GPU tests hold the kernels to on these values, so it is held to the executed shaders
+    here.  An infinite HDR texel makes inf / inf = NaN in the threshold's colour, which GLSL max(., 0) turns into 0; an infinite alpha in the
+    feedback history makes inf * 0 = NaN in mix()."""
+    import post_sweep as ps
+
+    def planted(w, h, seed):
+        bits = synth.make_hdr(w, h, seed=seed)
+        ps.plant_specials(bits)
+        return bits
+
+    hdr = planted(139, 97, 1)
+    for l in (None, np.array([0.2, 1.1, 0.9], np.float32)):
+        want = orc.bloom_threshold(hdr, 70, 49, lum3=l)
+        got = np.zeros_like(want)
+        ref.ref_bloom_threshold(ptr(hdr), 139, 97, ptr(got), 70, 49, ptr(l))
+        np.testing.assert_array_equal(got, want, err_msg="bloom_threshold")
+        assert not np.isnan(want.view(np.float16)).any() and np.isinf(want.view(np.float16)[..., 3]).any()
+    hist = planted(38, 25, 2)
+    for iw, ih in ((75, 49), (76, 50)):
+        src = planted(iw, ih, 3)
+        for h_bits in (None, hist):
+            want = orc.bloom_downsample(src, 38, 25, history=h_bits, lerp=0.0667)
+            got = np.zeros_like(want)
+            ref.ref_bloom_downsample(ptr(src), iw, ih, ptr(got), 38, 25, ptr(h_bits), 0.0667)
+            np.testing.assert_array_equal(got, want, err_msg="bloom_downsample")
+            assert np.isnan(want.view(np.float16)).any() == (h_bits is not None)
+    src = planted(38, 25, 4)
+    for ow, oh in ((75, 49), (76, 50), (38, 25)):
+        want = orc.bloom_upsample(src, ow, oh)
+        got = np.zeros_like(want)
+        ref.ref_bloom_upsample(ptr(src), 38, 25, ptr(got), ow, oh)
+        np.testing.assert_array_equal(got, want, err_msg="bloom_upsample")
+    bloom = synth.make_hdr(35, 25, seed=5)
+    for l, exposure in ((None, 0.7), (np.array([0.2, 1.1, 0.9], np.float32), 1.3)):
+        want = orc.tonemap(hdr, bloom, l, exposure)
+        got = np.zeros((97, 139, 4), np.uint8)
+        ref.ref_tonemap(ptr(hdr), 139, 97, ptr(bloom), 35, 25, ptr(l), exposure, ptr(got))
+        np.testing.assert_array_equal(got, want, err_msg="tonemap")
+    # four frames of the whole chain over one infinite texel: +inf alpha in frame 0, NaN alpha under it from frame 1 on (inf * 0 in the feedback
+    # mix, then NaN * 0), and a luminance whose clamp drops the NaN sum to min_loglum
+    frame = synth.make_hdr(136, 128, seed=77)
+    frame[61, 70, :3] = 0x7c00
+    ostate, rstate = {}, {}
+    for i in range(4):
+        want, got = orc.hdr_chain(frame, ostate), orc.hdr_chain_reference_shaders(frame, rstate)
+        for name in want:
+            np.testing.assert_array_equal(got[name], want[name], err_msg=f"frame {i} {name}")
+        assert not np.isnan(want["lum"]).any()
+        assert np.isnan(want["d3"].view(np.float16)[..., 3]).any() == (i > 0)
+
+
 def test_whole_chain_equals_hdr_chain_helper(ref):
     """The same shaders driven in orc.hdr_chain's order reproduce its outputs: the recorded order is part of the contract."""
     w, h = 192, 108

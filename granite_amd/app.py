@@ -66,6 +66,11 @@ class VideoLayout(C.Structure):
                 ("pitch", C.c_uint32 * 3), ("offset", C.c_uint64 * 3), ("frame_bytes", C.c_uint64)]
 
 
+class VideoPlayOptions(C.Structure):
+    _fields_ = [("format", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("info", capi.VideoYuvInfo),
+                ("output_format", C.c_uint32), ("ring_frames", C.c_uint32)]
+
+
 # gra_video_format
 VIDEO_FORMATS = {"nv12": 0, "yuv420p": 1, "yuv420p16": 2, "yuv444p": 3, "yuv444p16": 4, "p010": 5, "p016": 6}
 
@@ -83,6 +88,7 @@ EXPORTED_SYMBOLS = [
     "gra_upload_gbuffer_gtx", "gra_save_resource_gtx", "gra_get_render_size", "gra_upload_ambient_occlusion", "gra_upload_aa_bench_images", "gra_compute_rec709_to_display", "gra_set_exchange_callback", "gra_get_strip_plan", "gra_get_strip_plan_aa", "gra_get_strip_plan_taa_history",
     "gra_comm_create_unique_id", "gra_comm_init", "gra_comm_info", "gra_comm_init_output", "gra_install_ssr_tables", "gra_reset_timestamps", "gra_set_directional_light", "gra_set_fog", "gra_generate_mipmaps", "gra_write_resource", "gra_get_frame_state", "gra_set_frame_state",
     "gra_video_begin", "gra_video_frame_layout", "gra_video_read_frame", "gra_video_end",
+    "gra_video_play_begin", "gra_video_play_layout", "gra_video_play_frame", "gra_video_play_read_rgb", "gra_video_play_end",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -154,6 +160,11 @@ def load_library() -> C.CDLL:
         "gra_video_frame_layout": (C.c_int, [vp, P(VideoLayout)]),
         "gra_video_read_frame": (C.c_int, [vp, vp, C.c_uint64, P(C.c_int64)]),
         "gra_video_end": (C.c_int, [vp]),
+        "gra_video_play_begin": (C.c_int, [vp, P(VideoPlayOptions)]),
+        "gra_video_play_layout": (C.c_int, [vp, P(VideoLayout)]),
+        "gra_video_play_frame": (C.c_int, [vp, vp, C.c_uint64]),
+        "gra_video_play_read_rgb": (C.c_int, [vp, vp, C.c_uint64, P(C.c_int64)]),
+        "gra_video_play_end": (C.c_int, [vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)
@@ -386,6 +397,54 @@ class Application:
 
     def stop_video(self):
         self._check(self.lib.gra_video_end(self.handle))
+
+    # ---- frame playback (gra_video_play_*) ---------------------------------------------------------------------------
+    def start_playback(self, format: str, size, info: Optional["capi.VideoYuvInfo"] = None, output_format: int = capi.FORMAT_R8G8B8A8_UNORM,
+                       ring_frames: int = 0) -> VideoLayout:
+        """Packed YCbCr frames (`format`, one of VIDEO_FORMATS, at size (w, h)) handed to play_frame from now on are converted to
+        `output_format` and queued for read_playback.  info: capi.video_yuv_info(...); by default what recording writes (full range,
+        BT.709, centre-sited chroma, 8 or 16 bits)."""
+        if info is None:
+            wide = format.endswith("16") or format in ("p010", "p016")
+            info = capi.video_yuv_info(bit_depth=16 if wide else 8, full_range=1)
+        opts = VideoPlayOptions(VIDEO_FORMATS[format], int(size[0]), int(size[1]), info, int(output_format), ring_frames)
+        self._check(self.lib.gra_video_play_begin(self.handle, C.byref(opts)))
+        self._playback_shape = (int(size[1]), int(size[0]), int(output_format))
+        return self.playback_layout()
+
+    def playback_layout(self) -> VideoLayout:
+        layout = VideoLayout()
+        self._check(self.lib.gra_video_play_layout(self.handle, C.byref(layout)))
+        return layout
+
+    def play_frame(self, frame):
+        """One packed frame (bytes-like or a numpy array of exactly playback_layout().frame_bytes bytes)."""
+        buf = np.ascontiguousarray(np.frombuffer(frame, np.uint8) if not isinstance(frame, np.ndarray) else frame).view(np.uint8).reshape(-1)
+        self._check(self.lib.gra_video_play_frame(self.handle, buf.ctypes.data, buf.nbytes))
+
+    def read_playback(self):
+        """The oldest unread converted image: (image, frame_number), or None when none is pending.  image: (h, w, 4) uint8 for
+        RGBA8, (h, w) uint32 words for A2B10G10R10, (h, w, 4) fp16 bits for RGBA16F."""
+        if getattr(self, "_playback_shape", None) is None:
+            raise capi.GraniteHipError("gra_video_play_read_rgb: not playing")
+        h, w, fmt = self._playback_shape
+        buf = np.empty(h * w * capi.FORMAT_BPP[fmt], np.uint8)
+        number = C.c_int64(-1)
+        rc = self.lib.gra_video_play_read_rgb(self.handle, buf.ctypes.data, buf.nbytes, C.byref(number))
+        if rc == 1:
+            return None
+        self._check(rc)
+        if fmt == capi.FORMAT_R16G16B16A16_SFLOAT:
+            img = buf.view(np.uint16).reshape(h, w, 4)
+        elif fmt == capi.FORMAT_A2B10G10R10_UNORM_PACK32:
+            img = buf.view(np.uint32).reshape(h, w)
+        else:
+            img = buf.reshape(h, w, 4)
+        return img, int(number.value)
+
+    def end_playback(self):
+        self._check(self.lib.gra_video_play_end(self.handle))
+        self._playback_shape = None
 
     def backbuffer_info(self) -> ResourceInfo:
         info = ResourceInfo()

@@ -67,6 +67,9 @@ VIDEO_CONTROL_DITHER_BIT = 64
 VIDEO_TRANSFER_IDENTITY = 0
 VIDEO_TRANSFER_SRGB = 1
 VIDEO_TRANSFER_PQ = 2
+# gr_video_yuv_to_rgb: gr_video_yuv_info.matrix and .chroma_location
+VIDEO_MATRIX_UNSPECIFIED, VIDEO_MATRIX_BT601_525, VIDEO_MATRIX_BT601_625, VIDEO_MATRIX_BT709, VIDEO_MATRIX_BT2020, VIDEO_MATRIX_SMPTE240M = range(6)
+VIDEO_CHROMA_CENTER, VIDEO_CHROMA_LEFT, VIDEO_CHROMA_TOPLEFT, VIDEO_CHROMA_TOP, VIDEO_CHROMA_BOTTOMLEFT, VIDEO_CHROMA_BOTTOM = range(6)
 
 LIGHTING_DIRECTIONAL_BIT = 1
 LIGHTING_CLUSTERED_BIT = 2
@@ -101,6 +104,25 @@ assert C.sizeof(PushVideo) == 28
 class VideoPlan(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("eotf", C.c_uint32), ("oetf", C.c_uint32), ("num_planes", C.c_uint32), ("push", PushVideo),
                 ("gamma_space_transform", C.c_float * 12), ("primary_transform", C.c_float * 9)]
+
+
+class PushYuvToRgb(C.Structure):
+    _fields_ = [("yuv_to_rgb", C.c_float * 16), ("primary_conversion", C.c_float * 16), ("resolution", C.c_uint32 * 2),
+                ("inv_resolution", C.c_float * 2), ("chroma_siting", C.c_float * 2), ("chroma_clamp", C.c_float * 2),
+                ("unorm_rescale", C.c_float)]
+
+
+assert C.sizeof(PushYuvToRgb) == 164
+
+
+class VideoYuvInfo(C.Structure):
+    _fields_ = [("bit_depth", C.c_uint32), ("msb_aligned", C.c_uint32), ("full_range", C.c_uint32), ("matrix", C.c_uint32),
+                ("chroma_location", C.c_uint32), ("pq", C.c_uint32), ("nv21", C.c_uint32)]
+
+
+class VideoYuvPlan(C.Structure):
+    _fields_ = [("push", PushYuvToRgb), ("spec_pq", C.c_uint32), ("spec_num_planes", C.c_uint32), ("spec_nv21", C.c_uint32),
+                ("matrix", C.c_uint32)]
 
 
 class TimingEntry(C.Structure):
@@ -379,6 +401,8 @@ def load_library() -> C.CDLL:
         "gr_video_scale": (C.c_int, [vp, vp, P(Image), P(Image), C.c_uint32, C.c_uint32, C.c_uint32]),
         "gr_video_scale_plan": (C.c_int, [P(Image), P(Image), C.c_uint32, C.c_uint32, C.c_uint32, P(VideoPlan)]),
         "gr_video_scaler_weights": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_uint16)]),
+        "gr_video_yuv_to_rgb": (C.c_int, [vp, vp, P(Image), C.c_uint32, P(Image), P(VideoYuvInfo)]),
+        "gr_video_yuv_plan": (C.c_int, [P(Image), C.c_uint32, P(Image), P(VideoYuvInfo), P(VideoYuvPlan)]),
         "gr_fsr_sharpen": (C.c_int, [vp, vp, P(Image), P(Image), C.c_float]),
         "gr_mip_chain_offset": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
         "gr_mip_chain_size": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
@@ -399,7 +423,7 @@ EXPORTED_SYMBOLS = [
     "gr_cluster_spot_transform", "gr_cluster_setup", "gr_cluster_binning", "gr_cluster_z_range", "gr_cluster_front", "gr_lighting",
     "gr_smaa_set_luts", "gr_fxaa", "gr_blit", "gr_smaa_edge_detection", "gr_smaa_blend_weight", "gr_smaa_neighbor_blend", "gr_taa_resolve",
     "gr_hiz", "gr_mip_chain_offset", "gr_mip_chain_size", "gr_fsr_upscale", "gr_fsr_sharpen", "gr_fill_byte", "gr_fill_u32", "gr_pq10_encode", "gr_get_device_info", "gr_spd_downsample", "gr_debug_mix", "gr_pack_b10g11r11",
-    "gr_video_scale", "gr_video_scale_plan", "gr_video_scaler_weights",
+    "gr_video_scale", "gr_video_scale_plan", "gr_video_scaler_weights", "gr_video_yuv_to_rgb", "gr_video_yuv_plan",
 ]
 
 
@@ -434,6 +458,28 @@ def video_scaler_weights(input_width: int, input_height: int, output_width: int,
     if rc < 0:
         raise GraniteHipError(f"gr_video_scaler_weights({input_width}, {input_height}, {output_width}, {output_height}) failed")
     return out
+
+
+def video_yuv_info(bit_depth=8, msb_aligned=0, full_range=0, matrix=VIDEO_MATRIX_BT709, chroma_location=VIDEO_CHROMA_CENTER, pq=0,
+                   nv21=0) -> VideoYuvInfo:
+    return VideoYuvInfo(int(bit_depth), int(msb_aligned), int(full_range), int(matrix), int(chroma_location), int(pq), int(nv21))
+
+
+def video_yuv_plan(planes, out, info: VideoYuvInfo) -> Optional[dict]:
+    """What gr_video_yuv_to_rgb would launch (init_yuv_to_rgb's UBO and dispatch_conversion's specialization constants), computed on
+    the host; None when it refuses.  planes [(w, h, format), ...], out (w, h, format); matrices as (4, 4) indexed [col][row]."""
+    lib = load_library()
+    _, arr = _video_images((1, 1), FORMAT_R8G8B8A8_UNORM, planes)
+    dst = Image(None, int(out[0]), int(out[1]), int(out[0]) * FORMAT_BPP[out[2]], int(out[2]))
+    plan = VideoYuvPlan()
+    if lib.gr_video_yuv_plan(arr, len(planes), C.byref(dst), C.byref(info), C.byref(plan)) < 0:
+        return None
+    f = lambda v: np.array(v[:], dtype=np.float32)
+    return {"yuv_to_rgb": f(plan.push.yuv_to_rgb).reshape(4, 4), "primary_conversion": f(plan.push.primary_conversion).reshape(4, 4),
+            "resolution": tuple(plan.push.resolution), "inv_resolution": tuple(f(plan.push.inv_resolution)),
+            "chroma_siting": tuple(f(plan.push.chroma_siting)), "chroma_clamp": tuple(f(plan.push.chroma_clamp)),
+            "unorm_rescale": np.float32(plan.push.unorm_rescale), "spec_pq": plan.spec_pq, "spec_num_planes": plan.spec_num_planes,
+            "spec_nv21": plan.spec_nv21, "matrix": plan.matrix}
 
 
 class DeviceBuffer:
@@ -697,6 +743,12 @@ class Context:
         """gr_video_scale: `src` converted (and rescaled to planes[0]'s size) into 1-3 output planes (DeviceImage or Image)."""
         arr = (Image * len(planes))(*[p.desc if isinstance(p, DeviceImage) else p for p in planes])
         self.check(self.lib.gr_video_scale(self.handle, stream, src.desc, arr, len(planes), int(input_color_space), int(output_color_space)))
+
+    def video_yuv_to_rgb(self, planes, out, info: VideoYuvInfo, stream=None):
+        """gr_video_yuv_to_rgb: 1-3 YCbCr planes (DeviceImage or Image) converted into `out`."""
+        arr = (Image * len(planes))(*[p.desc if isinstance(p, DeviceImage) else p for p in planes])
+        dst = out.desc if isinstance(out, DeviceImage) else out
+        self.check(self.lib.gr_video_yuv_to_rgb(self.handle, stream, arr, len(planes), C.byref(dst), C.byref(info)))
 
     def hiz(self, depth: DeviceImage, z_transform, output_downsample: bool = False, chain: Optional[DeviceBuffer] = None,
             counter: Optional[DeviceBuffer] = None, stream=None):

@@ -785,3 +785,46 @@ int gra_video_end(gra_app *app)
 {
 	return guarded(app, [&]() { app->app->video_end(); });
 }
+
+int gra_video_play_begin(gra_app *app, const gra_video_play_options *options)
+{
+	return guarded(app, [&]() {
+		if (!options)
+			throw std::logic_error("gra_video_play_begin: options are required");
+		app->app->video_play_begin(*options);
+	});
+}
+
+int gra_video_play_layout(gra_app *app, gra_video_layout *layout)
+{
+	return guarded(app, [&]() {
+		if (!layout)
+			throw std::logic_error("gra_video_play_layout: layout is required");
+		*layout = app->app->video_play_layout();
+	});
+}
+
+int gra_video_play_frame(gra_app *app, const void *frame, uint64_t size_bytes)
+{
+	return guarded(app, [&]() {
+		if (!frame)
+			throw std::logic_error("gra_video_play_frame: frame is required");
+		app->app->video_play_frame(frame, size_bytes);
+	});
+}
+
+int gra_video_play_read_rgb(gra_app *app, void *dst_host, uint64_t size_bytes, int64_t *frame_number)
+{
+	bool got = false;
+	const int rc = guarded(app, [&]() {
+		if (!dst_host)
+			throw std::logic_error("gra_video_play_read_rgb: destination is required");
+		got = app->app->video_play_read(dst_host, size_bytes, frame_number);
+	});
+	return rc < 0 ? rc : (got ? 0 : 1);
+}
+
+int gra_video_play_end(gra_app *app)
+{
+	return guarded(app, [&]() { app->app->video_play_end(); });
+}

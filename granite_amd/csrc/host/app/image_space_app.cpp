@@ -141,6 +141,7 @@ ImageSpaceApplication::~ImageSpaceApplication()
 	if (device_holder)
 		device_holder->wait_idle();
 	video_release();
+	video_play_release();
 	for (auto &e : output_gather_done)
 		(void)hipEventDestroy(static_cast<hipEvent_t>(e.second));
 	if (output_ready_event)

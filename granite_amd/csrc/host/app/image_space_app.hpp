@@ -20,6 +20,7 @@
 #include "../render_graph.hpp"
 #include "../renderer.hpp"
 #include "../video/scaler.hpp"
+#include "../video/yuv_to_rgb.hpp"
 
 namespace Granite
 {
@@ -38,6 +39,8 @@ public:
 			device_holder->wait_idle();
 		if (video)
 			video_wait();
+		if (playback)
+			video_play_wait();
 		check_taa_history_reach();
 	}
 	// Row bands with a bounded TAA history reach: throws once a resolve has reported a fetch outside the rows this rank holds.
@@ -103,6 +106,12 @@ public:
 	void video_end();
 	const gra_video_layout &video_layout() const;
 	bool video_read(void *dst, uint64_t size, int64_t *frame_number); // false: nothing pending
+	// Frame playback (include/granite_app.h: gra_video_play_*; video_playback.cpp)
+	void video_play_begin(const gra_video_play_options &options);
+	void video_play_end();
+	const gra_video_layout &video_play_layout() const;
+	void video_play_frame(const void *frame, uint64_t size);
+	bool video_play_read(void *dst, uint64_t size, int64_t *frame_number); // false: nothing pending
 	std::string last_error;
 
 private:
@@ -190,6 +199,35 @@ private:
 	void video_before_frame(HIP::Image &backbuffer);
 	void video_after_frame(HIP::Image &backbuffer, uint64_t device_frame);
 	void video_release();
+	// The packed-frame layout and the plane formats of a gra_video_format at w x h; false for an unknown format.
+	static bool video_format_layout(uint32_t format, uint32_t w, uint32_t h, gra_video_layout &layout, uint32_t (&plane_format)[3]);
+
+	// Playback state: one device copy of the planes and one of the RGB image (upload, conversion and read-back are in order on
+	// `stream`), a ring of pinned frame / image pairs.
+	struct VideoPlayback
+	{
+		gra_video_play_options options = {};
+		gra_video_layout layout = {};
+		uint32_t plane_format[3] = {};
+		uint32_t rgb_pitch = 0;
+		uint64_t rgb_bytes = 0;
+		void *stream = nullptr;        // hipStream_t
+		void *planes = nullptr;        // device
+		void *rgb = nullptr;           // device
+		VideoYuvToRgb converter;
+		struct Slot
+		{
+			void *frame_host = nullptr; // pinned: the packed frame as handed over
+			void *rgb_host = nullptr;   // pinned: the converted image
+			void *converted = nullptr;  // hipEvent_t: the copy into `rgb_host` is done
+			int64_t frame = -1;
+		};
+		std::vector<Slot> ring;
+		uint64_t written = 0, read = 0; // frames handed over / handed back
+	};
+	std::unique_ptr<VideoPlayback> playback;
+	void video_play_wait();
+	void video_play_release();
 
 	void bake_render_graph();
 	void add_main_pass_deferred(const std::string &tag);

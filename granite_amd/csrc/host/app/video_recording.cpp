@@ -27,6 +27,39 @@ void hip_check(hipError_t err, const char *what)
 }
 } // namespace
 
+bool ImageSpaceApplication::video_format_layout(uint32_t f, uint32_t w, uint32_t h, gra_video_layout &l, uint32_t (&plane_format)[3])
+{
+	if (f > GRA_VIDEO_P016)
+		return false;
+	const bool wide = f == GRA_VIDEO_YUV420P16 || f == GRA_VIDEO_YUV444P16 || f == GRA_VIDEO_P010 || f == GRA_VIDEO_P016;
+	const bool sub = f != GRA_VIDEO_YUV444P && f != GRA_VIDEO_YUV444P16;
+	const bool two = f == GRA_VIDEO_NV12 || f == GRA_VIDEO_P010 || f == GRA_VIDEO_P016;
+	const uint32_t cw = sub ? (w + 1) / 2 : w, ch = sub ? (h + 1) / 2 : h;
+	const uint32_t bps = wide ? 2u : 1u;
+	l = {};
+	l.num_planes = two ? 2u : 3u;
+	l.bytes_per_sample = bps;
+	l.width[0] = w;
+	l.height[0] = h;
+	l.pitch[0] = w * bps;
+	plane_format[0] = wide ? GR_FORMAT_R16_UNORM : GR_FORMAT_R8_UNORM;
+	for (uint32_t i = 1; i < l.num_planes; i++)
+	{
+		l.width[i] = cw;
+		l.height[i] = ch;
+		l.pitch[i] = cw * bps * (two ? 2u : 1u);
+		plane_format[i] = two ? (wide ? GR_FORMAT_R16G16_UNORM : GR_FORMAT_R8G8_UNORM) : plane_format[0];
+	}
+	uint64_t offset = 0;
+	for (uint32_t i = 0; i < l.num_planes; i++)
+	{
+		l.offset[i] = offset;
+		offset += uint64_t(l.pitch[i]) * l.height[i];
+	}
+	l.frame_bytes = offset;
+	return true;
+}
+
 void ImageSpaceApplication::video_begin(const gra_video_options &options)
 {
 	if (video)
@@ -42,33 +75,8 @@ void ImageSpaceApplication::video_begin(const gra_video_options &options)
 	rec->options = options;
 	const uint32_t w = options.width ? options.width : config.width;
 	const uint32_t h = options.height ? options.height : config.height;
-	const uint32_t f = options.format;
-	const bool wide = f == GRA_VIDEO_YUV420P16 || f == GRA_VIDEO_YUV444P16 || f == GRA_VIDEO_P010 || f == GRA_VIDEO_P016;
-	const bool sub = f != GRA_VIDEO_YUV444P && f != GRA_VIDEO_YUV444P16;
-	const bool two = f == GRA_VIDEO_NV12 || f == GRA_VIDEO_P010 || f == GRA_VIDEO_P016;
-	const uint32_t cw = sub ? (w + 1) / 2 : w, ch = sub ? (h + 1) / 2 : h;
-	const uint32_t bps = wide ? 2u : 1u;
+	video_format_layout(options.format, w, h, rec->layout, rec->plane_format);
 	gra_video_layout &l = rec->layout;
-	l.num_planes = two ? 2u : 3u;
-	l.bytes_per_sample = bps;
-	l.width[0] = w;
-	l.height[0] = h;
-	l.pitch[0] = w * bps;
-	rec->plane_format[0] = wide ? GR_FORMAT_R16_UNORM : GR_FORMAT_R8_UNORM;
-	for (uint32_t i = 1; i < l.num_planes; i++)
-	{
-		l.width[i] = cw;
-		l.height[i] = ch;
-		l.pitch[i] = cw * bps * (two ? 2u : 1u);
-		rec->plane_format[i] = two ? (wide ? GR_FORMAT_R16G16_UNORM : GR_FORMAT_R8G8_UNORM) : rec->plane_format[0];
-	}
-	uint64_t offset = 0;
-	for (uint32_t i = 0; i < l.num_planes; i++)
-	{
-		l.offset[i] = offset;
-		offset += uint64_t(l.pitch[i]) * l.height[i];
-	}
-	l.frame_bytes = offset;
 
 	// The conversion's arguments are checked now, not at the first frame (gr_video_scale_plan needs no device).
 	gr_image input = {nullptr, config.width, config.height, config.width * 4u, uint32_t(backbuffer_format())};

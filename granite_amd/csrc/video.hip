@@ -934,3 +934,393 @@ extern "C" int gr_video_scale(gr_ctx *ctx, gr_stream stream, const gr_image *inp
 	GR_CHECK_LAUNCH(ctx);
 	return GR_OK;
 }
+
+// ---- playback: YCbCr planes -> RGB -------------------------------------------------------------------------------------------
+// VideoDecoder::Impl::init_yuv_to_rgb / dispatch_conversion (video/ffmpeg_decode.cpp) + assets/shaders/util/yuv_to_rgb.comp.  The
+// reference runs one invocation per output pixel with a nearest sampler on the luma plane and LinearClamp ones on the chroma planes;
+// here k_yuv_to_rgb is a pure stream shaped like k_video_direct: one lane converts 4 x 2 pixels, i.e. whole 2 x 2 chroma footprints
+// of a 4:2:0 frame: one 4-B luma load per row (8 B at 16 bits), the chroma taps filtered in software over the linear planes with
+// the library's sampler model (sample_linear_with: exact fp32 weights, 2^-8 texel snap), and one 16-B store per row (two for
+// RGBA16F).  The chroma coordinate keeps the shader's order -- min((coord + siting) * inv_resolution, chroma_clamp), then times the
+// plane's own size -- because the chroma plane of an odd-sized 4:2:0 frame is ceil(n / 2) texels wide: the ratio is not 0.5.
+// Unaligned pointers or pitches, and the last columns of a row, go element by element.  Everything in fp32; no LDS.
+namespace
+{
+enum YuvOut : int
+{
+	YUV_OUT_RGBA8 = 0,
+	YUV_OUT_A2B10G10R10 = 1,
+	YUV_OUT_RGBA16F = 2, // with the PQ specialization: EOTF + primary conversion instead of the dither
+};
+
+struct YuvArgs
+{
+	const uint8_t *plane[3];
+	uint32_t pitch[3];
+	int w, h;           // resolution: the luma plane's and the output's size
+	int cw, ch;         // chroma plane size
+	uint8_t *out;
+	uint32_t out_pitch;
+	uint32_t aligned;   // bit 0: the luma plane's pointer and pitch are multiples of 16 B (vector loads); bit 3: the output's (vector stores)
+	uint32_t nv21;
+	float m[12];        // yuv_to_rgb, row major 3 x 4: R, G, B of [Y Cb Cr 1]
+	float prim[9];      // primary_conversion, column major 3 x 3
+	float inv_resolution[2], chroma_siting[2], chroma_clamp[2];
+	float unorm_rescale;
+};
+
+template <bool WIDE> __device__ __forceinline__ float unorm_sample(uint32_t v)
+{
+	return WIDE ? float(v) * (1.0f / 65535.0f) : unorm8_to_float(v);
+}
+
+// four luma samples of one row from x0 (a multiple of 4); samples beyond the row read as zero and are never stored
+template <bool WIDE>
+__device__ __forceinline__ void load_luma4(const YuvArgs &a, int x0, int y, float (&v)[DIRECT_PX])
+{
+	typedef typename Sample<WIDE>::type S;
+	const S *row = reinterpret_cast<const S *>(a.plane[0] + size_t(y) * a.pitch[0]);
+	if ((a.aligned & 1u) && x0 + DIRECT_PX <= a.w)
+	{
+		if (WIDE)
+		{
+			const u32x2 q = *reinterpret_cast<const u32x2 *>(row + x0);
+			v[0] = unorm_sample<true>(q.x & 0xffffu);
+			v[1] = unorm_sample<true>(q.x >> 16);
+			v[2] = unorm_sample<true>(q.y & 0xffffu);
+			v[3] = unorm_sample<true>(q.y >> 16);
+		}
+		else
+		{
+			const uint32_t q = *reinterpret_cast<const uint32_t *>(row + x0);
+#pragma unroll
+			for (int i = 0; i < DIRECT_PX; i++)
+				v[i] = unorm_sample<false>((q >> (8 * i)) & 255u);
+		}
+		return;
+	}
+#pragma unroll
+	for (int i = 0; i < DIRECT_PX; i++)
+		v[i] = x0 + i < a.w ? unorm_sample<WIDE>(row[x0 + i]) : 0.0f;
+}
+
+// one chroma texel (x, y inside the plane) as (first channel, second channel): the two planes of a three-plane frame, or the pair of
+// an interleaved one
+template <int PLANES, bool WIDE>
+__device__ __forceinline__ float4 fetch_chroma(const YuvArgs &a, int x, int y)
+{
+	typedef typename Sample<WIDE>::type S;
+	if (PLANES == 3)
+	{
+		const S u = reinterpret_cast<const S *>(a.plane[1] + size_t(y) * a.pitch[1])[x];
+		const S v = reinterpret_cast<const S *>(a.plane[2] + size_t(y) * a.pitch[2])[x];
+		return make_float4(unorm_sample<WIDE>(u), unorm_sample<WIDE>(v), 0.0f, 0.0f);
+	}
+	const S *p = reinterpret_cast<const S *>(a.plane[1] + size_t(y) * a.pitch[1]) + 2 * x;
+	return make_float4(unorm_sample<WIDE>(p[0]), unorm_sample<WIDE>(p[1]), 0.0f, 0.0f);
+}
+
+// yuv_to_rgb.comp's EOTF: ST 2084 to scRGB units (80 nits = 1)
+__device__ __forceinline__ float pq_to_scrgb(float v) { return pq_eotf(v) * (1.0f / 80.0f); }
+
+template <int PLANES, bool WIDE, int OUT>
+__global__ __launch_bounds__(256) void k_yuv_to_rgb(YuvArgs a)
+{
+	const int x0 = (blockIdx.x * 64 + (threadIdx.x & 63)) * DIRECT_PX;
+	const int y0 = (blockIdx.y * DIRECT_ROWS + (threadIdx.x >> 6)) * 2;
+	if (x0 >= a.w || y0 >= a.h)
+		return;
+
+	float luma[2][DIRECT_PX];
+	load_luma4<WIDE>(a, x0, y0, luma[0]);
+	if (y0 + 1 < a.h)
+		load_luma4<WIDE>(a, x0, y0 + 1, luma[1]);
+
+#pragma unroll
+	for (int r = 0; r < 2; r++)
+	{
+		const int y = y0 + r;
+		if (y >= a.h)
+			break;
+		uint32_t words[DIRECT_PX], words_hi[DIRECT_PX]; // RGBA16F: R G / B A
+#pragma unroll
+		for (int i = 0; i < DIRECT_PX; i++)
+		{
+			const int x = min(x0 + i, a.w - 1); // columns beyond the row repeat the last one and are dropped by the store
+			float cb = 128.0f / 255.0f, cr = 128.0f / 255.0f;
+			if (PLANES > 1)
+			{
+				const float u = fminf((float(x) + a.chroma_siting[0]) * a.inv_resolution[0], a.chroma_clamp[0]);
+				const float v = fminf((float(y) + a.chroma_siting[1]) * a.inv_resolution[1], a.chroma_clamp[1]);
+				const float4 c = sample_linear_with([&a](int cx, int cy) { return fetch_chroma<PLANES, WIDE>(a, cx, cy); }, a.cw, a.ch, u, v);
+				cb = a.nv21 ? c.y : c.x;
+				cr = a.nv21 ? c.x : c.y;
+			}
+			const float yy = luma[r][i] * a.unorm_rescale;
+			cb *= a.unorm_rescale;
+			cr *= a.unorm_rescale;
+			float rgb[3];
+#pragma unroll
+			for (int k = 0; k < 3; k++)
+				rgb[k] = saturatef(fmaf(a.m[4 * k], yy, fmaf(a.m[4 * k + 1], cb, fmaf(a.m[4 * k + 2], cr, a.m[4 * k + 3]))));
+
+			if (OUT == YUV_OUT_RGBA16F)
+			{
+				const float lr = pq_to_scrgb(rgb[0]), lg = pq_to_scrgb(rgb[1]), lb = pq_to_scrgb(rgb[2]);
+				const float4 o = make_float4(a.prim[0] * lr + a.prim[3] * lg + a.prim[6] * lb, a.prim[1] * lr + a.prim[4] * lg + a.prim[7] * lb,
+				                             a.prim[2] * lr + a.prim[5] * lg + a.prim[8] * lb, 1.0f);
+				const u32x2 h = __builtin_bit_cast(u32x2, pack_rgba16f(o));
+				words[i] = h.x;
+				words_hi[i] = h.y;
+			}
+			else
+			{
+				const float d = dither_at(x, y) * (1.0f / 255.0f);
+				if (OUT == YUV_OUT_A2B10G10R10)
+					words[i] = unorm_code(rgb[0] + d, 1023.0f) | (unorm_code(rgb[1] + d, 1023.0f) << 10) | (unorm_code(rgb[2] + d, 1023.0f) << 20) | (3u << 30);
+				else
+					words[i] = unorm_code(rgb[0] + d, 255.0f) | (unorm_code(rgb[1] + d, 255.0f) << 8) | (unorm_code(rgb[2] + d, 255.0f) << 16) | (255u << 24);
+			}
+		}
+		uint8_t *row = a.out + size_t(y) * a.out_pitch;
+		if (OUT == YUV_OUT_RGBA16F)
+		{
+			const uint32_t lo[4] = {words[0], words_hi[0], words[1], words_hi[1]}, hi[4] = {words[2], words_hi[2], words[3], words_hi[3]};
+			store_run<uint32_t, 4>(row, 2 * x0, 2 * a.w, lo, a.aligned & 8u);
+			store_run<uint32_t, 4>(row, 2 * x0 + 4, 2 * a.w, hi, a.aligned & 8u);
+		}
+		else
+			store_run<uint32_t, DIRECT_PX>(row, x0, a.w, words, a.aligned & 8u);
+	}
+}
+
+// ---- host: the decisions of init_yuv_to_rgb and dispatch_conversion -----------------------------------------------------------------
+struct Mat4
+{
+	float c[4][4]; // column major
+};
+
+Mat4 identity4()
+{
+	Mat4 r = {};
+	for (int i = 0; i < 4; i++)
+		r.c[i][i] = 1.0f;
+	return r;
+}
+
+// columns of a * b summed in column order, one rounding per operation (the order of muglm's mat4 * vec4)
+Mat4 mul4(const Mat4 &a, const Mat4 &b)
+{
+	Mat4 r;
+	for (int col = 0; col < 4; col++)
+		for (int row = 0; row < 4; row++)
+			r.c[col][row] = a.c[0][row] * b.c[col][0] + a.c[1][row] * b.c[col][1] + a.c[2][row] * b.c[col][2] + a.c[3][row] * b.c[col][3];
+	return r;
+}
+
+Mat4 widen(const Mat3 &m)
+{
+	Mat4 r = identity4();
+	for (int col = 0; col < 3; col++)
+		for (int row = 0; row < 3; row++)
+			r.c[col][row] = m.c[col][row];
+	return r;
+}
+
+const char *plan_yuv(const gr_image *planes, uint32_t num_planes, const gr_image *out, const gr_video_yuv_info *info, struct gr_video_yuv_plan *p)
+{
+	if (!planes || !out || !info || !p)
+		return "null argument";
+	if (num_planes < 1 || num_planes > 3)
+		return "num_planes must be 1, 2 or 3";
+	const gr_image &y = planes[0];
+	if (!y.width || !y.height || y.width > 65535 || y.height > 65535)
+		return "bad luma extent";
+	const bool wide = y.format == GR_FORMAT_R16_UNORM;
+	if (y.format != GR_FORMAT_R8_UNORM && !wide)
+		return "the luma plane must be R8_UNORM or R16_UNORM";
+	if (info->bit_depth != 8 && info->bit_depth != 10 && info->bit_depth != 16)
+		return "bit_depth must be 8, 10 or 16";
+	if ((info->bit_depth == 8) == wide)
+		return "8 bits need R8 planes, 10 and 16 bits R16 planes";
+	if (info->matrix > GR_VIDEO_MATRIX_SMPTE240M)
+		return "unknown matrix";
+	if (info->chroma_location > GR_VIDEO_CHROMA_BOTTOM)
+		return "unknown chroma location";
+	if (info->nv21 && num_planes != 2)
+		return "nv21 needs two planes";
+	bool sub = false;
+	if (num_planes > 1)
+	{
+		const gr_image &c = planes[1];
+		sub = c.width < y.width || c.height < y.height;
+		if (sub ? (c.width != (y.width + 1) / 2 || c.height != (y.height + 1) / 2) : (c.width != y.width || c.height != y.height))
+			return "chroma planes must have the luma plane's size or half of it, rounded up";
+		const uint32_t want = num_planes == 2 ? (wide ? GR_FORMAT_R16G16_UNORM : GR_FORMAT_R8G8_UNORM) : y.format;
+		for (uint32_t i = 1; i < num_planes; i++)
+			if (planes[i].format != want || planes[i].width != c.width || planes[i].height != c.height)
+				return "chroma plane format or size does not match the luma plane";
+	}
+	for (uint32_t i = 0; i < num_planes; i++)
+		if (planes[i].pitch_bytes < planes[i].width * texel_bytes(planes[i].format))
+			return "plane pitch smaller than its row";
+	const bool rgba8 = out->format == GR_FORMAT_R8G8B8A8_UNORM || out->format == GR_FORMAT_R8G8B8A8_SRGB;
+	if (!rgba8 && out->format != GR_FORMAT_A2B10G10R10_UNORM_PACK32 && out->format != GR_FORMAT_R16G16B16A16_SFLOAT)
+		return "output format must be R8G8B8A8_{UNORM,SRGB}, A2B10G10R10_UNORM_PACK32 or R16G16B16A16_SFLOAT";
+	if (rgba8 == (info->pq != 0))
+		return "PQ content goes to A2B10G10R10 (left encoded) or R16G16B16A16_SFLOAT, everything else to R8G8B8A8";
+	if (out->width != y.width || out->height != y.height)
+		return "the output must have the luma plane's size";
+	if (out->pitch_bytes < out->width * texel_bytes(out->format))
+		return "output pitch smaller than its row";
+
+	memset(p, 0, sizeof(*p));
+	p->spec_pq = out->format == GR_FORMAT_R16G16B16A16_SFLOAT;
+	p->spec_num_planes = num_planes;
+	p->spec_nv21 = info->nv21 != 0;
+	gr_push_yuv_to_rgb &push = p->push;
+	push.resolution[0] = y.width;
+	push.resolution[1] = y.height;
+	push.inv_resolution[0] = 1.0f / float(y.width);
+	push.inv_resolution[1] = 1.0f / float(y.height);
+	const float half_texel = 0.5f * float(1u << (sub ? 1 : 0));
+	push.chroma_clamp[0] = (float(y.width) - half_texel) * push.inv_resolution[0];
+	push.chroma_clamp[1] = (float(y.height) - half_texel) * push.inv_resolution[1];
+	static const float sitings[6][2] = {{0.5f, 0.5f}, {1.0f, 0.5f}, {1.0f, 1.0f}, {0.5f, 1.0f}, {1.0f, 0.0f}, {0.5f, 0.0f}};
+	push.chroma_siting[0] = sitings[info->chroma_location][0];
+	push.chroma_siting[1] = sitings[info->chroma_location][1];
+	push.unorm_rescale = info->bit_depth != 10 ? 1.0f : info->msb_aligned ? float(0xffff) / float(1023 << 6) : float(0xffff) / float(1023);
+
+	// Vulkan 16.3.9 / Khronos Data Format Specification 15.1.1: bias and narrow-range scale for the bit depth
+	const int depth = int(info->bit_depth);
+	const int luma_offset = (info->full_range ? 0 : 16) << (depth - 8);
+	const int luma_narrow_range = 219 << (depth - 8), chroma_narrow_range = 224 << (depth - 8);
+	const float midpoint = float(1 << (depth - 1));
+	const float unorm_range = float((1 << depth) - 1);
+	const float unorm_divider = 1.0f / unorm_range;
+	const float chroma_shift = -midpoint * unorm_divider;
+	const float luma_scale = unorm_range / float(luma_narrow_range), chroma_scale = unorm_range / float(chroma_narrow_range);
+	const float bias[3] = {float(-luma_offset) * unorm_divider, chroma_shift, chroma_shift};
+	const float scale[3] = {info->full_range ? 1.0f : luma_scale, info->full_range ? 1.0f : chroma_scale, info->full_range ? 1.0f : chroma_scale};
+
+	uint32_t matrix = info->matrix;
+	if (matrix == GR_VIDEO_MATRIX_UNSPECIFIED)
+		matrix = y.height < 625 ? GR_VIDEO_MATRIX_BT601_525 : y.height < 720 ? GR_VIDEO_MATRIX_BT601_625 : y.height < 2160 ? GR_VIDEO_MATRIX_BT709 : GR_VIDEO_MATRIX_BT2020;
+	p->matrix = matrix;
+
+	static const float prim709[4][2] = {{0.640f, 0.330f}, {0.300f, 0.600f}, {0.150f, 0.060f}, {0.3127f, 0.3290f}};
+	static const float prim601_625[4][2] = {{0.640f, 0.330f}, {0.290f, 0.600f}, {0.150f, 0.060f}, {0.3127f, 0.3290f}};
+	static const float prim601_525[4][2] = {{0.630f, 0.340f}, {0.310f, 0.595f}, {0.155f, 0.070f}, {0.3127f, 0.3290f}};
+	static const float prim2020[4][2] = {{0.708f, 0.292f}, {0.170f, 0.797f}, {0.131f, 0.046f}, {0.3127f, 0.3290f}};
+	// columns: what Y, Cb and Cr contribute to (R, G, B)
+	Mat3 m = {};
+	const float (*source)[4][2] = nullptr;
+	m.c[0][0] = m.c[0][1] = m.c[0][2] = 1.0f;
+	switch (matrix)
+	{
+	case GR_VIDEO_MATRIX_BT2020:
+		m.c[1][1] = -0.11156702f / 0.6780f;
+		m.c[1][2] = 1.8814f;
+		m.c[2][0] = 1.4746f;
+		m.c[2][1] = -0.38737742f / 0.6780f;
+		source = &prim2020;
+		break;
+	case GR_VIDEO_MATRIX_BT601_525:
+	case GR_VIDEO_MATRIX_BT601_625:
+		m.c[1][1] = -0.202008f / 0.587f;
+		m.c[1][2] = 1.772f;
+		m.c[2][0] = 1.402f;
+		m.c[2][1] = -0.419198f / 0.587f;
+		source = matrix == GR_VIDEO_MATRIX_BT601_625 ? &prim601_625 : &prim601_525;
+		break;
+	case GR_VIDEO_MATRIX_SMPTE240M:
+		m.c[1][1] = -0.58862f / 0.701f;
+		m.c[1][2] = 1.826f;
+		m.c[2][0] = 1.576f;
+		m.c[2][1] = -0.334112f / 0.701f;
+		source = &prim601_525;
+		break;
+	default: // BT.709: sRGB shares its primaries
+		m.c[1][1] = -0.13397432f / 0.7152f;
+		m.c[1][2] = 1.8556f;
+		m.c[2][0] = 1.5748f;
+		m.c[2][1] = -0.33480248f / 0.7152f;
+		break;
+	}
+	const Mat4 conversion = source ? widen(mul3(inverse3(xyz_matrix(prim709)), xyz_matrix(*source))) : identity4();
+	Mat4 scaling = identity4(), translation = identity4();
+	for (int i = 0; i < 3; i++)
+	{
+		scaling.c[i][i] = scale[i];
+		translation.c[3][i] = bias[i];
+	}
+	const Mat4 to_rgb = mul4(mul4(widen(m), scaling), translation);
+	memcpy(push.yuv_to_rgb, to_rgb.c, sizeof(push.yuv_to_rgb));
+	memcpy(push.primary_conversion, conversion.c, sizeof(push.primary_conversion));
+	return nullptr;
+}
+} // namespace
+
+extern "C" int gr_video_yuv_plan(const gr_image *planes, uint32_t num_planes, const gr_image *out, const gr_video_yuv_info *info,
+                                 struct gr_video_yuv_plan *plan)
+{
+	return plan_yuv(planes, num_planes, out, info, plan) ? GR_ERR_INVALID_ARGUMENT : GR_OK;
+}
+
+extern "C" int gr_video_yuv_to_rgb(gr_ctx *ctx, gr_stream stream, const gr_image *planes, uint32_t num_planes, const gr_image *out,
+                                   const gr_video_yuv_info *info)
+{
+	if (!ctx)
+		return GR_ERR_INVALID_ARGUMENT;
+	struct gr_video_yuv_plan plan;
+	if (const char *why = plan_yuv(planes, num_planes, out, info, &plan))
+		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_video_yuv_to_rgb: %s", why);
+	GR_CHECK_ARG(ctx, out->ptr);
+	for (uint32_t i = 0; i < num_planes; i++)
+		GR_CHECK_ARG(ctx, planes[i].ptr);
+
+	YuvArgs a = {};
+	const auto aligned16 = [](const void *ptr, uint32_t pitch) { return (reinterpret_cast<uintptr_t>(ptr) & 15u) == 0 && (pitch & 15u) == 0; };
+	for (uint32_t i = 0; i < num_planes; i++)
+	{
+		a.plane[i] = static_cast<const uint8_t *>(planes[i].ptr);
+		a.pitch[i] = planes[i].pitch_bytes;
+	}
+	a.w = int(planes[0].width);
+	a.h = int(planes[0].height);
+	a.cw = num_planes > 1 ? int(planes[1].width) : 0;
+	a.ch = num_planes > 1 ? int(planes[1].height) : 0;
+	a.out = static_cast<uint8_t *>(out->ptr);
+	a.out_pitch = out->pitch_bytes;
+	a.aligned = (aligned16(planes[0].ptr, planes[0].pitch_bytes) ? 1u : 0u) | (aligned16(out->ptr, out->pitch_bytes) ? 8u : 0u);
+	a.nv21 = plan.spec_nv21;
+	const gr_push_yuv_to_rgb &push = plan.push;
+	for (int row = 0; row < 3; row++)
+		for (int col = 0; col < 4; col++)
+			a.m[4 * row + col] = push.yuv_to_rgb[4 * col + row];
+	for (int col = 0; col < 3; col++)
+		for (int row = 0; row < 3; row++)
+			a.prim[3 * col + row] = push.primary_conversion[4 * col + row];
+	memcpy(a.inv_resolution, push.inv_resolution, sizeof(a.inv_resolution));
+	memcpy(a.chroma_siting, push.chroma_siting, sizeof(a.chroma_siting));
+	memcpy(a.chroma_clamp, push.chroma_clamp, sizeof(a.chroma_clamp));
+	a.unorm_rescale = push.unorm_rescale;
+
+	const bool wide = planes[0].format == GR_FORMAT_R16_UNORM;
+	const int kind = out->format == GR_FORMAT_R16G16B16A16_SFLOAT ? YUV_OUT_RGBA16F : out->format == GR_FORMAT_A2B10G10R10_UNORM_PACK32 ? YUV_OUT_A2B10G10R10 : YUV_OUT_RGBA8;
+	hipStream_t s = gr_to_stream(stream);
+	gr_scoped_timing timing{ctx, s, "video_yuv_to_rgb"};
+	const dim3 grid(gr_div_up(planes[0].width, 64 * DIRECT_PX), gr_div_up(planes[0].height, 2 * DIRECT_ROWS)), block(256);
+#define YUV_KERNEL_CASE(planes_, wide_, out_)                                                                                  \
+	case (planes_) * 8 + (wide_) * 4 + (out_): hipLaunchKernelGGL((k_yuv_to_rgb<planes_, wide_ != 0, out_>), grid, block, 0, s, a); break;
+#define YUV_KERNEL_OUTPUTS(planes_, wide_) YUV_KERNEL_CASE(planes_, wide_, 0) YUV_KERNEL_CASE(planes_, wide_, 1) YUV_KERNEL_CASE(planes_, wide_, 2)
+	switch (int(num_planes) * 8 + (wide ? 4 : 0) + kind)
+	{
+		YUV_KERNEL_OUTPUTS(1, 0) YUV_KERNEL_OUTPUTS(1, 1) YUV_KERNEL_OUTPUTS(2, 0) YUV_KERNEL_OUTPUTS(2, 1) YUV_KERNEL_OUTPUTS(3, 0) YUV_KERNEL_OUTPUTS(3, 1)
+	default: return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_video_yuv_to_rgb: unsupported plane layout");
+	}
+#undef YUV_KERNEL_OUTPUTS
+#undef YUV_KERNEL_CASE
+	GR_CHECK_LAUNCH(ctx);
+	return GR_OK;
+}

@@ -10,6 +10,7 @@
 
 #include <stddef.h>
 #include <stdint.h>
+#include "granite_hip.h" /* gr_video_yuv_info */
 
 #ifdef __cplusplus
 extern "C" {
@@ -344,6 +345,29 @@ int gra_video_frame_layout(gra_app *app, gra_video_layout *layout);
  * gra_video_begin, from 0); 1: no frame pending; negative: error. */
 int gra_video_read_frame(gra_app *app, void *dst_host, uint64_t size_bytes, int64_t *frame_number);
 int gra_video_end(gra_app *app);
+
+/* ---- frame playback (VideoDecoder's upload + dispatch_conversion, ffmpeg_decode.cpp, without demuxer and decoder) ------------------
+ * The other direction: packed YCbCr frames in the layout recording produces (`format` at width x height, gra_video_play_layout) are
+ * uploaded and converted to RGB by gr_video_yuv_to_rgb on a stream of the player's own; the images come back in order through a
+ * ring of pinned host buffers.  No device sync on this path.  Not available with row bands (strip_count > 1). */
+typedef struct gra_video_play_options
+{
+	uint32_t format;        /* gra_video_format of the frames handed over */
+	uint32_t width, height; /* of the frames and of the RGB images */
+	gr_video_yuv_info info; /* what a decoder knows about the stream; recorded frames are full range, centre-sited, 8 or 16 bits */
+	uint32_t output_format; /* GR_FORMAT_R8G8B8A8_UNORM / _SRGB; with info.pq: A2B10G10R10_UNORM_PACK32 or R16G16B16A16_SFLOAT */
+	uint32_t ring_frames;   /* unread images held; 0 = 8 */
+} gra_video_play_options;
+int gra_video_play_begin(gra_app *app, const gra_video_play_options *options);
+int gra_video_play_layout(gra_app *app, gra_video_layout *layout);
+/* One frame of exactly gra_video_play_layout's frame_bytes: copied before the call returns, then uploaded and converted
+ * asynchronously.  Fails when `ring_frames` images are unread: images are never overwritten or dropped. */
+int gra_video_play_frame(gra_app *app, const void *frame, uint64_t size_bytes);
+/* The oldest unread image (width x height texels of output_format, tightly packed), in order: waits for that frame's conversion and
+ * copy only.  0: copied (frame_number = the frame's index since gra_video_play_begin, from 0); 1: none pending; negative: error. */
+int gra_video_play_read_rgb(gra_app *app, void *dst_host, uint64_t size_bytes, int64_t *frame_number);
+/* Frames still in flight are drained (the player's stream only), then everything is released. */
+int gra_video_play_end(gra_app *app);
 
 #ifdef __cplusplus
 }

@@ -725,6 +725,68 @@ int gr_video_scale_plan(const gr_image *input, const gr_image *planes, uint32_t 
                         uint32_t output_color_space, gr_video_plan *plan);
 int gr_video_scaler_weights(uint32_t input_width, uint32_t input_height, uint32_t output_width, uint32_t output_height, uint16_t *out);
 
+/* ---- video frame playback -------------------------------------------------------------------------------------------------
+ * VideoDecoder::Impl::init_yuv_to_rgb + dispatch_conversion (video/ffmpeg_decode.cpp) + assets/shaders/util/yuv_to_rgb.comp: what
+ * the decoder does to every decoded frame, minus the decoder.  planes:
+ *   1 plane   R8_UNORM / R16_UNORM luma only (chroma is the constant 128 / 255);
+ *   2 planes  R8 + R8G8 (NV12 / NV21) or R16_UNORM + R16G16_UNORM (P010 / P016): Y and interleaved chroma;
+ *   3 planes  R8 x 3 or R16_UNORM x 3: Y, Cb, Cr.
+ * Chroma planes have the luma plane's size (4:4:4) or half of it rounded up (4:2:0).  Luma is fetched nearest, chroma bilinearly
+ * (LinearClamp, the library's sampler model) at min((coord + chroma_siting) * inv_resolution, chroma_clamp).  out has the luma
+ * plane's size and is
+ *   R8G8B8A8_UNORM / _SRGB        (info.pq == 0) the non-linear code, stored through the UNORM view, 4 x 4 ordered dither;
+ *   A2B10G10R10_UNORM_PACK32      (info.pq != 0) PQ content left encoded, dither still added as the reference does;
+ *   R16G16B16A16_SFLOAT           (info.pq != 0) ST 2084 EOTF, scaled to scRGB (80 nits = 1), then primary_conversion.
+ * Any row pitch and byte offset; everything else is refused with GR_ERR_INVALID_ARGUMENT before anything is launched. */
+#define GR_VIDEO_MATRIX_UNSPECIFIED 0u /* by height: < 625 BT.601-525, < 720 BT.601-625, < 2160 BT.709, else BT.2020 */
+#define GR_VIDEO_MATRIX_BT601_525 1u
+#define GR_VIDEO_MATRIX_BT601_625 2u
+#define GR_VIDEO_MATRIX_BT709 3u
+#define GR_VIDEO_MATRIX_BT2020 4u
+#define GR_VIDEO_MATRIX_SMPTE240M 5u
+#define GR_VIDEO_CHROMA_CENTER 0u      /* chroma_siting (0.5, 0.5); also what an unspecified location means */
+#define GR_VIDEO_CHROMA_LEFT 1u        /* (1.0, 0.5) */
+#define GR_VIDEO_CHROMA_TOPLEFT 2u     /* (1.0, 1.0) */
+#define GR_VIDEO_CHROMA_TOP 3u         /* (0.5, 1.0) */
+#define GR_VIDEO_CHROMA_BOTTOMLEFT 4u  /* (1.0, 0.0) */
+#define GR_VIDEO_CHROMA_BOTTOM 5u      /* (0.5, 0.0) */
+/* yuv_to_rgb.comp UBO (std140), byte-identical */
+typedef struct gr_push_yuv_to_rgb
+{
+	float yuv_to_rgb[16];         /* column major: M * scale(yuv_scale) * translate(yuv_bias) */
+	float primary_conversion[16]; /* column major: source primaries -> BT.709 */
+	uint32_t resolution[2];
+	float inv_resolution[2];
+	float chroma_siting[2];
+	float chroma_clamp[2];
+	float unorm_rescale;
+} gr_push_yuv_to_rgb;
+/* What the decoder knows about the stream */
+typedef struct gr_video_yuv_info
+{
+	uint32_t bit_depth;       /* 8 (R8 planes), 10 or 16 (R16 planes) */
+	uint32_t msb_aligned;     /* 10 bits only: 1 = in the high bits (P010), 0 = in the low bits (software decoders' YUV420P10) */
+	uint32_t full_range;
+	uint32_t matrix;          /* GR_VIDEO_MATRIX_* */
+	uint32_t chroma_location; /* GR_VIDEO_CHROMA_* */
+	uint32_t pq;              /* transfer function is ST 2084 */
+	uint32_t nv21;            /* 2 planes: the chroma plane holds Cr Cb */
+} gr_video_yuv_info;
+/* Everything init_yuv_to_rgb and dispatch_conversion decide for one conversion: the UBO and the three specialization constants.
+ * (A struct tag without a typedef: the function below carries the same name.) */
+struct gr_video_yuv_plan
+{
+	gr_push_yuv_to_rgb push;
+	uint32_t spec_pq, spec_num_planes, spec_nv21;
+	uint32_t matrix;              /* the GR_VIDEO_MATRIX_* an unspecified one resolved to */
+};
+int gr_video_yuv_to_rgb(gr_ctx *ctx, gr_stream stream, const gr_image *planes, uint32_t num_planes, const gr_image *out,
+                        const gr_video_yuv_info *info);
+/* Host-only (no device): the plan gr_video_yuv_to_rgb would launch (image pointers are not read).  Negative on arguments
+ * gr_video_yuv_to_rgb refuses. */
+int gr_video_yuv_plan(const gr_image *planes, uint32_t num_planes, const gr_image *out, const gr_video_yuv_info *info,
+                      struct gr_video_yuv_plan *plan);
+
 /* Fill with a 32-bit pattern (count dwords): attachment clears to a colour. */
 int gr_fill_u32(gr_ctx *ctx, gr_stream stream, void *dst, uint32_t value, size_t count);
 /* Executor self-test operation (no counterpart in the reference): out[i] = hash(i, salt, one dword of each of up to four
@@ -811,6 +873,13 @@ GR_ASSERT_OFFSET(gr_cluster_params, z_scale, 160);
 GR_ASSERT_SIZE(gr_push_pq10, 80);             /* hdr.cpp:626-633 */
 GR_ASSERT_SIZE(gr_push_video, 28);            /* scaler.comp:78-84, scaler.cpp:184-190 */
 GR_ASSERT_OFFSET(gr_push_video, dither_strength, 24);
+GR_ASSERT_SIZE(gr_push_yuv_to_rgb, 164);      /* yuv_to_rgb.comp:9-18, ffmpeg_decode.cpp:588-598 */
+GR_ASSERT_OFFSET(gr_push_yuv_to_rgb, primary_conversion, 64);
+GR_ASSERT_OFFSET(gr_push_yuv_to_rgb, resolution, 128);
+GR_ASSERT_OFFSET(gr_push_yuv_to_rgb, inv_resolution, 136);
+GR_ASSERT_OFFSET(gr_push_yuv_to_rgb, chroma_siting, 144);
+GR_ASSERT_OFFSET(gr_push_yuv_to_rgb, chroma_clamp, 152);
+GR_ASSERT_OFFSET(gr_push_yuv_to_rgb, unorm_rescale, 160);
 GR_STATIC_ASSERT(GR_TRANSFORMS_OFFSET_SHADOW == GR_MAX_LIGHTS_BINDLESS * 48u, "ClustererBindlessTransforms: lights[4096] of 48 B");
 GR_STATIC_ASSERT(GR_TRANSFORMS_OFFSET_MODEL + GR_MAX_LIGHTS_BINDLESS * 48u == GR_TRANSFORMS_OFFSET_TYPE_MASK, "ClustererBindlessTransforms: model[4096] of 48 B");
 GR_STATIC_ASSERT(GR_TRANSFORMS_OFFSET_TYPE_MASK + GR_MAX_LIGHTS_BINDLESS / 8u == GR_TRANSFORMS_OFFSET_DECALS, "ClustererBindlessTransforms: type_mask[128]");

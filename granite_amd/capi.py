@@ -33,6 +33,22 @@ FORMAT_R32_SFLOAT = 100
 FORMAT_B10G11R11_UFLOAT_PACK32 = 122
 FORMAT_D16_UNORM = 124
 FORMAT_D32_SFLOAT = 126
+# block-compressed inputs of gr_texture_decode (VkFormat numbers; 140 / 142, the SNORM forms, are not handled)
+FORMAT_BC1_RGB_UNORM_BLOCK = 131
+FORMAT_BC1_RGB_SRGB_BLOCK = 132
+FORMAT_BC1_RGBA_UNORM_BLOCK = 133
+FORMAT_BC1_RGBA_SRGB_BLOCK = 134
+FORMAT_BC2_UNORM_BLOCK = 135
+FORMAT_BC2_SRGB_BLOCK = 136
+FORMAT_BC3_UNORM_BLOCK = 137
+FORMAT_BC3_SRGB_BLOCK = 138
+FORMAT_BC4_UNORM_BLOCK = 139
+FORMAT_BC5_UNORM_BLOCK = 141
+FORMAT_BC6H_UFLOAT_BLOCK = 143
+FORMAT_BC6H_SFLOAT_BLOCK = 144
+FORMAT_BC7_UNORM_BLOCK = 145
+FORMAT_BC7_SRGB_BLOCK = 146
+BLOCK_FORMATS = (131, 132, 133, 134, 135, 136, 137, 138, 139, 141, 143, 144, 145, 146)
 
 FORMAT_BPP = {
     FORMAT_R8_UNORM: 1,
@@ -403,6 +419,9 @@ def load_library() -> C.CDLL:
         "gr_video_scaler_weights": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_uint16)]),
         "gr_video_yuv_to_rgb": (C.c_int, [vp, vp, P(Image), C.c_uint32, P(Image), P(VideoYuvInfo)]),
         "gr_video_yuv_plan": (C.c_int, [P(Image), C.c_uint32, P(Image), P(VideoYuvInfo), P(VideoYuvPlan)]),
+        "gr_texture_decoded_format": (C.c_uint32, [C.c_uint32]),
+        "gr_texture_block_bytes": (C.c_uint32, [C.c_uint32]),
+        "gr_texture_decode": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint32, P(Image)]),
         "gr_fsr_sharpen": (C.c_int, [vp, vp, P(Image), P(Image), C.c_float]),
         "gr_mip_chain_offset": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
         "gr_mip_chain_size": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
@@ -424,6 +443,7 @@ EXPORTED_SYMBOLS = [
     "gr_smaa_set_luts", "gr_fxaa", "gr_blit", "gr_smaa_edge_detection", "gr_smaa_blend_weight", "gr_smaa_neighbor_blend", "gr_taa_resolve",
     "gr_hiz", "gr_mip_chain_offset", "gr_mip_chain_size", "gr_fsr_upscale", "gr_fsr_sharpen", "gr_fill_byte", "gr_fill_u32", "gr_pq10_encode", "gr_get_device_info", "gr_spd_downsample", "gr_debug_mix", "gr_pack_b10g11r11",
     "gr_video_scale", "gr_video_scale_plan", "gr_video_scaler_weights", "gr_video_yuv_to_rgb", "gr_video_yuv_plan",
+    "gr_texture_decoded_format", "gr_texture_block_bytes", "gr_texture_decode",
 ]
 
 
@@ -716,6 +736,11 @@ class Context:
         self.check(self.lib.gr_taa_resolve(self.handle, stream, current.desc, depth.desc, mv.desc,
                                            history.desc if history is not None else None, out_color.desc, out_history.desc, push,
                                            quality))
+
+    def texture_decode(self, block_format: int, blocks, block_row_pitch: int, out, stream=None):
+        """gr_texture_decode: one level of one layer of BC1-BC7 blocks (device pointer) into `out` (DeviceImage or Image)."""
+        desc = out.desc if isinstance(out, DeviceImage) else out
+        self.check(self.lib.gr_texture_decode(self.handle, stream, int(block_format), blocks, int(block_row_pitch), C.byref(desc)))
 
     def blit(self, src: DeviceImage, out: DeviceImage, linear: bool, stream=None):
         self.check(self.lib.gr_blit(self.handle, stream, src.desc, out.desc, int(linear)))

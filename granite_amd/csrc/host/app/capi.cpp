@@ -4,6 +4,7 @@
 #include "../post/ssr.hpp"
 #include "../post/spd.hpp"
 #include "../gtx.hpp"
+#include "../texture_decoder.hpp"
 #include "../post/hdr.hpp"
 #include <cstdio>
 #include <cstring>
@@ -217,6 +218,18 @@ int gra_gtx_write(const char *path, const gra_gtx_info *info, const void *payloa
 			throw std::logic_error("gra_gtx_write: payload_size does not match the layout of the described image");
 		img.payload.assign(static_cast<const uint8_t *>(payload), static_cast<const uint8_t *>(payload) + info->payload_size);
 		gtx_save(img, path);
+	});
+}
+
+int gra_gtx_decode(gra_app *app, const char *src_path, const char *dst_path)
+{
+	return guarded(app, [&]() {
+		if (!src_path || !dst_path)
+			throw std::logic_error("gra_gtx_decode: null path");
+		auto &device = app->app->get_device();
+		if (!device.get_context())
+			throw std::logic_error("gra_gtx_decode: the application has no device");
+		gtx_save(decode_compressed_image(device.get_context(), nullptr, gtx_load(src_path)), dst_path);
 	});
 }
 

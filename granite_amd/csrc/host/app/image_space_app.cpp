@@ -1,6 +1,7 @@
 // Follows MIT-licensed work (Granite, (c) 2017-2026 Hans-Kristian Arntzen; FidelityFX parts (c) 2021 Advanced Micro Devices, Inc.): see
 // THIRD_PARTY_NOTICES.md at the repository root.
 #include "image_space_app.hpp"
+#include "../texture_decoder.hpp"
 #include "../timeline_trace.hpp"
 #include <hip/hip_runtime_api.h>
 #include "../gtx.hpp"
@@ -453,6 +454,7 @@ void ImageSpaceApplication::upload_gbuffer_gtx(const char *const paths[6])
 	};
 	GtxImage images[6];
 	const void *level0[6] = {};
+	bool compressed[6] = {};
 	for (int i = 0; i < 6; i++)
 	{
 		if (!paths[i])
@@ -461,14 +463,44 @@ void ImageSpaceApplication::upload_gbuffer_gtx(const char *const paths[6])
 		auto &img = images[i];
 		if (img.type != 1 || img.layers != 1 || img.depth != 1)
 			throw std::runtime_error(std::string(paths[i]) + ": a 2-D single-layer image is expected for " + slots[i].what + ".");
-		if (img.format != slots[i].formats[0] && img.format != slots[i].formats[1])
+		// a block-compressed file stands for its decoded format (albedo as BC1/2/3/7, pbr as BC5, emissive as BC6H into RGBA16F targets)
+		const VkFormat decoded = compressed_format_to_decoded_format(img.format);
+		compressed[i] = decoded != VK_FORMAT_UNDEFINED;
+		const VkFormat format = compressed[i] ? decoded : img.format;
+		if (format != slots[i].formats[0] && format != slots[i].formats[1])
 			throw std::runtime_error(std::string(paths[i]) + ": wrong format for the " + slots[i].what + " attachment.");
 		if (img.width != render_width || img.height != render_height)
 			throw std::runtime_error(std::string(paths[i]) + ": " + std::to_string(img.width) + " x " + std::to_string(img.height) +
 			                         " does not match the configured frame.");
-		level0[i] = img.payload.data() + img.level_offset(0);
+		if (!compressed[i])
+			level0[i] = img.payload.data() + img.level_offset(0);
 	}
 	upload_gbuffer(level0[0], level0[1], level0[2], level0[3], level0[4], level0[5]);
+
+	// The blocks of level 0 go to the device as they are and are decoded straight into the attachment, on the stream the uploads above use.
+	HIP::ImageHandle *const targets[6] = {&src_emissive, &src_albedo, &src_normal, &src_pbr, &src_depth, &src_mv};
+	auto &device = get_device();
+	gr_ctx *ctx = device.get_context();
+	for (int i = 0; i < 6; i++)
+	{
+		if (!compressed[i])
+			continue;
+		if (!*targets[i])
+			throw std::logic_error(std::string("This graph has no ") + slots[i].what + " attachment.");
+		const GtxImage &img = images[i];
+		const uint32_t pitch = img.level_blocks_x(0) * gr_texture_block_bytes(uint32_t(img.format));
+		const size_t bytes = size_t(pitch) * img.level_blocks_y(0);
+		void *blocks = nullptr;
+		if (gr_alloc(ctx, bytes, &blocks) < 0)
+			throw std::runtime_error(gr_last_error(ctx));
+		gr_image view = (*targets[i])->get_level_view(0);
+		view.format = uint32_t(compressed_format_to_decoded_format(img.format)); // the same bytes as the attachment's own view
+		const bool ok = gr_upload(ctx, nullptr, blocks, img.payload.data() + img.level_offset(0), bytes) >= 0 &&
+		                gr_texture_decode(ctx, nullptr, uint32_t(img.format), blocks, pitch, &view) >= 0 && gr_sync(ctx, nullptr) >= 0;
+		gr_free(ctx, blocks);
+		if (!ok)
+			throw std::runtime_error(gr_last_error(ctx));
+	}
 }
 
 void ImageSpaceApplication::save_image_gtx(HIP::Image &image, const std::string &path)

@@ -12,7 +12,7 @@ static const char GtxMagic[16] = "GRANITE TEXFMT1";
 size_t GtxImage::level_size(uint32_t level) const
 {
 	const uint32_t d = (depth >> level) ? (depth >> level) : 1u;
-	return size_t(level_width(level)) * level_height(level) * d * layers * vk_format_block_size(format);
+	return size_t(level_blocks_x(level)) * level_blocks_y(level) * d * layers * vk_format_block_size(format);
 }
 
 size_t GtxImage::level_offset(uint32_t level) const

@@ -8,7 +8,8 @@
 // Header, 64 bytes, little endian: magic[16] = "GRANITE TEXFMT1\0"; u32 type (VkImageType), format (VkFormat), width,
 // height, depth, layers, levels, flags; u64 payload_size; u64 reserved.  Payload: mip levels in order, each starting at
 // a 16-byte aligned offset; inside a level the array layers (and depth slices) follow each other, rows tightly packed.
-// Only uncompressed formats the executor knows (vk_format_block_size) are accepted.
+// A block-compressed level holds ceil(w / 4) x ceil(h / 4) blocks per layer, rows of blocks tightly packed.
+// Only formats the executor knows (vk_format_block_size: its uncompressed formats and BC1-BC7 without SNORM) are accepted.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -32,6 +33,19 @@ struct GtxImage
 	size_t required_payload_size() const;
 	uint32_t level_width(uint32_t level) const { return (width >> level) ? (width >> level) : 1u; }
 	uint32_t level_height(uint32_t level) const { return (height >> level) ? (height >> level) : 1u; }
+	// Blocks per row / rows of blocks of a level: its texel extent for an uncompressed format.
+	uint32_t level_blocks_x(uint32_t level) const
+	{
+		unsigned bw, bh;
+		vk_format_block_dim(format, bw, bh);
+		return (level_width(level) + bw - 1) / bw;
+	}
+	uint32_t level_blocks_y(uint32_t level) const
+	{
+		unsigned bw, bh;
+		vk_format_block_dim(format, bw, bh);
+		return (level_height(level) + bh - 1) / bh;
+	}
 };
 
 // Throws std::runtime_error with the reason (bad magic, unsupported format, truncated / oversized payload ...).

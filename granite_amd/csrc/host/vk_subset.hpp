@@ -30,7 +30,24 @@ enum VkFormat : uint32_t
 	VK_FORMAT_R32_SFLOAT = 100,
 	VK_FORMAT_B10G11R11_UFLOAT_PACK32 = 122,
 	VK_FORMAT_D16_UNORM = 124,
-	VK_FORMAT_D32_SFLOAT = 126
+	VK_FORMAT_D32_SFLOAT = 126,
+	// Block-compressed: .gtx payloads and inputs of Granite::decode_compressed_image only (BC4 / BC5 SNORM are not handled)
+	VK_FORMAT_BC1_RGB_UNORM_BLOCK = 131,
+	VK_FORMAT_BC1_RGB_SRGB_BLOCK = 132,
+	VK_FORMAT_BC1_RGBA_UNORM_BLOCK = 133,
+	VK_FORMAT_BC1_RGBA_SRGB_BLOCK = 134,
+	VK_FORMAT_BC2_UNORM_BLOCK = 135,
+	VK_FORMAT_BC2_SRGB_BLOCK = 136,
+	VK_FORMAT_BC3_UNORM_BLOCK = 137,
+	VK_FORMAT_BC3_SRGB_BLOCK = 138,
+	VK_FORMAT_BC4_UNORM_BLOCK = 139,
+	VK_FORMAT_BC4_SNORM_BLOCK = 140, // named to be refused by name: no size, no decode
+	VK_FORMAT_BC5_UNORM_BLOCK = 141,
+	VK_FORMAT_BC5_SNORM_BLOCK = 142, // likewise
+	VK_FORMAT_BC6H_UFLOAT_BLOCK = 143,
+	VK_FORMAT_BC6H_SFLOAT_BLOCK = 144,
+	VK_FORMAT_BC7_UNORM_BLOCK = 145,
+	VK_FORMAT_BC7_SRGB_BLOCK = 146
 };
 
 enum VkImageUsageFlagBits : uint32_t
@@ -99,8 +116,29 @@ static inline unsigned vk_format_block_size(VkFormat format)
 	case VK_FORMAT_R32_SFLOAT:
 	case VK_FORMAT_D32_SFLOAT: return 4;
 	case VK_FORMAT_R16G16B16A16_SFLOAT: return 8;
+	case VK_FORMAT_BC1_RGB_UNORM_BLOCK:
+	case VK_FORMAT_BC1_RGB_SRGB_BLOCK:
+	case VK_FORMAT_BC1_RGBA_UNORM_BLOCK:
+	case VK_FORMAT_BC1_RGBA_SRGB_BLOCK:
+	case VK_FORMAT_BC4_UNORM_BLOCK: return 8;
+	case VK_FORMAT_BC2_UNORM_BLOCK:
+	case VK_FORMAT_BC2_SRGB_BLOCK:
+	case VK_FORMAT_BC3_UNORM_BLOCK:
+	case VK_FORMAT_BC3_SRGB_BLOCK:
+	case VK_FORMAT_BC5_UNORM_BLOCK:
+	case VK_FORMAT_BC6H_UFLOAT_BLOCK:
+	case VK_FORMAT_BC6H_SFLOAT_BLOCK:
+	case VK_FORMAT_BC7_UNORM_BLOCK:
+	case VK_FORMAT_BC7_SRGB_BLOCK: return 16;
 	default: return 0;
 	}
+}
+
+// Texels per block: 4 x 4 for the BC formats above, 1 x 1 for everything else (vulkan/texture/texture_format.cpp format_block_dim).
+static inline void vk_format_block_dim(VkFormat format, unsigned &width, unsigned &height)
+{
+	const bool block = format >= VK_FORMAT_BC1_RGB_UNORM_BLOCK && format <= VK_FORMAT_BC7_SRGB_BLOCK && vk_format_block_size(format) != 0; // not SNORM
+	width = height = block ? 4u : 1u;
 }
 
 static inline bool vk_format_is_srgb(VkFormat format) { return format == VK_FORMAT_R8G8B8A8_SRGB || format == VK_FORMAT_B8G8R8A8_SRGB; }

@@ -33,28 +33,43 @@ class GtxFile:
         return level_offset(self.info, level)
 
     def level(self, level: int = 0) -> np.ndarray:
-        """Raw bytes of one mip level (all layers), shaped (layers, height, width, bytes per texel)."""
-        w, h = max(self.info.width >> level, 1), max(self.info.height >> level, 1)
-        bpp = capi.FORMAT_BPP[self.info.format]
+        """Raw bytes of one mip level (all layers), shaped (layers, height, width, bytes per texel); for a block-compressed format
+        the raw blocks, shaped (layers, rows of blocks, blocks per row, bytes per block)."""
+        bx, by, bpp = level_blocks(self.info, level)
         o = self.level_offset(level)
-        return self.payload[o:o + self.info.layers * w * h * bpp].reshape(self.info.layers, h, w, bpp)
+        return self.payload[o:o + self.info.layers * bx * by * bpp].reshape(self.info.layers, by, bx, bpp)
+
+
+def block_bytes(fmt: int) -> int:
+    """Bytes per texel, or per 4 x 4 block of a BC format."""
+    return capi.load_library().gr_texture_block_bytes(fmt) or capi.FORMAT_BPP[fmt]
+
+
+def level_blocks(info: GtxInfo, level: int):
+    """(blocks per row, rows of blocks, bytes per block) of a level; a block is one texel unless the format is block-compressed."""
+    dim = 4 if info.format in capi.BLOCK_FORMATS else 1
+    w, h = max(info.width >> level, 1), max(info.height >> level, 1)
+    return (w + dim - 1) // dim, (h + dim - 1) // dim, block_bytes(info.format)
+
+
+def level_size(info: GtxInfo, level: int) -> int:
+    bx, by, bpp = level_blocks(info, level)
+    return bx * by * max(info.depth >> level, 1) * info.layers * bpp
 
 
 def level_offset(info: GtxInfo, level: int) -> int:
-    bpp = capi.FORMAT_BPP[info.format]
     offset = 0
     for l in range(level + 1):
         offset = (offset + 15) & ~15
         if l == level:
             return offset
-        offset += max(info.width >> l, 1) * max(info.height >> l, 1) * max(info.depth >> l, 1) * info.layers * bpp
+        offset += level_size(info, l)
     return offset
 
 
 def payload_size(info: GtxInfo) -> int:
     last = info.levels - 1
-    bpp = capi.FORMAT_BPP[info.format]
-    return level_offset(info, last) + max(info.width >> last, 1) * max(info.height >> last, 1) * max(info.depth >> last, 1) * info.layers * bpp
+    return level_offset(info, last) + level_size(info, last)
 
 
 def _lib():
@@ -79,17 +94,19 @@ def read(path: str) -> GtxFile:
     return GtxFile(info, payload)
 
 
-def write(path: str, fmt: int, levels: List[np.ndarray], flags: int = 0, layers: int = 1):
-    """levels[l]: array whose bytes are level l (all layers), level 0 first; shape[-3:-1] or [0:2] of level 0 gives h, w."""
+def write(path: str, fmt: int, levels: List[np.ndarray], flags: int = 0, layers: int = 1, size=None):
+    """levels[l]: array whose bytes are level l (all layers), level 0 first; shape[-3:-1] or [0:2] of level 0 gives h, w.
+    A block-compressed format takes raw blocks and needs size = (width, height) in texels."""
     first = np.ascontiguousarray(levels[0])
-    bpp = capi.FORMAT_BPP[fmt]
-    h, w = (first.shape[1], first.shape[2]) if layers > 1 else (first.shape[0], first.shape[1])
+    if fmt in capi.BLOCK_FORMATS and size is None:
+        raise GtxError("a block-compressed format needs size=(width, height)")
+    h, w = (size[1], size[0]) if size is not None else (first.shape[1], first.shape[2]) if layers > 1 else (first.shape[0], first.shape[1])
     info = GtxInfo(1, fmt, w, h, 1, layers, len(levels), flags, 0)
     info.payload_size = payload_size(info)
     payload = np.zeros(info.payload_size, np.uint8)
     for l, a in enumerate(levels):
         raw = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-        want = max(w >> l, 1) * max(h >> l, 1) * layers * bpp
+        want = level_size(info, l)
         if raw.size != want:
             raise GtxError(f"level {l}: {raw.size} bytes, layout wants {want}")
         o = level_offset(info, l)

@@ -260,7 +260,10 @@ def main(argv=None) -> int:
 
     if "rt_fp16" not in kw and scene_dir and os.path.exists(os.path.join(scene_dir, "emissive.gtx")):
         from . import gtx
-        kw["rt_fp16"] = gtx.probe(os.path.join(scene_dir, "emissive.gtx")).format != capi.FORMAT_B10G11R11_UFLOAT_PACK32
+        emissive_format = gtx.probe(os.path.join(scene_dir, "emissive.gtx")).format
+        if emissive_format in capi.BLOCK_FORMATS:  # BC6H decodes into RGBA16F targets
+            emissive_format = capi.load_library().gr_texture_decoded_format(emissive_format)
+        kw["rt_fp16"] = emissive_format != capi.FORMAT_B10G11R11_UFLOAT_PACK32
     try:
         app = gapp.Application(args.width, args.height, device=args.device, timestamps=args.timestamp,
                                frame_time=args.time_step, **kw)

@@ -165,9 +165,15 @@ int gra_gtx_read(const char *path, void *payload, uint64_t payload_capacity, cha
 int gra_gtx_write(const char *path, const gra_gtx_info *info, const void *payload, char *error, size_t error_size);
 /* gra_upload_gbuffer from .gtx files (2-D, one layer, level 0 is used).  Formats must be the attachment's own:
  * emissive / HDR R16G16B16A16_SFLOAT, albedo R8G8B8A8_SRGB or _UNORM, normal A2B10G10R10_UNORM_PACK32, pbr R8G8_UNORM,
- * depth D32_SFLOAT or R32_SFLOAT, motion vectors R16G16_SFLOAT; sizes must equal the configured frame.  NULL = unchanged. */
+ * depth D32_SFLOAT or R32_SFLOAT, motion vectors R16G16_SFLOAT; sizes must equal the configured frame.  NULL = unchanged.
+ * A block-compressed file is accepted where its decoded format (gr_texture_decoded_format) is the attachment's own -- albedo as
+ * BC1 / BC2 / BC3 / BC7, pbr as BC5, emissive as BC6H with RGBA16F targets: its blocks are uploaded and decoded into the attachment. */
 int gra_upload_gbuffer_gtx(gra_app *app, const char *emissive, const char *albedo, const char *normal, const char *pbr,
                            const char *depth, const char *motion_vectors);
+/* Decodes a block-compressed .gtx (BC1-BC7; no SNORM, no 3-D) on the application's device, every level and layer
+ * (Granite::decode_compressed_image, one gr_texture_decode each), and writes an uncompressed .gtx of the decoded format with the
+ * same extents, layers, levels and flags. */
+int gra_gtx_decode(gra_app *app, const char *src_path, const char *dst_path);
 /* Writes a graph texture (all its mip levels) or, with name == NULL, the last rendered backbuffer as .gtx. */
 int gra_save_resource_gtx(gra_app *app, const char *name, const char *path);
 

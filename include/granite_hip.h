@@ -55,7 +55,22 @@ typedef enum gr_format
 	GR_FORMAT_R32_SFLOAT = 100,
 	GR_FORMAT_B10G11R11_UFLOAT_PACK32 = 122, /* HDR targets with renderTargetFp16 = false (scene_viewer_application.cpp:881-883), TAA colour (temporal.cpp:211-213) */
 	GR_FORMAT_D16_UNORM = 124,
-	GR_FORMAT_D32_SFLOAT = 126
+	GR_FORMAT_D32_SFLOAT = 126,
+	/* Block-compressed inputs of gr_texture_decode only; no other entry point takes them.  140 and 142 (BC4 / BC5 SNORM) are absent. */
+	GR_FORMAT_BC1_RGB_UNORM_BLOCK = 131,
+	GR_FORMAT_BC1_RGB_SRGB_BLOCK = 132,
+	GR_FORMAT_BC1_RGBA_UNORM_BLOCK = 133,
+	GR_FORMAT_BC1_RGBA_SRGB_BLOCK = 134,
+	GR_FORMAT_BC2_UNORM_BLOCK = 135,
+	GR_FORMAT_BC2_SRGB_BLOCK = 136,
+	GR_FORMAT_BC3_UNORM_BLOCK = 137,
+	GR_FORMAT_BC3_SRGB_BLOCK = 138,
+	GR_FORMAT_BC4_UNORM_BLOCK = 139,
+	GR_FORMAT_BC5_UNORM_BLOCK = 141,
+	GR_FORMAT_BC6H_UFLOAT_BLOCK = 143,
+	GR_FORMAT_BC6H_SFLOAT_BLOCK = 144,
+	GR_FORMAT_BC7_UNORM_BLOCK = 145,
+	GR_FORMAT_BC7_SRGB_BLOCK = 146
 } gr_format;
 
 /* A 2-D attachment as the executor sees it: what Vulkan::ImageView is to the reference's callbacks. */
@@ -786,6 +801,24 @@ int gr_video_yuv_to_rgb(gr_ctx *ctx, gr_stream stream, const gr_image *planes, u
  * gr_video_yuv_to_rgb refuses. */
 int gr_video_yuv_plan(const gr_image *planes, uint32_t num_planes, const gr_image *out, const gr_video_yuv_info *info,
                       struct gr_video_yuv_plan *plan);
+
+/* ---- Block-compressed texture decode (vulkan/texture/texture_decoder.cpp, assets/shaders/decode/{s3tc,rgtc,bc7,bc6}.comp) ---- */
+
+/* Host-only. Decoded format of a block format as compressed_format_to_decoded_format (texture_decoder.cpp:28-129):
+ * BC1/2/3/7 -> R8G8B8A8_UNORM or _SRGB (same bytes; the view differs), BC4 -> R8_UNORM, BC5 -> R8G8_UNORM,
+ * BC6H -> R16G16B16A16_SFLOAT.  GR_FORMAT_UNDEFINED for anything else. */
+uint32_t gr_texture_decoded_format(uint32_t block_format);
+/* Host-only. Bytes per 4x4 block (8 or 16), 0 if not a block format handled here. */
+uint32_t gr_texture_block_bytes(uint32_t block_format);
+/* One level of one layer.  `blocks`: device pointer, ceil(w/4) x ceil(h/4) blocks, rows `block_row_pitch_bytes` apart
+ * (>= ceil(w/4) * block bytes).  out->width/height are texel extents (at most 65536), out->format must be gr_texture_decoded_format().
+ * Texels outside out->width x out->height are not written.  Any out pitch >= the row's bytes and any byte alignment of
+ * either pointer; everything else is refused with GR_ERR_INVALID_ARGUMENT / GR_ERR_UNSUPPORTED_FORMAT before a launch.
+ * width or height 0 returns GR_OK without launching.
+ * BC1 RGB stores alpha 255 everywhere, BC1 RGBA stores the punch-through texel as (0, 0, 0, 0); BC2 / BC3 colours are always four-colour;
+ * BC6H stores alpha 0x3C00; reserved BC6H / BC7 modes store what the shaders store (zero endpoints); _SRGB formats store the _UNORM bytes. */
+int gr_texture_decode(gr_ctx *ctx, gr_stream stream, uint32_t block_format, const void *blocks,
+                      uint32_t block_row_pitch_bytes, const gr_image *out);
 
 /* Fill with a 32-bit pattern (count dwords): attachment clears to a colour. */
 int gr_fill_u32(gr_ctx *ctx, gr_stream stream, void *dst, uint32_t value, size_t count);

@@ -9,6 +9,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "../../include/granite_hip.h"
 #include "row_span.hpp"
@@ -187,6 +188,25 @@ struct gr_scoped_timing
 
 static inline hipStream_t gr_to_stream(gr_stream s) { return static_cast<hipStream_t>(s); }
 static inline unsigned gr_div_up(unsigned a, unsigned b) { return (a + b - 1) / b; }
+// rows that 16-byte loads and stores can walk
+static inline bool is_aligned16(const gr_image *img) { return (img->pitch_bytes & 15u) == 0 && (reinterpret_cast<uintptr_t>(img->ptr) & 15u) == 0; }
+
+// Runtime flags to template arguments: f(std::bool_constant<flags>...), one instantiation of f per combination.
+template <typename F> static void with_flags(F &&f) { f(); }
+template <typename F, typename... Rest> static void with_flags(F &&f, bool flag, Rest... rest)
+{
+	if (flag)
+		with_flags([&](auto... constants) { f(std::true_type{}, constants...); }, rest...);
+	else
+		with_flags([&](auto... constants) { f(std::false_type{}, constants...); }, rest...);
+}
+// A runtime index in [0, N) to a template argument: f(std::integral_constant<int, index>); false, and no call, outside the range.
+template <int N, typename F> static bool with_index(int index, F &&f)
+{
+	if constexpr (N > 0)
+		return index == N - 1 ? (f(std::integral_constant<int, N - 1>{}), true) : with_index<N - 1>(index, f);
+	return false;
+}
 
 // Resolves a render area (gr_rows) against `height` output rows: [first, end), empty when the band lies outside the image.
 static inline RowSpan resolve_rows(const gr_rows *rows, uint32_t height)

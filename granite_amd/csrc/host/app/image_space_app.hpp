@@ -21,6 +21,7 @@
 #include "../renderer.hpp"
 #include "../video/scaler.hpp"
 #include "../video/yuv_to_rgb.hpp"
+#include "video_ring.hpp"
 
 namespace Granite
 {
@@ -38,9 +39,9 @@ public:
 		if (device_holder)
 			device_holder->wait_idle();
 		if (video)
-			video_wait();
+			video->ring.wait();
 		if (playback)
-			video_play_wait();
+			playback->ring.wait();
 		check_taa_history_reach();
 	}
 	// Row bands with a bounded TAA history reach: throws once a resolve has reported a fetch outside the rows this rank holds.
@@ -173,37 +174,28 @@ private:
 	uint64_t output_acquires = 0, output_acquire_waits = 0;
 	double host_seconds = 0.0;
 
-	// Recording state: one device copy of the planes (conversion and copy are in order on `stream`), a ring of pinned frames.
+	// Recording state: one device copy of the planes (conversion and copy are in order on the ring's stream), a ring of pinned frames.
 	struct VideoRecording
 	{
 		gra_video_options options = {};
 		gra_video_layout layout = {};
 		uint32_t plane_format[3] = {};
-		void *stream = nullptr;        // hipStream_t
 		void *planes = nullptr;        // device
 		VideoScaler scaler;
-		struct Slot
-		{
-			void *host = nullptr;      // pinned
-			void *copied = nullptr;    // hipEvent_t: the copy into `host` is done
-			int64_t frame = -1;
-		};
-		std::vector<Slot> ring;
-		uint64_t written = 0, read = 0; // frames converted / handed back
+		VideoRing ring;                // one buffer per slot: the packed frame
 		// per swapchain image: hipEvent_t after the conversion that read it (the image's next writer waits for it)
 		std::unordered_map<const void *, void *> read_done;
 	};
 	std::unique_ptr<VideoRecording> video;
 	void video_check_ring() const;
-	void video_wait();
 	void video_before_frame(HIP::Image &backbuffer);
 	void video_after_frame(HIP::Image &backbuffer, uint64_t device_frame);
 	void video_release();
 	// The packed-frame layout and the plane formats of a gra_video_format at w x h; false for an unknown format.
 	static bool video_format_layout(uint32_t format, uint32_t w, uint32_t h, gra_video_layout &layout, uint32_t (&plane_format)[3]);
 
-	// Playback state: one device copy of the planes and one of the RGB image (upload, conversion and read-back are in order on
-	// `stream`), a ring of pinned frame / image pairs.
+	// Playback state: one device copy of the planes and one of the RGB image (upload, conversion and read-back are in order on the
+	// ring's stream), a ring of pinned frame / image pairs.
 	struct VideoPlayback
 	{
 		gra_video_play_options options = {};
@@ -211,22 +203,12 @@ private:
 		uint32_t plane_format[3] = {};
 		uint32_t rgb_pitch = 0;
 		uint64_t rgb_bytes = 0;
-		void *stream = nullptr;        // hipStream_t
 		void *planes = nullptr;        // device
 		void *rgb = nullptr;           // device
 		VideoYuvToRgb converter;
-		struct Slot
-		{
-			void *frame_host = nullptr; // pinned: the packed frame as handed over
-			void *rgb_host = nullptr;   // pinned: the converted image
-			void *converted = nullptr;  // hipEvent_t: the copy into `rgb_host` is done
-			int64_t frame = -1;
-		};
-		std::vector<Slot> ring;
-		uint64_t written = 0, read = 0; // frames handed over / handed back
+		VideoRing ring;                // two buffers per slot: the packed frame as handed over, the converted image
 	};
 	std::unique_ptr<VideoPlayback> playback;
-	void video_play_wait();
 	void video_play_release();
 
 	void bake_render_graph();

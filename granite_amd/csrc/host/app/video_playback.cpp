@@ -17,12 +17,6 @@ namespace Granite
 {
 namespace
 {
-void hip_check(hipError_t err, const char *what)
-{
-	if (err != hipSuccess)
-		throw std::runtime_error(std::string("video playback: ") + what + " failed: " + hipGetErrorString(err));
-}
-
 uint32_t rgb_texel_bytes(uint32_t format)
 {
 	switch (format)
@@ -67,20 +61,10 @@ void ImageSpaceApplication::video_play_begin(const gra_video_play_options &optio
 	playback = std::move(play); // from here on video_play_release() undoes what follows
 	try
 	{
-		hipStream_t s;
-		hip_check(hipStreamCreateWithFlags(&s, hipStreamNonBlocking), "hipStreamCreateWithFlags");
-		playback->stream = s;
-		hip_check(hipMalloc(&playback->planes, l.frame_bytes), "hipMalloc");
-		hip_check(hipMalloc(&playback->rgb, playback->rgb_bytes), "hipMalloc");
-		playback->ring.resize(options.ring_frames ? options.ring_frames : 8u);
-		for (auto &slot : playback->ring)
-		{
-			hip_check(hipHostMalloc(&slot.frame_host, l.frame_bytes, hipHostMallocDefault), "hipHostMalloc");
-			hip_check(hipHostMalloc(&slot.rgb_host, playback->rgb_bytes, hipHostMallocDefault), "hipHostMalloc");
-			hipEvent_t e;
-			hip_check(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreateWithFlags");
-			slot.converted = e;
-		}
+		VideoRing &ring = playback->ring;
+		ring.create("video playback", options.ring_frames ? options.ring_frames : 8u, l.frame_bytes, playback->rgb_bytes);
+		ring.check(hipMalloc(&playback->planes, l.frame_bytes), "hipMalloc");
+		ring.check(hipMalloc(&playback->rgb, playback->rgb_bytes), "hipMalloc");
 	}
 	catch (...)
 	{
@@ -93,24 +77,11 @@ void ImageSpaceApplication::video_play_release()
 {
 	if (!playback)
 		return;
-	// frames may still be in flight: only this stream touches the player's buffers
-	if (playback->stream)
-		(void)hipStreamSynchronize(static_cast<hipStream_t>(playback->stream));
-	for (auto &slot : playback->ring)
-	{
-		if (slot.frame_host)
-			(void)hipHostFree(slot.frame_host);
-		if (slot.rgb_host)
-			(void)hipHostFree(slot.rgb_host);
-		if (slot.converted)
-			(void)hipEventDestroy(static_cast<hipEvent_t>(slot.converted));
-	}
+	playback->ring.release();
 	if (playback->planes)
 		(void)hipFree(playback->planes);
 	if (playback->rgb)
 		(void)hipFree(playback->rgb);
-	if (playback->stream)
-		(void)hipStreamDestroy(static_cast<hipStream_t>(playback->stream));
 	playback.reset();
 }
 
@@ -119,11 +90,6 @@ void ImageSpaceApplication::video_play_end()
 	if (!playback)
 		throw std::logic_error("gra_video_play_end: not playing");
 	video_play_release();
-}
-
-void ImageSpaceApplication::video_play_wait()
-{
-	hip_check(hipStreamSynchronize(static_cast<hipStream_t>(playback->stream)), "hipStreamSynchronize");
 }
 
 const gra_video_layout &ImageSpaceApplication::video_play_layout() const
@@ -140,15 +106,16 @@ void ImageSpaceApplication::video_play_frame(const void *frame, uint64_t size)
 	const gra_video_layout &l = playback->layout;
 	if (size != l.frame_bytes)
 		throw std::logic_error("gra_video_play_frame: size is not one frame's (gra_video_play_layout)");
-	if (playback->written - playback->read >= playback->ring.size())
-		throw std::runtime_error("video playback: " + std::to_string(playback->ring.size()) +
+	VideoRing &ring = playback->ring;
+	if (ring.full())
+		throw std::runtime_error("video playback: " + std::to_string(ring.slots.size()) +
 		                         " converted frames are unread; read them with gra_video_play_read_rgb before playing more");
 	auto &device = get_device();
 	device.make_current();
-	auto stream = static_cast<hipStream_t>(playback->stream);
-	auto &slot = playback->ring[playback->written % playback->ring.size()];
-	memcpy(slot.frame_host, frame, l.frame_bytes);
-	hip_check(hipMemcpyAsync(playback->planes, slot.frame_host, l.frame_bytes, hipMemcpyHostToDevice, stream), "hipMemcpyAsync");
+	hipStream_t stream = ring.stream;
+	VideoRing::Slot &slot = ring.next_slot();
+	memcpy(slot.host[0], frame, l.frame_bytes);
+	ring.check(hipMemcpyAsync(playback->planes, slot.host[0], l.frame_bytes, hipMemcpyHostToDevice, stream), "hipMemcpyAsync");
 
 	gr_image planes[3] = {};
 	for (uint32_t i = 0; i < l.num_planes; i++)
@@ -156,26 +123,19 @@ void ImageSpaceApplication::video_play_frame(const void *frame, uint64_t size)
 	const gr_image out = {playback->rgb, playback->options.width, playback->options.height, playback->rgb_pitch, playback->options.output_format};
 	playback->converter.convert(device.get_context(), stream, planes, out);
 
-	hip_check(hipMemcpyAsync(slot.rgb_host, playback->rgb, playback->rgb_bytes, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync");
-	hip_check(hipEventRecord(static_cast<hipEvent_t>(slot.converted), stream), "hipEventRecord");
-	slot.frame = int64_t(playback->written);
-	playback->written++;
+	ring.check(hipMemcpyAsync(slot.host[1], playback->rgb, playback->rgb_bytes, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync");
+	ring.commit_slot();
 }
 
 bool ImageSpaceApplication::video_play_read(void *dst, uint64_t size, int64_t *frame_number)
 {
 	if (!playback)
 		throw std::logic_error("gra_video_play_read_rgb: not playing");
-	if (playback->read == playback->written)
+	if (playback->ring.read == playback->ring.written)
 		return false;
 	if (size < playback->rgb_bytes)
 		throw std::logic_error("gra_video_play_read_rgb: destination smaller than one image (width x height texels, tightly packed)");
-	auto &slot = playback->ring[playback->read % playback->ring.size()];
-	hip_check(hipEventSynchronize(static_cast<hipEvent_t>(slot.converted)), "hipEventSynchronize");
-	memcpy(dst, slot.rgb_host, playback->rgb_bytes);
-	if (frame_number)
-		*frame_number = slot.frame;
-	playback->read++;
+	playback->ring.read_into(dst, 1, frame_number);
 	return true;
 }
 } // namespace Granite

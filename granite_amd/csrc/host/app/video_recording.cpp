@@ -18,15 +18,6 @@
 
 namespace Granite
 {
-namespace
-{
-void hip_check(hipError_t err, const char *what)
-{
-	if (err != hipSuccess)
-		throw std::runtime_error(std::string("video recording: ") + what + " failed: " + hipGetErrorString(err));
-}
-} // namespace
-
 bool ImageSpaceApplication::video_format_layout(uint32_t f, uint32_t w, uint32_t h, gra_video_layout &l, uint32_t (&plane_format)[3])
 {
 	if (f > GRA_VIDEO_P016)
@@ -92,18 +83,8 @@ void ImageSpaceApplication::video_begin(const gra_video_options &options)
 	video = std::move(rec); // from here on video_release() undoes what follows
 	try
 	{
-		hipStream_t s;
-		hip_check(hipStreamCreateWithFlags(&s, hipStreamNonBlocking), "hipStreamCreateWithFlags");
-		video->stream = s;
-		hip_check(hipMalloc(&video->planes, l.frame_bytes), "hipMalloc");
-		video->ring.resize(options.ring_frames ? options.ring_frames : 8u);
-		for (auto &slot : video->ring)
-		{
-			hip_check(hipHostMalloc(&slot.host, l.frame_bytes, hipHostMallocDefault), "hipHostMalloc");
-			hipEvent_t e;
-			hip_check(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreateWithFlags");
-			slot.copied = e;
-		}
+		video->ring.create("video recording", options.ring_frames ? options.ring_frames : 8u, l.frame_bytes);
+		video->ring.check(hipMalloc(&video->planes, l.frame_bytes), "hipMalloc");
 	}
 	catch (...)
 	{
@@ -116,21 +97,11 @@ void ImageSpaceApplication::video_release()
 {
 	if (!video)
 		return;
-	if (video->stream)
-		(void)hipStreamSynchronize(static_cast<hipStream_t>(video->stream));
-	for (auto &slot : video->ring)
-	{
-		if (slot.host)
-			(void)hipHostFree(slot.host);
-		if (slot.copied)
-			(void)hipEventDestroy(static_cast<hipEvent_t>(slot.copied));
-	}
+	video->ring.release();
 	for (auto &e : video->read_done)
 		(void)hipEventDestroy(static_cast<hipEvent_t>(e.second));
 	if (video->planes)
 		(void)hipFree(video->planes);
-	if (video->stream)
-		(void)hipStreamDestroy(static_cast<hipStream_t>(video->stream));
 	video.reset();
 }
 
@@ -150,15 +121,10 @@ const gra_video_layout &ImageSpaceApplication::video_layout() const
 	return video->layout;
 }
 
-void ImageSpaceApplication::video_wait()
-{
-	hip_check(hipStreamSynchronize(static_cast<hipStream_t>(video->stream)), "hipStreamSynchronize");
-}
-
 void ImageSpaceApplication::video_check_ring() const
 {
-	if (video->written - video->read >= video->ring.size())
-		throw std::runtime_error("video recording: " + std::to_string(video->ring.size()) +
+	if (video->ring.full())
+		throw std::runtime_error("video recording: " + std::to_string(video->ring.slots.size()) +
 		                         " recorded frames are unread; read them with gra_video_read_frame before rendering more");
 }
 
@@ -173,29 +139,27 @@ void ImageSpaceApplication::video_before_frame(HIP::Image &backbuffer)
 	// the conversion that read this swapchain image four frames ago is still running: no stream of this frame may write it before
 	auto &device = get_device();
 	for (int i = 0; i < int(HIP::CommandBuffer::Type::Count); i++)
-		hip_check(hipStreamWaitEvent(static_cast<hipStream_t>(device.get_stream(HIP::CommandBuffer::Type(i))), done, 0), "hipStreamWaitEvent");
+		video->ring.check(hipStreamWaitEvent(static_cast<hipStream_t>(device.get_stream(HIP::CommandBuffer::Type(i))), done, 0), "hipStreamWaitEvent");
 }
 
 void ImageSpaceApplication::video_after_frame(HIP::Image &backbuffer, uint64_t device_frame)
 {
 	auto &device = get_device();
-	auto stream = static_cast<hipStream_t>(video->stream);
+	VideoRing &ring = video->ring;
+	hipStream_t stream = ring.stream;
 	device.for_each_fence_of(device_frame, [&](void *fence) {
-		hip_check(hipStreamWaitEvent(stream, static_cast<hipEvent_t>(fence), 0), "hipStreamWaitEvent");
+		ring.check(hipStreamWaitEvent(stream, static_cast<hipEvent_t>(fence), 0), "hipStreamWaitEvent");
 	});
 
 	const gra_video_layout &l = video->layout;
 	gr_image planes[3] = {};
-	const gr_image *plane_ptrs[3] = {};
+	VideoScaler::RescaleInfo info = {};
 	for (uint32_t i = 0; i < l.num_planes; i++)
 	{
 		planes[i] = {static_cast<uint8_t *>(video->planes) + l.offset[i], l.width[i], l.height[i], l.pitch[i], video->plane_format[i]};
-		plane_ptrs[i] = &planes[i];
+		info.output_planes[i] = &planes[i];
 	}
 	const gr_image input = backbuffer.get_view();
-	VideoScaler::RescaleInfo info = {};
-	for (uint32_t i = 0; i < l.num_planes; i++)
-		info.output_planes[i] = plane_ptrs[i];
 	info.num_output_planes = l.num_planes;
 	info.input = &input;
 	info.input_color_space = config.hdr10 ? GR_COLOR_SPACE_HDR10_ST2084 : GR_COLOR_SPACE_SRGB_NONLINEAR;
@@ -206,32 +170,24 @@ void ImageSpaceApplication::video_after_frame(HIP::Image &backbuffer, uint64_t d
 	if (!done)
 	{
 		hipEvent_t e;
-		hip_check(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreateWithFlags");
+		ring.check(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreateWithFlags");
 		done = e;
 	}
-	hip_check(hipEventRecord(static_cast<hipEvent_t>(done), stream), "hipEventRecord");
+	ring.check(hipEventRecord(static_cast<hipEvent_t>(done), stream), "hipEventRecord");
 
-	auto &slot = video->ring[video->written % video->ring.size()];
-	hip_check(hipMemcpyAsync(slot.host, video->planes, l.frame_bytes, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync");
-	hip_check(hipEventRecord(static_cast<hipEvent_t>(slot.copied), stream), "hipEventRecord");
-	slot.frame = int64_t(video->written);
-	video->written++;
+	ring.check(hipMemcpyAsync(ring.next_slot().host[0], video->planes, l.frame_bytes, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync");
+	ring.commit_slot();
 }
 
 bool ImageSpaceApplication::video_read(void *dst, uint64_t size, int64_t *frame_number)
 {
 	if (!video)
 		throw std::logic_error("gra_video_read_frame: not recording");
-	if (video->read == video->written)
+	if (video->ring.read == video->ring.written)
 		return false;
 	if (size < video->layout.frame_bytes)
 		throw std::logic_error("gra_video_read_frame: destination smaller than one frame (gra_video_frame_layout)");
-	auto &slot = video->ring[video->read % video->ring.size()];
-	hip_check(hipEventSynchronize(static_cast<hipEvent_t>(slot.copied)), "hipEventSynchronize");
-	memcpy(dst, slot.host, video->layout.frame_bytes);
-	if (frame_number)
-		*frame_number = slot.frame;
-	video->read++;
+	video->ring.read_into(dst, 0, frame_number);
 	return true;
 }
 } // namespace Granite

@@ -1153,16 +1153,6 @@ __global__ __launch_bounds__(TONEMAP_BLOCK_X *TONEMAP_BLOCK_Y) void k_tonemap(De
 static bool allow_stencil() { static const bool allow = gr_measurement_switch("GR_NO_STENCIL") == nullptr; return allow; }
 static bool allow_tail_fusion() { static const bool allow = gr_measurement_switch("GR_NO_TAIL_FUSION") == nullptr; return allow; }
 
-// Runtime flags to template arguments: f(std::bool_constant<flags>...), one instantiation of f per combination.
-template <typename F> static void with_flags(F &&f) { f(); }
-template <typename F, typename... Rest> static void with_flags(F &&f, bool flag, Rest... rest)
-{
-	if (flag)
-		with_flags([&](auto... constants) { f(std::true_type{}, constants...); }, rest...);
-	else
-		with_flags([&](auto... constants) { f(std::false_type{}, constants...); }, rest...);
-}
-
 static bool is_rgba16f(const gr_image *img)
 {
 	return img && img->ptr && img->format == GR_FORMAT_R16G16B16A16_SFLOAT && img->width && img->height &&
@@ -1175,8 +1165,6 @@ static bool is_b10g11r11(const gr_image *img)
 }
 // an HDR colour target as the passes that only read it take it: RGBA16F, or the reference's default B10G11R11_UFLOAT_PACK32
 static bool is_hdr_target(const gr_image *img) { return is_rgba16f(img) || is_b10g11r11(img); }
-// rows that 16-byte loads can walk
-static bool is_aligned16(const gr_image *img) { return (img->pitch_bytes & 15u) == 0 && (reinterpret_cast<uintptr_t>(img->ptr) & 15u) == 0; }
 static bool same_size(const gr_image *a, const gr_image *b) { return a->width == b->width && a->height == b->height; }
 // a fused kernel writes whole levels: its push block names every texel of the image
 static bool covers(const uint32_t threads[2], const gr_image *img) { return threads[0] == img->width && threads[1] == img->height; }

@@ -6,13 +6,14 @@
 // Two kernels instead of the reference's one 64-thread group per 8 x 8 output tile:
 //   k_video_direct  (SKIP_RESCALE: the encode size is the frame size, what a recorder uses): a pure stream.  One lane converts
 //                   4 x 2 pixels: two 16-B loads (32 B for RGBA16F), the 2 x 2 chroma means inside the lane, one 4-B luma store
-//                   per row (8 B at 16 bits) and one store per chroma plane.  Everything in fp32.
+//                   per row (8 B at 16 bits; store_run) and one store per chroma plane (store_chroma).  Everything in fp32.
 //   k_video_rescale (the separable 8-tap, 256-phase filter, 16 x 16 outputs per 256-thread group): the EOTF'd input halo of the
 //                   tile is staged once in LDS as fp16 (as the reference stages it), filtered vertically into a second fp16 tile,
 //                   then horizontally; accumulation in fp32 with the fp16 weight table.  Sample positions are the reference's
 //                   8.8 fixed-point ones, computed from the same 8 x 8 tile bases, so phases and taps are the same.  With
 //                   SAMPLED_DOWNSCALING the staged texels are LinearClamp samples of the input at twice the target size.
-//                   The 2 x 2 chroma mean is taken across the quad by DPP.
+//                   The 2 x 2 chroma mean is taken across the quad by DPP; every lane stores its own samples.
+// Both end in the same tails: dither_term, then pack_rgba8 for the single plane or unorm_code per sample.
 // Stores outside a plane are dropped (imageStore out of bounds).  Input texels outside the frame read as zero on the direct path
 // (texelFetch with robust image access; the reference fetches unclamped there) and are clamped to the edge on the rescale path
 // (CLAMP_COORD).
@@ -163,6 +164,21 @@ __device__ __forceinline__ float dither_at(int x, int y)
 
 __device__ __forceinline__ uint32_t unorm_code(float v, float scale) { return uint32_t(saturatef(v) * scale + 0.5f); }
 
+// what the dither adds to the sample at (x, y) of a plane
+__device__ __forceinline__ float dither_term(const VideoArgs &a, bool dither, int x, int y) { return dither ? dither_at(x, y) * a.dither_strength : 0.0f; }
+
+// the single plane's word at (x, y): the dither on all four channels, R and B swapped for BGRA8
+__device__ __forceinline__ uint32_t pack_rgba8(const VideoArgs &a, float4 v, bool dither, int x, int y)
+{
+	if (dither)
+	{
+		const float d = dither_term(a, true, x, y);
+		v = make_float4(v.x + d, v.y + d, v.z + d, v.w + d);
+	}
+	const uint32_t c0 = unorm_code(a.swap_rb ? v.z : v.x, 255.0f), c2 = unorm_code(a.swap_rb ? v.x : v.z, 255.0f);
+	return c0 | (unorm_code(v.y, 255.0f) << 8) | (c2 << 16) | (unorm_code(v.w, 255.0f) << 24);
+}
+
 // Y / Cb / Cr of one pixel, clamped, fp32 (scaler.comp: clamp, then gamma_space_transform * vec4(rgb, 1))
 __device__ __forceinline__ float3 to_ycbcr(const VideoArgs &a, float4 v)
 {
@@ -200,6 +216,28 @@ __device__ __forceinline__ void store_run(uint8_t *row, int x, int limit, const 
 
 template <bool WIDE> struct Sample { typedef uint8_t type; static constexpr float scale = 255.0f; };
 template <> struct Sample<true> { typedef uint16_t type; static constexpr float scale = 65535.0f; };
+
+// N Cb / Cr pairs from chroma texel x of row y: interleaved into plane 1 (two planes), or a run into each of planes 1 and 2
+template <int PLANES, typename T, int N>
+__device__ __forceinline__ void store_chroma(const VideoArgs &a, int x, int y, const T (&cb)[N], const T (&cr)[N])
+{
+	if (PLANES == 2)
+	{
+		T cbcr[2 * N];
+#pragma unroll
+		for (int i = 0; i < N; i++)
+		{
+			cbcr[2 * i] = cb[i];
+			cbcr[2 * i + 1] = cr[i];
+		}
+		store_run<T, 2 * N>(a.plane[1] + size_t(y) * a.pitch[1], 2 * x, 2 * a.chroma_w, cbcr, a.aligned & 2u);
+	}
+	else
+	{
+		store_run<T, N>(a.plane[1] + size_t(y) * a.pitch[1], x, a.chroma_w, cb, a.aligned & 2u);
+		store_run<T, N>(a.plane[2] + size_t(y) * a.pitch[2], x, a.chroma_w, cr, a.aligned & 4u);
+	}
+}
 
 // ---- same size -------------------------------------------------------------------------------------------------------------
 constexpr int DIRECT_PX = 4;    // pixels per lane along x
@@ -272,16 +310,7 @@ __global__ __launch_bounds__(256) void k_video_direct(VideoArgs a)
 			uint32_t words[DIRECT_PX];
 #pragma unroll
 			for (int i = 0; i < DIRECT_PX; i++)
-			{
-				float4 v = px[r][i];
-				if (dither)
-				{
-					const float d = dither_at(x0 + i, y0 + r) * a.dither_strength;
-					v = make_float4(v.x + d, v.y + d, v.z + d, v.w + d);
-				}
-				const uint32_t c0 = unorm_code(a.swap_rb ? v.z : v.x, 255.0f), c2 = unorm_code(a.swap_rb ? v.x : v.z, 255.0f);
-				words[i] = c0 | (unorm_code(v.y, 255.0f) << 8) | (c2 << 16) | (unorm_code(v.w, 255.0f) << 24);
-			}
+				words[i] = pack_rgba8(a, px[r][i], dither, x0 + i, y0 + r);
 			store_run<uint32_t, DIRECT_PX>(a.plane[0] + size_t(y0 + r) * a.pitch[0], x0, a.out_w, words, a.aligned & 1u);
 		}
 		return;
@@ -302,7 +331,7 @@ __global__ __launch_bounds__(256) void k_video_direct(VideoArgs a)
 		S luma[DIRECT_PX];
 #pragma unroll
 		for (int i = 0; i < DIRECT_PX; i++)
-			luma[i] = S(unorm_code(ycc[r][i].y + (dither ? dither_at(x0 + i, y0 + r) * a.dither_strength : 0.0f), SCALE));
+			luma[i] = S(unorm_code(ycc[r][i].y + dither_term(a, dither, x0 + i, y0 + r), SCALE));
 		store_run<S, DIRECT_PX>(a.plane[0] + size_t(y0 + r) * a.pitch[0], x0, a.out_w, luma, a.aligned & 1u);
 	}
 
@@ -321,29 +350,14 @@ __global__ __launch_bounds__(256) void k_video_direct(VideoArgs a)
 			sr *= 0.25f;
 			if (dither)
 			{
-				const float d = dither_at(cx0 + k, cy) * a.dither_strength;
+				const float d = dither_term(a, true, cx0 + k, cy);
 				sb += d;
 				sr += d;
 			}
 			cb[k] = S(unorm_code(sb, SCALE));
 			cr[k] = S(unorm_code(sr, SCALE));
 		}
-		if (PLANES == 2)
-		{
-			S cbcr[2 * NC];
-#pragma unroll
-			for (int k = 0; k < NC; k++)
-			{
-				cbcr[2 * k] = cb[k];
-				cbcr[2 * k + 1] = cr[k];
-			}
-			store_run<S, 2 * NC>(a.plane[1] + size_t(cy) * a.pitch[1], 2 * cx0, 2 * a.chroma_w, cbcr, a.aligned & 2u);
-		}
-		else
-		{
-			store_run<S, NC>(a.plane[1] + size_t(cy) * a.pitch[1], cx0, a.chroma_w, cb, a.aligned & 2u);
-			store_run<S, NC>(a.plane[2] + size_t(cy) * a.pitch[2], cx0, a.chroma_w, cr, a.aligned & 4u);
-		}
+		store_chroma<PLANES, S, NC>(a, cx0, cy, cb, cr);
 		return;
 	}
 
@@ -356,26 +370,11 @@ __global__ __launch_bounds__(256) void k_video_direct(VideoArgs a)
 #pragma unroll
 		for (int i = 0; i < DIRECT_PX; i++)
 		{
-			const float d = dither ? dither_at(x0 + i, y0 + r) * a.dither_strength : 0.0f;
+			const float d = dither_term(a, dither, x0 + i, y0 + r);
 			cb[i] = S(unorm_code(ycc[r][i].x + d, SCALE));
 			cr[i] = S(unorm_code(ycc[r][i].z + d, SCALE));
 		}
-		if (PLANES == 2)
-		{
-			S cbcr[2 * DIRECT_PX];
-#pragma unroll
-			for (int i = 0; i < DIRECT_PX; i++)
-			{
-				cbcr[2 * i] = cb[i];
-				cbcr[2 * i + 1] = cr[i];
-			}
-			store_run<S, 2 * DIRECT_PX>(a.plane[1] + size_t(y0 + r) * a.pitch[1], 2 * x0, 2 * a.chroma_w, cbcr, a.aligned & 2u);
-		}
-		else
-		{
-			store_run<S, DIRECT_PX>(a.plane[1] + size_t(y0 + r) * a.pitch[1], x0, a.chroma_w, cb, a.aligned & 2u);
-			store_run<S, DIRECT_PX>(a.plane[2] + size_t(y0 + r) * a.pitch[2], x0, a.chroma_w, cr, a.aligned & 4u);
-		}
+		store_chroma<PLANES, S, DIRECT_PX>(a, x0, y0 + r, cb, cr);
 	}
 }
 
@@ -492,25 +491,16 @@ __global__ __launch_bounds__(256) void k_video_rescale(VideoArgs a)
 	const bool inside = ox < a.out_w && oy < a.out_h;
 	if (PLANES == 1)
 	{
-		if (dither)
-		{
-			const float d = dither_at(ox, oy) * a.dither_strength;
-			v = make_float4(v.x + d, v.y + d, v.z + d, v.w + d);
-		}
+		const uint32_t word = pack_rgba8(a, v, dither, ox, oy);
 		if (inside)
-		{
-			const uint32_t c0 = unorm_code(a.swap_rb ? v.z : v.x, 255.0f), c2 = unorm_code(a.swap_rb ? v.x : v.z, 255.0f);
-			*reinterpret_cast<uint32_t *>(a.plane[0] + size_t(oy) * a.pitch[0] + size_t(ox) * 4u) =
-			    c0 | (unorm_code(v.y, 255.0f) << 8) | (c2 << 16) | (unorm_code(v.w, 255.0f) << 24);
-		}
+			*reinterpret_cast<uint32_t *>(a.plane[0] + size_t(oy) * a.pitch[0] + size_t(ox) * 4u) = word;
 		return;
 	}
 
 	const float3 ycc = to_ycbcr(a, v);
 	if (inside)
 	{
-		const float d = dither ? dither_at(ox, oy) * a.dither_strength : 0.0f;
-		*reinterpret_cast<S *>(a.plane[0] + size_t(oy) * a.pitch[0] + size_t(ox) * sizeof(S)) = S(unorm_code(ycc.y + d, SCALE));
+		*reinterpret_cast<S *>(a.plane[0] + size_t(oy) * a.pitch[0] + size_t(ox) * sizeof(S)) = S(unorm_code(ycc.y + dither_term(a, dither, ox, oy), SCALE));
 	}
 	float cb = ycc.x, cr = ycc.z;
 	int cx = ox, cy = oy;
@@ -531,7 +521,7 @@ __global__ __launch_bounds__(256) void k_video_rescale(VideoArgs a)
 		return;
 	if (dither)
 	{
-		const float d = dither_at(cx, cy) * a.dither_strength;
+		const float d = dither_term(a, true, cx, cy);
 		cb += d;
 		cr += d;
 	}
@@ -643,7 +633,8 @@ Mat3 inverse3(const Mat3 &m)
 }
 
 // RGB -> XYZ for chromaticities (x, y) of the primaries and the white point: the construction of host/post/hdr.cpp's
-// compute_xyz_matrix (that one lives in the host library, which links against this one)
+// compute_xyz_matrix.  Not shared with it: that file's inverse multiplies by 1 / det where inverse3 divides by det, the results differ
+// in the last bit, and each is pinned by its own CPU test.
 Mat3 xyz_matrix(const float (&xy)[4][2])
 {
 	Mat3 primaries;
@@ -665,6 +656,12 @@ Mat3 xyz_matrix(const float (&xy)[4][2])
 	}
 	return r;
 }
+
+// chromaticities of R, G, B and the white point (D65)
+const float prim709[4][2] = {{0.640f, 0.330f}, {0.300f, 0.600f}, {0.150f, 0.060f}, {0.3127f, 0.3290f}};
+const float prim2020[4][2] = {{0.708f, 0.292f}, {0.170f, 0.797f}, {0.131f, 0.046f}, {0.3127f, 0.3290f}};
+const float prim601_625[4][2] = {{0.640f, 0.330f}, {0.290f, 0.600f}, {0.150f, 0.060f}, {0.3127f, 0.3290f}};
+const float prim601_525[4][2] = {{0.630f, 0.340f}, {0.310f, 0.595f}, {0.155f, 0.070f}, {0.3127f, 0.3290f}};
 
 bool recognized_color_space(uint32_t space)
 {
@@ -694,6 +691,27 @@ bool is_rgba8_output(uint32_t f)
 	return f == GR_FORMAT_R8G8B8A8_UNORM || f == GR_FORMAT_R8G8B8A8_SRGB || f == GR_FORMAT_B8G8R8A8_UNORM || f == GR_FORMAT_B8G8R8A8_SRGB;
 }
 
+// The plane layout of a YCbCr frame, for plan_video and plan_yuv: chroma planes of the luma plane's size or, with `sub` (each caller's own
+// reading of the sizes), half of it rounded up; one interleaved or two of the luma's format; pitches hold a row.  The reason of a refusal, or nullptr.
+const char *check_plane_layout(const gr_image *planes, uint32_t num_planes, bool wide, bool sub)
+{
+	const gr_image &y = planes[0];
+	if (num_planes > 1)
+	{
+		const gr_image &c = planes[1];
+		if (sub ? (c.width != (y.width + 1) / 2 || c.height != (y.height + 1) / 2) : (c.width != y.width || c.height != y.height))
+			return "chroma planes must have the luma plane's size or half of it, rounded up";
+		const uint32_t want = num_planes == 2 ? (wide ? GR_FORMAT_R16G16_UNORM : GR_FORMAT_R8G8_UNORM) : y.format;
+		for (uint32_t i = 1; i < num_planes; i++)
+			if (planes[i].format != want || planes[i].width != c.width || planes[i].height != c.height)
+				return "chroma plane format or size does not match the luma plane";
+	}
+	for (uint32_t i = 0; i < num_planes; i++)
+		if (planes[i].pitch_bytes < planes[i].width * texel_bytes(planes[i].format))
+			return "plane pitch smaller than its row";
+	return nullptr;
+}
+
 // Checks the arguments and fills the plan; returns the reason of a refusal, or nullptr.
 const char *plan_video(const gr_image *in, const gr_image *planes, uint32_t num_planes, uint32_t in_space, uint32_t out_space, gr_video_plan *p)
 {
@@ -718,20 +736,11 @@ const char *plan_video(const gr_image *in, const gr_image *planes, uint32_t num_
 	const bool wide = y.format == GR_FORMAT_R16_UNORM;
 	if (num_planes > 1 && y.format != GR_FORMAT_R8_UNORM && !wide)
 		return "the luma plane must be R8_UNORM or R16_UNORM";
-	if (num_planes > 1)
-	{
-		const gr_image &c = planes[1];
-		const bool sub = c.width < y.width;
-		if (sub ? (c.width != (y.width + 1) / 2 || c.height != (y.height + 1) / 2) : (c.width != y.width || c.height != y.height))
-			return "chroma planes must have the luma plane's size or half of it, rounded up";
-		const uint32_t want = num_planes == 2 ? (wide ? GR_FORMAT_R16G16_UNORM : GR_FORMAT_R8G8_UNORM) : y.format;
-		for (uint32_t i = 1; i < num_planes; i++)
-			if (planes[i].format != want || planes[i].width != c.width || planes[i].height != c.height)
-				return "chroma plane format or size does not match the luma plane";
-	}
-	for (uint32_t i = 0; i < num_planes; i++)
-		if (planes[i].pitch_bytes < planes[i].width * texel_bytes(planes[i].format))
-			return "plane pitch smaller than its row";
+	// 4:2:0 by the width alone, as VideoScaler::rescale: a frame one pixel wide is refused, which plan_yuv accepts, on purpose
+	// (test_plan_refuses_invalid_conversions in tests/test_video_scaler_cpu.py, assert_refused in tests/test_gpu_video_scaler.py).
+	const bool sub = num_planes > 1 && planes[1].width < y.width;
+	if (const char *why = check_plane_layout(planes, num_planes, wide, sub))
+		return why;
 
 	memset(p, 0, sizeof(*p));
 	p->num_planes = num_planes;
@@ -764,7 +773,7 @@ const char *plan_video(const gr_image *in, const gr_image *planes, uint32_t num_
 	if (in_space != out_space)
 		flags |= GR_VIDEO_CONTROL_PRIMARY_CONVERSION_BIT;
 	flags |= GR_VIDEO_CONTROL_CLAMP_COORD_BIT;
-	if (num_planes > 1 && y.width > planes[1].width)
+	if (sub)
 		flags |= GR_VIDEO_CONTROL_CHROMA_SUBSAMPLE_BIT;
 	if (is_rgba8_output(y.format))
 	{
@@ -784,8 +793,6 @@ const char *plan_video(const gr_image *in, const gr_image *planes, uint32_t num_
 
 	if (in_space != out_space)
 	{
-		static const float prim709[4][2] = {{0.640f, 0.330f}, {0.300f, 0.600f}, {0.150f, 0.060f}, {0.3127f, 0.3290f}};
-		static const float prim2020[4][2] = {{0.708f, 0.292f}, {0.170f, 0.797f}, {0.131f, 0.046f}, {0.3127f, 0.3290f}};
 		const Mat3 to_out = inverse3(xyz_matrix(out_space == GR_COLOR_SPACE_HDR10_ST2084 ? prim2020 : prim709));
 		const Mat3 from_in = xyz_matrix(in_space == GR_COLOR_SPACE_HDR10_ST2084 ? prim2020 : prim709);
 		const Mat3 conv = mul3(to_out, from_in);
@@ -807,20 +814,18 @@ const char *plan_video(const gr_image *in, const gr_image *planes, uint32_t num_
 	return nullptr;
 }
 
-#define VIDEO_KERNEL_TABLE(kernel)                                                                                             \
-	switch (num_planes * 4 + (sub ? 2 : 0) + (wide ? 1 : 0))                                                               \
-	{                                                                                                                          \
-	case 4: hipLaunchKernelGGL((kernel<1, false, false>), grid, block, 0, s, a); break;                                  \
-	case 8: hipLaunchKernelGGL((kernel<2, false, false>), grid, block, 0, s, a); break;                                  \
-	case 9: hipLaunchKernelGGL((kernel<2, false, true>), grid, block, 0, s, a); break;                                   \
-	case 10: hipLaunchKernelGGL((kernel<2, true, false>), grid, block, 0, s, a); break;                                  \
-	case 11: hipLaunchKernelGGL((kernel<2, true, true>), grid, block, 0, s, a); break;                                   \
-	case 12: hipLaunchKernelGGL((kernel<3, false, false>), grid, block, 0, s, a); break;                                 \
-	case 13: hipLaunchKernelGGL((kernel<3, false, true>), grid, block, 0, s, a); break;                                  \
-	case 14: hipLaunchKernelGGL((kernel<3, true, false>), grid, block, 0, s, a); break;                                  \
-	case 15: hipLaunchKernelGGL((kernel<3, true, true>), grid, block, 0, s, a); break;                                   \
-	default: return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_video_scale: unsupported plane layout");                       \
+// launch(<PLANES>, <SUB>, <WIDE>) with the constants of k_video_direct / k_video_rescale: nine instantiations per kernel, a single plane
+// (RGBA8) being neither subsampled nor wide.  False, and no call, for any other combination.
+template <typename F> bool with_plane_layout(uint32_t num_planes, bool sub, bool wide, F &&launch)
+{
+	switch (num_planes)
+	{
+	case 1: return !sub && !wide && (launch(std::integral_constant<int, 1>{}, std::false_type{}, std::false_type{}), true);
+	case 2: return with_flags([&](auto s, auto w) { launch(std::integral_constant<int, 2>{}, s, w); }, sub, wide), true;
+	case 3: return with_flags([&](auto s, auto w) { launch(std::integral_constant<int, 3>{}, s, w); }, sub, wide), true;
+	default: return false;
 	}
+}
 } // namespace
 
 extern "C" int gr_video_scaler_weights(uint32_t in_w, uint32_t in_h, uint32_t out_w, uint32_t out_h, uint16_t *out)
@@ -857,14 +862,13 @@ extern "C" int gr_video_scale(gr_ctx *ctx, gr_stream stream, const gr_image *inp
 	a.in_kind = input->format == GR_FORMAT_R8G8B8A8_SRGB ? IN_RGBA8_SRGB
 	            : input->format == GR_FORMAT_A2B10G10R10_UNORM_PACK32 ? IN_A2B10G10R10
 	            : input->format == GR_FORMAT_R16G16B16A16_SFLOAT ? IN_RGBA16F : IN_RGBA8;
-	const auto aligned16 = [](const void *ptr, uint32_t pitch) { return (reinterpret_cast<uintptr_t>(ptr) & 15u) == 0 && (pitch & 15u) == 0; };
 	for (uint32_t i = 0; i < num_planes; i++)
 	{
 		a.plane[i] = static_cast<uint8_t *>(planes[i].ptr);
 		a.pitch[i] = planes[i].pitch_bytes;
-		a.aligned |= aligned16(planes[i].ptr, planes[i].pitch_bytes) ? 1u << i : 0u;
+		a.aligned |= is_aligned16(&planes[i]) ? 1u << i : 0u;
 	}
-	a.aligned |= aligned16(input->ptr, input->pitch_bytes) ? 8u : 0u;
+	a.aligned |= is_aligned16(input) ? 8u : 0u;
 	a.out_w = int(planes[0].width);
 	a.out_h = int(planes[0].height);
 	a.chroma_w = num_planes > 1 ? int(planes[1].width) : 0;
@@ -884,10 +888,13 @@ extern "C" int gr_video_scale(gr_ctx *ctx, gr_stream stream, const gr_image *inp
 	const bool wide = planes[0].format == GR_FORMAT_R16_UNORM;
 	hipStream_t s = gr_to_stream(stream);
 	gr_scoped_timing timing{ctx, s, "video_scale"};
+	bool launched;
 	if (plan.flags & GR_VIDEO_CONTROL_SKIP_RESCALE_BIT)
 	{
 		const dim3 grid(gr_div_up(planes[0].width, 64 * DIRECT_PX), gr_div_up(planes[0].height, 2 * DIRECT_ROWS)), block(256);
-		VIDEO_KERNEL_TABLE(k_video_direct)
+		launched = with_plane_layout(num_planes, sub, wide, [&](auto n, auto sb, auto wd) {
+			hipLaunchKernelGGL((k_video_direct<n.value, sb.value, wd.value>), grid, block, 0, s, a);
+		});
 	}
 	else
 	{
@@ -929,8 +936,12 @@ extern "C" int gr_video_scale(gr_ctx *ctx, gr_stream stream, const gr_image *inp
 			GR_CHECK_HIP(ctx, hipStreamWaitEvent(s, ready, 0));
 		a.weights = static_cast<const uint16_t *>(table);
 		const dim3 grid(gr_div_up(planes[0].width, TILE), gr_div_up(planes[0].height, TILE)), block(256);
-		VIDEO_KERNEL_TABLE(k_video_rescale)
+		launched = with_plane_layout(num_planes, sub, wide, [&](auto n, auto sb, auto wd) {
+			hipLaunchKernelGGL((k_video_rescale<n.value, sb.value, wd.value>), grid, block, 0, s, a);
+		});
 	}
+	if (!launched)
+		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_video_scale: unsupported plane layout");
 	GR_CHECK_LAUNCH(ctx);
 	return GR_OK;
 }
@@ -1023,6 +1034,14 @@ __device__ __forceinline__ float4 fetch_chroma(const YuvArgs &a, int x, int y)
 // yuv_to_rgb.comp's EOTF: ST 2084 to scRGB units (80 nits = 1)
 __device__ __forceinline__ float pq_to_scrgb(float v) { return pq_eotf(v) * (1.0f / 80.0f); }
 
+// R, G, B + d as BITS-wide codes from bit 0 up, `alpha` in the bits above them: an RGBA8 (8) or A2B10G10R10 (10) word
+template <int BITS>
+__device__ __forceinline__ uint32_t pack_unorm_rgb(const float (&rgb)[3], float d, uint32_t alpha)
+{
+	constexpr float SCALE = float((1 << BITS) - 1);
+	return unorm_code(rgb[0] + d, SCALE) | (unorm_code(rgb[1] + d, SCALE) << BITS) | (unorm_code(rgb[2] + d, SCALE) << (2 * BITS)) | (alpha << (3 * BITS));
+}
+
 template <int PLANES, bool WIDE, int OUT>
 __global__ __launch_bounds__(256) void k_yuv_to_rgb(YuvArgs a)
 {
@@ -1076,10 +1095,7 @@ __global__ __launch_bounds__(256) void k_yuv_to_rgb(YuvArgs a)
 			else
 			{
 				const float d = dither_at(x, y) * (1.0f / 255.0f);
-				if (OUT == YUV_OUT_A2B10G10R10)
-					words[i] = unorm_code(rgb[0] + d, 1023.0f) | (unorm_code(rgb[1] + d, 1023.0f) << 10) | (unorm_code(rgb[2] + d, 1023.0f) << 20) | (3u << 30);
-				else
-					words[i] = unorm_code(rgb[0] + d, 255.0f) | (unorm_code(rgb[1] + d, 255.0f) << 8) | (unorm_code(rgb[2] + d, 255.0f) << 16) | (255u << 24);
+				words[i] = OUT == YUV_OUT_A2B10G10R10 ? pack_unorm_rgb<10>(rgb, d, 3u) : pack_unorm_rgb<8>(rgb, d, 255u);
 			}
 		}
 		uint8_t *row = a.out + size_t(y) * a.out_pitch;
@@ -1149,21 +1165,11 @@ const char *plan_yuv(const gr_image *planes, uint32_t num_planes, const gr_image
 		return "unknown chroma location";
 	if (info->nv21 && num_planes != 2)
 		return "nv21 needs two planes";
-	bool sub = false;
-	if (num_planes > 1)
-	{
-		const gr_image &c = planes[1];
-		sub = c.width < y.width || c.height < y.height;
-		if (sub ? (c.width != (y.width + 1) / 2 || c.height != (y.height + 1) / 2) : (c.width != y.width || c.height != y.height))
-			return "chroma planes must have the luma plane's size or half of it, rounded up";
-		const uint32_t want = num_planes == 2 ? (wide ? GR_FORMAT_R16G16_UNORM : GR_FORMAT_R8G8_UNORM) : y.format;
-		for (uint32_t i = 1; i < num_planes; i++)
-			if (planes[i].format != want || planes[i].width != c.width || planes[i].height != c.height)
-				return "chroma plane format or size does not match the luma plane";
-	}
-	for (uint32_t i = 0; i < num_planes; i++)
-		if (planes[i].pitch_bytes < planes[i].width * texel_bytes(planes[i].format))
-			return "plane pitch smaller than its row";
+	// 4:2:0 by the width or the height: a frame one pixel wide is accepted, which plan_video refuses, on purpose
+	// (test_plan_accepts_one_pixel_wide_420 in tests/test_yuv_ref_cpu.py, the 1 x 2 cases of test_edge_sizes in tests/test_gpu_yuv_to_rgb.py).
+	const bool sub = num_planes > 1 && (planes[1].width < y.width || planes[1].height < y.height);
+	if (const char *why = check_plane_layout(planes, num_planes, wide, sub))
+		return why;
 	const bool rgba8 = out->format == GR_FORMAT_R8G8B8A8_UNORM || out->format == GR_FORMAT_R8G8B8A8_SRGB;
 	if (!rgba8 && out->format != GR_FORMAT_A2B10G10R10_UNORM_PACK32 && out->format != GR_FORMAT_R16G16B16A16_SFLOAT)
 		return "output format must be R8G8B8A8_{UNORM,SRGB}, A2B10G10R10_UNORM_PACK32 or R16G16B16A16_SFLOAT";
@@ -1208,10 +1214,6 @@ const char *plan_yuv(const gr_image *planes, uint32_t num_planes, const gr_image
 		matrix = y.height < 625 ? GR_VIDEO_MATRIX_BT601_525 : y.height < 720 ? GR_VIDEO_MATRIX_BT601_625 : y.height < 2160 ? GR_VIDEO_MATRIX_BT709 : GR_VIDEO_MATRIX_BT2020;
 	p->matrix = matrix;
 
-	static const float prim709[4][2] = {{0.640f, 0.330f}, {0.300f, 0.600f}, {0.150f, 0.060f}, {0.3127f, 0.3290f}};
-	static const float prim601_625[4][2] = {{0.640f, 0.330f}, {0.290f, 0.600f}, {0.150f, 0.060f}, {0.3127f, 0.3290f}};
-	static const float prim601_525[4][2] = {{0.630f, 0.340f}, {0.310f, 0.595f}, {0.155f, 0.070f}, {0.3127f, 0.3290f}};
-	static const float prim2020[4][2] = {{0.708f, 0.292f}, {0.170f, 0.797f}, {0.131f, 0.046f}, {0.3127f, 0.3290f}};
 	// columns: what Y, Cb and Cr contribute to (R, G, B)
 	Mat3 m = {};
 	const float (*source)[4][2] = nullptr;
@@ -1280,7 +1282,6 @@ extern "C" int gr_video_yuv_to_rgb(gr_ctx *ctx, gr_stream stream, const gr_image
 		GR_CHECK_ARG(ctx, planes[i].ptr);
 
 	YuvArgs a = {};
-	const auto aligned16 = [](const void *ptr, uint32_t pitch) { return (reinterpret_cast<uintptr_t>(ptr) & 15u) == 0 && (pitch & 15u) == 0; };
 	for (uint32_t i = 0; i < num_planes; i++)
 	{
 		a.plane[i] = static_cast<const uint8_t *>(planes[i].ptr);
@@ -1292,7 +1293,7 @@ extern "C" int gr_video_yuv_to_rgb(gr_ctx *ctx, gr_stream stream, const gr_image
 	a.ch = num_planes > 1 ? int(planes[1].height) : 0;
 	a.out = static_cast<uint8_t *>(out->ptr);
 	a.out_pitch = out->pitch_bytes;
-	a.aligned = (aligned16(planes[0].ptr, planes[0].pitch_bytes) ? 1u : 0u) | (aligned16(out->ptr, out->pitch_bytes) ? 8u : 0u);
+	a.aligned = (is_aligned16(&planes[0]) ? 1u : 0u) | (is_aligned16(out) ? 8u : 0u);
 	a.nv21 = plan.spec_nv21;
 	const gr_push_yuv_to_rgb &push = plan.push;
 	for (int row = 0; row < 3; row++)
@@ -1311,16 +1312,14 @@ extern "C" int gr_video_yuv_to_rgb(gr_ctx *ctx, gr_stream stream, const gr_image
 	hipStream_t s = gr_to_stream(stream);
 	gr_scoped_timing timing{ctx, s, "video_yuv_to_rgb"};
 	const dim3 grid(gr_div_up(planes[0].width, 64 * DIRECT_PX), gr_div_up(planes[0].height, 2 * DIRECT_ROWS)), block(256);
-#define YUV_KERNEL_CASE(planes_, wide_, out_)                                                                                  \
-	case (planes_) * 8 + (wide_) * 4 + (out_): hipLaunchKernelGGL((k_yuv_to_rgb<planes_, wide_ != 0, out_>), grid, block, 0, s, a); break;
-#define YUV_KERNEL_OUTPUTS(planes_, wide_) YUV_KERNEL_CASE(planes_, wide_, 0) YUV_KERNEL_CASE(planes_, wide_, 1) YUV_KERNEL_CASE(planes_, wide_, 2)
-	switch (int(num_planes) * 8 + (wide ? 4 : 0) + kind)
-	{
-		YUV_KERNEL_OUTPUTS(1, 0) YUV_KERNEL_OUTPUTS(1, 1) YUV_KERNEL_OUTPUTS(2, 0) YUV_KERNEL_OUTPUTS(2, 1) YUV_KERNEL_OUTPUTS(3, 0) YUV_KERNEL_OUTPUTS(3, 1)
-	default: return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_video_yuv_to_rgb: unsupported plane layout");
-	}
-#undef YUV_KERNEL_OUTPUTS
-#undef YUV_KERNEL_CASE
+	bool launched = false; // <PLANES 1..3, WIDE, OUT 0..2>: all 18 combinations exist
+	with_index<3>(int(num_planes) - 1, [&](auto n) {
+		launched = with_index<3>(kind, [&](auto o) {
+			with_flags([&](auto wd) { hipLaunchKernelGGL((k_yuv_to_rgb<n.value + 1, wd.value, o.value>), grid, block, 0, s, a); }, wide);
+		});
+	});
+	if (!launched)
+		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_video_yuv_to_rgb: unsupported plane layout");
 	GR_CHECK_LAUNCH(ctx);
 	return GR_OK;
 }

@@ -21,40 +21,11 @@ import pytest
 
 import video_ref as vr
 from granite_amd import capi
+from video_planes import EDGE_SIZES, GuardedImage, nv12, yuv
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 4096
-FILL = 0xA5
 S, HDR, LIN = capi.COLOR_SPACE_SRGB_NONLINEAR, capi.COLOR_SPACE_HDR10_ST2084, capi.COLOR_SPACE_EXTENDED_SRGB_LINEAR
-CHANNELS = {vr.R8: (1, np.uint8), vr.R16: (1, np.uint16), vr.R8G8: (2, np.uint8), vr.R16G16: (2, np.uint16),
-            vr.RGBA8: (4, np.uint8), vr.BGRA8: (4, np.uint8), vr.RGBA8_SRGB: (4, np.uint8), vr.BGRA8_SRGB: (4, np.uint8)}
-
-
-class GuardedPlane:
-    """A plane inside a larger allocation: row pitch padded past the row (by default to a multiple of 16 plus 16: the vector stores;
-    `pad` gives row + pad bytes instead) starting `offset` bytes into the buffer, GUARD bytes after the last row, all filled with FILL
-    before the launch.  An offset or pitch that is not a multiple of 16 takes the store-by-store path of every run."""
-
-    def __init__(self, gr, w, h, fmt, offset=0, pad=None):
-        self.w, self.h, self.fmt = w, h, fmt
-        self.ch, self.dtype = CHANNELS[fmt]
-        self.row = w * self.ch * np.dtype(self.dtype).itemsize
-        self.pitch = (self.row + 15) // 16 * 16 + 16 if pad is None else self.row + pad
-        self.offset = offset
-        self.buf = capi.DeviceBuffer(gr, offset + self.pitch * h + GUARD)
-        self.buf.upload(np.full(self.buf.nbytes, FILL, np.uint8))
-        self.desc = capi.Image(self.buf.ptr + offset, w, h, self.pitch, fmt)
-
-    def read(self):
-        raw = self.buf.download(np.uint8)
-        assert (raw[:self.offset] == FILL).all(), "bytes written before the plane"
-        raw = raw[self.offset:]
-        rows = raw[:self.pitch * self.h].reshape(self.h, self.pitch)
-        assert (rows[:, self.row:] == FILL).all(), "bytes written in a row's pitch padding"
-        assert (raw[self.pitch * self.h:] == FILL).all(), "bytes written after the plane's last row"
-        data = np.ascontiguousarray(rows[:, :self.row]).view(self.dtype)
-        return data.reshape(self.h, self.w, self.ch) if self.ch > 1 else data.reshape(self.h, self.w)
 
 
 def make_input(gr, fmt, w, h, seed, smooth=False, offset=0, pad=None):
@@ -78,27 +49,16 @@ def make_input(gr, fmt, w, h, seed, smooth=False, offset=0, pad=None):
         data = rng.uniform(0.0, 1.2, (h, w, 4)).astype(np.float16).view(np.uint16)
     if not offset and pad is None:
         return data, capi.DeviceImage(gr, w, h, fmt).upload(data)
-    row = w * capi.FORMAT_BPP[fmt]
-    pitch = row + pad
-    buf = capi.DeviceBuffer(gr, offset + pitch * h + GUARD)
-    raw = np.full(buf.nbytes, FILL, np.uint8)
-    raw[offset:offset + pitch * h].reshape(h, pitch)[:, :row] = np.ascontiguousarray(data).view(np.uint8).reshape(h, row)
-    buf.upload(raw)
-    return data, OffsetImage(buf, capi.Image(buf.ptr + offset, w, h, pitch, fmt))
-
-
-class OffsetImage:
-    def __init__(self, buf, desc):
-        self.buf, self.desc = buf, desc
+    return data, GuardedImage(gr, w, h, fmt, data, offset, pad)
 
 
 def run_case(gr, in_fmt, in_size, planes, src_space, dst_space, tol, seed=1, smooth=False, offset=0, pad=None, in_offset=0, in_pad=None):
     data, img = make_input(gr, in_fmt, in_size[0], in_size[1], seed, smooth, in_offset, in_pad)
-    outs = [GuardedPlane(gr, *p, offset=offset, pad=pad) for p in planes]
+    outs = [GuardedImage(gr, *p, offset=offset, pad=pad) for p in planes]
     arr = (capi.Image * len(outs))(*[o.desc for o in outs])
     gr.check(gr.lib.gr_video_scale(gr.handle, None, img.desc, arr, len(outs), src_space, dst_space))
     gr.sync()
-    got = [o.read() for o in outs]
+    got = [o.samples() for o in outs]
     ref = vr.video_scale(data, in_fmt, planes, src_space, dst_space)
     for i, (g, r) in enumerate(zip(got, ref)):
         assert g.shape == r.shape, (i, g.shape, r.shape)
@@ -106,16 +66,6 @@ def run_case(gr, in_fmt, in_size, planes, src_space, dst_space, tol, seed=1, smo
         worst = np.unravel_index(np.argmax(err), err.shape)
         assert err.max() <= tol, f"plane {i}: {int((err > tol).sum())} samples beyond {tol} codes, worst {err.max()} at {worst}"
     return got
-
-
-def nv12(w, h, wide=False):
-    return [(w, h, vr.R16 if wide else vr.R8), ((w + 1) // 2, (h + 1) // 2, vr.R16G16 if wide else vr.R8G8)]
-
-
-def yuv(w, h, sub=True, wide=False):
-    cw, ch = ((w + 1) // 2, (h + 1) // 2) if sub else (w, h)
-    f = vr.R16 if wide else vr.R8
-    return [(w, h, f), (cw, ch, f), (cw, ch, f)]
 
 
 SAME_SIZE_LAYOUTS = {
@@ -202,37 +152,34 @@ def test_rescale_16_bit(gr):
 
 def test_refusals_report_an_error(gr):
     data, img = make_input(gr, vr.RGBA8, 64, 32, 3)
-    y = GuardedPlane(gr, 64, 32, vr.R8)
-    c = GuardedPlane(gr, 31, 16, vr.R8G8)  # neither half nor full size
+    y = GuardedImage(gr, 64, 32, vr.R8)
+    c = GuardedImage(gr, 31, 16, vr.R8G8)  # neither half nor full size
     arr = (capi.Image * 2)(y.desc, c.desc)
     rc = gr.lib.gr_video_scale(gr.handle, None, img.desc, arr, 2, S, S)
     assert rc == -1 and b"chroma" in gr.lib.gr_last_error(gr.handle)
-    good = GuardedPlane(gr, 32, 16, vr.R8G8)
+    good = GuardedImage(gr, 32, 16, vr.R8G8)
     arr = (capi.Image * 2)(y.desc, good.desc)
     assert gr.lib.gr_video_scale(gr.handle, None, img.desc, arr, 2, S, LIN) == -1
     assert gr.lib.gr_video_scale(gr.handle, None, img.desc, arr, 2, 7, S) == -1
     gr.sync()
     # nothing was launched: the planes still hold the fill
-    assert (y.buf.download(np.uint8) == FILL).all()
+    assert y.untouched()
 
 
 # ---- edge shapes -----------------------------------------------------------------------------------------------------------------
-# The direct path converts 4 x 2 pixels per lane, 256 pixels per group row and 8 rows per group; the rescale path 16 x 16 outputs per
-# group from a staging window of at most STAGE = 41 texels per axis, with the prefilter above a ratio of 2.
-EDGE_SIZES = [(1, 1), (2, 1), (1, 2), (3, 3), (5, 3), (7, 9), (255, 1), (256, 2), (257, 3), (1023, 7)]
-
-
+# The direct path runs over EDGE_SIZES (tests/video_planes.py); the rescale path converts 16 x 16 outputs per group from a staging
+# window of at most STAGE = 41 texels per axis, with the prefilter above a ratio of 2: RESCALE_EDGES below.
 def assert_refused(gr, in_size, planes):
     """A 4:2:0 frame one pixel wide has chroma as wide as its luma: the plan (as VideoScaler::rescale) tells subsampling by the
     width alone, so the chroma height does not match and the conversion is refused, with nothing written."""
     data, img = make_input(gr, vr.RGBA8, in_size[0], in_size[1], 1)
-    outs = [GuardedPlane(gr, *p) for p in planes]
+    outs = [GuardedImage(gr, *p) for p in planes]
     arr = (capi.Image * len(outs))(*[o.desc for o in outs])
     assert gr.lib.gr_video_scale(gr.handle, None, img.desc, arr, len(outs), S, S) == -1
     assert b"chroma" in gr.lib.gr_last_error(gr.handle)
     gr.sync()
     for o in outs:
-        assert (o.buf.download(np.uint8) == FILL).all()
+        assert o.untouched()
 
 
 @pytest.mark.parametrize("layout", sorted(SAME_SIZE_LAYOUTS) + ["p010_pq"])
@@ -315,15 +262,15 @@ def test_dither_table_and_index_exact(gr):
     data, want = vr.dither_probe()
     for fmt in (vr.RGBA8, vr.BGRA8):
         img = capi.DeviceImage(gr, 64, 16, vr.RGBA16F).upload(data)
-        out = GuardedPlane(gr, 64, 16, fmt)
+        out = GuardedImage(gr, 64, 16, fmt)
         arr = (capi.Image * 1)(out.desc)
         gr.check(gr.lib.gr_video_scale(gr.handle, None, img.desc, arr, 1, LIN, LIN))
         gr.sync()
-        assert np.array_equal(out.read(), want), fmt
+        assert np.array_equal(out.samples(), want), fmt
 
 
 def _launch(gr, img, planes, src, dst, stream):
-    outs = [GuardedPlane(gr, *p) for p in planes]
+    outs = [GuardedImage(gr, *p) for p in planes]
     arr = (capi.Image * len(outs))(*[o.desc for o in outs])
     gr.check(gr.lib.gr_video_scale(gr.handle, stream, img.desc, arr, len(outs), src, dst))
     return outs
@@ -351,7 +298,7 @@ def test_weight_cache_switches_size_pairs_across_streams(gr):
                 want = _launch(fresh, img, pairs[key][1], S, S, None)
                 fresh.sync()
                 for o, w in zip(outs, want):
-                    assert np.array_equal(o.read(), w.read()), key
+                    assert np.array_equal(o.samples(), w.samples()), key
             finally:
                 fresh.close()
     finally:
@@ -380,5 +327,5 @@ def test_kernel_matches_executed_shader(gr, case):
     p = capi.video_scale_plan(in_size, in_fmt, planes, src, dst)
     want = vr.shader_scale(data, in_fmt, planes, p, capi.video_scaler_weights(in_size[0], in_size[1], planes[0][0], planes[0][1]))
     for i, (o, w) in enumerate(zip(outs, want)):
-        err = np.abs(o.read().astype(np.int64) - w)
+        err = np.abs(o.samples().astype(np.int64) - w)
         assert err.max() <= tol, f"plane {i}: {int((err > tol).sum())} samples beyond {tol}, worst {err.max()}"

@@ -30,13 +30,9 @@ import pytest
 import yuv_ref as yr
 from granite_amd import capi
 from util import rgba16f_mismatch, ulp_fp16
+from video_planes import EDGE_SIZES, GuardedImage
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 4096
-FILL = 0xA5
-OUT_TEXEL = {yr.RGBA8: 4, yr.RGBA8_SRGB: 4, yr.A2B10G10R10: 4, yr.RGBA16F: 8}
-EDGE_SIZES = [(1, 1), (2, 1), (1, 2), (3, 3), (5, 3), (7, 9), (255, 1), (256, 2), (257, 3), (1023, 7)]
 
 # name -> (number of planes, 16-bit planes, 4:2:0)
 LAYOUTS = {
@@ -76,37 +72,8 @@ def plane_format(p):
     return {(1, 2): yr.R8, (2, 2): yr.R16, (1, 3): yr.R8G8, (2, 3): yr.R16G16}[(p.dtype.itemsize, p.ndim)]
 
 
-class GuardedImage:
-    """An image inside a larger allocation, `offset` bytes in, with a row pitch of row + pad bytes (by default padded to a multiple of
-    16 plus 16), GUARD bytes after the last row; everything outside the rows holds FILL.  data: what the rows hold (None: FILL, an
-    output).  An offset or pitch that is not a multiple of 16 takes the element-by-element path."""
-
-    def __init__(self, gr, w, h, fmt, row_bytes, data=None, offset=0, pad=None):
-        self.w, self.h, self.fmt, self.row, self.offset = w, h, fmt, row_bytes, offset
-        self.pitch = (row_bytes + 15) // 16 * 16 + 16 if pad is None else row_bytes + pad
-        self.buf = capi.DeviceBuffer(gr, offset + self.pitch * h + GUARD)
-        raw = np.full(self.buf.nbytes, FILL, np.uint8)
-        if data is not None:
-            raw[offset:offset + self.pitch * h].reshape(h, self.pitch)[:, :row_bytes] = np.ascontiguousarray(data).view(np.uint8).reshape(h, row_bytes)
-        self.buf.upload(raw)
-        self.desc = capi.Image(self.buf.ptr + offset, w, h, self.pitch, fmt)
-
-    def read(self):
-        raw = self.buf.download(np.uint8)
-        assert (raw[:self.offset] == FILL).all(), "bytes written before the image"
-        raw = raw[self.offset:]
-        rows = raw[:self.pitch * self.h].reshape(self.h, self.pitch)
-        assert (rows[:, self.row:] == FILL).all(), "bytes written in a row's pitch padding"
-        assert (raw[self.pitch * self.h:] == FILL).all(), "bytes written after the image's last row"
-        return np.ascontiguousarray(rows[:, :self.row])
-
-    def untouched(self):
-        return bool((self.buf.download(np.uint8) == FILL).all())
-
-
 def upload_planes(gr, planes, offset=0, pad=None):
-    return [GuardedImage(gr, p.shape[1], p.shape[0], plane_format(p), p.shape[1] * p.itemsize * (2 if p.ndim == 3 else 1), p, offset, pad)
-            for p in planes]
+    return [GuardedImage(gr, p.shape[1], p.shape[0], plane_format(p), p, offset, pad) for p in planes]
 
 
 def compare(got_rows, ref, out_fmt, w, h, what="", allowance=None):
@@ -133,7 +100,7 @@ def run_case(gr, layout, size, out_fmt, inf, seed=1, bits=None, offset=0, pad=No
     w, h = size
     planes = make_planes(layout, w, h, seed, bits)
     src = upload_planes(gr, planes, offset, pad)
-    out = GuardedImage(gr, w, h, out_fmt, w * OUT_TEXEL[out_fmt], None, out_offset, out_pad)
+    out = GuardedImage(gr, w, h, out_fmt, None, out_offset, out_pad)
     gr.video_yuv_to_rgb([s.desc for s in src], out.desc, capi.video_yuv_info(**inf))
     gr.sync()
     p = yr.plan([(q.shape[1], q.shape[0], plane_format(q)) for q in planes], (w, h, out_fmt), yr.info(**inf))
@@ -225,7 +192,7 @@ def test_dither_probe_exact(gr):
     h, w = plane.shape
     for out_fmt, want, pq in ((yr.RGBA8, c8, 0), (yr.A2B10G10R10, c10, 1)):
         src = upload_planes(gr, [plane])
-        out = GuardedImage(gr, w, h, out_fmt, w * 4)
+        out = GuardedImage(gr, w, h, out_fmt)
         gr.video_yuv_to_rgb([src[0].desc], out.desc, capi.video_yuv_info(full_range=0, pq=pq))
         gr.sync()
         rows = out.read()
@@ -244,7 +211,7 @@ def test_coordinate_probe(gr, size, sub, location):
     w, h = size
     planes, _, _ = yr.coordinate_probe(w, h, sub, location)
     src = upload_planes(gr, planes)
-    out = GuardedImage(gr, w, h, yr.RGBA8, w * 4)
+    out = GuardedImage(gr, w, h, yr.RGBA8)
     inf = dict(full_range=1, chroma_location=location)
     gr.video_yuv_to_rgb([s.desc for s in src], out.desc, capi.video_yuv_info(**inf))
     gr.sync()
@@ -259,8 +226,8 @@ def test_refusals_leave_the_output_untouched(gr):
     wide = upload_planes(gr, make_planes("p010", w, h, 1))
     bgra = 44
 
-    def refused(descs, out_fmt, texel, what, out_size=(w, h), **inf):
-        out = GuardedImage(gr, out_size[0], out_size[1], out_fmt, out_size[0] * texel)
+    def refused(descs, out_fmt, what, out_size=(w, h), **inf):
+        out = GuardedImage(gr, out_size[0], out_size[1], out_fmt)
         arr = (capi.Image * len(descs))(*descs)
         i = capi.video_yuv_info(**inf)
         rc = gr.lib.gr_video_yuv_to_rgb(gr.handle, None, arr, len(descs), C.byref(out.desc), C.byref(i))
@@ -269,20 +236,20 @@ def test_refusals_leave_the_output_untouched(gr):
         assert out.untouched(), what + ": the refused call wrote"
 
     d = [s.desc for s in src]
-    refused(d, bgra, 4, "BGRA output", full_range=1)
-    refused(d, yr.RGBA16F, 8, "RGBA16F without PQ", full_range=1)
-    refused(d, yr.A2B10G10R10, 4, "A2B10G10R10 without PQ", full_range=1)
-    refused(d, yr.RGBA8, 4, "RGBA8 with PQ", pq=1)
-    refused(d, yr.RGBA8, 4, "8-bit planes declared 10-bit", bit_depth=10)
-    refused([s.desc for s in wide], yr.RGBA8, 4, "16-bit planes declared 8-bit", bit_depth=8)
-    refused(d, yr.RGBA8, 4, "unknown matrix", matrix=6)
-    refused(d, yr.RGBA8, 4, "unknown chroma location", chroma_location=6)
-    refused(d[:1], yr.RGBA8, 4, "nv21 with one plane", nv21=1)
-    refused(d, yr.RGBA8, 4, "output of another size", out_size=(w, h - 1))
-    refused([d[0], wide[1].desc], yr.RGBA8, 4, "R8 luma with R16G16 chroma")
+    refused(d, bgra, "BGRA output", full_range=1)
+    refused(d, yr.RGBA16F, "RGBA16F without PQ", full_range=1)
+    refused(d, yr.A2B10G10R10, "A2B10G10R10 without PQ", full_range=1)
+    refused(d, yr.RGBA8, "RGBA8 with PQ", pq=1)
+    refused(d, yr.RGBA8, "8-bit planes declared 10-bit", bit_depth=10)
+    refused([s.desc for s in wide], yr.RGBA8, "16-bit planes declared 8-bit", bit_depth=8)
+    refused(d, yr.RGBA8, "unknown matrix", matrix=6)
+    refused(d, yr.RGBA8, "unknown chroma location", chroma_location=6)
+    refused(d[:1], yr.RGBA8, "nv21 with one plane", nv21=1)
+    refused(d, yr.RGBA8, "output of another size", out_size=(w, h - 1))
+    refused([d[0], wide[1].desc], yr.RGBA8, "R8 luma with R16G16 chroma")
     third = capi.Image(d[1].ptr, w // 3, h // 2, d[1].pitch_bytes, yr.R8G8)
-    refused([d[0], third], yr.RGBA8, 4, "chroma plane neither full nor half size")
+    refused([d[0], third], yr.RGBA8, "chroma plane neither full nor half size")
     short = capi.Image(d[0].ptr, w, h, w - 1, yr.R8)
-    refused([short, d[1]], yr.RGBA8, 4, "luma pitch smaller than a row")
+    refused([short, d[1]], yr.RGBA8, "luma pitch smaller than a row")
     null = capi.Image(None, w, h, w, yr.R8)
-    refused([null, d[1]], yr.RGBA8, 4, "null plane pointer")
+    refused([null, d[1]], yr.RGBA8, "null plane pointer")

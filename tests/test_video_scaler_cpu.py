@@ -10,6 +10,7 @@ import pytest
 
 import video_ref as vr
 from granite_amd import capi
+from video_planes import nv12, yuv
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -38,16 +39,6 @@ def test_float_to_half_rounds_ties_away_from_zero():
 
 S, HDR, LIN = capi.COLOR_SPACE_SRGB_NONLINEAR, capi.COLOR_SPACE_HDR10_ST2084, capi.COLOR_SPACE_EXTENDED_SRGB_LINEAR
 K4, K2, P1080 = (3840, 2160), (2560, 1440), (1920, 1080)
-
-
-def nv12(w, h, wide=False):
-    return [(w, h, vr.R16 if wide else vr.R8), ((w + 1) // 2, (h + 1) // 2, vr.R16G16 if wide else vr.R8G8)]
-
-
-def yuv(w, h, sub=True, wide=False):
-    cw, ch = ((w + 1) // 2, (h + 1) // 2) if sub else (w, h)
-    f = vr.R16 if wide else vr.R8
-    return [(w, h, f), (cw, ch, f), (cw, ch, f)]
 
 
 PLAN_CASES = {
@@ -113,9 +104,12 @@ def test_plan_primary_matrices_are_the_known_conversions():
     (K4, vr.RGBA8, [(3840, 2160, vr.R8)], S, S),                        # one plane must be RGBA8 / BGRA8
     (K4, vr.R8, nv12(*K4), S, S),                                        # input format
     (K4, vr.RGBA8, [], S, S),
-    ((1, 2), vr.RGBA8, nv12(1, 2), S, S),                               # one pixel wide: 4:2:0 chroma is as wide as the luma
+    # one pixel wide: 4:2:0 chroma (1 x 1) is as wide as the luma (1 x 2), and the plan tells subsampling by the width alone, as
+    # VideoScaler::rescale does; gr_video_yuv_plan accepts the same planes (tests/test_yuv_ref_cpu.py)
+    ((1, 2), vr.RGBA8, nv12(1, 2), S, S),
+    ((1, 2), vr.RGBA8, yuv(1, 2), S, S),
 ], ids=["space_in", "space_out", "nv12_linear", "yuv_linear", "chroma_size", "chroma_depth", "plane3_size", "luma_alone",
-        "input_format", "no_planes", "one_wide_420"])
+        "input_format", "no_planes", "one_wide_420", "one_wide_420_three_planes"])
 def test_plan_refuses_invalid_conversions(args):
     in_size, in_fmt, planes, src_space, dst_space = args
     assert capi.video_scale_plan(in_size, in_fmt, planes, src_space, dst_space) is None

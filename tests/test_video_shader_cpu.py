@@ -26,18 +26,9 @@ import pytest
 
 import video_ref as vr
 from granite_amd import capi
+from video_planes import nv12, yuv
 
 S, HDR, LIN = capi.COLOR_SPACE_SRGB_NONLINEAR, capi.COLOR_SPACE_HDR10_ST2084, capi.COLOR_SPACE_EXTENDED_SRGB_LINEAR
-
-
-def nv12(w, h, wide=False):
-    return [(w, h, vr.R16 if wide else vr.R8), ((w + 1) // 2, (h + 1) // 2, vr.R16G16 if wide else vr.R8G8)]
-
-
-def yuv(w, h, sub=True, wide=False):
-    cw, ch = ((w + 1) // 2, (h + 1) // 2) if sub else (w, h)
-    f = vr.R16 if wide else vr.R8
-    return [(w, h, f), (cw, ch, f), (cw, ch, f)]
 
 
 def make_input(fmt, w, h, seed, src, dst):

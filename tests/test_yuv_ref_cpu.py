@@ -235,6 +235,15 @@ def test_refusals_return_negative():
     assert lib.gr_video_yuv_plan(None, 1, None, None, None) < 0
 
 
+@pytest.mark.parametrize("planes", [[(1, 2, yr.R8), (1, 1, yr.R8G8)], [(1, 2, yr.R8), (1, 1, yr.R8), (1, 1, yr.R8)]], ids=["nv12", "three_planes"])
+def test_plan_accepts_one_pixel_wide_420(planes):
+    """A 4:2:0 frame one pixel wide has chroma as wide as its luma.  Playback tells subsampling by the width or the height and takes
+    it; gr_video_scale_plan, by the width alone, refuses the same planes (tests/test_video_scaler_cpu.py)."""
+    q = capi.video_yuv_plan(planes, (1, 2, yr.RGBA8), capi.video_yuv_info())
+    assert q is not None
+    assert capi.video_scale_plan((1, 2), yr.RGBA8, planes, capi.COLOR_SPACE_SRGB_NONLINEAR, capi.COLOR_SPACE_SRGB_NONLINEAR) is None
+
+
 def test_golden_regenerates_identically(tmp_path):
     """Needs the reference's sources: re-spells and re-runs the shader, and must reproduce the committed file's every array."""
     import importlib.util

@@ -47,7 +47,8 @@ def _inverse3(a):
 
 
 def _xyz_matrix(prims):
-    """compute_xyz_matrix in float32: RGB -> XYZ for CIE xy chromaticities of the primaries and the white point; column major."""
+    """compute_xyz_matrix in float32: RGB -> XYZ for CIE xy chromaticities of the primaries and the white point; column major.  Not
+    video_ref's: that one inverts in float64 (numpy), this one rounds every operation to float32 in the product's order."""
     cols = [[F(x) / F(y), F(1.0), (F(1.0) - F(x) - F(y)) / F(y)] for x, y in prims]
     p, white = cols[:3], cols[3]
     inv = _inverse3(p)

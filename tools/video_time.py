@@ -17,18 +17,23 @@ from granite_amd import capi, synth  # noqa: E402
 S, HDR = capi.COLOR_SPACE_SRGB_NONLINEAR, capi.COLOR_SPACE_HDR10_ST2084
 
 
-def planes_nv12(gr, w, h, wide=False):
+def planes_nv12(gr, w, h, wide=False, sub=True):
+    """Luma and interleaved chroma; sub=False: chroma at full size (two-plane 4:4:4)."""
+    cw, ch = ((w + 1) // 2, (h + 1) // 2) if sub else (w, h)
     return [capi.DeviceImage(gr, w, h, capi.FORMAT_R16_UNORM if wide else capi.FORMAT_R8_UNORM),
-            capi.DeviceImage(gr, (w + 1) // 2, (h + 1) // 2, capi.FORMAT_R16G16_UNORM if wide else capi.FORMAT_R8G8_UNORM)]
+            capi.DeviceImage(gr, cw, ch, capi.FORMAT_R16G16_UNORM if wide else capi.FORMAT_R8G8_UNORM)]
 
 
 CASES = [
-    ("4K sRGB -> NV12 (same size)", (3840, 2160), capi.FORMAT_R8G8B8A8_UNORM, (3840, 2160), False, S, S),
-    ("4K -> 1080p NV12", (3840, 2160), capi.FORMAT_R8G8B8A8_UNORM, (1920, 1080), False, S, S),
-    ("2560x1440 -> 1920x1080 NV12", (2560, 1440), capi.FORMAT_R8G8B8A8_UNORM, (1920, 1080), False, S, S),
-    ("1280x720 -> 1920x1080 NV12", (1280, 720), capi.FORMAT_R8G8B8A8_UNORM, (1920, 1080), False, S, S),
-    ("7680x4320 -> 1920x1080 NV12 (sampled)", (7680, 4320), capi.FORMAT_R8G8B8A8_UNORM, (1920, 1080), False, S, S),
-    ("4K HDR10 -> P010 (same size)", (3840, 2160), capi.FORMAT_A2B10G10R10_UNORM_PACK32, (3840, 2160), True, HDR, HDR),
+    ("4K sRGB -> NV12 (same size)", (3840, 2160), capi.FORMAT_R8G8B8A8_UNORM, (3840, 2160), dict(), S, S),
+    ("4K -> 1080p NV12", (3840, 2160), capi.FORMAT_R8G8B8A8_UNORM, (1920, 1080), dict(), S, S),
+    ("2560x1440 -> 1920x1080 NV12", (2560, 1440), capi.FORMAT_R8G8B8A8_UNORM, (1920, 1080), dict(), S, S),
+    ("1280x720 -> 1920x1080 NV12", (1280, 720), capi.FORMAT_R8G8B8A8_UNORM, (1920, 1080), dict(), S, S),
+    ("7680x4320 -> 1920x1080 NV12 (sampled)", (7680, 4320), capi.FORMAT_R8G8B8A8_UNORM, (1920, 1080), dict(), S, S),
+    ("4K HDR10 -> P010 (same size)", (3840, 2160), capi.FORMAT_A2B10G10R10_UNORM_PACK32, (3840, 2160), dict(wide=True), HDR, HDR),
+    # interleaved chroma at full size: k_video_direct<2, false, *>, which no recording format reaches
+    ("4K sRGB -> 2-plane 4:4:4 8 bit", (3840, 2160), capi.FORMAT_R8G8B8A8_UNORM, (3840, 2160), dict(sub=False), S, S),
+    ("4K sRGB -> 2-plane 4:4:4 16 bit", (3840, 2160), capi.FORMAT_R8G8B8A8_UNORM, (3840, 2160), dict(wide=True, sub=False), S, S),
 ]
 
 
@@ -40,9 +45,9 @@ def main():
     ceiling = copy.value / 1e3
     print(f"copy ceiling {ceiling:.2f} TB/s (gr_bandwidth_probe, 1 GiB, best of 20)")
     rng = np.random.default_rng(0)
-    for name, (iw, ih), fmt, (ow, oh), wide, src_space, dst_space in CASES:
+    for name, (iw, ih), fmt, (ow, oh), layout, src_space, dst_space in CASES:
         src = capi.DeviceImage(gr, iw, ih, fmt).upload(rng.integers(0, 256, (ih, iw * 4), dtype=np.uint8))
-        planes = planes_nv12(gr, ow, oh, wide)
+        planes = planes_nv12(gr, ow, oh, **layout)
         for _ in range(5):
             gr.video_scale(src, planes, src_space, dst_space)
         gr.sync()

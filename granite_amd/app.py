@@ -84,7 +84,7 @@ EXPORTED_SYMBOLS = [
     "gra_get_render_parameters", "gra_set_lights", "gra_upload_gbuffer", "gra_render_frames", "gra_sync",
     "gra_get_resource", "gra_read_resource", "gra_get_backbuffer", "gra_read_backbuffer", "gra_get_cluster_state",
     "gra_dump_graph", "gra_collect_timestamps", "gra_get_kernel_context", "gra_get_stream", "gra_get_taa_reprojection",
-    "gra_set_smaa_luts", "gra_get_host_stats", "gra_get_output_gather_stats", "gra_get_prefetched_refreshes", "gra_get_launch_graph_replays", "gra_get_allocated_bytes", "gra_gtx_probe", "gra_gtx_read", "gra_gtx_write", "gra_gtx_decode",
+    "gra_set_smaa_luts", "gra_get_host_stats", "gra_get_output_gather_stats", "gra_get_prefetched_refreshes", "gra_get_launch_graph_replays", "gra_get_allocated_bytes", "gra_gtx_probe", "gra_gtx_read", "gra_gtx_write", "gra_gtx_decode", "gra_environment_bake",
     "gra_upload_gbuffer_gtx", "gra_save_resource_gtx", "gra_get_render_size", "gra_upload_ambient_occlusion", "gra_upload_aa_bench_images", "gra_compute_rec709_to_display", "gra_set_exchange_callback", "gra_get_strip_plan", "gra_get_strip_plan_aa", "gra_get_strip_plan_taa_history",
     "gra_comm_create_unique_id", "gra_comm_init", "gra_comm_info", "gra_comm_init_output", "gra_install_ssr_tables", "gra_reset_timestamps", "gra_set_directional_light", "gra_set_fog", "gra_generate_mipmaps", "gra_write_resource", "gra_get_frame_state", "gra_set_frame_state",
     "gra_video_begin", "gra_video_frame_layout", "gra_video_read_frame", "gra_video_end",
@@ -140,6 +140,7 @@ def load_library() -> C.CDLL:
         "gra_gtx_read": (C.c_int, [C.c_char_p, vp, C.c_uint64, vp, C.c_size_t]),
         "gra_gtx_write": (C.c_int, [C.c_char_p, vp, vp, vp, C.c_size_t]),
         "gra_gtx_decode": (C.c_int, [vp, C.c_char_p, C.c_char_p]),
+        "gra_environment_bake": (C.c_int, [vp, C.c_char_p, C.c_float] + [C.c_char_p] * 3),
         "gra_upload_gbuffer_gtx": (C.c_int, [vp] + [C.c_char_p] * 6),
         "gra_save_resource_gtx": (C.c_int, [vp, C.c_char_p, C.c_char_p]),
         "gra_reset_timestamps": (C.c_int, [vp]),
@@ -295,6 +296,14 @@ class Application:
     def decode_gtx(self, src: str, dst: str):
         """Decode the block-compressed .gtx `src` (BC1-BC7) on the device, every level and layer, into the uncompressed .gtx `dst`."""
         self._check(self.lib.gra_gtx_decode(self.handle, str(src).encode(), str(dst).encode()))
+
+    def bake_environment(self, equirect: str, cube: Optional[str] = None, reflection: Optional[str] = None, irradiance: Optional[str] = None,
+                         cube_scale: float = 1.0):
+        """Bake the 2-D RGBA16F .gtx `equirect` on the device into cube .gtx files: the lat-long image as a cube with a full mip chain
+        (`cube`), its 128-texel, 8-level GGX reflection cube (`reflection`) and its 32-texel irradiance cube (`irradiance`).  A path left
+        None is not written, and its bake is not run."""
+        enc = lambda p: None if p is None else str(p).encode()
+        self._check(self.lib.gra_environment_bake(self.handle, str(equirect).encode(), float(cube_scale), enc(cube), enc(reflection), enc(irradiance)))
 
     def save_gtx(self, path: str, name: Optional[str] = None):
         """Write graph texture `name` (None = the last backbuffer) as .gtx."""

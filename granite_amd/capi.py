@@ -104,6 +104,11 @@ TRANSFORMS_OFFSET_DECALS = 655872
 TRANSFORMS_SIZE = 852480
 
 
+class Cube(C.Structure):
+    """gr_cube: an R16G16B16A16_SFLOAT cube mip chain in GTX payload layout (device pointer, texels a side, levels)."""
+    _fields_ = [("ptr", C.c_void_p), ("size", C.c_uint32), ("levels", C.c_uint32)]
+
+
 class Image(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("pitch_bytes", C.c_uint32),
                 ("format", C.c_uint32)]
@@ -422,6 +427,11 @@ def load_library() -> C.CDLL:
         "gr_texture_decoded_format": (C.c_uint32, [C.c_uint32]),
         "gr_texture_block_bytes": (C.c_uint32, [C.c_uint32]),
         "gr_texture_decode": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint32, P(Image)]),
+        "gr_cube_chain_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32]),
+        "gr_cube_chain_offset": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32]),
+        "gr_env_equirect_to_cube": (C.c_int, [vp, vp, P(Image), vp, C.c_uint32, C.c_uint32]),
+        "gr_env_specular": (C.c_int, [vp, vp, P(Cube), vp, C.c_uint32, C.c_uint32]),
+        "gr_env_diffuse": (C.c_int, [vp, vp, P(Cube), vp, C.c_uint32]),
         "gr_fsr_sharpen": (C.c_int, [vp, vp, P(Image), P(Image), C.c_float]),
         "gr_mip_chain_offset": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
         "gr_mip_chain_size": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
@@ -444,6 +454,7 @@ EXPORTED_SYMBOLS = [
     "gr_hiz", "gr_mip_chain_offset", "gr_mip_chain_size", "gr_fsr_upscale", "gr_fsr_sharpen", "gr_fill_byte", "gr_fill_u32", "gr_pq10_encode", "gr_get_device_info", "gr_spd_downsample", "gr_debug_mix", "gr_pack_b10g11r11",
     "gr_video_scale", "gr_video_scale_plan", "gr_video_scaler_weights", "gr_video_yuv_to_rgb", "gr_video_yuv_plan",
     "gr_texture_decoded_format", "gr_texture_block_bytes", "gr_texture_decode",
+    "gr_cube_chain_bytes", "gr_cube_chain_offset", "gr_env_equirect_to_cube", "gr_env_specular", "gr_env_diffuse",
 ]
 
 
@@ -741,6 +752,22 @@ class Context:
         """gr_texture_decode: one level of one layer of BC1-BC7 blocks (device pointer) into `out` (DeviceImage or Image)."""
         desc = out.desc if isinstance(out, DeviceImage) else out
         self.check(self.lib.gr_texture_decode(self.handle, stream, int(block_format), blocks, int(block_row_pitch), C.byref(desc)))
+
+    # ---- environment baking: cubes are DeviceBuffers holding an RGBA16F chain in GTX payload layout (gr_cube_chain_bytes) ----------
+    def env_equirect_to_cube(self, equirect: DeviceImage, cube: DeviceBuffer, size: int, levels: int, stream=None):
+        """gr_env_equirect_to_cube: lat-long RGBA16F image -> cube level 0, then `levels - 1` linear-blit mips."""
+        assert cube.nbytes >= self.lib.gr_cube_chain_bytes(size, levels) or not (0 < size <= 16384), (cube.nbytes, size, levels)
+        self.check(self.lib.gr_env_equirect_to_cube(self.handle, stream, equirect.desc, cube.ptr, int(size), int(levels)))
+
+    def env_specular(self, src: DeviceBuffer, src_size: int, src_levels: int, out: DeviceBuffer, out_size: int, out_levels: int, stream=None):
+        """gr_env_specular: the GGX-prefiltered reflection chain of a cube, all faces and levels in one launch."""
+        assert src.nbytes >= self.lib.gr_cube_chain_bytes(src_size, src_levels) and out.nbytes >= self.lib.gr_cube_chain_bytes(out_size, out_levels)
+        self.check(self.lib.gr_env_specular(self.handle, stream, C.byref(Cube(src.ptr, src_size, src_levels)), out.ptr, int(out_size), int(out_levels)))
+
+    def env_diffuse(self, src: DeviceBuffer, src_size: int, src_levels: int, out: DeviceBuffer, out_size: int, stream=None):
+        """gr_env_diffuse: the irradiance cube (one level) of a cube."""
+        assert src.nbytes >= self.lib.gr_cube_chain_bytes(src_size, src_levels) and out.nbytes >= self.lib.gr_cube_chain_bytes(out_size, 1)
+        self.check(self.lib.gr_env_diffuse(self.handle, stream, C.byref(Cube(src.ptr, src_size, src_levels)), out.ptr, int(out_size)))
 
     def blit(self, src: DeviceImage, out: DeviceImage, linear: bool, stream=None):
         self.check(self.lib.gr_blit(self.handle, stream, src.desc, out.desc, int(linear)))

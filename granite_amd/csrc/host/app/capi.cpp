@@ -5,6 +5,7 @@
 #include "../post/spd.hpp"
 #include "../gtx.hpp"
 #include "../texture_decoder.hpp"
+#include "../utils/image_utils.hpp"
 #include "../post/hdr.hpp"
 #include <cstdio>
 #include <cstring>
@@ -230,6 +231,26 @@ int gra_gtx_decode(gra_app *app, const char *src_path, const char *dst_path)
 		if (!device.get_context())
 			throw std::logic_error("gra_gtx_decode: the application has no device");
 		gtx_save(decode_compressed_image(device.get_context(), nullptr, gtx_load(src_path)), dst_path);
+	});
+}
+
+int gra_environment_bake(gra_app *app, const char *equirect_gtx, float cube_scale, const char *cube_path, const char *reflection_path,
+                         const char *irradiance_path)
+{
+	return guarded(app, [&]() {
+		if (!equirect_gtx)
+			throw std::logic_error("gra_environment_bake: null input path");
+		auto &device = app->app->get_device();
+		if (!device.get_context())
+			throw std::logic_error("gra_environment_bake: the application has no device");
+		gr_ctx *ctx = device.get_context();
+		const GtxImage cube = convert_equirect_to_cube(ctx, nullptr, gtx_load(equirect_gtx), cube_scale);
+		if (cube_path)
+			gtx_save(cube, cube_path);
+		if (reflection_path)
+			gtx_save(convert_cube_to_ibl_specular(ctx, nullptr, cube), reflection_path);
+		if (irradiance_path)
+			gtx_save(convert_cube_to_ibl_diffuse(ctx, nullptr, cube), irradiance_path);
 	});
 }
 

@@ -81,6 +81,93 @@ mat4 look_at(const vec3 &eye, const vec3 &center, const vec3 &up)
 	return m;
 }
 
+namespace
+{
+// muglm's forms: normalize multiplies by 1 / sqrt(dot), dot sums left to right
+vec3 mu_normalize(const vec3 &v) { return v * (1.0f / std::sqrt(dot(v, v))); }
+float mu_clamp01(float v) { return v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); }
+
+vec3 rotate(const quat &q, const vec3 &v)
+{
+	const vec3 quat_vector(q.x, q.y, q.z);
+	const vec3 uv = cross(quat_vector, v);
+	const vec3 uuv = cross(quat_vector, uv);
+	return v + ((uv * q.w) + uuv) * 2.0f;
+}
+
+quat mul(const quat &p, const quat &q)
+{
+	return {p.w * q.w - p.x * q.x - p.y * q.y - p.z * q.z, p.w * q.x + p.x * q.w + p.y * q.z - p.z * q.y,
+	        p.w * q.y + p.y * q.w + p.z * q.x - p.x * q.z, p.w * q.z + p.z * q.w + p.x * q.y - p.y * q.x};
+}
+
+quat rotate_vector(vec3 from, vec3 to)
+{
+	from = mu_normalize(from);
+	to = mu_normalize(to);
+	const float cos_angle = dot(from, to);
+	if (std::fabs(cos_angle) > 0.9999f)
+	{
+		if (cos_angle > 0.9999f)
+			return {1.0f, 0.0f, 0.0f, 0.0f};
+		vec3 rotation = cross(vec3(1.0f, 0.0f, 0.0f), from);
+		if (dot(rotation, rotation) > 0.001f)
+			rotation = mu_normalize(rotation);
+		else
+			rotation = mu_normalize(cross(vec3(0.0f, 1.0f, 0.0f), from));
+		return {0.0f, rotation};
+	}
+	const vec3 rotation = mu_normalize(cross(from, to));
+	const vec3 half_vector = mu_normalize(from + to);
+	const float cos_half_range = mu_clamp01(dot(half_vector, from));
+	const float sin_half_angle = std::sqrt(1.0f - cos_half_range * cos_half_range);
+	return {cos_half_range, rotation * sin_half_angle};
+}
+
+quat rotate_vector_axis(vec3 from, vec3 to, vec3 axis)
+{
+	axis = mu_normalize(axis);
+	from = mu_normalize(cross(axis, from));
+	to = mu_normalize(cross(axis, to));
+	if (dot(to, from) < -0.9999f)
+		return {0.0f, axis};
+	const float d = dot(axis, cross(from, to));
+	const float quat_sign = d < 0.0f ? -1.0f : (d > 0.0f ? 1.0f : 0.0f);
+	const vec3 half_vector = mu_normalize(from + to);
+	const float cos_half_range = mu_clamp01(dot(half_vector, from));
+	const float sin_half_angle = quat_sign * std::sqrt(1.0f - cos_half_range * cos_half_range);
+	return {cos_half_range, axis * sin_half_angle};
+}
+} // namespace
+
+quat look_at(const vec3 &direction_, const vec3 &up)
+{
+	const vec3 z(0.0f, 0.0f, -1.0f), y(0.0f, 1.0f, 0.0f);
+	const vec3 direction = mu_normalize(direction_);
+	const vec3 right = cross(direction, up);
+	const vec3 actual_up = cross(right, direction);
+	const quat look_transform = rotate_vector(direction, z);
+	const quat up_transform = rotate_vector_axis(rotate(look_transform, actual_up), y, z);
+	return mul(up_transform, look_transform);
+}
+
+mat4 mat4_cast(const quat &q)
+{
+	mat4 res(1.0f);
+	const float qxx = q.x * q.x, qyy = q.y * q.y, qzz = q.z * q.z, qxz = q.x * q.z, qxy = q.x * q.y, qyz = q.y * q.z;
+	const float qwx = q.w * q.x, qwy = q.w * q.y, qwz = q.w * q.z;
+	res[0][0] = 1.0f - 2.0f * (qyy + qzz);
+	res[0][1] = 2.0f * (qxy + qwz);
+	res[0][2] = 2.0f * (qxz - qwy);
+	res[1][0] = 2.0f * (qxy - qwz);
+	res[1][1] = 1.0f - 2.0f * (qxx + qzz);
+	res[1][2] = 2.0f * (qyz + qwx);
+	res[2][0] = 2.0f * (qxz + qwy);
+	res[2][1] = 2.0f * (qyz - qwx);
+	res[2][2] = 1.0f - 2.0f * (qxx + qyy);
+	return res;
+}
+
 uint16_t floatToHalf(float v)
 {
 	uint32_t bits;

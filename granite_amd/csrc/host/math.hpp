@@ -96,6 +96,20 @@ mat4 scale(const vec3 &v);
 mat4 perspective(float fovy, float aspect, float z_near, float z_far);
 mat4 look_at(const vec3 &eye, const vec3 &center, const vec3 &up);
 
+// muglm::quat and the reference's look_at(direction, up) (math/transforms.cpp:122-178: rotate_vector, rotate_vector_axis) with
+// mat4_cast (muglm.cpp:29-62), operation for operation in fp32: the view rotation compute_cube_render_transform builds.  Its entries are
+// a rounding away from 0 and +-1 (-5.96e-8 where look_at(eye, center, up) has 0), and a cube face's centre column sits exactly on the
+// lat-long seam of atan, so which side it falls on is decided by those roundings.
+struct quat
+{
+	float w = 1, x = 0, y = 0, z = 0;
+	quat() = default;
+	quat(float w_, float x_, float y_, float z_) : w(w_), x(x_), y(y_), z(z_) {}
+	quat(float w_, const vec3 &v) : w(w_), x(v.x), y(v.y), z(v.z) {}
+};
+quat look_at(const vec3 &direction, const vec3 &up);
+mat4 mat4_cast(const quat &q);
+
 struct mat_affine
 {
 	vec4 rows[3];

@@ -174,6 +174,13 @@ int gra_upload_gbuffer_gtx(gra_app *app, const char *emissive, const char *albed
  * (Granite::decode_compressed_image, one gr_texture_decode each), and writes an uncompressed .gtx of the decoded format with the
  * same extents, layers, levels and flags. */
 int gra_gtx_decode(gra_app *app, const char *src_path, const char *dst_path);
+/* Environment baking on the application's device, what tools/convert_equirect_to_environment.cpp does: the 2-D R16G16B16A16_SFLOAT
+ * .gtx `equirect_gtx` becomes a cube of unsigned(cube_scale * max(width / 3, height / 2)) texels with a full mip chain
+ * (Granite::convert_equirect_to_cube), from which the 128-texel, 8-level GGX reflection cube (convert_cube_to_ibl_specular) and the
+ * 32-texel irradiance cube (convert_cube_to_ibl_diffuse) are made.  Each is written as a cube .gtx (6 layers, the cube bit set in
+ * flags) where its path is not NULL; a bake nobody asked for is not run. */
+int gra_environment_bake(gra_app *app, const char *equirect_gtx, float cube_scale, const char *cube_path, const char *reflection_path,
+                         const char *irradiance_path);
 /* Writes a graph texture (all its mip levels) or, with name == NULL, the last rendered backbuffer as .gtx. */
 int gra_save_resource_gtx(gra_app *app, const char *name, const char *path);
 

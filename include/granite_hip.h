@@ -820,6 +820,32 @@ uint32_t gr_texture_block_bytes(uint32_t block_format);
 int gr_texture_decode(gr_ctx *ctx, gr_stream stream, uint32_t block_format, const void *blocks,
                       uint32_t block_row_pitch_bytes, const gr_image *out);
 
+/* ---- environment baking ---------------------------------------------------------------------------------------------------
+ * renderer/utils/image_utils.cpp: convert_equirect_to_cube, convert_cube_to_ibl_specular, convert_cube_to_ibl_diffuse
+ * (skybox.vert + skybox_latlon.frag / util/ibl_specular.frag / util/ibl_diffuse.frag per face and level, generate_mipmap).
+ * A cube is an R16G16B16A16_SFLOAT mip chain laid out as a GTX payload: levels in order, each starting 16-byte aligned; inside a
+ * level the faces +X -X +Y -Y +Z -Z follow each other, rows tightly packed; level l is max(size >> l, 1) texels a side.
+ * Cube pointers must be 16-byte aligned.  How a cube is sampled (face selection, seamless edges, trilinear) is DESIGN.md 7.8.
+ * Refused before anything is launched: null pointers, size 0 or above 16384, levels 0 or beyond the chain of the size, unaligned
+ * pointers (GR_ERR_INVALID_ARGUMENT), an equirect that is not R16G16B16A16_SFLOAT (GR_ERR_UNSUPPORTED_FORMAT). */
+typedef struct gr_cube
+{
+	const void *ptr; /* device pointer */
+	uint32_t size;   /* texels a side at level 0 */
+	uint32_t levels;
+} gr_cube;
+/* Host-only. Bytes of a chain of `levels` levels, and the offset of a face of a level in it. */
+uint64_t gr_cube_chain_bytes(uint32_t size, uint32_t levels);
+uint64_t gr_cube_chain_offset(uint32_t size, uint32_t level, uint32_t face);
+/* Level 0: the lat-long lookup of skybox_latlon.frag (LinearWrap, LOD 0) along each texel's direction; levels 1 and up: each a
+ * linear-filter blit of the one above, per face, rounded to fp16 before the next reads it.  Alpha is 1. */
+int gr_env_equirect_to_cube(gr_ctx *ctx, gr_stream stream, const gr_image *equirect, void *cube, uint32_t size, uint32_t levels);
+/* GGX-prefiltered reflection chain: level l with roughness mix(0.001, 1, l / (out_levels - 1)), 1024 Hammersley samples read through
+ * TrilinearWrap at lod = log2(src size) - log2(out_size) + l.  One launch for all faces and levels. */
+int gr_env_specular(gr_ctx *ctx, gr_stream stream, const gr_cube *src, void *out, uint32_t out_size, uint32_t out_levels);
+/* Irradiance: 252 x 63 hemisphere taps per texel through LinearWrap at lod = max(log2(out_size) - 5, 0); one level. */
+int gr_env_diffuse(gr_ctx *ctx, gr_stream stream, const gr_cube *src, void *out, uint32_t out_size);
+
 /* Fill with a 32-bit pattern (count dwords): attachment clears to a colour. */
 int gr_fill_u32(gr_ctx *ctx, gr_stream stream, void *dst, uint32_t value, size_t count);
 /* Executor self-test operation (no counterpart in the reference): out[i] = hash(i, salt, one dword of each of up to four

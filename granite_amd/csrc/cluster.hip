@@ -22,6 +22,12 @@ __device__ __forceinline__ v4 mul_mat4(const float *m, v4 v)
 	return r;
 }
 
+// min / max of the set-up path: of -0 and +0 the SECOND operand is returned, as where the reference's shaders are executed on the CPU
+// (fminf / fmaxf there); v_min_f32 / v_max_f32 order the two zeros instead.  Only the sign of a zero depends on it, but the build is
+// pinned bit for bit.  No NaN reaches these.
+__device__ __forceinline__ float min_tie2(float a, float b) { return a < b ? a : b; }
+__device__ __forceinline__ float max_tie2(float a, float b) { return a > b ? a : b; }
+
 struct TransformedSpot { v4 clip[5]; v4 z; };
 struct CullSetup { v4 data[32]; };
 
@@ -60,8 +66,8 @@ __device__ __forceinline__ TransformedSpot spot_transform_of(const gr_mat_affine
 	for (int i = 1; i < 5; i++)
 	{
 		const float z = dot3(p[i] - cam, front);
-		z_lo = fminf(z_lo, z);
-		z_hi = fmaxf(z_hi, z);
+		z_lo = min_tie2(z_lo, z);
+		z_hi = max_tie2(z_hi, z);
 	}
 	float cull;
 	if (z_lo <= push.z_near && z_hi >= push.z_far)
@@ -124,8 +130,8 @@ __device__ void emit_triangle(CullSetup &cs, uint32_t &num_triangles, const Tri2
 		cs.data[o] = mk4(inv_z * cross_2d(ab, -c0), inv_z * cross_2d(bc, -c1), inv_z * cross_2d(ca, -c2), 0.0f);
 		cs.data[o + 1u] = mk4(inv_z * (-ab.y), inv_z * (-bc.y), inv_z * (-ca.y), z);
 		cs.data[o + 2u] = mk4(inv_z * ab.x, inv_z * bc.x, inv_z * ca.x, inv_z);
-		cs.data[o + 3u] = mk4(fminf(fminf(c0.x, c1.x), c2.x), fminf(fminf(c0.y, c1.y), c2.y), fmaxf(fmaxf(c0.x, c1.x), c2.x),
-		                      fmaxf(fmaxf(c0.y, c1.y), c2.y));
+		cs.data[o + 3u] = mk4(min_tie2(min_tie2(c0.x, c1.x), c2.x), min_tie2(min_tie2(c0.y, c1.y), c2.y), max_tie2(max_tie2(c0.x, c1.x), c2.x),
+		                      max_tie2(max_tie2(c0.y, c1.y), c2.y));
 	}
 	num_triangles++;
 }

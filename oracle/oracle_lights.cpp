@@ -89,6 +89,12 @@ static inline vec3 aff_up(const Affine &m) { return V3(m.rows[0][1], m.rows[1][1
 static inline float aff_uniform_scale(const Affine &m) { return length(V3(m.rows[0][0], m.rows[0][1], m.rows[0][2])); }
 
 // PositionalLight::recompute_range (lights.cpp:63-70): falloff range where attenuation drops below 0.1.
+// min / max as the executed reference shaders evaluate them (oracle/ref_build: fminf / fmaxf): of -0 and +0 the second operand is
+// returned.  Only the sign of a zero depends on it -- z_lo / z_hi of a light whose vertices lie in the camera plane, a bounding box
+// that ends on the screen centre -- but the cluster build is pinned bit for bit.  No NaN reaches these.
+static inline float min_glsl(float a, float b) { return a < b ? a : b; }
+static inline float max_glsl(float a, float b) { return a > b ? a : b; }
+
 static inline float falloff_range(const LightDesc &d)
 {
 	float max_color = std::max(std::max(d.color[0], d.color[1]), d.color[2]);
@@ -281,8 +287,8 @@ void orc_cluster_spot_transform(const RenderParams *rp, const Affine *model, int
 		float z_lo = z[0], z_hi = z[0];
 		for (int i = 1; i < 5; i++)
 		{
-			z_lo = std::min(z_lo, z[i]);
-			z_hi = std::max(z_hi, z[i]);
+			z_lo = min_glsl(z_lo, z[i]);
+			z_hi = max_glsl(z_hi, z[i]);
 		}
 		float cull;
 		if (z_lo <= rp->z_near && z_hi >= rp->z_far)
@@ -385,8 +391,8 @@ static void setup_triangle_2d(CullSetup &cs, uint32_t &num_triangles, const mat3
 		cs.data[4u * num_triangles + 1u] = V4(dx, z);
 		cs.data[4u * num_triangles + 2u] = V4(dy, inv_z);
 		cs.data[4u * num_triangles + 3u] =
-		    V4(std::min(std::min(c0.x, c1.x), c2.x), std::min(std::min(c0.y, c1.y), c2.y),
-		       std::max(std::max(c0.x, c1.x), c2.x), std::max(std::max(c0.y, c1.y), c2.y));
+		    V4(min_glsl(min_glsl(c0.x, c1.x), c2.x), min_glsl(min_glsl(c0.y, c1.y), c2.y),
+		       max_glsl(max_glsl(c0.x, c1.x), c2.x), max_glsl(max_glsl(c0.y, c1.y), c2.y));
 	}
 	num_triangles++;
 }

@@ -13,7 +13,21 @@ class Scene:
         self.cam = synth.Camera(w, h)
         self.rp = self.cam.render_params()
         self.gbuf = synth.make_gbuffer(self.cam, seed, scene=scene)
-        self.descs = synth.make_lights(self.cam, num_lights, spot_fraction, seed=seed, scene=scene)
+        self._pack(synth.make_lights(self.cam, num_lights, spot_fraction, seed=seed, scene=scene), res)
+
+    @classmethod
+    def from_camera(cls, cam, descs, res=(128, 64, 4096), seed=synth.SEED, scene="default"):
+        """A scene under a given camera with given light descs (tests/cluster_cases.py); the G-buffer is the synthetic one of that camera."""
+        self = cls.__new__(cls)
+        self.w, self.h = cam.width, cam.height
+        self.cam = cam
+        self.rp = cam.render_params()
+        self.gbuf = synth.make_gbuffer(cam, seed, scene=scene)
+        self._pack(descs, res)
+        return self
+
+    def _pack(self, descs, res):
+        self.descs = descs
         self.res = res
         self.n, self.lights, self.model, self.type_mask, self.order = orc.pack_lights(self.descs, self.rp[99:102])
         self.prm = orc.cluster_params(self.rp, res[0], res[1], res[2], self.n)

@@ -50,6 +50,32 @@ def assert_rgba16f_close_but_for_ill_conditioned_pixels(a_bits, b_bits, ulps=2.0
         assert_rgba16f_close(a_bits, b_bits, outer_ulps, abs_tol, what=what + " (ill-conditioned pixels)")
 
 
+def assert_words_equal_or_both_nan(got, ref, integer_words=None, what=""):
+    """32-bit words equal bit for bit, except that a word which is a float NaN on BOTH sides counts as equal (sign and payload of a
+    NaN are not defined by the operations that make one: inf - inf is 0xffc00000 on x86 and 0x7fc00000 elsewhere).  NaN-ness itself
+    must match.  `integer_words` (bool, same shape) marks words that hold integers -- 0xffffffff there is a value, not a NaN: they
+    are compared as bits.  Returns the number of words that took the exception, which can not exceed `ref`'s own NaN count."""
+    g = np.ascontiguousarray(got).view(np.uint32)
+    r = np.ascontiguousarray(ref).view(np.uint32)
+    assert g.shape == r.shape, f"{what}: shapes {g.shape} vs {r.shape}"
+
+    def is_nan(words):
+        nan = ((words & np.uint32(0x7f800000)) == np.uint32(0x7f800000)) & ((words & np.uint32(0x007fffff)) != 0)
+        return nan & ~integer_words if integer_words is not None else nan
+
+    g_nan, r_nan = is_nan(g), is_nan(r)
+    if (g_nan != r_nan).any():
+        idx = tuple(np.argwhere(g_nan != r_nan)[0])
+        raise AssertionError(f"{what}: NaN on one side only in {(g_nan != r_nan).sum()} words; first at {idx}: {g[idx]:#010x} vs {r[idx]:#010x}")
+    excepted = g_nan & r_nan & (g != r)
+    bad = (g != r) & ~excepted
+    if bad.any():
+        idx = tuple(np.argwhere(bad)[0])
+        raise AssertionError(f"{what}: {bad.sum()} of {bad.size} words differ; first at {idx}: {g[idx]:#010x} vs {r[idx]:#010x}")
+    assert excepted.sum() <= r_nan.sum()
+    return int(excepted.sum())
+
+
 def assert_rgba8_close(a, b, lsb=1, what=""):
     d = np.abs(np.asarray(a, np.int16) - np.asarray(b, np.int16))
     if (d > lsb).any():

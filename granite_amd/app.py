@@ -75,6 +75,14 @@ class VideoPlayOptions(C.Structure):
 VIDEO_FORMATS = {"nv12": 0, "yuv420p": 1, "yuv420p16": 2, "yuv444p": 3, "yuv444p16": 4, "p010": 5, "p016": 6}
 
 
+class FftRequest(C.Structure):
+    """gra_fft_request."""
+    _fields_ = [("nx", C.c_uint32), ("ny", C.c_uint32), ("nz", C.c_uint32), ("dimensions", C.c_uint32), ("mode", C.c_uint32), ("data_type", C.c_uint32),
+                ("input", C.c_void_p), ("input_bytes", C.c_uint64), ("input_row_stride", C.c_uint32), ("input_layer_stride", C.c_uint32),
+                ("output", C.c_void_p), ("output_bytes", C.c_uint64), ("output_row_stride", C.c_uint32), ("output_layer_stride", C.c_uint32),
+                ("image_width", C.c_uint32), ("image_height", C.c_uint32), ("image_byte_offset", C.c_uint64), ("output_offset", C.c_int32 * 2)]
+
+
 class Timestamp(C.Structure):
     _fields_ = [("tag", C.c_char * 64), ("count", C.c_uint64), ("total_ms", C.c_double)]
 
@@ -84,7 +92,7 @@ EXPORTED_SYMBOLS = [
     "gra_get_render_parameters", "gra_set_lights", "gra_upload_gbuffer", "gra_render_frames", "gra_sync",
     "gra_get_resource", "gra_read_resource", "gra_get_backbuffer", "gra_read_backbuffer", "gra_get_cluster_state",
     "gra_dump_graph", "gra_collect_timestamps", "gra_get_kernel_context", "gra_get_stream", "gra_get_taa_reprojection",
-    "gra_set_smaa_luts", "gra_get_host_stats", "gra_get_output_gather_stats", "gra_get_prefetched_refreshes", "gra_get_launch_graph_replays", "gra_get_allocated_bytes", "gra_gtx_probe", "gra_gtx_read", "gra_gtx_write", "gra_gtx_decode", "gra_environment_bake",
+    "gra_set_smaa_luts", "gra_get_host_stats", "gra_get_output_gather_stats", "gra_get_prefetched_refreshes", "gra_get_launch_graph_replays", "gra_get_allocated_bytes", "gra_gtx_probe", "gra_gtx_read", "gra_gtx_write", "gra_gtx_decode", "gra_environment_bake", "gra_fft_transform",
     "gra_upload_gbuffer_gtx", "gra_save_resource_gtx", "gra_get_render_size", "gra_upload_ambient_occlusion", "gra_upload_aa_bench_images", "gra_compute_rec709_to_display", "gra_set_exchange_callback", "gra_get_strip_plan", "gra_get_strip_plan_aa", "gra_get_strip_plan_taa_history",
     "gra_comm_create_unique_id", "gra_comm_init", "gra_comm_info", "gra_comm_init_output", "gra_install_ssr_tables", "gra_reset_timestamps", "gra_set_directional_light", "gra_set_fog", "gra_generate_mipmaps", "gra_write_resource", "gra_get_frame_state", "gra_set_frame_state",
     "gra_video_begin", "gra_video_frame_layout", "gra_video_read_frame", "gra_video_end",
@@ -141,6 +149,7 @@ def load_library() -> C.CDLL:
         "gra_gtx_write": (C.c_int, [C.c_char_p, vp, vp, vp, C.c_size_t]),
         "gra_gtx_decode": (C.c_int, [vp, C.c_char_p, C.c_char_p]),
         "gra_environment_bake": (C.c_int, [vp, C.c_char_p, C.c_float] + [C.c_char_p] * 3),
+        "gra_fft_transform": (C.c_int, [vp, P(FftRequest)]),
         "gra_upload_gbuffer_gtx": (C.c_int, [vp] + [C.c_char_p] * 6),
         "gra_save_resource_gtx": (C.c_int, [vp, C.c_char_p, C.c_char_p]),
         "gra_reset_timestamps": (C.c_int, [vp]),
@@ -304,6 +313,20 @@ class Application:
         None is not written, and its bake is not run."""
         enc = lambda p: None if p is None else str(p).encode()
         self._check(self.lib.gra_environment_bake(self.handle, str(equirect).encode(), float(cube_scale), enc(cube), enc(reflection), enc(irradiance)))
+
+    def fft(self, options, src: np.ndarray, src_strides, dst: np.ndarray, dst_strides=(0, 0), image=None, output_offset=(0, 0)):
+        """gra_fft_transform: one transform through Granite::FFT.  options: nx, ny, nz, dimensions, mode, data_type (capi.FFT_*); src and dst are
+        flat numpy arrays laid out as the device buffers are, strides (row, layer) in elements.  dst is uploaded first and rewritten in
+        place.  image = (width, height, byte offset into dst): texture output, written at output_offset."""
+        assert src.flags.c_contiguous and dst.flags.c_contiguous and dst.flags.writeable
+        r = FftRequest()
+        r.nx, r.ny, r.nz, r.dimensions, r.mode, r.data_type = (int(v) for v in options)
+        r.input, r.input_bytes, r.input_row_stride, r.input_layer_stride = src.ctypes.data, src.nbytes, int(src_strides[0]), int(src_strides[1])
+        r.output, r.output_bytes, r.output_row_stride, r.output_layer_stride = dst.ctypes.data, dst.nbytes, int(dst_strides[0]), int(dst_strides[1])
+        if image is not None:
+            r.image_width, r.image_height, r.image_byte_offset = int(image[0]), int(image[1]), int(image[2])
+        r.output_offset[:] = [int(output_offset[0]), int(output_offset[1])]
+        self._check(self.lib.gra_fft_transform(self.handle, C.byref(r)))
 
     def save_gtx(self, path: str, name: Optional[str] = None):
         """Write graph texture `name` (None = the last backbuffer) as .gtx."""

@@ -30,6 +30,7 @@ FORMAT_R16G16_UNORM = 77
 FORMAT_R16G16_SFLOAT = 83
 FORMAT_R16G16B16A16_SFLOAT = 97
 FORMAT_R32_SFLOAT = 100
+FORMAT_R32G32_SFLOAT = 103
 FORMAT_B10G11R11_UFLOAT_PACK32 = 122
 FORMAT_D16_UNORM = 124
 FORMAT_D32_SFLOAT = 126
@@ -64,6 +65,7 @@ FORMAT_BPP = {
     FORMAT_R16G16_SFLOAT: 4,
     FORMAT_R16G16B16A16_SFLOAT: 8,
     FORMAT_R32_SFLOAT: 4,
+    FORMAT_R32G32_SFLOAT: 8,
     FORMAT_B10G11R11_UFLOAT_PACK32: 4,
     FORMAT_D16_UNORM: 2,
     FORMAT_D32_SFLOAT: 4,
@@ -112,6 +114,32 @@ class Cube(C.Structure):
 class Image(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("pitch_bytes", C.c_uint32),
                 ("format", C.c_uint32)]
+
+
+# gr_fft_mode, gr_fft_data_type, gr_fft_resource_type, gr_fft_pass_kind, gr_fft_buffer_id
+FFT_FORWARD_C2C, FFT_INVERSE_C2C, FFT_R2C, FFT_C2R = 0, 1, 2, 3
+FFT_FP32, FFT_FP16 = 0, 1
+FFT_RESOURCE_TEXTURE, FFT_RESOURCE_BUFFER = 0, 1
+FFT_PASS_C2C, FFT_PASS_R2C_RESOLVE, FFT_PASS_C2R_RESOLVE = 0, 1, 2
+FFT_BUFFER_SRC, FFT_BUFFER_DST, FFT_BUFFER_SCRATCH_A, FFT_BUFFER_SCRATCH_B = 0, 1, 2, 3
+
+
+class FftOptions(C.Structure):
+    """gr_fft_options."""
+    _fields_ = [("nx", C.c_uint32), ("ny", C.c_uint32), ("nz", C.c_uint32), ("dimensions", C.c_uint32), ("mode", C.c_uint32),
+                ("data_type", C.c_uint32), ("input_resource", C.c_uint32), ("output_resource", C.c_uint32)]
+
+
+class FftResource(C.Structure):
+    """gr_fft_resource: a buffer (ptr, size_bytes, strides in elements) or an image with its output offset."""
+    _fields_ = [("type", C.c_uint32), ("ptr", C.c_void_p), ("size_bytes", C.c_uint64), ("row_stride", C.c_uint32), ("layer_stride", C.c_uint32),
+                ("image", Image), ("output_offset", C.c_int32 * 2)]
+
+
+class FftPass(C.Structure):
+    """gr_fft_pass: one entry of gr_fft_describe."""
+    _fields_ = [("kind", C.c_uint32), ("dimension", C.c_uint32), ("points", C.c_uint32), ("p", C.c_uint32), ("columns", C.c_uint32),
+                ("workgroup_size", C.c_uint32), ("grid_size", C.c_uint32), ("lds_bytes", C.c_uint32), ("reads", C.c_uint32), ("writes", C.c_uint32)]
 
 
 class PushVideo(C.Structure):
@@ -432,6 +460,12 @@ def load_library() -> C.CDLL:
         "gr_env_equirect_to_cube": (C.c_int, [vp, vp, P(Image), vp, C.c_uint32, C.c_uint32]),
         "gr_env_specular": (C.c_int, [vp, vp, P(Cube), vp, C.c_uint32, C.c_uint32]),
         "gr_env_diffuse": (C.c_int, [vp, vp, P(Cube), vp, C.c_uint32]),
+        "gr_fft_describe": (C.c_int, [P(FftOptions), P(FftPass), C.c_uint32]),
+        "gr_fft_plan_create": (C.c_int, [vp, P(FftOptions), P(vp)]),
+        "gr_fft_plan_destroy": (None, [vp, vp]),
+        "gr_fft_plan_iterations": (C.c_uint32, [vp]),
+        "gr_fft_execute": (C.c_int, [vp, vp, vp, P(FftResource), P(FftResource)]),
+        "gr_fft_execute_iteration": (C.c_int, [vp, vp, vp, P(FftResource), P(FftResource), C.c_uint32]),
         "gr_fsr_sharpen": (C.c_int, [vp, vp, P(Image), P(Image), C.c_float]),
         "gr_mip_chain_offset": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
         "gr_mip_chain_size": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
@@ -455,7 +489,34 @@ EXPORTED_SYMBOLS = [
     "gr_video_scale", "gr_video_scale_plan", "gr_video_scaler_weights", "gr_video_yuv_to_rgb", "gr_video_yuv_plan",
     "gr_texture_decoded_format", "gr_texture_block_bytes", "gr_texture_decode",
     "gr_cube_chain_bytes", "gr_cube_chain_offset", "gr_env_equirect_to_cube", "gr_env_specular", "gr_env_diffuse",
+    "gr_fft_describe", "gr_fft_plan_create", "gr_fft_plan_destroy", "gr_fft_plan_iterations", "gr_fft_execute", "gr_fft_execute_iteration",
 ]
+
+
+def fft_options(nx, ny=1, nz=1, dimensions=1, mode=FFT_FORWARD_C2C, data_type=FFT_FP32, input_resource=FFT_RESOURCE_BUFFER,
+                output_resource=FFT_RESOURCE_BUFFER) -> FftOptions:
+    return FftOptions(int(nx), int(ny), int(nz), int(dimensions), int(mode), int(data_type), int(input_resource), int(output_resource))
+
+
+def fft_describe(options: FftOptions):
+    """gr_fft_describe (host-only): the pass list of a plan as FftPass entries, or None where gr_fft_plan_create refuses the options."""
+    lib = load_library()
+    passes = (FftPass * 16)()
+    n = lib.gr_fft_describe(C.byref(options), passes, 16)
+    return None if n < 0 else [passes[i] for i in range(n)]
+
+
+def fft_buffer_resource(ptr, size_bytes, row_stride, layer_stride) -> FftResource:
+    r = FftResource()
+    r.type, r.ptr, r.size_bytes, r.row_stride, r.layer_stride = FFT_RESOURCE_BUFFER, ptr, int(size_bytes), int(row_stride), int(layer_stride)
+    return r
+
+
+def fft_image_resource(image: Image, output_offset=(0, 0)) -> FftResource:
+    r = FftResource()
+    r.type, r.image = FFT_RESOURCE_TEXTURE, image
+    r.output_offset[:] = [int(output_offset[0]), int(output_offset[1])]
+    return r
 
 
 def _video_images(input_size, input_format, planes):
@@ -768,6 +829,23 @@ class Context:
         """gr_env_diffuse: the irradiance cube (one level) of a cube."""
         assert src.nbytes >= self.lib.gr_cube_chain_bytes(src_size, src_levels) and out.nbytes >= self.lib.gr_cube_chain_bytes(out_size, 1)
         self.check(self.lib.gr_env_diffuse(self.handle, stream, C.byref(Cube(src.ptr, src_size, src_levels)), out.ptr, int(out_size)))
+
+    # ---- FFT: a plan owns its scratch and twiddles and may be in flight on one stream at a time ---------------------------------
+    def fft_plan(self, options: FftOptions):
+        """gr_fft_plan_create: an opaque plan handle (free it with fft_plan_destroy)."""
+        plan = C.c_void_p()
+        self.check(self.lib.gr_fft_plan_create(self.handle, C.byref(options), C.byref(plan)))
+        return plan
+
+    def fft_plan_destroy(self, plan):
+        self.lib.gr_fft_plan_destroy(self.handle, plan)
+
+    def fft_execute(self, plan, dst: FftResource, src: FftResource, stream=None, iteration: Optional[int] = None):
+        """gr_fft_execute, or gr_fft_execute_iteration for one pass of the plan."""
+        if iteration is None:
+            self.check(self.lib.gr_fft_execute(self.handle, stream, plan, C.byref(dst), C.byref(src)))
+        else:
+            self.check(self.lib.gr_fft_execute_iteration(self.handle, stream, plan, C.byref(dst), C.byref(src), int(iteration)))
 
     def blit(self, src: DeviceImage, out: DeviceImage, linear: bool, stream=None):
         self.check(self.lib.gr_blit(self.handle, stream, src.desc, out.desc, int(linear)))

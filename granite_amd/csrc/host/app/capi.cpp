@@ -6,6 +6,7 @@
 #include "../gtx.hpp"
 #include "../texture_decoder.hpp"
 #include "../utils/image_utils.hpp"
+#include "../fft/fft.hpp"
 #include "../post/hdr.hpp"
 #include <cstdio>
 #include <cstring>
@@ -251,6 +252,66 @@ int gra_environment_bake(gra_app *app, const char *equirect_gtx, float cube_scal
 			gtx_save(convert_cube_to_ibl_specular(ctx, nullptr, cube), reflection_path);
 		if (irradiance_path)
 			gtx_save(convert_cube_to_ibl_diffuse(ctx, nullptr, cube), irradiance_path);
+	});
+}
+
+int gra_fft_transform(gra_app *app, const gra_fft_request *request)
+{
+	return guarded(app, [&]() {
+		if (!request || !request->input || !request->output || request->input_bytes == 0 || request->output_bytes == 0)
+			throw std::logic_error("gra_fft_transform: null request, input or output");
+		if (request->mode > GR_FFT_COMPLEX_TO_REAL || request->data_type > GR_FFT_FP16)
+			throw std::logic_error("gra_fft_transform: unknown mode or data type");
+		auto &device = app->app->get_device();
+		gr_ctx *ctx = device.get_context();
+		if (!ctx)
+			throw std::logic_error("gra_fft_transform: the application has no device");
+		const bool texture = request->image_width != 0;
+		const bool fp16 = request->data_type == GR_FFT_FP16, real_out = request->mode == GR_FFT_COMPLEX_TO_REAL;
+		const VkFormat format = real_out ? (fp16 ? VK_FORMAT_R16_SFLOAT : VK_FORMAT_R32_SFLOAT) : (fp16 ? VK_FORMAT_R16G16_SFLOAT : VK_FORMAT_R32G32_SFLOAT);
+		if (texture)
+		{
+			const uint64_t image_bytes = uint64_t(request->image_width) * request->image_height * vk_format_block_size(format);
+			if (request->image_height == 0 || request->image_byte_offset > request->output_bytes || image_bytes > request->output_bytes - request->image_byte_offset)
+				throw std::logic_error("gra_fft_transform: the image does not lie inside the output block");
+		}
+
+		FFT::Options options;
+		options.Nx = request->nx;
+		options.Ny = request->ny;
+		options.Nz = request->nz;
+		options.dimensions = request->dimensions;
+		options.mode = FFT::Mode(request->mode);
+		options.data_type = FFT::DataType(request->data_type);
+		options.output_resource = texture ? FFT::ResourceType::Texture : FFT::ResourceType::Buffer;
+		FFT fft;
+		if (!fft.plan(&device, options))
+			throw std::runtime_error(std::string("gra_fft_transform: ") + gr_last_error(ctx));
+
+		device.wait_idle();
+		auto stream = device.get_stream(HIP::CommandBuffer::Type::Generic);
+		auto input = device.create_buffer(request->input_bytes, VK_BUFFER_USAGE_STORAGE_BUFFER_BIT, "fft-input");
+		auto output = device.create_buffer(request->output_bytes, VK_BUFFER_USAGE_STORAGE_BUFFER_BIT, "fft-output");
+		if (gr_upload(ctx, stream, input->get_device_pointer(), request->input, request->input_bytes) < 0 ||
+		    gr_upload(ctx, stream, output->get_device_pointer(), request->output, request->output_bytes) < 0)
+			throw std::runtime_error(gr_last_error(ctx));
+
+		FFT::Resource src = {}, dst = {};
+		src.buffer = {input.get(), 0, size_t(request->input_bytes), request->input_row_stride, request->input_layer_stride};
+		std::unique_ptr<HIP::Image> image;
+		if (texture)
+		{
+			image.reset(new HIP::Image(request->image_width, request->image_height, format,
+			                           static_cast<uint8_t *>(output->get_device_pointer()) + request->image_byte_offset));
+			dst.image = {image.get(), {request->output_offset[0], request->output_offset[1]}};
+		}
+		else
+			dst.buffer = {output.get(), 0, size_t(request->output_bytes), request->output_row_stride, request->output_layer_stride};
+		HIP::CommandBuffer cmd(device, stream, HIP::CommandBuffer::Type::Generic);
+		fft.execute(cmd, dst, src);
+		if (gr_download(ctx, stream, request->output, output->get_device_pointer(), request->output_bytes) < 0 || gr_sync(ctx, stream) < 0)
+			throw std::runtime_error(gr_last_error(ctx));
+		fft.release();
 	});
 }
 

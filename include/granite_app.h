@@ -181,6 +181,27 @@ int gra_gtx_decode(gra_app *app, const char *src_path, const char *dst_path);
  * flags) where its path is not NULL; a bake nobody asked for is not run. */
 int gra_environment_bake(gra_app *app, const char *equirect_gtx, float cube_scale, const char *cube_path, const char *reflection_path,
                          const char *irradiance_path);
+/* One FFT on the application's device through Granite::FFT (host/fft/fft.hpp; renderer/fft/fft.hpp): upload, plan, execute, download.
+ * nx, ny, nz, dimensions, mode (gr_fft_mode) and data_type (gr_fft_data_type) as gr_fft_options has them; strides in elements.
+ * `input` and `output` are host memory.  `output` is uploaded before the transform and downloaded after it, so bytes the transform
+ * does not write come back as they went in.  With image_width == 0 the output is a buffer of output_bytes with the output strides.
+ * Otherwise it is a texture: a tightly packed image_width x image_height image of the format the mode stores (gr_fft_resource),
+ * image_byte_offset bytes into the output_bytes block, written at output_offset; the bytes of the block before and after the image are
+ * guard bytes no store may touch.  Fails (gra_last_error) where the plan or the library refuses. */
+typedef struct gra_fft_request
+{
+	uint32_t nx, ny, nz, dimensions, mode, data_type;
+	const void *input;
+	uint64_t input_bytes;
+	uint32_t input_row_stride, input_layer_stride;
+	void *output;
+	uint64_t output_bytes;
+	uint32_t output_row_stride, output_layer_stride;
+	uint32_t image_width, image_height;
+	uint64_t image_byte_offset;
+	int32_t output_offset[2];
+} gra_fft_request;
+int gra_fft_transform(gra_app *app, const gra_fft_request *request);
 /* Writes a graph texture (all its mip levels) or, with name == NULL, the last rendered backbuffer as .gtx. */
 int gra_save_resource_gtx(gra_app *app, const char *name, const char *path);
 

@@ -53,6 +53,7 @@ typedef enum gr_format
 	GR_FORMAT_R16G16_SFLOAT = 83,
 	GR_FORMAT_R16G16B16A16_SFLOAT = 97,
 	GR_FORMAT_R32_SFLOAT = 100,
+	GR_FORMAT_R32G32_SFLOAT = 103,     /* complex fp32 output of gr_fft_execute */
 	GR_FORMAT_B10G11R11_UFLOAT_PACK32 = 122, /* HDR targets with renderTargetFp16 = false (scene_viewer_application.cpp:881-883), TAA colour (temporal.cpp:211-213) */
 	GR_FORMAT_D16_UNORM = 124,
 	GR_FORMAT_D32_SFLOAT = 126,
@@ -845,6 +846,96 @@ int gr_env_equirect_to_cube(gr_ctx *ctx, gr_stream stream, const gr_image *equir
 int gr_env_specular(gr_ctx *ctx, gr_stream stream, const gr_cube *src, void *out, uint32_t out_size, uint32_t out_levels);
 /* Irradiance: 252 x 63 hemisphere taps per texel through LinearWrap at lod = max(log2(out_size) - 5, 0); one level. */
 int gr_env_diffuse(gr_ctx *ctx, gr_stream stream, const gr_cube *src, void *out, uint32_t out_size);
+
+/* ---- FFT (renderer/fft/fft.{hpp,cpp}) ------------------------------------------------------------------------------------------
+ * Complex-to-complex, real-to-complex and complex-to-real transforms in 1 to 3 dimensions, FP32 or FP16 in memory (arithmetic is fp32).
+ * Forward C2C and R2C use the exponent sign -1, inverse C2C and C2R +1; nothing is normalised (inverse of forward gives N x).
+ * nx, ny, nz: a dimension above `dimensions` with extent > 1 is a batch.  Transformed extents are powers of two of at least 4; for R2C
+ * and C2R nx is the real length and at least 8.  R2C writes, and C2R reads, columns 0 .. nx / 2 of a row (nx / 2 + 1 complex numbers)
+ * and nothing else of it; C2R does not read the imaginary parts of columns 0 and nx / 2 of its input rows (they are taken as zero
+ * after the transforms along y and z, which makes a 2-D or 3-D C2R numpy's irfftn times N).
+ * gr_fft_plan_create refuses (GR_ERR_INVALID_ARGUMENT): such extents, nx * ny * nz of 2^31 or more, texture input, texture output with
+ * nz > 1 or with a real mode in one dimension or wider than 65536.  A plan owns its twiddle table and scratch buffers; creating one
+ * allocates and synchronises, executing does neither.  A plan may be in flight on ONE stream at a time (the scratch is the plan's).
+ * gr_fft_execute checks both resources before it launches anything (GR_ERR_INVALID_ARGUMENT, nothing launched): null pointers, a type
+ * other than the plan's, misaligned pointers, a byte size below what the strides span, an odd stride on an FP16 real side, a row
+ * stride below the row or a layer stride below the layer, source and destination byte ranges that overlap; an image of another
+ * format than the mode stores (GR_ERR_UNSUPPORTED_FORMAT).  Every load and store lies inside the stated sizes. */
+typedef enum gr_fft_mode
+{
+	GR_FFT_FORWARD_COMPLEX_TO_COMPLEX = 0,
+	GR_FFT_INVERSE_COMPLEX_TO_COMPLEX = 1,
+	GR_FFT_REAL_TO_COMPLEX = 2,
+	GR_FFT_COMPLEX_TO_REAL = 3
+} gr_fft_mode;
+typedef enum gr_fft_data_type
+{
+	GR_FFT_FP32 = 0, /* float2; float on a real side */
+	GR_FFT_FP16 = 1  /* half2; half on a real side */
+} gr_fft_data_type;
+typedef enum gr_fft_resource_type
+{
+	GR_FFT_RESOURCE_TEXTURE = 0,
+	GR_FFT_RESOURCE_BUFFER = 1
+} gr_fft_resource_type;
+typedef struct gr_fft_options
+{
+	uint32_t nx, ny, nz;
+	uint32_t dimensions;      /* 1 .. 3 */
+	uint32_t mode;            /* gr_fft_mode */
+	uint32_t data_type;       /* gr_fft_data_type */
+	uint32_t input_resource;  /* gr_fft_resource_type; only buffers are accepted */
+	uint32_t output_resource; /* gr_fft_resource_type */
+} gr_fft_options;
+/* A buffer (ptr, size_bytes, strides) or an image (image, output_offset).  Strides count elements: scalars on a real side, complex
+ * numbers otherwise.  Texture output: R32G32_SFLOAT / R16G16_SFLOAT, or R32_SFLOAT / R16_SFLOAT for C2R, where complex column i goes to
+ * texels 2 i and 2 i + 1; output_offset is added to the texel coordinate and a store outside the image is dropped. */
+typedef struct gr_fft_resource
+{
+	uint32_t type; /* gr_fft_resource_type */
+	void *ptr;     /* device pointer */
+	uint64_t size_bytes;
+	uint32_t row_stride;
+	uint32_t layer_stride;
+	gr_image image;
+	int32_t output_offset[2];
+} gr_fft_resource;
+typedef enum gr_fft_pass_kind
+{
+	GR_FFT_PASS_C2C = 0,
+	GR_FFT_PASS_R2C_RESOLVE = 1,
+	GR_FFT_PASS_C2R_RESOLVE = 2
+} gr_fft_pass_kind;
+typedef enum gr_fft_buffer_id
+{
+	GR_FFT_BUFFER_SRC = 0,
+	GR_FFT_BUFFER_DST = 1,
+	GR_FFT_BUFFER_SCRATCH_A = 2,
+	GR_FFT_BUFFER_SCRATCH_B = 3
+} gr_fft_buffer_id;
+typedef struct gr_fft_pass
+{
+	uint32_t kind;           /* gr_fft_pass_kind */
+	uint32_t dimension;      /* 0 = x */
+	uint32_t points;         /* points of one workgroup transform (the radix of the pass); 0 for a resolve */
+	uint32_t p;              /* product of the radices of the earlier passes of this dimension; 0 for a resolve */
+	uint32_t columns;        /* adjacent columns a workgroup holds */
+	uint32_t workgroup_size;
+	uint32_t grid_size;      /* workgroups */
+	uint32_t lds_bytes;
+	uint32_t reads, writes;  /* gr_fft_buffer_id */
+} gr_fft_pass;
+typedef struct gr_fft_plan gr_fft_plan;
+/* Host-only (no context, no device): the passes a plan of these options runs, in order.  Returns their number (also when it exceeds
+ * `capacity`; at most `capacity` are written), or GR_ERR_INVALID_ARGUMENT for options gr_fft_plan_create refuses. */
+int gr_fft_describe(const gr_fft_options *options, gr_fft_pass *out, uint32_t capacity);
+int gr_fft_plan_create(gr_ctx *ctx, const gr_fft_options *options, gr_fft_plan **plan);
+void gr_fft_plan_destroy(gr_ctx *ctx, gr_fft_plan *plan);
+uint32_t gr_fft_plan_iterations(const gr_fft_plan *plan);
+int gr_fft_execute(gr_ctx *ctx, gr_stream stream, const gr_fft_plan *plan, const gr_fft_resource *dst, const gr_fft_resource *src);
+/* One pass of the plan; all of them in order are gr_fft_execute. */
+int gr_fft_execute_iteration(gr_ctx *ctx, gr_stream stream, const gr_fft_plan *plan, const gr_fft_resource *dst, const gr_fft_resource *src,
+                             uint32_t iteration);
 
 /* Fill with a 32-bit pattern (count dwords): attachment clears to a colour. */
 int gr_fill_u32(gr_ctx *ctx, gr_stream stream, void *dst, uint32_t value, size_t count);

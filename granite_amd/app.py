@@ -83,6 +83,20 @@ class FftRequest(C.Structure):
                 ("image_width", C.c_uint32), ("image_height", C.c_uint32), ("image_byte_offset", C.c_uint64), ("output_offset", C.c_int32 * 2)]
 
 
+class OceanConfig(C.Structure):
+    """gra_ocean_config."""
+    _fields_ = [("fft_resolution", C.c_uint32), ("displacement_downsample", C.c_uint32), ("grid_count", C.c_uint32), ("grid_resolution", C.c_uint32),
+                ("ocean_size", C.c_float * 2), ("wind_velocity", C.c_float * 2), ("normal_mod", C.c_float), ("amplitude", C.c_float),
+                ("heightmap", C.c_uint32), ("lod_bias", C.c_float), ("force_mipmap_shader", C.c_uint32), ("through_render_graph", C.c_uint32),
+                ("freq_band_modulation", C.c_uint32), ("frequency_bands", C.c_float * 8)]
+
+
+class OceanResourceInfo(C.Structure):
+    """gra_ocean_resource_info."""
+    _fields_ = [("exists", C.c_uint32), ("is_image", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("format", C.c_uint32),
+                ("levels", C.c_uint32), ("size_bytes", C.c_uint64)]
+
+
 class Timestamp(C.Structure):
     _fields_ = [("tag", C.c_char * 64), ("count", C.c_uint64), ("total_ms", C.c_double)]
 
@@ -97,6 +111,8 @@ EXPORTED_SYMBOLS = [
     "gra_comm_create_unique_id", "gra_comm_init", "gra_comm_info", "gra_comm_init_output", "gra_install_ssr_tables", "gra_reset_timestamps", "gra_set_directional_light", "gra_set_fog", "gra_generate_mipmaps", "gra_write_resource", "gra_get_frame_state", "gra_set_frame_state",
     "gra_video_begin", "gra_video_frame_layout", "gra_video_read_frame", "gra_video_end",
     "gra_video_play_begin", "gra_video_play_layout", "gra_video_play_frame", "gra_video_play_read_rgb", "gra_video_play_end",
+    "gra_ocean_default_config", "gra_ocean_create", "gra_ocean_update", "gra_ocean_describe", "gra_ocean_read", "gra_ocean_distribution",
+    "gra_ocean_parameters", "gra_ocean_destroy",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -176,6 +192,14 @@ def load_library() -> C.CDLL:
         "gra_video_play_frame": (C.c_int, [vp, vp, C.c_uint64]),
         "gra_video_play_read_rgb": (C.c_int, [vp, vp, C.c_uint64, P(C.c_int64)]),
         "gra_video_play_end": (C.c_int, [vp]),
+        "gra_ocean_default_config": (None, [P(OceanConfig)]),
+        "gra_ocean_create": (C.c_int, [vp, P(OceanConfig), P(vp)]),
+        "gra_ocean_update": (C.c_int, [vp, C.c_double]),
+        "gra_ocean_describe": (C.c_int, [vp, C.c_uint32, P(OceanResourceInfo)]),
+        "gra_ocean_read": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, C.c_uint64]),
+        "gra_ocean_distribution": (C.c_int, [vp, C.c_uint32, vp]),
+        "gra_ocean_parameters": (C.c_int, [vp, vp]),
+        "gra_ocean_destroy": (None, [vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)

@@ -174,6 +174,26 @@ class VideoYuvPlan(C.Structure):
                 ("matrix", C.c_uint32)]
 
 
+# gr_ocean_generate_fft variants
+OCEAN_VARIANT_HEIGHT, OCEAN_VARIANT_GRADIENT_NORMAL, OCEAN_VARIANT_GRADIENT_DISPLACEMENT = 0, 1, 2
+OCEAN_NUM_FREQ_BANDS = 8
+
+
+class PushOceanGenerate(C.Structure):
+    """gr_push_ocean_generate: generate_fft.comp's Registers."""
+    _fields_ = [("mod_factor", C.c_float * 2), ("N", C.c_uint32 * 2), ("freq_to_band_mod", C.c_float), ("time", C.c_float), ("period", C.c_float)]
+
+
+class PushOceanBake(C.Structure):
+    """gr_push_ocean_bake: bake_maps.comp's Registers."""
+    _fields_ = [("inv_size", C.c_float * 4), ("scale", C.c_float * 4)]
+
+
+class PushOceanMipmap(C.Structure):
+    """gr_push_ocean_mipmap: mipmap.comp's Registers."""
+    _fields_ = [("result_mod", C.c_float * 4), ("inv_resolution", C.c_float * 2), ("count", C.c_uint32 * 2), ("lod", C.c_float)]
+
+
 class TimingEntry(C.Structure):
     _fields_ = [("name", C.c_char_p), ("count", C.c_uint64), ("total_ms", C.c_double)]
 
@@ -466,6 +486,9 @@ def load_library() -> C.CDLL:
         "gr_fft_plan_iterations": (C.c_uint32, [vp]),
         "gr_fft_execute": (C.c_int, [vp, vp, vp, P(FftResource), P(FftResource)]),
         "gr_fft_execute_iteration": (C.c_int, [vp, vp, vp, P(FftResource), P(FftResource), C.c_uint32]),
+        "gr_ocean_generate_fft": (C.c_int, [vp, vp, vp, vp, P(PushOceanGenerate), C.c_uint32, P(C.c_float)]),
+        "gr_ocean_bake_maps": (C.c_int, [vp, vp, P(Image), P(Image), P(Image), P(Image), P(PushOceanBake)]),
+        "gr_ocean_mipmap": (C.c_int, [vp, vp, P(Image), P(Image), P(PushOceanMipmap)]),
         "gr_fsr_sharpen": (C.c_int, [vp, vp, P(Image), P(Image), C.c_float]),
         "gr_mip_chain_offset": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
         "gr_mip_chain_size": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
@@ -490,6 +513,7 @@ EXPORTED_SYMBOLS = [
     "gr_texture_decoded_format", "gr_texture_block_bytes", "gr_texture_decode",
     "gr_cube_chain_bytes", "gr_cube_chain_offset", "gr_env_equirect_to_cube", "gr_env_specular", "gr_env_diffuse",
     "gr_fft_describe", "gr_fft_plan_create", "gr_fft_plan_destroy", "gr_fft_plan_iterations", "gr_fft_execute", "gr_fft_execute_iteration",
+    "gr_ocean_generate_fft", "gr_ocean_bake_maps", "gr_ocean_mipmap",
 ]
 
 
@@ -846,6 +870,23 @@ class Context:
             self.check(self.lib.gr_fft_execute(self.handle, stream, plan, C.byref(dst), C.byref(src)))
         else:
             self.check(self.lib.gr_fft_execute_iteration(self.handle, stream, plan, C.byref(dst), C.byref(src), int(iteration)))
+
+    # ---- ocean: the FFT update's own dispatches -----------------------------------------------------------------------------------
+    def ocean_generate_fft(self, distribution, out, push: PushOceanGenerate, variant: int, freq_bands=None, stream=None):
+        """gr_ocean_generate_fft: distribution (N.x * N.y float2) -> out (N.x * N.y packed half2); both device pointers.  freq_bands: eight
+        amplitudes (FREQ_BAND_MODULATION) or None."""
+        bands = None if freq_bands is None else (C.c_float * OCEAN_NUM_FREQ_BANDS)(*[float(v) for v in freq_bands])
+        self.check(self.lib.gr_ocean_generate_fft(self.handle, stream, distribution, out, C.byref(push), int(variant), bands))
+
+    def ocean_bake_maps(self, height: DeviceImage, displacement: DeviceImage, grad_jacobian: DeviceImage, height_displacement: Optional[DeviceImage],
+                        push: PushOceanBake, stream=None):
+        """gr_ocean_bake_maps: R16F height + RG16F displacement -> RGBA16F gradient / Jacobian and (unless None) height / displacement."""
+        hd = None if height_displacement is None else height_displacement.desc
+        self.check(self.lib.gr_ocean_bake_maps(self.handle, stream, height.desc, displacement.desc, grad_jacobian.desc, hd, C.byref(push)))
+
+    def ocean_mipmap(self, src: DeviceImage, out: DeviceImage, push: PushOceanMipmap, stream=None):
+        """gr_ocean_mipmap: one LinearWrap tap per texel of `out` (push.count texels) from `src`, times push.result_mod."""
+        self.check(self.lib.gr_ocean_mipmap(self.handle, stream, src.desc, out.desc, C.byref(push)))
 
     def blit(self, src: DeviceImage, out: DeviceImage, linear: bool, stream=None):
         self.check(self.lib.gr_blit(self.handle, stream, src.desc, out.desc, int(linear)))

@@ -7,6 +7,7 @@
 #include "../texture_decoder.hpp"
 #include "../utils/image_utils.hpp"
 #include "../fft/fft.hpp"
+#include "../ocean.hpp"
 #include "../post/hdr.hpp"
 #include <cstdio>
 #include <cstring>
@@ -17,6 +18,16 @@ struct gra_app
 {
 	std::unique_ptr<ImageSpaceApplication> app;
 	std::string error;
+};
+
+// Declared before the graph so that the graph, whose pass callback points at the ocean, goes first.
+struct gra_ocean
+{
+	gra_app *app = nullptr;
+	std::unique_ptr<Ocean> ocean;
+	HIP::ImageHandle swapchain;
+	std::unique_ptr<RenderGraph> graph;
+	bool updated = false;
 };
 
 template <typename Fn>
@@ -34,6 +45,14 @@ static int guarded(gra_app *app, Fn &&fn)
 		app->error = e.what();
 		return -1;
 	}
+}
+
+template <typename Fn>
+static int ocean_guarded(gra_ocean *ocean, Fn &&fn)
+{
+	if (!ocean)
+		return -1;
+	return guarded(ocean->app, fn);
 }
 
 static void unpack_mat4(mat4 &m, const float *src)
@@ -253,6 +272,210 @@ int gra_environment_bake(gra_app *app, const char *equirect_gtx, float cube_scal
 		if (irradiance_path)
 			gtx_save(convert_cube_to_ibl_diffuse(ctx, nullptr, cube), irradiance_path);
 	});
+}
+
+void gra_ocean_default_config(gra_ocean_config *config)
+{
+	if (!config)
+		return;
+	const OceanConfig defaults;
+	*config = {};
+	config->fft_resolution = defaults.fft_resolution;
+	config->displacement_downsample = defaults.displacement_downsample;
+	config->grid_count = defaults.grid_count;
+	config->grid_resolution = defaults.grid_resolution;
+	config->ocean_size[0] = defaults.ocean_size.x;
+	config->ocean_size[1] = defaults.ocean_size.y;
+	config->wind_velocity[0] = defaults.wind_velocity.x;
+	config->wind_velocity[1] = defaults.wind_velocity.y;
+	config->normal_mod = defaults.normal_mod;
+	config->amplitude = defaults.amplitude;
+	config->heightmap = defaults.heightmap ? 1u : 0u;
+	config->lod_bias = defaults.lod_bias;
+	for (float &band : config->frequency_bands)
+		band = 1.0f;
+}
+
+int gra_ocean_create(gra_app *app, const gra_ocean_config *config, gra_ocean **ocean)
+{
+	return guarded(app, [&]() {
+		if (!config || !ocean)
+			throw std::logic_error("gra_ocean_create: null config or result");
+		*ocean = nullptr;
+		OceanConfig c;
+		c.fft_resolution = config->fft_resolution;
+		c.displacement_downsample = config->displacement_downsample;
+		c.grid_count = config->grid_count;
+		c.grid_resolution = config->grid_resolution;
+		c.ocean_size = vec2(config->ocean_size[0], config->ocean_size[1]);
+		c.wind_velocity = vec2(config->wind_velocity[0], config->wind_velocity[1]);
+		c.normal_mod = config->normal_mod;
+		c.amplitude = config->amplitude;
+		c.heightmap = config->heightmap != 0;
+		c.lod_bias = config->lod_bias;
+		auto handle = std::make_unique<gra_ocean>();
+		handle->app = app;
+		handle->ocean = std::make_unique<Ocean>(c, config->force_mipmap_shader != 0); // refuses before anything is allocated
+		auto &device = app->app->get_device();
+		if (!device.get_context())
+			throw std::logic_error("gra_ocean_create: the application has no device");
+		device.wait_idle();
+		handle->ocean->set_frequency_band_modulation(config->freq_band_modulation != 0);
+		for (unsigned i = 0; i < Ocean::FrequencyBands; i++)
+			handle->ocean->set_frequency_band_amplitude(i, config->frequency_bands[i]);
+		handle->ocean->on_device_created(device);
+		if (config->through_render_graph)
+		{
+			// A graph of the ocean's own: the update pass, and a pass that consumes everything it writes and produces the backbuffer,
+			// so that nothing of the update is culled or aliased before it is read back.
+			const unsigned n = c.fft_resolution;
+			handle->graph = std::make_unique<RenderGraph>();
+			auto &graph = *handle->graph;
+			graph.set_device(&device);
+			ResourceDimensions dim;
+			dim.width = n;
+			dim.height = n;
+			dim.format = VK_FORMAT_R16G16B16A16_SFLOAT;
+			graph.set_backbuffer_dimensions(dim);
+			handle->ocean->add_fft_update_pass(graph);
+			auto &present = graph.add_pass("ocean-present", RENDER_GRAPH_QUEUE_COMPUTE_BIT);
+			for (unsigned i = 0; i < Ocean::ResourceCount; i++)
+			{
+				if (i <= GRA_OCEAN_DISPLACEMENT_FFT_INPUT || i == GRA_OCEAN_SPD_COUNTER)
+					present.add_storage_read_only_input(Ocean::ResourceNames[i]);
+				else if (i != GRA_OCEAN_HEIGHT_DISPLACEMENT_OUTPUT || c.heightmap)
+					present.add_texture_input(Ocean::ResourceNames[i]);
+			}
+			AttachmentInfo out;
+			out.size_class = SizeClass::Absolute;
+			out.size_x = out.size_y = float(n);
+			out.format = VK_FORMAT_R16G16B16A16_SFLOAT;
+			auto *target = &present.add_storage_texture_output("ocean-present-output", out);
+			RenderGraph *g = handle->graph.get();
+			present.set_build_render_pass([g, target](HIP::CommandBuffer &cmd) { cmd.clear_image(g->get_physical_texture_resource(*target)); });
+			graph.set_backbuffer_source("ocean-present-output");
+			graph.bake();
+			handle->swapchain = device.create_image(n, n, VK_FORMAT_R16G16B16A16_SFLOAT, "ocean-present-swapchain");
+		}
+		else
+			handle->ocean->create_resources(device);
+		*ocean = handle.release();
+	});
+}
+
+int gra_ocean_update(gra_ocean *ocean, double elapsed_time)
+{
+	return ocean_guarded(ocean, [&]() {
+		auto &device = ocean->app->app->get_device();
+		ocean->ocean->set_elapsed_time(elapsed_time);
+		if (ocean->graph)
+		{
+			TaskComposer composer;
+			ocean->graph->setup_attachments(device, ocean->swapchain.get());
+			ocean->graph->enqueue_render_passes(device, composer);
+		}
+		else
+		{
+			HIP::CommandBuffer cmd(device, device.get_stream(HIP::CommandBuffer::Type::Generic), HIP::CommandBuffer::Type::Generic);
+			ocean->ocean->update_fft_pass(cmd);
+		}
+		device.wait_idle();
+		ocean->updated = true;
+	});
+}
+
+int gra_ocean_describe(gra_ocean *ocean, uint32_t which, gra_ocean_resource_info *info)
+{
+	return ocean_guarded(ocean, [&]() {
+		if (!info || which >= Ocean::ResourceCount)
+			throw std::logic_error("gra_ocean_describe: null info or unknown resource");
+		if (ocean->graph && !ocean->updated)
+			throw std::logic_error("gra_ocean_describe: a graph's resources exist after the first update");
+		*info = {};
+		if (HIP::Buffer *buffer = ocean->ocean->get_buffer(which))
+		{
+			info->exists = 1;
+			info->size_bytes = buffer->get_size();
+		}
+		else if (HIP::Image *image = ocean->ocean->get_image(which))
+		{
+			info->exists = info->is_image = 1;
+			info->width = image->get_width();
+			info->height = image->get_height();
+			info->format = uint32_t(image->get_format());
+			info->levels = ocean->ocean->get_levels(which);
+			const gr_image view = image->get_level_view(0);
+			info->size_bytes = uint64_t(view.pitch_bytes) * view.height;
+		}
+	});
+}
+
+int gra_ocean_read(gra_ocean *ocean, uint32_t which, uint32_t level, void *out, uint64_t size)
+{
+	return ocean_guarded(ocean, [&]() {
+		if (!out || which >= Ocean::ResourceCount)
+			throw std::logic_error("gra_ocean_read: null output or unknown resource");
+		if (!ocean->updated)
+			throw std::logic_error("gra_ocean_read: nothing has been computed yet");
+		auto &device = ocean->app->app->get_device();
+		gr_ctx *ctx = device.get_context();
+		const void *src = nullptr;
+		uint64_t bytes = 0;
+		if (HIP::Buffer *buffer = ocean->ocean->get_buffer(which))
+		{
+			if (level != 0)
+				throw std::logic_error("gra_ocean_read: a buffer has one level");
+			src = buffer->get_device_pointer();
+			bytes = buffer->get_size();
+		}
+		else if (HIP::Image *image = ocean->ocean->get_image(which))
+		{
+			if (level >= ocean->ocean->get_levels(which))
+				throw std::logic_error("gra_ocean_read: the resource has no such level");
+			const gr_image view = image->get_level_view(level);
+			src = view.ptr;
+			bytes = uint64_t(view.pitch_bytes) * view.height;
+		}
+		else
+			throw std::logic_error(std::string("gra_ocean_read: ") + Ocean::ResourceNames[which] + " does not exist");
+		if (size != bytes)
+			throw std::logic_error("gra_ocean_read: size is not that of the level");
+		if (gr_download(ctx, nullptr, out, src, size_t(bytes)) < 0 || gr_sync(ctx, nullptr) < 0)
+			throw std::runtime_error(gr_last_error(ctx));
+	});
+}
+
+int gra_ocean_distribution(gra_ocean *ocean, uint32_t which, void *out)
+{
+	return ocean_guarded(ocean, [&]() {
+		auto &d = ocean->ocean->get_distributions();
+		const std::vector<vec2> *source = which == GRA_OCEAN_DISTRIBUTION_HEIGHT         ? &d.height
+		                                  : which == GRA_OCEAN_DISTRIBUTION_DISPLACEMENT ? &d.displacement
+		                                  : which == GRA_OCEAN_DISTRIBUTION_NORMAL       ? &d.normal
+		                                                                                 : nullptr;
+		if (!out || !source)
+			throw std::logic_error("gra_ocean_distribution: null output or unknown distribution");
+		memcpy(out, source->data(), source->size() * sizeof(vec2));
+	});
+}
+
+int gra_ocean_parameters(gra_ocean *ocean, float *out8)
+{
+	return ocean_guarded(ocean, [&]() {
+		if (!out8)
+			throw std::logic_error("gra_ocean_parameters: null output");
+		const vec2 world = ocean->ocean->heightmap_world_size(), normal = ocean->ocean->normalmap_world_size(), wind = ocean->ocean->get_wind_direction();
+		const float values[8] = {world.x, world.y, normal.x, normal.y, wind.x, wind.y, ocean->ocean->get_phillips_L(), ocean->ocean->get_config().amplitude};
+		memcpy(out8, values, sizeof(values));
+	});
+}
+
+void gra_ocean_destroy(gra_ocean *ocean)
+{
+	if (!ocean)
+		return;
+	ocean->app->app->get_device().wait_idle();
+	delete ocean;
 }
 
 int gra_fft_transform(gra_app *app, const gra_fft_request *request)

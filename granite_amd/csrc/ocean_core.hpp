@@ -1,0 +1,206 @@
+// Follows MIT-licensed work (Granite, (c) 2017-2026 Hans-Kristian Arntzen): see THIRD_PARTY_NOTICES.md at the repository root.
+// The ocean's FFT update, the per-lane arithmetic: ocean/generate_fft.comp, ocean/bake_maps.comp and ocean/mipmap.comp.  Shared by the
+// gfx950 kernels (ocean.hip) and by a host build the CPU tests hold to the executed shaders (tests/cpp/ocean_core_host.cpp): the
+// kernels add the mapping of bins and texels to lanes, nothing else.  Both builds compile this header with -ffp-contract=off and with
+// correctly rounded fp32 sqrt and division: generate_bin quantises an angular velocity with round(), and a last-bit difference in
+// x * x + y * y, the square root, the product with period or the division flips it, which moves a bin's phase by time / period radians.
+//
+// LinearWrap sampling model (the reference leaves it to the Vulkan implementation):
+//   - per axis linear_axis(u * size - 0.5): exact fp32 weights, a coordinate within 2^-8 of a texel centre reads that texel alone;
+//   - the four texels are joined as linear_combine joins them: two lerps along x, t * (1 - a) + t' * a, then one along y; a weight
+//     of exactly 0 does not read its texel;
+//   - texel indices, textureLodOffset's offset included, are taken modulo the size (Euclidean: -1 is size - 1).
+// fp16 conversion, linear_axis and the Euclidean modulo are env_core.hpp's (the project's one host + device statement of them).
+#pragma once
+#include "env_core.hpp"
+
+#if defined(__HIPCC__)
+#define OCEAN_HD __host__ __device__ __forceinline__
+#else
+#define OCEAN_HD inline
+#endif
+
+namespace gr_ocean
+{
+using gr_env::half_to_float;
+using gr_env::linear_axis;
+using gr_env::wrapi;
+
+constexpr uint32_t NUM_FREQ_BANDS = 8u;
+constexpr float GRAVITY = 9.81f;
+constexpr float LAMBDA = 1.2f;
+enum Variant : uint32_t { HEIGHT = 0, GRADIENT_NORMAL = 1, GRADIENT_DISPLACEMENT = 2, VARIANT_COUNT = 3 };
+
+// The fp16 store conversion of a value that is an fp32 result first, as the shaders' are.  On the device the value is pinned in a
+// register before it is converted: otherwise the compiler fuses a multiply and the conversion behind it into one mixed-precision
+// instruction that rounds the exact product once, to fp16, and a store differs from the shader's in its last bit now and then.
+OCEAN_HD uint32_t float_to_half(float f)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+	asm("" : "+v"(f));
+#endif
+	return gr_env::float_to_half(f);
+}
+
+struct c2
+{
+	float x, y;
+};
+// cmul of generate_fft.comp: (a.x b.x - b.y a.y, a.y b.x + b.y a.x), each product rounded before the sum
+OCEAN_HD c2 cmul(c2 a, c2 b) { return {a.x * b.x - b.y * a.y, a.y * b.x + b.y * a.x}; }
+
+struct GenerateArgs
+{
+	float mod_x, mod_y;
+	uint32_t nx, ny;
+	float freq_to_band_mod, time, period;
+	uint32_t variant;
+	uint32_t use_bands;
+	float bands[NUM_FREQ_BANDS];
+};
+
+// i > N / 2 goes negative (the Nyquist bin itself stays positive)
+OCEAN_HD float alias(uint32_t i, uint32_t n)
+{
+	const float f = float(i);
+	return f > 0.5f * float(n) ? f - float(n) : f;
+}
+
+OCEAN_HD float band_amplitude(const GenerateArgs &g, float fx, float fy)
+{
+	const float bx = fx * g.freq_to_band_mod, by = fy * g.freq_to_band_mod;
+	float band = bx > by ? bx : by;
+	const float top = float(NUM_FREQ_BANDS) - 1.001f;
+	band = band > 0.0f ? (band > top ? top : band) : 0.0f; // a NaN lands on 0, so the index below stays inside bands[]
+	const int low = int(band);
+	const float t = band - floorf(band);
+	return g.bands[low] * (1.0f - t) + g.bands[low + 1] * t;
+}
+
+// Bin (x, y) of the animated spectrum; `a` is the distribution at the bin, `b` at its mirror ((N - i) & (N - 1)).  sincosf is the
+// full-range one: w reaches thousands of radians.
+OCEAN_HD uint32_t generate_bin(const GenerateArgs &g, uint32_t x, uint32_t y, c2 a, c2 b)
+{
+	const float fx = alias(x, g.nx), fy = alias(y, g.ny);
+	const float kx = g.mod_x * fx, ky = g.mod_y * fy;
+	const float k_len = sqrtf(kx * kx + ky * ky);
+	float angular_velocity = sqrtf(GRAVITY * k_len);
+	angular_velocity = roundf(angular_velocity * g.period) / g.period;
+	const float w = angular_velocity * g.time;
+	float sw, cw;
+	sincosf(w, &sw, &cw);
+	const c2 rot = {cw, sw};
+	a = cmul(a, rot);
+	b = cmul(b, rot);
+	c2 res = {a.x + b.x, a.y + -b.y};
+	if (g.variant == GRADIENT_NORMAL)
+		res = cmul(res, {-ky, kx});
+	else if (g.variant == GRADIENT_DISPLACEMENT)
+		res = cmul(res, {-ky / (k_len + 0.00001f), kx / (k_len + 0.00001f)});
+	if (g.use_bands)
+	{
+		const float amplitude = band_amplitude(g, fx, fy);
+		res.x *= amplitude;
+		res.y *= amplitude;
+	}
+	return float_to_half(res.x) | (float_to_half(res.y) << 16);
+}
+
+// ---- LinearWrap over a linear image of C fp16 channels a texel ---------------------------------------------------------------
+struct Texture
+{
+	const uint8_t *ptr;
+	int w, h;
+	uint32_t pitch;
+};
+template <int C> struct Texel
+{
+	float v[C];
+};
+template <int C> OCEAN_HD Texel<C> fetch_wrap(const Texture &t, int x, int y)
+{
+	const uint16_t *p = reinterpret_cast<const uint16_t *>(t.ptr + size_t(wrapi(y, t.h)) * t.pitch) + size_t(wrapi(x, t.w)) * C;
+	Texel<C> r;
+	for (int c = 0; c < C; c++)
+		r.v[c] = half_to_float(p[c]);
+	return r;
+}
+template <int C> OCEAN_HD Texel<C> lerp(const Texel<C> &lo, const Texel<C> &hi, float t)
+{
+	Texel<C> r;
+	for (int c = 0; c < C; c++)
+		r.v[c] = lo.v[c] * (1.0f - t) + hi.v[c] * t;
+	return r;
+}
+// textureLodOffset(sampler, (u, v), 0, (ox, oy))
+template <int C> OCEAN_HD Texel<C> sample_wrap(const Texture &t, float u, float v, int ox, int oy)
+{
+	int x0, y0;
+	float a, b;
+	linear_axis(u * float(t.w) - 0.5f, x0, a);
+	linear_axis(v * float(t.h) - 0.5f, y0, b);
+	x0 += ox;
+	y0 += oy;
+	const Texel<C> top = a == 0.0f ? fetch_wrap<C>(t, x0, y0) : lerp(fetch_wrap<C>(t, x0, y0), fetch_wrap<C>(t, x0 + 1, y0), a);
+	if (b == 0.0f)
+		return top;
+	const Texel<C> bottom = a == 0.0f ? fetch_wrap<C>(t, x0, y0 + 1) : lerp(fetch_wrap<C>(t, x0, y0 + 1), fetch_wrap<C>(t, x0 + 1, y0 + 1), a);
+	return lerp(top, bottom, b);
+}
+
+struct uint2_bits
+{
+	uint32_t x, y;
+};
+OCEAN_HD uint2_bits pack4(float x, float y, float z, float w)
+{
+	return {float_to_half(x) | (float_to_half(y) << 16), float_to_half(z) | (float_to_half(w) << 16)};
+}
+
+// ---- bake_maps.comp ------------------------------------------------------------------------------------------------------------
+struct BakeArgs
+{
+	Texture height, displacement; // R16F, RG16F
+	float inv_size[4], scale[4];
+};
+// Texel (x, y): what the shader stores to iHeightDisplacement and to iGradJacobian.  Both coordinate pairs advance by inv_size.xy; the
+// displacement pair only starts at half a displacement texel, as the shader has it.
+OCEAN_HD void bake_texel(const BakeArgs &a, uint32_t x, uint32_t y, uint2_bits &height_displacement, uint2_bits &grad_jacobian)
+{
+	const float px = float(x) * a.inv_size[0], py = float(y) * a.inv_size[1];
+	const float u = px + 0.5f * a.inv_size[0], v = py + 0.5f * a.inv_size[1];
+	const float du = px + 0.5f * a.inv_size[2], dv = py + 0.5f * a.inv_size[3];
+
+	const float h = sample_wrap<1>(a.height, u, v, 0, 0).v[0];
+	const float x0 = sample_wrap<1>(a.height, u, v, -1, 0).v[0], x1 = sample_wrap<1>(a.height, u, v, 1, 0).v[0];
+	const float y0 = sample_wrap<1>(a.height, u, v, 0, -1).v[0], y1 = sample_wrap<1>(a.height, u, v, 0, 1).v[0];
+	const float grad_x = (a.scale[0] * 0.5f) * (x1 - x0), grad_y = (a.scale[1] * 0.5f) * (y1 - y0);
+
+	const Texel<2> d = sample_wrap<2>(a.displacement, du, dv, 0, 0);
+	const Texel<2> dxp = sample_wrap<2>(a.displacement, du, dv, 1, 0), dxm = sample_wrap<2>(a.displacement, du, dv, -1, 0);
+	const Texel<2> dyp = sample_wrap<2>(a.displacement, du, dv, 0, 1), dym = sample_wrap<2>(a.displacement, du, dv, 0, -1);
+	const float half_lambda = 0.5f * LAMBDA;
+	const float ddx_x = (half_lambda * (dxp.v[0] - dxm.v[0])) * a.scale[2], ddx_y = (half_lambda * (dxp.v[1] - dxm.v[1])) * a.scale[2];
+	const float ddy_x = (half_lambda * (dyp.v[0] - dym.v[0])) * a.scale[3], ddy_y = (half_lambda * (dyp.v[1] - dym.v[1])) * a.scale[3];
+	const float j = (1.0f + ddx_x) * (1.0f + ddy_y) - ddx_y * ddy_x;
+
+	height_displacement = pack4(h, LAMBDA * d.v[0], LAMBDA * d.v[1], 0.0f);
+	grad_jacobian = pack4(grad_x, grad_y, j, 0.0f);
+}
+
+// ---- mipmap.comp ---------------------------------------------------------------------------------------------------------------
+struct MipmapArgs
+{
+	Texture in;
+	float result_mod[4], inv_resolution[2];
+	uint32_t count_x, count_y;
+};
+// Texel (x, y) of the output, C channels: one LinearWrap tap at (2 gid + 1) * inv_resolution, times result_mod.
+template <int C> OCEAN_HD void mipmap_texel(const MipmapArgs &a, uint32_t x, uint32_t y, uint16_t *out)
+{
+	const float u = (2.0f * float(x) + 1.0f) * a.inv_resolution[0], v = (2.0f * float(y) + 1.0f) * a.inv_resolution[1];
+	const Texel<C> t = sample_wrap<C>(a.in, u, v, 0, 0);
+	for (int c = 0; c < C; c++)
+		out[c] = uint16_t(float_to_half(a.result_mod[c] * t.v[c]));
+}
+} // namespace gr_ocean

@@ -202,6 +202,57 @@ typedef struct gra_fft_request
 	int32_t output_offset[2];
 } gra_fft_request;
 int gra_fft_transform(gra_app *app, const gra_fft_request *request);
+/* ---- the ocean's FFT update (Granite::Ocean, host/ocean.hpp) -------------------------------------------------------------------
+ * gra_ocean_create derives the constructor's values, generates the three Phillips distributions and uploads them, plans the three
+ * FFTs and allocates the pass's nine resources; it fails (gra_last_error) for an fft_resolution that is no power of two, for
+ * fft_resolution >> displacement_downsample below 64, for a zero grid_count or grid_resolution and for a zero wind velocity, before
+ * anything is allocated.  With through_render_graph the pass is added to a render graph of the ocean's own (add_fft_update_pass),
+ * baked and executed by the graph; otherwise update_fft_pass runs directly on the generic stream.  Either way gra_ocean_update
+ * returns after the pass has completed.  time = fmod(elapsed_time, 256), period = 256 / (2 pi), both narrowed to float. */
+#define GRA_OCEAN_HEIGHT_FFT_INPUT 0u
+#define GRA_OCEAN_NORMAL_FFT_INPUT 1u
+#define GRA_OCEAN_DISPLACEMENT_FFT_INPUT 2u
+#define GRA_OCEAN_HEIGHT_FFT_OUTPUT 3u
+#define GRA_OCEAN_DISPLACEMENT_FFT_OUTPUT 4u
+#define GRA_OCEAN_NORMAL_FFT_OUTPUT 5u
+#define GRA_OCEAN_SPD_COUNTER 6u
+#define GRA_OCEAN_GRADIENT_JACOBIAN_OUTPUT 7u
+#define GRA_OCEAN_HEIGHT_DISPLACEMENT_OUTPUT 8u
+#define GRA_OCEAN_RESOURCE_COUNT 9u
+#define GRA_OCEAN_DISTRIBUTION_HEIGHT 0u
+#define GRA_OCEAN_DISTRIBUTION_DISPLACEMENT 1u
+#define GRA_OCEAN_DISTRIBUTION_NORMAL 2u
+typedef struct gra_ocean_config /* OceanConfig, renderer/ocean.hpp:40-75, and two switches of this executor */
+{
+	uint32_t fft_resolution, displacement_downsample, grid_count, grid_resolution;
+	float ocean_size[2], wind_velocity[2];
+	float normal_mod, amplitude;
+	uint32_t heightmap;
+	float lod_bias;
+	uint32_t force_mipmap_shader;  /* every mip chain level by level through gr_ocean_mipmap */
+	uint32_t through_render_graph; /* run the pass inside a RenderGraph */
+	uint32_t freq_band_modulation;
+	float frequency_bands[8];
+} gra_ocean_config;
+typedef struct gra_ocean gra_ocean;
+typedef struct gra_ocean_resource_info
+{
+	uint32_t exists, is_image, width, height, format, levels;
+	uint64_t size_bytes; /* of a buffer, or of level 0 of an image */
+} gra_ocean_resource_info;
+void gra_ocean_default_config(gra_ocean_config *config);
+int gra_ocean_create(gra_app *app, const gra_ocean_config *config, gra_ocean **ocean);
+int gra_ocean_update(gra_ocean *ocean, double elapsed_time);
+int gra_ocean_describe(gra_ocean *ocean, uint32_t which, gra_ocean_resource_info *info);
+/* Level `level` of resource `which` (0 for a buffer), tightly packed, `size` bytes exactly.  Fails for a resource or level that does
+ * not exist (ocean-height-displacement-output without a heightmap) and for a size that is not the level's. */
+int gra_ocean_read(gra_ocean *ocean, uint32_t which, uint32_t level, void *out, uint64_t size);
+/* The host's copy of a distribution: N * N float2, N = fft_resolution (>> displacement_downsample for the displacement one). */
+int gra_ocean_distribution(gra_ocean *ocean, uint32_t which, void *out);
+/* Heightmap and normal map world sizes, wind direction, Phillips L and the normalised amplitude: 8 floats. */
+int gra_ocean_parameters(gra_ocean *ocean, float *out8);
+void gra_ocean_destroy(gra_ocean *ocean);
+
 /* Writes a graph texture (all its mip levels) or, with name == NULL, the last rendered backbuffer as .gtx. */
 int gra_save_resource_gtx(gra_app *app, const char *name, const char *path);
 

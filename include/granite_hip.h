@@ -937,6 +937,50 @@ int gr_fft_execute(gr_ctx *ctx, gr_stream stream, const gr_fft_plan *plan, const
 int gr_fft_execute_iteration(gr_ctx *ctx, gr_stream stream, const gr_fft_plan *plan, const gr_fft_resource *dst, const gr_fft_resource *src,
                              uint32_t iteration);
 
+/* ---- ocean: the FFT update (renderer/ocean.cpp Ocean::update_fft_pass, assets/shaders/ocean/{generate_fft,bake_maps,mipmap}.comp) ----
+ * The three dispatches of the pass that are neither an FFT nor the single-pass downsampler.  Push blocks are byte-identical to the
+ * shaders'.  Images are linear fp16 images (gr_image) of the stated format, any pitch that covers a row; sampling is LinearWrap by the
+ * model of DESIGN.md 7.10.  Everything refused is refused with GR_ERR_INVALID_ARGUMENT before anything is launched. */
+#define GR_OCEAN_VARIANT_HEIGHT 0u
+#define GR_OCEAN_VARIANT_GRADIENT_NORMAL 1u
+#define GR_OCEAN_VARIANT_GRADIENT_DISPLACEMENT 2u
+#define GR_OCEAN_NUM_FREQ_BANDS 8u
+typedef struct gr_push_ocean_generate /* generate_fft.comp Registers, ocean.cpp:421-428 */
+{
+	float mod_factor[2]; /* 2 pi / world size */
+	uint32_t N[2];
+	float freq_to_band_mod;
+	float time;
+	float period;
+} gr_push_ocean_generate;
+typedef struct gr_push_ocean_bake /* bake_maps.comp Registers, ocean.cpp:519-523 */
+{
+	float inv_size[4]; /* 1 / height map size, 1 / displacement map size */
+	float scale[4];    /* 1 / sample distance of the height map (xy) and of the displacement map (zw) */
+} gr_push_ocean_bake;
+typedef struct gr_push_ocean_mipmap /* mipmap.comp Registers, ocean.cpp:553-559 */
+{
+	float result_mod[4];
+	float inv_resolution[2]; /* 1 / size of `in` */
+	uint32_t count[2];       /* size of `out` */
+	float lod;               /* accepted and unused: `in` is a single-level view */
+} gr_push_ocean_mipmap;
+/* One bin per lane: distribution N.x * N.y float2 (device), out N.x * N.y packed half2 (device), rows of N.x.  out[i] = (h0(i) e^{iwt} +
+ * conj(h0(-i) e^{iwt})) times the variant's gradient factor and the band amplitude, w = round(sqrt(9.81 |k|) period) / period.
+ * freq_bands: GR_OCEAN_NUM_FREQ_BANDS floats in host memory (FREQ_BAND_MODULATION), or NULL.  Refused: null pointers, N.x or N.y not a
+ * power of two, N.x < 64, N.x * N.y >= 2^31, period <= 0, an unknown variant, a distribution not 8-byte or an out not 4-byte aligned.
+ * All three entry points refuse an output that shares bytes with an input or with the other output: lanes would read what other lanes
+ * of the same launch have written.  A NaN freq_to_band_mod selects band 0. */
+int gr_ocean_generate_fft(gr_ctx *ctx, gr_stream stream, const void *distribution, void *out, const gr_push_ocean_generate *push,
+                          uint32_t variant, const float *freq_bands);
+/* height R16_SFLOAT, displacement R16G16_SFLOAT (any power-of-two size), grad_jacobian R16G16B16A16_SFLOAT of height's size =
+ * (gradient.xy, jacobian, 0); height_displacement the same or NULL (VERTEX_TEXTURE = 0) = (height, 1.2 displacement.xy, 0). */
+int gr_ocean_bake_maps(gr_ctx *ctx, gr_stream stream, const gr_image *height, const gr_image *displacement, const gr_image *grad_jacobian,
+                       const gr_image *height_displacement, const gr_push_ocean_bake *push);
+/* in and out of one format, R16_SFLOAT / R16G16_SFLOAT / R16G16B16A16_SFLOAT; out is push->count texels: one tap at
+ * (2 gid + 1) * inv_resolution, times result_mod. */
+int gr_ocean_mipmap(gr_ctx *ctx, gr_stream stream, const gr_image *in, const gr_image *out, const gr_push_ocean_mipmap *push);
+
 /* Fill with a 32-bit pattern (count dwords): attachment clears to a colour. */
 int gr_fill_u32(gr_ctx *ctx, gr_stream stream, void *dst, uint32_t value, size_t count);
 /* Executor self-test operation (no counterpart in the reference): out[i] = hash(i, salt, one dword of each of up to four
@@ -1030,6 +1074,17 @@ GR_ASSERT_OFFSET(gr_push_yuv_to_rgb, inv_resolution, 136);
 GR_ASSERT_OFFSET(gr_push_yuv_to_rgb, chroma_siting, 144);
 GR_ASSERT_OFFSET(gr_push_yuv_to_rgb, chroma_clamp, 152);
 GR_ASSERT_OFFSET(gr_push_yuv_to_rgb, unorm_rescale, 160);
+GR_ASSERT_SIZE(gr_push_ocean_generate, 28);   /* generate_fft.comp:23-30, ocean.cpp:421-428 */
+GR_ASSERT_OFFSET(gr_push_ocean_generate, N, 8);
+GR_ASSERT_OFFSET(gr_push_ocean_generate, freq_to_band_mod, 16);
+GR_ASSERT_OFFSET(gr_push_ocean_generate, time, 20);
+GR_ASSERT_OFFSET(gr_push_ocean_generate, period, 24);
+GR_ASSERT_SIZE(gr_push_ocean_bake, 32);       /* bake_maps.comp:4-8, ocean.cpp:519-523 */
+GR_ASSERT_OFFSET(gr_push_ocean_bake, scale, 16);
+GR_ASSERT_SIZE(gr_push_ocean_mipmap, 36);     /* mipmap.comp:17-23, ocean.cpp:553-559 */
+GR_ASSERT_OFFSET(gr_push_ocean_mipmap, inv_resolution, 16);
+GR_ASSERT_OFFSET(gr_push_ocean_mipmap, count, 24);
+GR_ASSERT_OFFSET(gr_push_ocean_mipmap, lod, 32);
 GR_STATIC_ASSERT(GR_TRANSFORMS_OFFSET_SHADOW == GR_MAX_LIGHTS_BINDLESS * 48u, "ClustererBindlessTransforms: lights[4096] of 48 B");
 GR_STATIC_ASSERT(GR_TRANSFORMS_OFFSET_MODEL + GR_MAX_LIGHTS_BINDLESS * 48u == GR_TRANSFORMS_OFFSET_TYPE_MASK, "ClustererBindlessTransforms: model[4096] of 48 B");
 GR_STATIC_ASSERT(GR_TRANSFORMS_OFFSET_TYPE_MASK + GR_MAX_LIGHTS_BINDLESS / 8u == GR_TRANSFORMS_OFFSET_DECALS, "ClustererBindlessTransforms: type_mask[128]");

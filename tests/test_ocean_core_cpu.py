@@ -1,0 +1,66 @@
+"""CPU: granite_amd/csrc/ocean_core.hpp built for the host (tests/cpp/ocean_core_host.cpp, -ffp-contract=off) and held to the reference's
+ocean shaders executed on the CPU (tests/golden/ocean_shader_v1.npz): generate within ocean_ref.GENERATE_BOUND_UNITS of the float64
+reference (a tolerance: sin / cos differ between math libraries), bake_maps and mipmap bit for bit.  The same cases run on the device in
+tests/test_gpu_ocean.py."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import ocean_ref as ocr
+from ocean_cases import BAKE, GENERATE, GOLDEN, MIPMAP, generate_inputs, hermitian_defect
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def ptr(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+@pytest.fixture(scope="module")
+def host(tmp_path_factory):
+    lib = tmp_path_factory.mktemp("ocean_core") / "libocean_core_host.so"
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-ffp-contract=off", "-shared", "-fPIC", "-o", str(lib),
+                           os.path.join(ROOT, "tests", "cpp", "ocean_core_host.cpp")])
+    return C.CDLL(str(lib))
+
+
+@pytest.mark.parametrize("name", GENERATE)
+def test_generate(host, name):
+    d, push, variant, bands = generate_inputs(name)
+    ny, nx = d.shape[:2]
+    out = np.full(ny * nx + 64, 0xdeadbeef, np.uint32)
+    host.ocean_host_generate(ptr(d), ptr(out), ptr(push), variant, ptr(bands))
+    assert np.all(out[ny * nx:] == 0xdeadbeef)
+    out = out[:ny * nx].reshape(ny, nx)
+    spectrum, s = ocr.generate(d, push, variant, bands)
+    distance = ocr.generate_distance(out, spectrum, s)
+    print(f"{name}: host build {distance:.3f} units")
+    assert distance <= ocr.GENERATE_BOUND_UNITS
+    # with band modulation the amplitude follows max(F.x, F.y) of the aliased frequency, which the mirror does not share
+    if variant == ocr.HEIGHT and bands is None and push.view(np.float32)[5] == 0.0:
+        assert hermitian_defect(out) == 0
+
+
+@pytest.mark.parametrize("name", BAKE)
+def test_bake_maps(host, name):
+    size, vertex = (int(v) for v in GOLDEN[name + "/spec"])
+    height, disp, push = np.ascontiguousarray(GOLDEN["bake/height"]), np.ascontiguousarray(GOLDEN[f"bake/displacement{size}"]), GOLDEN[name + "/push"]
+    gj, hd = np.zeros((64, 64, 4), np.uint16), np.zeros((64, 64, 4), np.uint16)
+    host.ocean_host_bake(ptr(height), 64, 64, ptr(disp), size, size, ptr(push), ptr(gj), ptr(hd) if vertex else None)
+    assert np.array_equal(gj, GOLDEN[name + "/grad_jacobian"])
+    if vertex:
+        assert np.array_equal(hd, GOLDEN[name + "/height_displacement"])
+    else:
+        assert not hd.any()
+
+
+@pytest.mark.parametrize("name", MIPMAP)
+def test_mipmap(host, name):
+    w, h, channels = (int(v) for v in GOLDEN[name + "/spec"])
+    src, push = np.ascontiguousarray(GOLDEN[f"mipmap/in_{w}x{h}_c{channels}"]), GOLDEN[name + "/push"]
+    out = np.zeros_like(GOLDEN[name + "/out"])
+    assert host.ocean_host_mipmap(ptr(src), w, h, channels, ptr(push), ptr(out)) == 0
+    assert np.array_equal(out, GOLDEN[name + "/out"])

@@ -491,11 +491,6 @@ __global__ __launch_bounds__(AA_BLOCK_X *AA_BLOCK_Y) void k_blit(BlitArgs a)
 	}
 }
 
-static bool check_image(const gr_image *img, uint32_t bpp, uint32_t w, uint32_t h)
-{
-	return img && img->ptr && img->width == w && img->height == h && img->pitch_bytes >= w * bpp;
-}
-static bool is_rgba8(uint32_t f) { return f == GR_FORMAT_R8G8B8A8_SRGB || f == GR_FORMAT_R8G8B8A8_UNORM; }
 static dim3 aa_grid(uint32_t w, uint32_t h) { return dim3(gr_div_up(w, AA_BLOCK_X), gr_div_up(h, AA_BLOCK_Y)); }
 static dim3 fast_grid(uint32_t w, uint32_t h) { return dim3(gr_div_up(w, FAST_BW), gr_div_up(h, FAST_BH)); }
 } // namespace
@@ -531,9 +526,10 @@ int gr_fxaa_rows(gr_ctx *ctx, gr_stream stream, const gr_image *in, const gr_ima
 {
 	if (!ctx)
 		return GR_ERR_INVALID_ARGUMENT;
-	GR_CHECK_ARG(ctx, push && in && out && in->width && in->height);
-	GR_CHECK_ARG(ctx, check_image(in, 4, in->width, in->height) && check_image(out, 4, in->width, in->height));
-	GR_CHECK_ARG(ctx, is_rgba8(in->format) && is_rgba8(out->format) && in->ptr != out->ptr);
+	GR_CHECK_ARG(ctx, push);
+	GR_CHECK_IMAGE(ctx, in, GR_RGBA8_FORMATS);
+	GR_CHECK_IMAGE(ctx, out, GR_RGBA8_FORMATS, in->width, in->height);
+	GR_CHECK_ARG(ctx, !gr_images_overlap(in, out));
 	const RowSpan span = resolve_rows(rows, in->height);
 	if (span.count() == 0)
 		return GR_OK;
@@ -597,10 +593,10 @@ int gr_smaa_edge_detection_rows(gr_ctx *ctx, gr_stream stream, const gr_image *c
 {
 	if (!ctx)
 		return GR_ERR_INVALID_ARGUMENT;
-	GR_CHECK_ARG(ctx, push && color && edges && color->width && color->height);
+	GR_CHECK_ARG(ctx, push);
 	GR_CHECK_ARG(ctx, quality >= 0 && quality <= 3);
-	GR_CHECK_ARG(ctx, check_image(color, 4, color->width, color->height) && is_rgba8(color->format));
-	GR_CHECK_ARG(ctx, check_image(edges, 2, color->width, color->height) && edges->format == GR_FORMAT_R8G8_UNORM);
+	GR_CHECK_IMAGE(ctx, color, GR_RGBA8_FORMATS);
+	GR_CHECK_IMAGE(ctx, edges, GR_FORMAT_R8G8_UNORM, color->width, color->height);
 	const RowSpan span = resolve_rows(rows, color->height);
 	if (span.count() == 0)
 		return GR_OK;
@@ -627,10 +623,10 @@ int gr_smaa_blend_weight_rows(gr_ctx *ctx, gr_stream stream, const gr_image *edg
 {
 	if (!ctx)
 		return GR_ERR_INVALID_ARGUMENT;
-	GR_CHECK_ARG(ctx, push && edges && weights && edges->width && edges->height);
+	GR_CHECK_ARG(ctx, push);
 	GR_CHECK_ARG(ctx, quality >= 0 && quality <= 3);
-	GR_CHECK_ARG(ctx, check_image(edges, 2, edges->width, edges->height) && edges->format == GR_FORMAT_R8G8_UNORM);
-	GR_CHECK_ARG(ctx, check_image(weights, 4, edges->width, edges->height) && weights->format == GR_FORMAT_R8G8B8A8_UNORM);
+	GR_CHECK_IMAGE(ctx, edges, GR_FORMAT_R8G8_UNORM);
+	GR_CHECK_IMAGE(ctx, weights, GR_FORMAT_R8G8B8A8_UNORM, edges->width, edges->height);
 	if (!ctx->smaa_area || !ctx->smaa_search)
 		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_smaa_blend_weight: SMAA lookup tables not set (gr_smaa_set_luts)");
 	SmaaWeightsArgs S;
@@ -686,10 +682,11 @@ int gr_smaa_neighbor_blend_rows(gr_ctx *ctx, gr_stream stream, const gr_image *c
 {
 	if (!ctx)
 		return GR_ERR_INVALID_ARGUMENT;
-	GR_CHECK_ARG(ctx, push && color && weights && out && color->width && color->height);
-	GR_CHECK_ARG(ctx, check_image(color, 4, color->width, color->height) && is_rgba8(color->format));
-	GR_CHECK_ARG(ctx, check_image(weights, 4, color->width, color->height) && weights->format == GR_FORMAT_R8G8B8A8_UNORM);
-	GR_CHECK_ARG(ctx, check_image(out, 4, color->width, color->height) && is_rgba8(out->format) && out->ptr != color->ptr);
+	GR_CHECK_ARG(ctx, push);
+	GR_CHECK_IMAGE(ctx, color, GR_RGBA8_FORMATS);
+	GR_CHECK_IMAGE(ctx, weights, GR_FORMAT_R8G8B8A8_UNORM, color->width, color->height);
+	GR_CHECK_IMAGE(ctx, out, GR_RGBA8_FORMATS, color->width, color->height);
+	GR_CHECK_ARG(ctx, !gr_images_overlap(out, color));
 	const RowSpan span = resolve_rows(rows, color->height);
 	if (span.count() == 0)
 		return GR_OK;
@@ -699,8 +696,7 @@ int gr_smaa_neighbor_blend_rows(gr_ctx *ctx, gr_stream stream, const gr_image *c
 	{
 		const ColorImage c = {static_cast<const uint8_t *>(color->ptr), color->pitch_bytes, int(color->width), int(color->height)};
 		const ColorImage b = {static_cast<const uint8_t *>(weights->ptr), weights->pitch_bytes, int(weights->width), int(weights->height)};
-		const bool wide = color->width % 4 == 0 && ((color->pitch_bytes | weights->pitch_bytes | out->pitch_bytes) & 15u) == 0 &&
-		                  ((uintptr_t(color->ptr) | uintptr_t(weights->ptr) | uintptr_t(out->ptr)) & 15u) == 0;
+		const bool wide = color->width % 4 == 0 && is_aligned(color, 16u) && is_aligned(weights, 16u) && is_aligned(out, 16u);
 		const dim3 block(64, 4);
 		if (wide)
 			hipLaunchKernelGGL(k_smaa_blend_fast<4>, dim3(gr_div_up(color->width, 256), gr_div_up(span.count(), 4)), block, 0, gr_to_stream(stream), c, b,
@@ -734,17 +730,18 @@ int gr_taa_resolve_band(gr_ctx *ctx, gr_stream stream, const gr_image *current, 
 {
 	if (!ctx)
 		return GR_ERR_INVALID_ARGUMENT;
-	GR_CHECK_ARG(ctx, push && current && depth && mv && out_color && out_history);
+	GR_CHECK_ARG(ctx, push);
 	GR_CHECK_ARG(ctx, quality >= 0 && quality <= 2);
+	GR_CHECK_IMAGE(ctx, current, GR_HDR_FORMATS);
 	const uint32_t w = current->width, h = current->height;
-	GR_CHECK_ARG(ctx, w && h);
+	GR_CHECK_IMAGE(ctx, depth, GR_FORMAT_D32_SFLOAT, w, h);
+	GR_CHECK_IMAGE(ctx, mv, GR_FORMAT_R16G16_SFLOAT, w, h);
+	GR_CHECK_IMAGE(ctx, out_color, GR_HDR_FORMATS, w, h);
+	GR_CHECK_IMAGE(ctx, out_history, GR_FORMAT_R16G16B16A16_SFLOAT, w, h);
+	if (history)
+		GR_CHECK_IMAGE(ctx, history, GR_FORMAT_R16G16B16A16_SFLOAT, w, h);
+	GR_CHECK_ARG(ctx, !history || !gr_images_overlap(history, out_history));
 	const bool current_b10 = current->format == GR_FORMAT_B10G11R11_UFLOAT_PACK32, color_b10 = out_color->format == GR_FORMAT_B10G11R11_UFLOAT_PACK32;
-	GR_CHECK_ARG(ctx, check_image(current, current_b10 ? 4 : 8, w, h) && (current_b10 || current->format == GR_FORMAT_R16G16B16A16_SFLOAT));
-	GR_CHECK_ARG(ctx, check_image(depth, 4, w, h) && depth->format == GR_FORMAT_D32_SFLOAT);
-	GR_CHECK_ARG(ctx, check_image(mv, 4, w, h) && mv->format == GR_FORMAT_R16G16_SFLOAT);
-	GR_CHECK_ARG(ctx, check_image(out_color, color_b10 ? 4 : 8, w, h) && (color_b10 || out_color->format == GR_FORMAT_R16G16B16A16_SFLOAT));
-	GR_CHECK_ARG(ctx, check_image(out_history, 8, w, h) && out_history->format == GR_FORMAT_R16G16B16A16_SFLOAT);
-	GR_CHECK_ARG(ctx, !history || (check_image(history, 8, w, h) && history->format == GR_FORMAT_R16G16B16A16_SFLOAT && history->ptr != out_history->ptr));
 	const RowSpan span = resolve_rows(rows, h);
 	if (span.count() == 0)
 		return GR_OK;
@@ -797,14 +794,13 @@ int gr_blit(gr_ctx *ctx, gr_stream stream, const gr_image *in, const gr_image *o
 {
 	if (!ctx)
 		return GR_ERR_INVALID_ARGUMENT;
-	GR_CHECK_ARG(ctx, in && out && in->ptr && out->ptr && in->ptr != out->ptr && in->width && in->height && out->width && out->height);
-	auto supported = [](uint32_t f) { return f == GR_FORMAT_R16G16B16A16_SFLOAT || f == GR_FORMAT_R8G8B8A8_SRGB || f == GR_FORMAT_R8G8B8A8_UNORM; };
-	GR_CHECK_ARG(ctx, supported(in->format) && supported(out->format));
-	GR_CHECK_ARG(ctx, in->pitch_bytes >= in->width * (in->format == GR_FORMAT_R16G16B16A16_SFLOAT ? 8u : 4u));
-	GR_CHECK_ARG(ctx, out->pitch_bytes >= out->width * (out->format == GR_FORMAT_R16G16B16A16_SFLOAT ? 8u : 4u));
+	constexpr gr_format_set supported{GR_FORMAT_R16G16B16A16_SFLOAT, GR_FORMAT_R8G8B8A8_SRGB, GR_FORMAT_R8G8B8A8_UNORM};
+	GR_CHECK_IMAGE(ctx, in, supported);
+	GR_CHECK_IMAGE(ctx, out, supported);
+	GR_CHECK_ARG(ctx, !gr_images_overlap(in, out));
 	BlitArgs a = {};
-	a.in = DevImage{static_cast<const uint8_t *>(in->ptr), int(in->width), int(in->height), in->pitch_bytes};
-	a.out = DevImageRW{static_cast<uint8_t *>(out->ptr), int(out->width), int(out->height), out->pitch_bytes};
+	a.in = to_dev(in);
+	a.out = to_dev_rw(out);
 	a.in_format = in->format;
 	a.out_format = out->format;
 	a.linear = linear ? 1 : 0;

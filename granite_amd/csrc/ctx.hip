@@ -428,17 +428,12 @@ int gr_fill_byte(gr_ctx *ctx, gr_stream stream, void *dst, int value, size_t byt
 	return GR_OK;
 }
 
-static bool rgba8_target(const gr_image *image)
-{
-	return image && image->ptr && image->width && image->height && image->pitch_bytes >= image->width * 4u &&
-	       (image->format == GR_FORMAT_R8G8B8A8_SRGB || image->format == GR_FORMAT_R8G8B8A8_UNORM);
-}
-
 int gr_pack_rgb8_rows(gr_ctx *ctx, gr_stream stream, const gr_image *image, const gr_rows *rows, void *packed)
 {
 	if (!ctx)
 		return GR_ERR_INVALID_ARGUMENT;
-	GR_CHECK_ARG(ctx, rgba8_target(image) && packed && (reinterpret_cast<uintptr_t>(packed) & 3u) == 0);
+	GR_CHECK_IMAGE(ctx, image, GR_RGBA8_FORMATS);
+	GR_CHECK_ARG(ctx, packed && (reinterpret_cast<uintptr_t>(packed) & 3u) == 0);
 	const RowSpan span = resolve_rows(rows, image->height);
 	if (span.count() == 0)
 		return GR_OK;
@@ -453,7 +448,8 @@ int gr_unpack_rgb8_rows(gr_ctx *ctx, gr_stream stream, const void *packed, const
 {
 	if (!ctx)
 		return GR_ERR_INVALID_ARGUMENT;
-	GR_CHECK_ARG(ctx, rgba8_target(image) && packed && (reinterpret_cast<uintptr_t>(packed) & 3u) == 0);
+	GR_CHECK_IMAGE(ctx, image, GR_RGBA8_FORMATS);
+	GR_CHECK_ARG(ctx, packed && (reinterpret_cast<uintptr_t>(packed) & 3u) == 0);
 	const RowSpan span = resolve_rows(rows, image->height);
 	if (span.count() == 0)
 		return GR_OK;

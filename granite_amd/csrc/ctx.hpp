@@ -12,6 +12,7 @@
 #include <type_traits>
 #include <vector>
 #include "../../include/granite_hip.h"
+#include "image_args.hpp"
 #include "row_span.hpp"
 
 struct gr_timing_span
@@ -170,6 +171,14 @@ struct gr_scoped_timing
 			return (ctx)->fail(GR_ERR_INVALID_ARGUMENT, "%s: invalid argument: %s", __func__, #cond); \
 	} while (0)
 
+// One gr_image argument against the contract of image_args.hpp: GR_CHECK_IMAGE(ctx, out, GR_RGBA8_FORMATS[, width, height]); named as written, less a leading &.
+#define GR_CHECK_IMAGE(ctx, img, ...)                                                                          \
+	do                                                                                                         \
+	{                                                                                                          \
+		if (const char *rule__ = gr_image_rule(img, __VA_ARGS__))                                              \
+			return (ctx)->fail(GR_ERR_INVALID_ARGUMENT, "%s: invalid argument: %s%s", __func__, &#img[#img[0] == '&'], rule__); \
+	} while (0)
+
 #define GR_CHECK_HIP(ctx, expr)                                                                        \
 	do                                                                                                 \
 	{                                                                                                  \
@@ -188,8 +197,8 @@ struct gr_scoped_timing
 
 static inline hipStream_t gr_to_stream(gr_stream s) { return static_cast<hipStream_t>(s); }
 static inline unsigned gr_div_up(unsigned a, unsigned b) { return (a + b - 1) / b; }
-// rows that 16-byte loads and stores can walk
-static inline bool is_aligned16(const gr_image *img) { return (img->pitch_bytes & 15u) == 0 && (reinterpret_cast<uintptr_t>(img->ptr) & 15u) == 0; }
+// rows that `bytes`-wide (a power of two) loads and stores can walk
+static inline bool is_aligned(const gr_image *img, uint32_t bytes) { return ((img->pitch_bytes | reinterpret_cast<uintptr_t>(img->ptr)) & (bytes - 1u)) == 0; }
 
 // Runtime flags to template arguments: f(std::bool_constant<flags>...), one instantiation of f per combination.
 template <typename F> static void with_flags(F &&f) { f(); }

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/granite_hip.h"
 #include "packed_float.hpp"
 
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
@@ -24,6 +25,15 @@ struct DevImageRW
 	int w, h;
 	uint32_t pitch;
 };
+
+static inline DevImage to_dev(const gr_image *img)
+{
+	return {static_cast<const uint8_t *>(img->ptr), int(img->width), int(img->height), img->pitch_bytes};
+}
+static inline DevImageRW to_dev_rw(const gr_image *img)
+{
+	return {static_cast<uint8_t *>(img->ptr), int(img->width), int(img->height), img->pitch_bytes};
+}
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 

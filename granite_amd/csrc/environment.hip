@@ -164,7 +164,6 @@ __global__ __launch_bounds__(GROUP) void k_env_diffuse(DiffuseArgs a)
 
 void face_matrices(FaceMatrices &m) { face_inverse_matrices(m.inv); }
 
-bool aligned(const void *ptr, uintptr_t to) { return (reinterpret_cast<uintptr_t>(ptr) & (to - 1u)) == 0; }
 constexpr uint32_t MAX_CUBE_SIZE = 16384u; // 6 n^2 texel indices stay below 2^32
 
 // What every entry point asks of a cube it reads or writes.
@@ -176,7 +175,7 @@ int check_chain(gr_ctx *ctx, const char *who, const char *what, const void *ptr,
 		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "%s: %s size %u is outside 1 .. %u", who, what, size, MAX_CUBE_SIZE);
 	if (levels == 0 || levels > full_chain_levels(size))
 		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "%s: %s levels %u are beyond the chain of size %u (1 .. %u)", who, what, levels, size, full_chain_levels(size));
-	if (!aligned(ptr, 16))
+	if (reinterpret_cast<uintptr_t>(ptr) & 15u)
 		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "%s: %s is not 16-byte aligned", who, what);
 	return GR_OK;
 }
@@ -201,13 +200,9 @@ extern "C" int gr_env_equirect_to_cube(gr_ctx *ctx, gr_stream stream, const gr_i
 		return ctx->fail(GR_ERR_UNSUPPORTED_FORMAT, "gr_env_equirect_to_cube: equirect format %u is not R16G16B16A16_SFLOAT", equirect->format);
 	if (int code = check_chain(ctx, "gr_env_equirect_to_cube", "cube", cube, size, levels))
 		return code;
-	GR_CHECK_ARG(ctx, equirect->ptr);
-	if (equirect->width == 0 || equirect->height == 0 || equirect->width > 65536u || equirect->height > 65536u)
+	GR_CHECK_IMAGE(ctx, equirect, GR_FORMAT_R16G16B16A16_SFLOAT);
+	if (equirect->width > 65536u || equirect->height > 65536u)
 		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_env_equirect_to_cube: equirect extent %u x %u is outside 1 .. 65536", equirect->width, equirect->height);
-	if (equirect->pitch_bytes < equirect->width * 8u)
-		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_env_equirect_to_cube: equirect pitch %u is smaller than a row of %u texels", equirect->pitch_bytes, equirect->width);
-	if (!aligned(equirect->ptr, 8) || (equirect->pitch_bytes & 7u))
-		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_env_equirect_to_cube: equirect pointer or pitch is not 8-byte aligned");
 
 	hipStream_t s = gr_to_stream(stream);
 	gr_scoped_timing timing{ctx, s, "env_equirect_to_cube"};

@@ -93,14 +93,12 @@ int check_resource(gr_ctx *ctx, const Options &o, const gr_fft_resource *r, bool
 	{
 		const gr_image &img = r->image;
 		const uint32_t bpp = view_unit_bytes(kind);
-		if (!img.ptr)
-			return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_fft_execute: invalid argument: %s image pointer is null", what);
-		if (img.format != image_format_of(kind))
+		if (img.ptr && img.format != image_format_of(kind))
 			return ctx->fail(GR_ERR_UNSUPPORTED_FORMAT, "gr_fft_execute: %s image format %u, this mode and data type store format %u", what, img.format, image_format_of(kind));
-		if (img.width == 0 || img.height == 0 || img.width > MAX_IMAGE_EXTENT || img.height > MAX_IMAGE_EXTENT)
+		if (const char *rule = gr_image_rule(&img, image_format_of(kind)))
+			return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_fft_execute: invalid argument: %s image%s", what, rule);
+		if (img.width > MAX_IMAGE_EXTENT || img.height > MAX_IMAGE_EXTENT)
 			return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_fft_execute: %s image extent %u x %u is outside 1 .. %u", what, img.width, img.height, MAX_IMAGE_EXTENT);
-		if (img.pitch_bytes < img.width * bpp || (img.pitch_bytes % bpp) || (reinterpret_cast<uintptr_t>(img.ptr) % bpp))
-			return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_fft_execute: %s image pitch %u or pointer does not hold rows of %u texels of %u bytes", what, img.pitch_bytes, img.width, bpp);
 		view = {};
 		view.ptr = static_cast<uint8_t *>(img.ptr);
 		view.kind = kind;

@@ -333,11 +333,6 @@ __global__ __launch_bounds__(FSR_BLOCK_X *FSR_BLOCK_Y) void k_fsr_rcas(Rgba8 in,
 	*reinterpret_cast<uint32_t *>(out + size_t(y) * out_pitch + size_t(x) * 4u) = packed;
 }
 
-bool rgba8(const gr_image *img)
-{
-	return img && img->ptr && img->width && img->height && img->pitch_bytes >= img->width * 4u &&
-	       (img->format == GR_FORMAT_R8G8B8A8_UNORM || img->format == GR_FORMAT_R8G8B8A8_SRGB);
-}
 } // namespace
 
 extern "C" {
@@ -346,7 +341,9 @@ int gr_fsr_upscale(gr_ctx *ctx, gr_stream stream, const gr_image *in, const gr_i
 {
 	if (!ctx)
 		return GR_ERR_INVALID_ARGUMENT;
-	GR_CHECK_ARG(ctx, rgba8(in) && rgba8(out) && in->ptr != out->ptr);
+	GR_CHECK_IMAGE(ctx, in, GR_RGBA8_FORMATS);
+	GR_CHECK_IMAGE(ctx, out, GR_RGBA8_FORMATS);
+	GR_CHECK_ARG(ctx, !gr_images_overlap(in, out));
 	EasuArgs a;
 	a.in = {static_cast<const uint8_t *>(in->ptr), int(in->width), int(in->height), in->pitch_bytes};
 	a.out = static_cast<uint8_t *>(out->ptr);
@@ -372,7 +369,9 @@ int gr_fsr_sharpen(gr_ctx *ctx, gr_stream stream, const gr_image *in, const gr_i
 {
 	if (!ctx)
 		return GR_ERR_INVALID_ARGUMENT;
-	GR_CHECK_ARG(ctx, rgba8(in) && rgba8(out) && in->ptr != out->ptr && in->width == out->width && in->height == out->height);
+	GR_CHECK_IMAGE(ctx, in, GR_RGBA8_FORMATS);
+	GR_CHECK_IMAGE(ctx, out, GR_RGBA8_FORMATS, in->width, in->height);
+	GR_CHECK_ARG(ctx, !gr_images_overlap(in, out));
 	const Rgba8 src = {static_cast<const uint8_t *>(in->ptr), int(in->width), int(in->height), in->pitch_bytes};
 	gr_scoped_timing timing{ctx, gr_to_stream(stream), "fsr_sharpen"};
 	const dim3 grid(gr_div_up(out->width, FSR_BLOCK_X), gr_div_up(out->height, FSR_BLOCK_Y)), block(FSR_BLOCK_X, FSR_BLOCK_Y);

@@ -65,16 +65,14 @@ extern "C" int gr_pq10_encode(gr_ctx *ctx, gr_stream stream, const gr_image *hdr
 {
 	if (!ctx)
 		return GR_ERR_INVALID_ARGUMENT;
-	GR_CHECK_ARG(ctx, hdr && ui && out && push && hdr->ptr && ui->ptr && out->ptr && hdr->width && hdr->height);
-	GR_CHECK_ARG(ctx, hdr->format == GR_FORMAT_R16G16B16A16_SFLOAT && hdr->pitch_bytes >= hdr->width * 8u);
-	GR_CHECK_ARG(ctx, (ui->format == GR_FORMAT_R8G8B8A8_SRGB || ui->format == GR_FORMAT_R8G8B8A8_UNORM) && ui->width == hdr->width &&
-	                      ui->height == hdr->height && ui->pitch_bytes >= ui->width * 4u);
-	GR_CHECK_ARG(ctx, out->format == GR_FORMAT_A2B10G10R10_UNORM_PACK32 && out->width == hdr->width && out->height == hdr->height &&
-	                      out->pitch_bytes >= out->width * 4u);
+	GR_CHECK_ARG(ctx, push);
+	GR_CHECK_IMAGE(ctx, hdr, GR_FORMAT_R16G16B16A16_SFLOAT);
+	GR_CHECK_IMAGE(ctx, ui, GR_RGBA8_FORMATS, hdr->width, hdr->height);
+	GR_CHECK_IMAGE(ctx, out, GR_FORMAT_A2B10G10R10_UNORM_PACK32, hdr->width, hdr->height);
 	GR_CHECK_ARG(ctx, push->max_light_level > 0.0f);
 	Pq10Args a;
-	a.hdr = DevImage{static_cast<const uint8_t *>(hdr->ptr), int(hdr->width), int(hdr->height), hdr->pitch_bytes};
-	a.ui = DevImage{static_cast<const uint8_t *>(ui->ptr), int(ui->width), int(ui->height), ui->pitch_bytes};
+	a.hdr = to_dev(hdr);
+	a.ui = to_dev(ui);
 	a.out = static_cast<uint8_t *>(out->ptr);
 	a.out_pitch = out->pitch_bytes;
 	for (int col = 0; col < 3; col++) // mat3(config.primary_conversion): the upper-left 3 x 3 of the column-major mat4

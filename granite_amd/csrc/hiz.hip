@@ -221,9 +221,8 @@ int gr_hiz(gr_ctx *ctx, gr_stream stream, const gr_hiz_args *args)
 {
 	if (!ctx)
 		return GR_ERR_INVALID_ARGUMENT;
-	GR_CHECK_ARG(ctx, args && args->depth.ptr && args->chain && args->counter);
-	GR_CHECK_ARG(ctx, args->depth.format == GR_FORMAT_D32_SFLOAT || args->depth.format == GR_FORMAT_R32_SFLOAT);
-	GR_CHECK_ARG(ctx, args->depth.width > 0 && args->depth.height > 0 && args->depth.pitch_bytes >= args->depth.width * 4u);
+	GR_CHECK_ARG(ctx, args && args->chain && args->counter);
+	GR_CHECK_IMAGE(ctx, &args->depth, gr_format_set(GR_FORMAT_D32_SFLOAT, GR_FORMAT_R32_SFLOAT));
 	const uint32_t ds = args->output_downsample ? 1u : 0u;
 	const uint32_t res_w = args->chain_width << ds, res_h = args->chain_height << ds;
 	GR_CHECK_ARG(ctx, res_w > 0 && res_h > 0 && (res_w & 63u) == 0 && (res_h & 63u) == 0);
@@ -236,7 +235,7 @@ int gr_hiz(gr_ctx *ctx, gr_stream stream, const gr_hiz_args *args)
 	p.iw = int(args->depth.width);
 	p.ih = int(args->depth.height);
 	p.pitch = args->depth.pitch_bytes;
-	p.aligned = ((reinterpret_cast<uintptr_t>(args->depth.ptr) & 15u) == 0 && (args->depth.pitch_bytes & 15u) == 0) ? 1 : 0;
+	p.aligned = is_aligned(&args->depth, 16u) ? 1 : 0;
 	p.chain = static_cast<float *>(args->chain);
 	p.res_w = int(res_w);
 	p.res_h = int(res_h);

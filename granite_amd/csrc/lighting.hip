@@ -345,7 +345,7 @@ struct RawTile
 // Lanes outside the target read the texels their coordinates clamp to (no exec-mask region, no zero-filled registers): what they
 // hold is never stored, and their depth is not looked at (`inside` gates `active`).  The clamp is to the whole target, not to the render
 // area: a band launch (gr_rows) may read rows of the attachments it does not shade -- every attachment has the target's full height
-// (check_image in gr_lighting) -- and, with emissive aliased to the target, texels another wave or another band's launch is writing;
+// (GR_CHECK_IMAGE in gr_lighting) -- and, with emissive aliased to the target, texels another wave or another band's launch is writing;
 // the values are dropped, so this is a benign read of a location being written (a race detector would name it).
 template <int PX, bool B10>
 __device__ __forceinline__ void load_raw(const KernelArgs &a, int x0, int y, RawTile<PX, B10> &r)
@@ -933,11 +933,6 @@ __global__ __launch_bounds__(64 * LIGHT_WAVES) LV_OCCUPANCY_ATTR void k_lighting
 	shade_tile<PX, AO, B10>(a, tile_x0, tile_y0, wave, lane, raw, s_lights[threadIdx.x >> 6], s_srgb LV_STAMP_ARG);
 }
 
-static bool check_image(const gr_image &img, uint32_t format, uint32_t bpp, uint32_t w, uint32_t h)
-{
-	return img.ptr && img.format == format && img.width == w && img.height == h && img.pitch_bytes >= w * bpp &&
-	       (img.pitch_bytes % bpp) == 0;
-}
 } // namespace
 
 extern "C" {
@@ -947,17 +942,16 @@ int gr_lighting(gr_ctx *ctx, gr_stream stream, const gr_lighting_args *args)
 	if (!ctx)
 		return GR_ERR_INVALID_ARGUMENT;
 	GR_CHECK_ARG(ctx, args != nullptr);
-	const uint32_t W = args->hdr.width, H = args->hdr.height;
-	GR_CHECK_ARG(ctx, W != 0 && H != 0);
 	// HDR target and emissive share a format: RGBA16F, or B10G11R11_UFLOAT_PACK32 (renderTargetFp16 = false in the reference)
+	GR_CHECK_IMAGE(ctx, &args->hdr, GR_HDR_FORMATS);
+	const uint32_t W = args->hdr.width, H = args->hdr.height;
 	const bool b10 = args->hdr.format == GR_FORMAT_B10G11R11_UFLOAT_PACK32;
-	const uint32_t hdr_format = b10 ? uint32_t(GR_FORMAT_B10G11R11_UFLOAT_PACK32) : uint32_t(GR_FORMAT_R16G16B16A16_SFLOAT), hdr_bpp = b10 ? 4u : 8u;
-	GR_CHECK_ARG(ctx, check_image(args->hdr, hdr_format, hdr_bpp, W, H));
-	GR_CHECK_ARG(ctx, check_image(args->emissive, hdr_format, hdr_bpp, W, H));
-	GR_CHECK_ARG(ctx, check_image(args->albedo, GR_FORMAT_R8G8B8A8_SRGB, 4, W, H));
-	GR_CHECK_ARG(ctx, check_image(args->normal, GR_FORMAT_A2B10G10R10_UNORM_PACK32, 4, W, H));
-	GR_CHECK_ARG(ctx, check_image(args->pbr, GR_FORMAT_R8G8_UNORM, 2, W, H));
-	GR_CHECK_ARG(ctx, check_image(args->depth, GR_FORMAT_D32_SFLOAT, 4, W, H));
+	const uint32_t hdr_bpp = gr_format_texel_bytes(args->hdr.format);
+	GR_CHECK_IMAGE(ctx, &args->emissive, args->hdr.format, W, H);
+	GR_CHECK_IMAGE(ctx, &args->albedo, GR_FORMAT_R8G8B8A8_SRGB, W, H);
+	GR_CHECK_IMAGE(ctx, &args->normal, GR_FORMAT_A2B10G10R10_UNORM_PACK32, W, H);
+	GR_CHECK_IMAGE(ctx, &args->pbr, GR_FORMAT_R8G8_UNORM, W, H);
+	GR_CHECK_IMAGE(ctx, &args->depth, GR_FORMAT_D32_SFLOAT, W, H);
 	const bool clustered = (args->flags & GR_LIGHTING_CLUSTERED_BIT) != 0 && args->cluster.num_lights > 0;
 	if (clustered)
 	{
@@ -967,20 +961,18 @@ int gr_lighting(gr_ctx *ctx, gr_stream stream, const gr_lighting_args *args)
 	}
 
 	KernelArgs k{};
-	auto dev = [](const gr_image &i) { return DevImage{static_cast<const uint8_t *>(i.ptr), int(i.width), int(i.height), i.pitch_bytes}; };
-	k.albedo = dev(args->albedo);
-	k.normal = dev(args->normal);
-	k.pbr = dev(args->pbr);
-	k.depth = dev(args->depth);
-	k.emissive = dev(args->emissive);
+	k.albedo = to_dev(&args->albedo);
+	k.normal = to_dev(&args->normal);
+	k.pbr = to_dev(&args->pbr);
+	k.depth = to_dev(&args->depth);
+	k.emissive = to_dev(&args->emissive);
 	if (args->flags & GR_LIGHTING_AMBIENT_OCCLUSION_BIT)
 	{
 		GR_CHECK_ARG(ctx, (args->flags & GR_LIGHTING_AMBIENT_FALLBACK_BIT) != 0);
-		GR_CHECK_ARG(ctx, args->ambient_occlusion.ptr && args->ambient_occlusion.format == GR_FORMAT_R8_UNORM && args->ambient_occlusion.width &&
-		                      args->ambient_occlusion.height && args->ambient_occlusion.pitch_bytes >= args->ambient_occlusion.width);
-		k.ao = dev(args->ambient_occlusion);
+		GR_CHECK_IMAGE(ctx, &args->ambient_occlusion, GR_FORMAT_R8_UNORM);
+		k.ao = to_dev(&args->ambient_occlusion);
 	}
-	k.hdr = DevImageRW{static_cast<uint8_t *>(args->hdr.ptr), int(W), int(H), args->hdr.pitch_bytes};
+	k.hdr = to_dev_rw(&args->hdr);
 	for (int i = 0; i < 16; i++)
 		k.inv_vp[i] = args->inv_view_projection[i];
 	for (int i = 0; i < 4; i++)
@@ -1028,18 +1020,12 @@ int gr_lighting(gr_ctx *ctx, gr_stream stream, const gr_lighting_args *args)
 	k.fog_falloff = args->fog_falloff > 0.0f ? args->fog_falloff : 0.0f;
 
 	// Render area: tiles stay aligned to multiples of 8 rows of the full target, rows outside the band are masked.
-	uint32_t row_first = 0, row_end = H;
-	if (args->rows.count != 0)
-	{
-		row_first = args->rows.first < H ? args->rows.first : H;
-		const uint64_t end = uint64_t(args->rows.first) + args->rows.count;
-		row_end = end < H ? uint32_t(end) : H;
-	}
-	if (row_first >= row_end)
+	const RowSpan span = resolve_rows(args->rows.count ? &args->rows : nullptr, H); // {0, 0} = the whole image (granite_hip.h: gr_rows)
+	if (span.count() == 0)
 		return GR_OK;
-	k.row_first = int(row_first);
-	k.row_end = int(row_end);
-	k.block_row0 = int(row_first / LIGHT_TILE);
+	k.row_first = int(span.first);
+	k.row_end = int(span.end);
+	k.block_row0 = int(span.first / LIGHT_TILE);
 	// Pixels per lane: 2 (GR_LIGHTING_PX=1 selects the one-pixel form for A/B measurements) whenever the lane's pair of
 	// texels is one naturally aligned access in every attachment: even width, pitches that are multiples of two texels.
 	// Odd-sized targets run the one-pixel kernel.
@@ -1047,17 +1033,12 @@ int gr_lighting(gr_ctx *ctx, gr_stream stream, const gr_lighting_args *args)
 		const char *env = gr_measurement_switch("GR_LIGHTING_PX");
 		return env && atoi(env) == 1 ? 1 : 2;
 	}();
-	const bool pairs_aligned = (W & 1u) == 0 && (args->depth.pitch_bytes & 7u) == 0 && (args->albedo.pitch_bytes & 7u) == 0 &&
-	                           (args->normal.pitch_bytes & 7u) == 0 && (args->pbr.pitch_bytes & 3u) == 0 &&
-	                           (args->emissive.pitch_bytes & (2u * hdr_bpp - 1u)) == 0 && (args->hdr.pitch_bytes & (2u * hdr_bpp - 1u)) == 0 &&
-	                           (reinterpret_cast<uintptr_t>(args->emissive.ptr) & (2u * hdr_bpp - 1u)) == 0 &&
-	                           (reinterpret_cast<uintptr_t>(args->hdr.ptr) & (2u * hdr_bpp - 1u)) == 0 &&
-	                           (reinterpret_cast<uintptr_t>(args->depth.ptr) & 7u) == 0 && (reinterpret_cast<uintptr_t>(args->albedo.ptr) & 7u) == 0 &&
-	                           (reinterpret_cast<uintptr_t>(args->normal.ptr) & 7u) == 0 && (reinterpret_cast<uintptr_t>(args->pbr.ptr) & 3u) == 0;
+	const bool pairs_aligned = (W & 1u) == 0 && is_aligned(&args->depth, 8u) && is_aligned(&args->albedo, 8u) && is_aligned(&args->normal, 8u) &&
+	                           is_aligned(&args->pbr, 4u) && is_aligned(&args->emissive, 2u * hdr_bpp) && is_aligned(&args->hdr, 2u * hdr_bpp);
 	const int px = pairs_aligned ? px_pref : 1;
 	// 32-bit byte offsets inside the kernel.
 	GR_CHECK_ARG(ctx, uint64_t(args->hdr.pitch_bytes) * H <= 0xffffffffull && uint64_t(args->emissive.pitch_bytes) * H <= 0xffffffffull);
-	const dim3 grid(gr_div_up(W, unsigned(LIGHT_TILE * px * LIGHT_WAVES)), gr_div_up(row_end, unsigned(LIGHT_TILE)) - unsigned(k.block_row0));
+	const dim3 grid(gr_div_up(W, unsigned(LIGHT_TILE * px * LIGHT_WAVES)), gr_div_up(span.end, unsigned(LIGHT_TILE)) - unsigned(k.block_row0));
 	// Residency cap.  The kernel is bound by the vector pipe; at full occupancy it owns every wave slot of the chip for the whole launch
 	// and the executor's other streams (the previous frame's bloom / tonemap, the next frame's cluster build) cannot get a single wave
 	// in.  Padding the workgroup's LDS footprint so that only `max_wgs` workgroups fit per CU leaves the remaining slots to them.  With

@@ -87,45 +87,8 @@ uint32_t log2_of(uint32_t v)
 		l++;
 	return l;
 }
-uint32_t channels_of(uint32_t format)
-{
-	switch (format)
-	{
-	case GR_FORMAT_R16_SFLOAT: return 1;
-	case GR_FORMAT_R16G16_SFLOAT: return 2;
-	case GR_FORMAT_R16G16B16A16_SFLOAT: return 4;
-	default: return 0;
-	}
-}
-constexpr uint32_t MAX_EXTENT = 32768u; // texel indices of an image stay below 2^31
-
-// What both image entry points ask of an image: the stated format, an extent the index arithmetic holds, a pitch that covers a row,
-// and the alignment of one texel.
-int check_image(gr_ctx *ctx, const char *who, const char *what, const gr_image *img, uint32_t format)
-{
-	if (!img || !img->ptr)
-		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "%s: invalid argument: %s is a null pointer", who, what);
-	if (img->format != format)
-		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "%s: %s has format %u, not %u", who, what, img->format, format);
-	if (img->width == 0 || img->height == 0 || img->width > MAX_EXTENT || img->height > MAX_EXTENT)
-		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "%s: %s extent %u x %u is outside 1 .. %u", who, what, img->width, img->height, MAX_EXTENT);
-	const uint32_t texel = 2u * channels_of(format);
-	if (img->pitch_bytes < img->width * texel || (img->pitch_bytes & (texel - 1u)) || (reinterpret_cast<uintptr_t>(img->ptr) & (texel - 1u)))
-		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "%s: %s pitch %u does not cover a row of %u texels, or pointer or pitch is not %u-byte aligned", who, what,
-		                 img->pitch_bytes, img->width, texel);
-	return GR_OK;
-}
-
-// Lanes read texels that other lanes of the same launch write when an output shares bytes with an input.
-bool overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
-{
-	const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-	return pa < pb + b_bytes && pb < pa + a_bytes;
-}
-bool overlap(const gr_image *a, const gr_image *b)
-{
-	return overlap(a->ptr, size_t(a->pitch_bytes) * a->height, b->ptr, size_t(b->pitch_bytes) * b->height);
-}
+// What both image entry points ask of an image beyond the contract: texel indices stay below 2^31.
+constexpr uint32_t MAX_EXTENT = 32768u;
 
 Texture texture_of(const gr_image *img) { return {static_cast<const uint8_t *>(img->ptr), int(img->width), int(img->height), img->pitch_bytes}; }
 } // namespace
@@ -151,7 +114,7 @@ extern "C" int gr_ocean_generate_fft(gr_ctx *ctx, gr_stream stream, const void *
 		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_ocean_generate_fft: unknown variant %u", variant);
 	if ((reinterpret_cast<uintptr_t>(distribution) & 7u) || (reinterpret_cast<uintptr_t>(out) & 3u))
 		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_ocean_generate_fft: distribution is not 8-byte or out is not 4-byte aligned");
-	if (overlap(distribution, size_t(nx) * ny * 8u, out, size_t(nx) * ny * 4u))
+	if (gr_images_overlap(distribution, size_t(nx) * ny * 8u, out, size_t(nx) * ny * 4u))
 		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_ocean_generate_fft: out overlaps distribution");
 
 	GenerateLaunch a = {};
@@ -182,23 +145,21 @@ extern "C" int gr_ocean_bake_maps(gr_ctx *ctx, gr_stream stream, const gr_image 
 	if (!ctx)
 		return GR_ERR_INVALID_ARGUMENT;
 	GR_CHECK_ARG(ctx, push);
-	if (int code = check_image(ctx, "gr_ocean_bake_maps", "height", height, GR_FORMAT_R16_SFLOAT))
-		return code;
-	if (int code = check_image(ctx, "gr_ocean_bake_maps", "displacement", displacement, GR_FORMAT_R16G16_SFLOAT))
-		return code;
-	if (int code = check_image(ctx, "gr_ocean_bake_maps", "grad_jacobian", grad_jacobian, GR_FORMAT_R16G16B16A16_SFLOAT))
-		return code;
+	GR_CHECK_IMAGE(ctx, height, GR_FORMAT_R16_SFLOAT);
+	GR_CHECK_IMAGE(ctx, displacement, GR_FORMAT_R16G16_SFLOAT);
+	GR_CHECK_IMAGE(ctx, grad_jacobian, GR_FORMAT_R16G16B16A16_SFLOAT);
 	if (height_displacement)
-		if (int code = check_image(ctx, "gr_ocean_bake_maps", "height_displacement", height_displacement, GR_FORMAT_R16G16B16A16_SFLOAT))
-			return code;
+		GR_CHECK_IMAGE(ctx, height_displacement, GR_FORMAT_R16G16B16A16_SFLOAT);
+	GR_CHECK_ARG(ctx, height->width <= MAX_EXTENT && height->height <= MAX_EXTENT); // (the outputs have the height map's size, below)
+	GR_CHECK_ARG(ctx, displacement->width <= MAX_EXTENT && displacement->height <= MAX_EXTENT);
 	if (!power_of_two(displacement->width) || !power_of_two(displacement->height))
 		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_ocean_bake_maps: displacement %u x %u is not a power of two each way", displacement->width, displacement->height);
 	if (grad_jacobian->width != height->width || grad_jacobian->height != height->height ||
 	    (height_displacement && (height_displacement->width != height->width || height_displacement->height != height->height)))
 		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_ocean_bake_maps: the outputs do not have the height map's size %u x %u", height->width, height->height);
 	for (const gr_image *o : {grad_jacobian, height_displacement})
-		if (o && (overlap(o, height) || overlap(o, displacement) || (o == height_displacement && overlap(o, grad_jacobian))))
-			return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_ocean_bake_maps: an output overlaps an input or the other output");
+		if (o && (gr_images_overlap(o, height) || gr_images_overlap(o, displacement) || (o == height_displacement && gr_images_overlap(o, grad_jacobian))))
+			return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_ocean_bake_maps: %s overlaps an input or the other output", o == grad_jacobian ? "grad_jacobian" : "height_displacement");
 
 	BakeLaunch a = {};
 	a.b.height = texture_of(height);
@@ -223,17 +184,15 @@ extern "C" int gr_ocean_mipmap(gr_ctx *ctx, gr_stream stream, const gr_image *in
 	if (!ctx)
 		return GR_ERR_INVALID_ARGUMENT;
 	GR_CHECK_ARG(ctx, push);
-	GR_CHECK_ARG(ctx, in);
-	const uint32_t channels = channels_of(in->format);
-	if (!channels)
-		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_ocean_mipmap: format %u is none of R16_SFLOAT, R16G16_SFLOAT, R16G16B16A16_SFLOAT", in->format);
-	if (int code = check_image(ctx, "gr_ocean_mipmap", "in", in, in->format))
-		return code;
-	if (int code = check_image(ctx, "gr_ocean_mipmap", "out", out, in->format))
-		return code;
+	constexpr gr_format_set half_floats{GR_FORMAT_R16_SFLOAT, GR_FORMAT_R16G16_SFLOAT, GR_FORMAT_R16G16B16A16_SFLOAT};
+	GR_CHECK_IMAGE(ctx, in, half_floats);
+	GR_CHECK_IMAGE(ctx, out, in->format);
+	const uint32_t channels = gr_format_texel_bytes(in->format) / 2u;
+	GR_CHECK_ARG(ctx, in->width <= MAX_EXTENT && in->height <= MAX_EXTENT);
+	GR_CHECK_ARG(ctx, out->width <= MAX_EXTENT && out->height <= MAX_EXTENT);
 	if (out->width != push->count[0] || out->height != push->count[1])
 		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_ocean_mipmap: out is %u x %u, count says %u x %u", out->width, out->height, push->count[0], push->count[1]);
-	if (overlap(in, out))
+	if (gr_images_overlap(in, out))
 		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_ocean_mipmap: out overlaps in");
 
 	MipmapLaunch a = {};

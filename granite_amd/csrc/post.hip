@@ -24,15 +24,6 @@ __device__ __forceinline__ void post_wave_priority()
 		__builtin_amdgcn_s_setprio(GR_POST_WAVE_PRIORITY);
 }
 
-static inline DevImage to_dev(const gr_image *img)
-{
-	return {static_cast<const uint8_t *>(img->ptr), int(img->width), int(img->height), img->pitch_bytes};
-}
-static inline DevImageRW to_dev_rw(const gr_image *img)
-{
-	return {static_cast<uint8_t *>(img->ptr), int(img->width), int(img->height), img->pitch_bytes};
-}
-
 // ---- bloom threshold (bloom_threshold.comp:23-44) ------------------------------------------------------------------
 template <bool DYNAMIC_EXPOSURE>
 __global__ __launch_bounds__(POST_BLOCK_X *POST_BLOCK_Y) void k_bloom_threshold(DevImage hdr, DevImageRW out,
@@ -1153,18 +1144,7 @@ __global__ __launch_bounds__(TONEMAP_BLOCK_X *TONEMAP_BLOCK_Y) void k_tonemap(De
 static bool allow_stencil() { static const bool allow = gr_measurement_switch("GR_NO_STENCIL") == nullptr; return allow; }
 static bool allow_tail_fusion() { static const bool allow = gr_measurement_switch("GR_NO_TAIL_FUSION") == nullptr; return allow; }
 
-static bool is_rgba16f(const gr_image *img)
-{
-	return img && img->ptr && img->format == GR_FORMAT_R16G16B16A16_SFLOAT && img->width && img->height &&
-	       img->pitch_bytes >= img->width * 8u && (img->pitch_bytes & 7u) == 0;
-}
-static bool is_b10g11r11(const gr_image *img)
-{
-	return img && img->ptr && img->format == GR_FORMAT_B10G11R11_UFLOAT_PACK32 && img->width && img->height &&
-	       img->pitch_bytes >= img->width * 4u && (img->pitch_bytes & 3u) == 0;
-}
-// an HDR colour target as the passes that only read it take it: RGBA16F, or the reference's default B10G11R11_UFLOAT_PACK32
-static bool is_hdr_target(const gr_image *img) { return is_rgba16f(img) || is_b10g11r11(img); }
+constexpr uint32_t RGBA16F = GR_FORMAT_R16G16B16A16_SFLOAT;
 static bool same_size(const gr_image *a, const gr_image *b) { return a->width == b->width && a->height == b->height; }
 // a fused kernel writes whole levels: its push block names every texel of the image
 static bool covers(const uint32_t threads[2], const gr_image *img) { return threads[0] == img->width && threads[1] == img->height; }
@@ -1188,7 +1168,7 @@ static bool has_texels(const gr_push_luminance *push) { return push->size[0] != 
 // What gr_bloom_downsample / gr_bloom_upsample pick for a level: the constant-weight stencil when it is exactly 2:1 / 1:2.
 static bool downsample_is_exact(const gr_image *in, const gr_push_bloom_downsample *push)
 {
-	return allow_stencil() && in->width == 2u * push->threads[0] && in->height == 2u * push->threads[1] && is_aligned16(in) &&
+	return allow_stencil() && in->width == 2u * push->threads[0] && in->height == 2u * push->threads[1] && is_aligned(in, 16u) &&
 	       is_reciprocal_of(push->inv_output_size, push->threads[0], push->threads[1]) && is_reciprocal_of(push->inv_input_size, in->width, in->height);
 }
 static bool upsample_is_exact(const gr_image *in, const gr_push_bloom_upsample *push)
@@ -1200,13 +1180,15 @@ static bool upsample_is_exact(const gr_image *in, const gr_push_bloom_upsample *
 static bool threshold_is_exact(const gr_image *hdr, const gr_image *out, const gr_push_bloom_threshold *push)
 {
 	return allow_stencil() && hdr->width == 2u * push->threads[0] && hdr->height == 2u * push->threads[1] && (push->threads[0] & 1u) == 0 &&
-	       out->width == push->threads[0] && is_aligned16(hdr) && is_aligned16(out) && is_reciprocal_of(push->inv_output_size, push->threads[0], push->threads[1]);
+	       out->width == push->threads[0] && is_aligned(hdr, 16u) && is_aligned(out, 16u) && is_reciprocal_of(push->inv_output_size, push->threads[0], push->threads[1]);
 }
 
 // "Do these arguments fit this kernel", one function per fused launch: nullptr when they do, else the rule they break, which an entry point
 // reports (GR_CHECK_FIT) and a _supported query turns into 0.  What is not a matter of correctness -- measurement switches, the size limits
 // with their measurements -- is the queries' alone.
 #define GR_RULE(cond) do { if (!(cond)) return #cond; } while (0)
+// an image argument against the contract of image_args.hpp
+#define GR_RULE_IMAGE(img, formats) do { if (gr_image_rule(img, formats)) return #img " is not a valid " #formats " image (image_args.hpp)"; } while (0)
 #define GR_CHECK_FIT(ctx, fit) do { if (const char *rule__ = (fit)) return (ctx)->fail(GR_ERR_INVALID_ARGUMENT, "%s: invalid argument: %s", __func__, rule__); } while (0)
 
 // k_bloom_down_pair: downsample-0 + downsample-1 (gr_bloom_down_mid), downsample-2 + downsample-3 (gr_bloom_down_tail)
@@ -1214,7 +1196,9 @@ static const char *down_pair_fits(const gr_image *in, const gr_image *fine, cons
                                   const gr_push_bloom_downsample *push_coarse)
 {
 	GR_RULE(push_fine != nullptr && push_coarse != nullptr);
-	GR_RULE(is_rgba16f(in) && is_rgba16f(fine) && is_rgba16f(coarse));
+	GR_RULE_IMAGE(in, RGBA16F);
+	GR_RULE_IMAGE(fine, RGBA16F);
+	GR_RULE_IMAGE(coarse, RGBA16F);
 	GR_RULE(covers(push_fine->threads, fine) && covers(push_coarse->threads, coarse));
 	GR_RULE(down_patch_fits(fine, coarse));
 	return nullptr;
@@ -1225,12 +1209,15 @@ static const char *down_pair_fits(const gr_image *in, const gr_image *fine, cons
 static const char *down_head_fits(const gr_image *hdr, const gr_image *threshold, const gr_image *d0, const gr_image *d1, const gr_push_bloom_threshold *push_t,
                                   const gr_push_bloom_downsample *push_d0, const gr_push_bloom_downsample *push_d1)
 {
-	GR_RULE(hdr && threshold && d0 && d1 && push_t && push_d0 && push_d1);
-	GR_RULE(is_hdr_target(hdr) && is_rgba16f(threshold) && is_rgba16f(d0) && is_rgba16f(d1));
+	GR_RULE(push_t && push_d0 && push_d1);
+	GR_RULE_IMAGE(hdr, GR_HDR_FORMATS);
+	GR_RULE_IMAGE(threshold, RGBA16F);
+	GR_RULE_IMAGE(d0, RGBA16F);
+	GR_RULE_IMAGE(d1, RGBA16F);
 	GR_RULE(is_half_of(threshold, hdr) && is_half_of(d0, threshold) && is_half_of(d1, d0));
 	GR_RULE(covers(push_t->threads, threshold) && push_d0->threads[0] == d0->width && push_d1->threads[0] == d1->width);
 	GR_RULE(downsample_is_exact(threshold, push_d0) && downsample_is_exact(d0, push_d1));
-	GR_RULE(is_aligned16(hdr));
+	GR_RULE(is_aligned(hdr, 16u));
 	return nullptr;
 }
 
@@ -1239,7 +1226,9 @@ static const char *up_tail_fits(const gr_image *d3, const gr_image *u2, const gr
                                 const gr_push_bloom_upsample *push_u1)
 {
 	GR_RULE(push_u2 != nullptr && push_u1 != nullptr);
-	GR_RULE(is_rgba16f(d3) && is_rgba16f(u2) && is_rgba16f(u1));
+	GR_RULE_IMAGE(d3, RGBA16F);
+	GR_RULE_IMAGE(u2, RGBA16F);
+	GR_RULE_IMAGE(u1, RGBA16F);
 	GR_RULE(covers(push_u2->threads, u2) && covers(push_u1->threads, u1));
 	GR_RULE(up_patch_fits(u1, u2));
 	return nullptr;
@@ -1249,10 +1238,11 @@ static const char *up_tail_fits(const gr_image *d3, const gr_image *u2, const gr
 static const char *up_all_fits(const gr_image *d3, const gr_image *u2, const gr_image *u1, const gr_image *u0, const gr_push_bloom_upsample *push_u2,
                                const gr_push_bloom_upsample *push_u1, const gr_push_bloom_upsample *push_u0)
 {
-	GR_RULE(d3 && u2 && u1 && u0 && push_u0 != nullptr);
+	GR_RULE(push_u0 != nullptr);
 	if (const char *rule = up_tail_fits(d3, u2, u1, push_u2, push_u1))
 		return rule;
-	GR_RULE(is_rgba16f(u0) && covers(push_u0->threads, u0) && upsample_is_exact(u1, push_u0));
+	GR_RULE_IMAGE(u0, RGBA16F);
+	GR_RULE(covers(push_u0->threads, u0) && upsample_is_exact(u1, push_u0));
 	return nullptr;
 }
 
@@ -1269,7 +1259,8 @@ static const char *luminance_fits(const gr_luminance_data *lum, const gr_push_lu
 static const char *pyramid_own_fits(const gr_bloom_pyramid_args *a)
 {
 	GR_RULE(same_size(&a->u2, &a->d2));
-	GR_RULE(is_rgba16f(&a->history) && same_size(&a->history, &a->d3) && a->history.ptr != a->d3.ptr);
+	GR_RULE_IMAGE(&a->history, RGBA16F);
+	GR_RULE(same_size(&a->history, &a->d3) && !gr_images_overlap(&a->history, &a->d3));
 	GR_RULE(!a->lum || has_texels(&a->push_luminance));
 	return nullptr;
 }
@@ -1290,7 +1281,8 @@ int gr_bloom_threshold_rows(gr_ctx *ctx, gr_stream stream, const gr_image *hdr, 
 	if (!ctx)
 		return GR_ERR_INVALID_ARGUMENT;
 	GR_CHECK_ARG(ctx, push != nullptr);
-	GR_CHECK_ARG(ctx, is_hdr_target(hdr) && is_rgba16f(out));
+	GR_CHECK_IMAGE(ctx, hdr, GR_HDR_FORMATS);
+	GR_CHECK_IMAGE(ctx, out, RGBA16F);
 	GR_CHECK_ARG(ctx, push->threads[0] <= out->width && push->threads[1] <= out->height);
 	const bool b10 = hdr->format == GR_FORMAT_B10G11R11_UFLOAT_PACK32;
 	if (push->threads[0] == 0 || push->threads[1] == 0)
@@ -1329,8 +1321,11 @@ int gr_bloom_downsample_rows(gr_ctx *ctx, gr_stream stream, const gr_image *in, 
 	if (!ctx)
 		return GR_ERR_INVALID_ARGUMENT;
 	GR_CHECK_ARG(ctx, push != nullptr);
-	GR_CHECK_ARG(ctx, is_rgba16f(in) && is_rgba16f(out));
-	GR_CHECK_ARG(ctx, !history || (is_rgba16f(history) && history->ptr != out->ptr));
+	GR_CHECK_IMAGE(ctx, in, RGBA16F);
+	GR_CHECK_IMAGE(ctx, out, RGBA16F);
+	if (history)
+		GR_CHECK_IMAGE(ctx, history, RGBA16F);
+	GR_CHECK_ARG(ctx, !history || !gr_images_overlap(history, out));
 	GR_CHECK_ARG(ctx, push->threads[0] <= out->width && push->threads[1] <= out->height);
 	if (push->threads[0] == 0 || push->threads[1] == 0)
 		return GR_OK;
@@ -1368,7 +1363,8 @@ int gr_bloom_upsample_rows(gr_ctx *ctx, gr_stream stream, const gr_image *in, co
 	if (!ctx)
 		return GR_ERR_INVALID_ARGUMENT;
 	GR_CHECK_ARG(ctx, push != nullptr);
-	GR_CHECK_ARG(ctx, is_rgba16f(in) && is_rgba16f(out));
+	GR_CHECK_IMAGE(ctx, in, RGBA16F);
+	GR_CHECK_IMAGE(ctx, out, RGBA16F);
 	GR_CHECK_ARG(ctx, push->threads[0] <= out->width && push->threads[1] <= out->height);
 	if (push->threads[0] == 0 || push->threads[1] == 0)
 		return GR_OK;
@@ -1408,7 +1404,7 @@ int gr_bloom_down_mid(gr_ctx *ctx, gr_stream stream, const gr_image *threshold, 
 	if (!ctx)
 		return GR_ERR_INVALID_ARGUMENT;
 	GR_CHECK_FIT(ctx, down_pair_fits(threshold, d0, d1, push_d0, push_d1));
-	GR_CHECK_ARG(ctx, d0->ptr != d1->ptr && threshold->ptr != d0->ptr); // the entry point's own: the query does not look at the pointers
+	GR_CHECK_ARG(ctx, !gr_images_overlap(d0, d1) && !gr_images_overlap(threshold, d0)); // the entry point's own: the query does not look at the pointers
 	const RowSpan span = resolve_rows(rows_d1, d1->height);
 	if (span.count() == 0)
 		return GR_OK;
@@ -1445,7 +1441,7 @@ int gr_bloom_down_head(gr_ctx *ctx, gr_stream stream, const gr_image *hdr, const
 	if (!ctx)
 		return GR_ERR_INVALID_ARGUMENT;
 	GR_CHECK_FIT(ctx, down_head_fits(hdr, threshold, d0, d1, push_t, push_d0, push_d1));
-	GR_CHECK_ARG(ctx, hdr->ptr != threshold->ptr && threshold->ptr != d0->ptr && d0->ptr != d1->ptr); // the entry point's own, as above
+	GR_CHECK_ARG(ctx, !gr_images_overlap(hdr, threshold) && !gr_images_overlap(threshold, d0) && !gr_images_overlap(d0, d1)); // the entry point's own, as above
 	const dim3 grid(gr_div_up(d1->width, TAIL_TILE), gr_div_up(d1->height, TAIL_TILE));
 	const bool b10 = hdr->format == GR_FORMAT_B10G11R11_UFLOAT_PACK32;
 	gr_scoped_timing timing{ctx, gr_to_stream(stream), "bloom_down_head"};
@@ -1475,7 +1471,8 @@ int gr_bloom_down_tail(gr_ctx *ctx, gr_stream stream, const gr_image *d1, const 
 		return GR_ERR_INVALID_ARGUMENT;
 	GR_CHECK_FIT(ctx, down_pair_fits(d1, d2, d3, push_d2, push_d3));
 	// the entry point's own (the query does not see the history): the last level of the pyramid always carries the temporal feedback (hdr.cpp)
-	GR_CHECK_ARG(ctx, is_rgba16f(history) && history->ptr != d3->ptr);
+	GR_CHECK_IMAGE(ctx, history, RGBA16F);
+	GR_CHECK_ARG(ctx, !gr_images_overlap(history, d3));
 	dim3 grid(gr_div_up(d3->width, TAIL_TILE), gr_div_up(d3->height, TAIL_TILE));
 	gr_scoped_timing timing{ctx, gr_to_stream(stream), "bloom_down_tail"};
 	with_flags(
@@ -1531,7 +1528,7 @@ int gr_bloom_up_all(gr_ctx *ctx, gr_stream stream, const gr_image *d3, const gr_
 	if (!ctx)
 		return GR_ERR_INVALID_ARGUMENT;
 	GR_CHECK_FIT(ctx, up_all_fits(d3, u2, u1, u0, push_u2, push_u1, push_u0));
-	GR_CHECK_ARG(ctx, u0->ptr != u1->ptr && u1->ptr != u2->ptr && u2->ptr != d3->ptr); // the entry point's own: the query does not look at the pointers
+	GR_CHECK_ARG(ctx, !gr_images_overlap(u0, u1) && !gr_images_overlap(u1, u2) && !gr_images_overlap(u2, d3)); // the entry point's own: the query does not look at the pointers
 	GR_CHECK_FIT(ctx, luminance_fits(lum, push_lum));
 	dim3 grid(gr_div_up(u0->width, UPALL_TILE), gr_div_up(u0->height, UPALL_TILE));
 	gr_scoped_timing timing{ctx, gr_to_stream(stream), "bloom_up_all"};
@@ -1580,11 +1577,11 @@ int gr_bloom_pyramid(gr_ctx *ctx, gr_stream stream, const gr_bloom_pyramid_args 
 	GR_CHECK_FIT(ctx, up_all_fits(&a->d3, &a->u2, &a->u1, &a->u0, &a->push_u2, &a->push_u1, &a->push_u0));
 	GR_CHECK_FIT(ctx, pyramid_own_fits(a));
 	{
-		// the entry point's own (the queries do not look at the pointers, but for history / downsample-3): one launch, so no two images may alias
-		const void *levels[] = {a->hdr.ptr, a->threshold.ptr, a->d0.ptr, a->d1.ptr, a->d2.ptr, a->d3.ptr, a->u2.ptr, a->u1.ptr, a->u0.ptr, a->history.ptr};
+		// the entry point's own (the queries do not look at the pointers, but for history / downsample-3): one launch, so no two images may share bytes
+		const gr_image *levels[] = {&a->hdr, &a->threshold, &a->d0, &a->d1, &a->d2, &a->d3, &a->u2, &a->u1, &a->u0, &a->history};
 		for (size_t i = 0; i < sizeof(levels) / sizeof(levels[0]); i++)
 			for (size_t j = i + 1; j < sizeof(levels) / sizeof(levels[0]); j++)
-				GR_CHECK_ARG(ctx, levels[i] != levels[j]);
+				GR_CHECK_ARG(ctx, !gr_images_overlap(levels[i], levels[j]));
 	}
 	PyramidArgs k{};
 	k.hdr = to_dev(&a->hdr), k.history = to_dev(&a->history);
@@ -1633,7 +1630,7 @@ int gr_luminance(gr_ctx *ctx, gr_stream stream, const gr_image *in, gr_luminance
 	if (!ctx)
 		return GR_ERR_INVALID_ARGUMENT;
 	GR_CHECK_ARG(ctx, push != nullptr && lum != nullptr);
-	GR_CHECK_ARG(ctx, is_rgba16f(in));
+	GR_CHECK_IMAGE(ctx, in, RGBA16F);
 	GR_CHECK_ARG(ctx, has_texels(push));
 	gr_scoped_timing timing{ctx, gr_to_stream(stream), "luminance"};
 	hipLaunchKernelGGL(k_luminance, dim3(1), dim3(LUM_THREADS), 0, gr_to_stream(stream), to_dev(in), lum, *push);
@@ -1653,12 +1650,13 @@ int gr_tonemap_rows(gr_ctx *ctx, gr_stream stream, const gr_image *hdr, const gr
 	if (!ctx)
 		return GR_ERR_INVALID_ARGUMENT;
 	GR_CHECK_ARG(ctx, push != nullptr);
-	GR_CHECK_ARG(ctx, is_hdr_target(hdr) && is_rgba16f(bloom));
-	GR_CHECK_ARG(ctx, out && out->ptr && out->width == hdr->width && out->height == hdr->height &&
-	                       out->pitch_bytes >= out->width * 4u);
+	GR_CHECK_IMAGE(ctx, hdr, GR_HDR_FORMATS);
+	GR_CHECK_IMAGE(ctx, bloom, RGBA16F);
+	GR_CHECK_ARG(ctx, out != nullptr);
 	const bool srgb = out->format == GR_FORMAT_R8G8B8A8_SRGB;
 	if (!srgb && out->format != GR_FORMAT_R8G8B8A8_UNORM)
 		return ctx->fail(GR_ERR_UNSUPPORTED_FORMAT, "gr_tonemap: output format %u unsupported", out->format);
+	GR_CHECK_IMAGE(ctx, out, GR_RGBA8_FORMATS, hdr->width, hdr->height);
 	const RowSpan span = resolve_rows(rows, hdr->height);
 	if (span.count() == 0)
 		return GR_OK;

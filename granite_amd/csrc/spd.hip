@@ -185,9 +185,8 @@ int gr_spd_downsample(gr_ctx *ctx, gr_stream stream, const gr_spd_args *args)
 {
 	if (!ctx)
 		return GR_ERR_INVALID_ARGUMENT;
-	GR_CHECK_ARG(ctx, args && args->input.ptr && args->chain);
-	GR_CHECK_ARG(ctx, args->input.format == GR_FORMAT_R16G16B16A16_SFLOAT && args->input.width > 0 && args->input.height > 0 &&
-	                      args->input.pitch_bytes >= args->input.width * 8u && (args->input.pitch_bytes & 7u) == 0);
+	GR_CHECK_ARG(ctx, args && args->chain);
+	GR_CHECK_IMAGE(ctx, &args->input, GR_FORMAT_R16G16B16A16_SFLOAT);
 	GR_CHECK_ARG(ctx, args->width > 0 && args->height > 0);
 	GR_CHECK_ARG(ctx, args->mips >= 1 && args->mips <= uint32_t(SPD_MAX_MIPS));
 	GR_CHECK_ARG(ctx, args->components >= 1 && args->components <= 4);

@@ -579,12 +579,6 @@ __global__ __launch_bounds__(256) void k_ssr_apply(ApplyParams p)
 	*dst = d;
 }
 
-bool image_ok(const gr_image &img, uint32_t format, uint32_t bpp, uint32_t w, uint32_t h)
-{
-	return img.ptr && img.format == format && img.width == w && img.height == h && img.pitch_bytes >= w * bpp && (img.pitch_bytes % bpp) == 0;
-}
-DevImage dev(const gr_image &i) { return DevImage{static_cast<const uint8_t *>(i.ptr), int(i.width), int(i.height), i.pitch_bytes}; }
-DevImageRW dev_rw(const gr_image &i) { return DevImageRW{static_cast<uint8_t *>(i.ptr), int(i.width), int(i.height), i.pitch_bytes}; }
 } // namespace
 
 extern "C" {
@@ -601,13 +595,13 @@ int gr_ssr_trace(gr_ctx *ctx, gr_stream stream, const gr_ssr_args *args)
 		return GR_ERR_INVALID_ARGUMENT;
 	GR_CHECK_ARG(ctx, args != nullptr);
 	const uint32_t W = args->output.width, H = args->output.height;
-	GR_CHECK_ARG(ctx, W != 0 && H != 0 && W < 16384u && H < 16384u); // PackRay: 14 bits per coordinate
-	GR_CHECK_ARG(ctx, image_ok(args->output, GR_FORMAT_R16G16B16A16_SFLOAT, 8, W, H));
-	GR_CHECK_ARG(ctx, image_ok(args->ray_length, GR_FORMAT_R16_SFLOAT, 2, W, H));
-	GR_CHECK_ARG(ctx, image_ok(args->ray_confidence, GR_FORMAT_R8_UNORM, 1, W, H));
-	GR_CHECK_ARG(ctx, image_ok(args->light, GR_FORMAT_R16G16B16A16_SFLOAT, 8, W, H));
-	GR_CHECK_ARG(ctx, image_ok(args->normal, GR_FORMAT_A2B10G10R10_UNORM_PACK32, 4, W, H));
-	GR_CHECK_ARG(ctx, image_ok(args->pbr, GR_FORMAT_R8G8_UNORM, 2, W, H));
+	GR_CHECK_IMAGE(ctx, &args->output, GR_FORMAT_R16G16B16A16_SFLOAT);
+	GR_CHECK_ARG(ctx, W < 16384u && H < 16384u); // PackRay: 14 bits per coordinate
+	GR_CHECK_IMAGE(ctx, &args->ray_length, GR_FORMAT_R16_SFLOAT, W, H);
+	GR_CHECK_IMAGE(ctx, &args->ray_confidence, GR_FORMAT_R8_UNORM, W, H);
+	GR_CHECK_IMAGE(ctx, &args->light, GR_FORMAT_R16G16B16A16_SFLOAT, W, H);
+	GR_CHECK_IMAGE(ctx, &args->normal, GR_FORMAT_A2B10G10R10_UNORM_PACK32, W, H);
+	GR_CHECK_IMAGE(ctx, &args->pbr, GR_FORMAT_R8G8_UNORM, W, H);
 	GR_CHECK_ARG(ctx, args->depth_chain && args->chain_levels >= 1 && args->chain_levels <= 16 && args->chain_width >= W && args->chain_height >= H);
 	GR_CHECK_ARG(ctx, args->dither_lut && args->ray_list && args->ray_counter && args->scratch);
 	GR_CHECK_ARG(ctx, args->frame < 64u);
@@ -621,9 +615,9 @@ int gr_ssr_trace(gr_ctx *ctx, gr_stream stream, const gr_ssr_args *args)
 	p.hier_levels = int(args->chain_levels);
 	for (uint32_t l = 0; l < args->chain_levels; l++)
 		p.hier_offset[l] = uint32_t(gr_mip_chain_offset(args->chain_width, args->chain_height, 4, l) / 4);
-	p.pbr = dev(args->pbr);
-	p.normal = dev(args->normal);
-	p.light = dev(args->light);
+	p.pbr = to_dev(&args->pbr);
+	p.normal = to_dev(&args->normal);
+	p.light = to_dev(&args->light);
 	p.noise = static_cast<const uint16_t *>(args->dither_lut);
 	p.azimuth = ctx->ssr_azimuth_lut;
 	p.frame = int(args->frame);
@@ -634,9 +628,9 @@ int gr_ssr_trace(gr_ctx *ctx, gr_stream stream, const gr_ssr_args *args)
 	}
 	for (int i = 0; i < 3; i++)
 		p.camera[i] = args->camera_position[i];
-	p.output = dev_rw(args->output);
-	p.ray_length = dev_rw(args->ray_length);
-	p.confidence = dev_rw(args->ray_confidence);
+	p.output = to_dev_rw(&args->output);
+	p.ray_length = to_dev_rw(&args->ray_length);
+	p.confidence = to_dev_rw(&args->ray_confidence);
 	p.ray_list = args->ray_list;
 	p.ray_counter = args->ray_counter;
 	p.tiles_x = int((W + 7u) / 8u);
@@ -671,23 +665,22 @@ int gr_ssr_apply(gr_ctx *ctx, gr_stream stream, const gr_ssr_apply_args *args)
 		return GR_ERR_INVALID_ARGUMENT;
 	GR_CHECK_ARG(ctx, args != nullptr);
 	const uint32_t W = args->hdr.width, H = args->hdr.height;
-	GR_CHECK_ARG(ctx, W != 0 && H != 0);
-	GR_CHECK_ARG(ctx, image_ok(args->hdr, GR_FORMAT_R16G16B16A16_SFLOAT, 8, W, H));
-	GR_CHECK_ARG(ctx, image_ok(args->reflected, GR_FORMAT_R16G16B16A16_SFLOAT, 8, W, H));
-	GR_CHECK_ARG(ctx, image_ok(args->albedo, GR_FORMAT_R8G8B8A8_SRGB, 4, W, H));
-	GR_CHECK_ARG(ctx, image_ok(args->normal, GR_FORMAT_A2B10G10R10_UNORM_PACK32, 4, W, H));
-	GR_CHECK_ARG(ctx, image_ok(args->pbr, GR_FORMAT_R8G8_UNORM, 2, W, H));
-	GR_CHECK_ARG(ctx, image_ok(args->depth, GR_FORMAT_D32_SFLOAT, 4, W, H));
-	GR_CHECK_ARG(ctx, args->brdf_lut.ptr && args->brdf_lut.format == GR_FORMAT_R16G16_SFLOAT && args->brdf_lut.width && args->brdf_lut.height &&
-	                      args->brdf_lut.pitch_bytes == args->brdf_lut.width * 4u);
+	GR_CHECK_IMAGE(ctx, &args->hdr, GR_FORMAT_R16G16B16A16_SFLOAT);
+	GR_CHECK_IMAGE(ctx, &args->reflected, GR_FORMAT_R16G16B16A16_SFLOAT, W, H);
+	GR_CHECK_IMAGE(ctx, &args->albedo, GR_FORMAT_R8G8B8A8_SRGB, W, H);
+	GR_CHECK_IMAGE(ctx, &args->normal, GR_FORMAT_A2B10G10R10_UNORM_PACK32, W, H);
+	GR_CHECK_IMAGE(ctx, &args->pbr, GR_FORMAT_R8G8_UNORM, W, H);
+	GR_CHECK_IMAGE(ctx, &args->depth, GR_FORMAT_D32_SFLOAT, W, H);
+	GR_CHECK_IMAGE(ctx, &args->brdf_lut, GR_FORMAT_R16G16_SFLOAT);
+	GR_CHECK_ARG(ctx, args->brdf_lut.pitch_bytes == args->brdf_lut.width * 4u); // the kernel indexes the table without a pitch
 	ApplyParams p = {};
 	p.width = int(W);
 	p.height = int(H);
-	p.reflected = dev(args->reflected);
-	p.albedo = dev(args->albedo);
-	p.normal = dev(args->normal);
-	p.pbr = dev(args->pbr);
-	p.depth = dev(args->depth);
+	p.reflected = to_dev(&args->reflected);
+	p.albedo = to_dev(&args->albedo);
+	p.normal = to_dev(&args->normal);
+	p.pbr = to_dev(&args->pbr);
+	p.depth = to_dev(&args->depth);
 	p.brdf_lut = static_cast<const uint16_t *>(args->brdf_lut.ptr);
 	p.lut_w = int(args->brdf_lut.width);
 	p.lut_h = int(args->brdf_lut.height);
@@ -696,7 +689,7 @@ int gr_ssr_apply(gr_ctx *ctx, gr_stream stream, const gr_ssr_apply_args *args)
 		p.inv_vp[i] = args->inv_view_projection[i];
 	for (int i = 0; i < 3; i++)
 		p.camera[i] = args->camera_position[i];
-	p.hdr = dev_rw(args->hdr);
+	p.hdr = to_dev_rw(&args->hdr);
 	gr_scoped_timing timing{ctx, gr_to_stream(stream), "ssr_apply"};
 	hipLaunchKernelGGL(k_ssr_apply, dim3(gr_div_up(W, 32u), gr_div_up(H, 8u)), dim3(256), 0, gr_to_stream(stream), p);
 	GR_CHECK_LAUNCH(ctx);

@@ -158,7 +158,7 @@ extern "C" int gr_texture_decode(gr_ctx *ctx, gr_stream stream, uint32_t block_f
 		return ctx->fail(GR_ERR_UNSUPPORTED_FORMAT, "gr_texture_decode: output format %u is not the decoded format %u of block format %u", out->format,
 		                 gr_texture_decoded_format(block_format), block_format);
 	if (out->width > 65536u || out->height > 65536u)
-		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_texture_decode: extent %u x %u is larger than 65536", out->width, out->height);
+		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_texture_decode: output extent %u x %u is larger than 65536", out->width, out->height);
 	if (out->width == 0 || out->height == 0)
 		return GR_OK;
 	DecodeArgs a = {};
@@ -169,18 +169,17 @@ extern "C" int gr_texture_decode(gr_ctx *ctx, gr_stream stream, uint32_t block_f
 	const uint32_t block_bytes = uint32_t(gr_bc::block_bytes(kind)), texel_bytes = uint32_t(gr_bc::texel_bytes(kind));
 	if (block_row_pitch_bytes < a.blocks_x * block_bytes)
 		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_texture_decode: block row pitch %u is smaller than a row of %u blocks", block_row_pitch_bytes, a.blocks_x);
-	if (out->pitch_bytes < out->width * texel_bytes)
-		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_texture_decode: output pitch %u is smaller than a row of %u texels", out->pitch_bytes, out->width);
+	if (const char *rule = gr_image_layout_rule(out, out->format)) // the kernel stores bytes where the output is not aligned (out_aligned, below)
+		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_texture_decode: invalid argument: output%s", rule);
 	GR_CHECK_ARG(ctx, blocks);
 	GR_CHECK_ARG(ctx, out->ptr);
 	a.blocks = static_cast<const uint8_t *>(blocks);
 	a.out = static_cast<uint8_t *>(out->ptr);
 	a.block_pitch = block_row_pitch_bytes;
 	a.out_pitch = out->pitch_bytes;
-	const auto aligned = [](const void *ptr, uint32_t pitch, uint32_t to) { return (reinterpret_cast<uintptr_t>(ptr) & (to - 1u)) == 0 && (pitch & (to - 1u)) == 0; };
-	a.blocks_aligned = aligned(blocks, block_row_pitch_bytes, block_bytes);
+	a.blocks_aligned = ((reinterpret_cast<uintptr_t>(blocks) | block_row_pitch_bytes) & (block_bytes - 1u)) == 0;
 	const uint32_t row_bytes = 4u * texel_bytes;
-	a.out_aligned = aligned(out->ptr, out->pitch_bytes, row_bytes < 16u ? row_bytes : 16u);
+	a.out_aligned = is_aligned(out, row_bytes < 16u ? row_bytes : 16u);
 
 	hipStream_t s = gr_to_stream(stream);
 	gr_scoped_timing timing{ctx, s, "texture_decode"};

@@ -668,24 +668,6 @@ bool recognized_color_space(uint32_t space)
 	return space == GR_COLOR_SPACE_SRGB_NONLINEAR || space == GR_COLOR_SPACE_HDR10_ST2084 || space == GR_COLOR_SPACE_EXTENDED_SRGB_LINEAR;
 }
 
-uint32_t texel_bytes(uint32_t format)
-{
-	switch (format)
-	{
-	case GR_FORMAT_R8_UNORM: return 1;
-	case GR_FORMAT_R8G8_UNORM:
-	case GR_FORMAT_R16_UNORM: return 2;
-	case GR_FORMAT_R8G8B8A8_UNORM:
-	case GR_FORMAT_R8G8B8A8_SRGB:
-	case GR_FORMAT_B8G8R8A8_UNORM:
-	case GR_FORMAT_B8G8R8A8_SRGB:
-	case GR_FORMAT_A2B10G10R10_UNORM_PACK32:
-	case GR_FORMAT_R16G16_UNORM: return 4;
-	case GR_FORMAT_R16G16B16A16_SFLOAT: return 8;
-	default: return 0;
-	}
-}
-
 bool is_rgba8_output(uint32_t f)
 {
 	return f == GR_FORMAT_R8G8B8A8_UNORM || f == GR_FORMAT_R8G8B8A8_SRGB || f == GR_FORMAT_B8G8R8A8_UNORM || f == GR_FORMAT_B8G8R8A8_SRGB;
@@ -707,8 +689,8 @@ const char *check_plane_layout(const gr_image *planes, uint32_t num_planes, bool
 				return "chroma plane format or size does not match the luma plane";
 	}
 	for (uint32_t i = 0; i < num_planes; i++)
-		if (planes[i].pitch_bytes < planes[i].width * texel_bytes(planes[i].format))
-			return "plane pitch smaller than its row";
+		if (gr_image_layout_rule(&planes[i], planes[i].format))
+			return "a plane's pitch_bytes does not hold its rows";
 	return nullptr;
 }
 
@@ -726,7 +708,7 @@ const char *plan_video(const gr_image *in, const gr_image *planes, uint32_t num_
 	if (in->format != GR_FORMAT_R8G8B8A8_UNORM && in->format != GR_FORMAT_R8G8B8A8_SRGB && in->format != GR_FORMAT_A2B10G10R10_UNORM_PACK32 &&
 	    in->format != GR_FORMAT_R16G16B16A16_SFLOAT)
 		return "input format must be R8G8B8A8_{UNORM,SRGB}, A2B10G10R10_UNORM_PACK32 or R16G16B16A16_SFLOAT";
-	if (!in->width || !in->height || in->width > 65535 || in->height > 65535 || in->pitch_bytes < in->width * texel_bytes(in->format))
+	if (in->width > 65535 || in->height > 65535 || gr_image_layout_rule(in, in->format))
 		return "bad input extent or pitch";
 	const gr_image &y = planes[0];
 	if (!y.width || !y.height || y.width > 65535 || y.height > 65535)
@@ -866,9 +848,9 @@ extern "C" int gr_video_scale(gr_ctx *ctx, gr_stream stream, const gr_image *inp
 	{
 		a.plane[i] = static_cast<uint8_t *>(planes[i].ptr);
 		a.pitch[i] = planes[i].pitch_bytes;
-		a.aligned |= is_aligned16(&planes[i]) ? 1u << i : 0u;
+		a.aligned |= is_aligned(&planes[i], 16u) ? 1u << i : 0u;
 	}
-	a.aligned |= is_aligned16(input) ? 8u : 0u;
+	a.aligned |= is_aligned(input, 16u) ? 8u : 0u;
 	a.out_w = int(planes[0].width);
 	a.out_h = int(planes[0].height);
 	a.chroma_w = num_planes > 1 ? int(planes[1].width) : 0;
@@ -1177,8 +1159,8 @@ const char *plan_yuv(const gr_image *planes, uint32_t num_planes, const gr_image
 		return "PQ content goes to A2B10G10R10 (left encoded) or R16G16B16A16_SFLOAT, everything else to R8G8B8A8";
 	if (out->width != y.width || out->height != y.height)
 		return "the output must have the luma plane's size";
-	if (out->pitch_bytes < out->width * texel_bytes(out->format))
-		return "output pitch smaller than its row";
+	if (gr_image_layout_rule(out, out->format))
+		return "output pitch_bytes does not hold its rows";
 
 	memset(p, 0, sizeof(*p));
 	p->spec_pq = out->format == GR_FORMAT_R16G16B16A16_SFLOAT;
@@ -1293,7 +1275,7 @@ extern "C" int gr_video_yuv_to_rgb(gr_ctx *ctx, gr_stream stream, const gr_image
 	a.ch = num_planes > 1 ? int(planes[1].height) : 0;
 	a.out = static_cast<uint8_t *>(out->ptr);
 	a.out_pitch = out->pitch_bytes;
-	a.aligned = (is_aligned16(&planes[0]) ? 1u : 0u) | (is_aligned16(out) ? 8u : 0u);
+	a.aligned = (is_aligned(&planes[0], 16u) ? 1u : 0u) | (is_aligned(out, 16u) ? 8u : 0u);
 	a.nv21 = plan.spec_nv21;
 	const gr_push_yuv_to_rgb &push = plan.push;
 	for (int row = 0; row < 3; row++)

@@ -74,7 +74,14 @@ typedef enum gr_format
 	GR_FORMAT_BC7_SRGB_BLOCK = 146
 } gr_format;
 
-/* A 2-D attachment as the executor sees it: what Vulkan::ImageView is to the reference's callbacks. */
+/* A 2-D attachment as the executor sees it: what Vulkan::ImageView is to the reference's callbacks.
+ * Every launcher asks the same of an image argument (granite_amd/csrc/image_args.hpp) before anything is launched: the image and its ptr
+ * are not NULL; the format is one the argument takes; width and height are not 0 and match the call's other images where they must;
+ * width * texel size <= pitch_bytes (in 64 bits); pitch_bytes and ptr are multiples of the texel size (gr_video_scale, gr_video_yuv_to_rgb
+ * and gr_texture_decode address bytes and take any alignment).  A broken rule is GR_ERR_INVALID_ARGUMENT, with the argument and the rule in
+ * gr_last_error(); a wrong format alone is GR_ERR_UNSUPPORTED_FORMAT from gr_tonemap, gr_fft_execute, gr_env_equirect_to_cube and
+ * gr_texture_decode.  Where an entry point refuses an output that is its input, it refuses any shared byte of [ptr, ptr + pitch_bytes *
+ * height).  Limits of a single kernel (a largest extent, 16-byte alignment for a faster path) are documented at its entry point. */
 typedef struct gr_image
 {
 	void *ptr;            /* device pointer */

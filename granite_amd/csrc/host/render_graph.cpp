@@ -327,9 +327,6 @@ void RenderGraph::install_persistent_physical_buffer_resource(unsigned index, HI
 
 RenderGraph::~RenderGraph()
 {
-	for (void *e : pass_done_event)
-		if (e)
-			(void)hipEventDestroy(static_cast<hipEvent_t>(e));
 	for (void *e : event_pool)
 		if (e)
 			(void)hipEventDestroy(static_cast<hipEvent_t>(e));
@@ -823,6 +820,7 @@ void RenderGraph::bake()
 	                     backbuffer_dim.format == swapchain_dimensions.format;
 	bool has_history = physical_image_has_history[backbuffer_phys];
 	swapchain_physical_index = (same_geometry && !has_history) ? backbuffer_phys : unsigned(RenderResource::Unused);
+	blit_source_physical_index = swapchain_physical_index == RenderResource::Unused ? backbuffer_phys : unsigned(RenderResource::Unused);
 	build_physical_passes();
 	build_stream_assignment();
 	build_aliases();
@@ -875,12 +873,6 @@ void RenderGraph::setup_attachments(HIP::Device &device_, HIP::ImageView *swapch
 		v.resize(count);
 	for (auto &v : physical_images_alternate)
 		v.resize(count);
-	if (physical_sync.size() != count)
-	{
-		physical_sync.assign(count, {});
-		for (auto &v : physical_sync_alternate)
-			v.assign(count, {});
-	}
 	swapchain_attachment = swapchain;
 
 	for (unsigned i = 0; i < count; i++)
@@ -893,29 +885,11 @@ void RenderGraph::setup_attachments(HIP::Device &device_, HIP::ImageView *swapch
 		auto &att = physical_dimensions[i];
 		if (physical_buffer_is_double_buffered(i))
 		{
-			// rotate: current -> newest spare, oldest spare -> current
-			constexpr int spares = HandOverCopies - 1;
 			if (att.buffer_info.size != 0)
-			{
-				auto current = physical_buffers[i];
-				physical_buffers[i] = physical_buffers_alternate[0][i];
-				for (int k = 0; k + 1 < spares; k++)
-					physical_buffers_alternate[k][i] = physical_buffers_alternate[k + 1][i];
-				physical_buffers_alternate[spares - 1][i] = current;
-			}
+				rotate_hand_over(physical_buffers, physical_buffers_alternate, i);
 			else
-			{
-				auto current = physical_image_attachments[i];
-				physical_image_attachments[i] = physical_images_alternate[0][i];
-				for (int k = 0; k + 1 < spares; k++)
-					physical_images_alternate[k][i] = physical_images_alternate[k + 1][i];
-				physical_images_alternate[spares - 1][i] = current;
-			}
-			auto current_sync = physical_sync[i];
-			physical_sync[i] = physical_sync_alternate[0][i];
-			for (int k = 0; k + 1 < spares; k++)
-				physical_sync_alternate[k][i] = physical_sync_alternate[k + 1][i];
-			physical_sync_alternate[spares - 1][i] = current_sync;
+				rotate_hand_over(physical_image_attachments, physical_images_alternate, i);
+			hazards.rotate(i);
 		}
 		if ((att.flags & ATTACHMENT_INFO_INTERNAL_PROXY_BIT) != 0)
 			continue;
@@ -970,11 +944,6 @@ void *RenderGraph::acquire_event()
 
 void RenderGraph::build_stream_assignment()
 {
-	pass_stream.assign(passes.size(), 0);
-	pass_reads_physical.assign(passes.size(), {});
-	pass_writes_physical.assign(passes.size(), {});
-	uses_async_stream = false;
-
 	auto add = [](std::vector<unsigned> &list, const RenderResource *res) {
 		if (!res || res->get_physical_index() == RenderResource::Unused)
 			return;
@@ -982,11 +951,14 @@ void RenderGraph::build_stream_assignment()
 			list.push_back(res->get_physical_index());
 	};
 
+	std::vector<StreamPlan::Pass> baked;
+	std::vector<std::string> pass_names;
 	for (unsigned pass_index : pass_stack)
 	{
 		auto &pass = *passes[pass_index];
-		auto &reads = pass_reads_physical[pass_index];
-		auto &writes = pass_writes_physical[pass_index];
+		baked.emplace_back();
+		auto &reads = baked.back().reads;
+		auto &writes = baked.back().writes;
 		for (auto *r : pass.get_color_inputs()) add(reads, r);
 		for (auto *r : pass.get_color_scale_inputs()) add(reads, r);
 		for (auto *r : pass.get_storage_texture_inputs()) add(reads, r);
@@ -1006,212 +978,34 @@ void RenderGraph::build_stream_assignment()
 		for (auto *r : pass.get_transfer_outputs()) add(writes, r);
 		add(writes, pass.get_depth_stencil_output());
 
-		pass_stream[pass_index] = (pass.get_queue() & RENDER_GRAPH_QUEUE_ASYNC_COMPUTE_BIT) != 0 ? 1 : 0;
+		baked.back().async_compute_queue = (pass.get_queue() & RENDER_GRAPH_QUEUE_ASYNC_COMPUTE_BIT) != 0;
+		baked.back().has_history_inputs = !pass.get_history_inputs().empty();
+		baked.back().conditional = pass.may_not_need_render_pass();
+		pass_names.push_back(pass.get_name());
 	}
 
-	// Frame pipelining (HIP executor policy, set_hoist_independent_compute): the "front" of a frame is every pass that
-	// does not depend, directly or through other passes, on anything carried over from the previous frame (history
-	// inputs, buffers that are read before they are written within the frame) -- cluster build, G-buffer, lighting.  The
-	// front runs on the second stream, so the front of frame N+1 executes while the back of frame N (bloom pyramid with
-	// its feedback, exposure, tonemap, AA) is still in flight on the first stream.
-	std::vector<bool> front(passes.size(), false);
-	if (hoist_independent_compute)
+	std::vector<StreamPlan::Resource> plan_resources(physical_dimensions.size());
+	std::vector<std::string> resource_names;
+	for (size_t i = 0; i < physical_dimensions.size(); i++)
 	{
-		std::vector<int> first_writer(physical_dimensions.size(), -1), any_writer(physical_dimensions.size(), 0);
-		std::vector<int> order(passes.size(), -1);
-		int position = 0;
-		for (unsigned pass_index : pass_stack)
-		{
-			order[pass_index] = position++;
-			for (unsigned w : pass_writes_physical[pass_index])
-			{
-				if (first_writer[w] < 0)
-					first_writer[w] = int(pass_index);
-				any_writer[w]++;
-			}
-		}
-		std::vector<bool> written_by_back(physical_dimensions.size(), false);
-		bool any_back = false;
-		for (unsigned pass_index : pass_stack)
-		{
-			auto &pass = *passes[pass_index];
-			bool ok = pass_stream[pass_index] == 0 && pass.get_history_inputs().empty() && !pass_writes_physical[pass_index].empty();
-			for (unsigned w : pass_writes_physical[pass_index])
-				ok = ok && w != swapchain_physical_index && !physical_image_has_history[w];
-			for (unsigned r : pass_reads_physical[pass_index])
-			{
-				// Every producer of what it reads must already have run in this frame, on the front.
-				const bool produced_before = first_writer[r] >= 0 && order[first_writer[r]] < order[pass_index];
-				const bool rmw_of_own_output = std::find(pass_writes_physical[pass_index].begin(), pass_writes_physical[pass_index].end(), r) !=
-				                               pass_writes_physical[pass_index].end();
-				ok = ok && !written_by_back[r] && (produced_before || (any_writer[r] == 0)) && !(rmw_of_own_output && first_writer[r] == int(pass_index));
-			}
-			front[pass_index] = ok;
-			if (!ok)
-			{
-				any_back = true;
-				for (unsigned w : pass_writes_physical[pass_index])
-					written_by_back[w] = true;
-			}
-		}
-		if (!any_back) // nothing to overlap with: keep the whole frame on one stream
-			front.assign(passes.size(), false);
-	}
-	for (unsigned pass_index : pass_stack)
-	{
-		if (front[pass_index])
-			pass_stream[pass_index] = pass_reads_physical[pass_index].empty() ? 1 : 2;
-		uses_async_stream = uses_async_stream || pass_stream[pass_index] != 0;
+		plan_resources[i].is_buffer = physical_dimensions[i].buffer_info.size != 0;
+		plan_resources[i].has_history = physical_image_has_history[i];
+		resource_names.push_back(physical_dimensions[i].name);
 	}
 
-	// The tail: the longest run of passes at the end of the baked order that (a) stand on the generic stream, (b) write nothing the next
-	// frame reads (no image with history, nothing read before it is written within the frame: bloom's feedback, exposure) and (c) whose
-	// first pass -- and with it the whole run -- takes exactly ONE physical resource from the passes in front of it.  For the application's
-	// graphs that is post-tonemap anti-aliasing reading `tonemapped`; a frame that ends with the tonemap has no tail.  Frame N's tail then
-	// runs beside frame N + 1's back instead of in front of it (the passes of the tail depend on nothing frame N + 1 produces and
-	// produce nothing it consumes): TAA resolve N + 1 no longer queues behind SMAA N.
-	// (a frame that ends in a blit to the swapchain keeps its end on the generic stream, where the blit is)
-	if (hoist_independent_compute && split_tail && uses_async_stream && swapchain_physical_index != RenderResource::Unused)
-	{
-		std::vector<bool> carried(physical_dimensions.size(), false); // read by some pass before any pass of the frame has written it
-		{
-			std::vector<bool> written(physical_dimensions.size(), false);
-			for (unsigned pass_index : pass_stack)
-			{
-				for (unsigned r : pass_reads_physical[pass_index])
-					if (!written[r])
-						carried[r] = true;
-				for (unsigned w : pass_writes_physical[pass_index])
-					written[w] = true;
-			}
-		}
-		// the longest suffix satisfying (a) and (b)
-		size_t begin = pass_stack.size();
-		while (begin > 0)
-		{
-			const unsigned pass_index = pass_stack[begin - 1];
-			bool ok = pass_stream[pass_index] == 0 && passes[pass_index]->get_history_inputs().empty() && !passes[pass_index]->may_not_need_render_pass();
-			for (unsigned w : pass_writes_physical[pass_index])
-				ok = ok && !physical_image_has_history[w] && !carried[w] && physical_dimensions[w].buffer_info.size == 0;
-			if (!ok)
-				break;
-			begin--;
-		}
-		// (c): shrink from the front until what crosses into the run is one image, written once, by a back pass
-		for (; begin < pass_stack.size(); begin++)
-		{
-			std::vector<bool> inside(physical_dimensions.size(), false);
-			for (size_t i = begin; i < pass_stack.size(); i++)
-				for (unsigned w : pass_writes_physical[pass_stack[i]])
-					inside[w] = true;
-			std::vector<unsigned> crossing;
-			for (size_t i = begin; i < pass_stack.size(); i++)
-				for (unsigned r : pass_reads_physical[pass_stack[i]])
-					if (!inside[r] && std::find(crossing.begin(), crossing.end(), r) == crossing.end())
-						crossing.push_back(r);
-			if (crossing.size() != 1)
-				continue;
-			unsigned writers = 0;
-			bool back_writer = true;
-			for (size_t i = 0; i < begin; i++)
-				for (unsigned w : pass_writes_physical[pass_stack[i]])
-					if (w == crossing[0])
-					{
-						writers++;
-						back_writer = back_writer && pass_stream[pass_stack[i]] == 0;
-					}
-			const auto &dim = physical_dimensions[crossing[0]];
-			if (writers == 1 && back_writer && dim.buffer_info.size == 0 && !physical_image_has_history[crossing[0]] && !carried[crossing[0]] &&
-			    crossing[0] != swapchain_physical_index)
-				break;
-		}
-		// ... and something must be left in front of it on the generic stream for the run to overlap with
-		bool back_in_front = false;
-		for (size_t i = 0; i < begin && i < pass_stack.size(); i++)
-			back_in_front = back_in_front || pass_stream[pass_stack[i]] == 0;
-		if (back_in_front)
-			for (size_t i = begin; i < pass_stack.size(); i++)
-				pass_stream[pass_stack[i]] = 3;
-	}
-	physical_sync.assign(physical_dimensions.size(), {});
-	for (auto &v : physical_sync_alternate)
-		v.assign(physical_dimensions.size(), {});
+	StreamPlan::Options options;
+	options.hoist_independent_compute = hoist_independent_compute;
+	options.split_tail = split_tail;
+	options.front_alternates = device && device->front_alternates();
+	stream_plan.build(std::move(baked), plan_resources, swapchain_physical_index, blit_source_physical_index, options);
+	hazards.reset(std::move(resource_names), std::move(pass_names));
+}
 
-	// Only passes that touch a resource which is also touched from the other stream take part in event ordering; every
-	// other pass is ordered by its in-order stream alone and records nothing (event / barrier packets are not free:
-	// each one is a command-processor round trip between two kernels).
-	pass_needs_sync.assign(passes.size(), false);
-	blit_needs_sync = false;
-	if (uses_async_stream)
-	{
-		std::vector<uint8_t> touched(physical_dimensions.size(), 0); // bit s: touched from stream s
-		auto several = [](uint8_t bits) { return (bits & (bits - 1)) != 0; };
-		for (unsigned pass_index : pass_stack)
-		{
-			const uint8_t bit = uint8_t(1u << pass_stream[pass_index]);
-			for (unsigned r : pass_reads_physical[pass_index])
-				touched[r] |= bit;
-			for (unsigned w : pass_writes_physical[pass_index])
-				touched[w] |= bit;
-		}
-		if (swapchain_physical_index == RenderResource::Unused)
-		{
-			auto itr = resource_to_index.find(backbuffer_source);
-			if (itr != resource_to_index.end() && resources[itr->second]->get_physical_index() != RenderResource::Unused)
-			{
-				touched[resources[itr->second]->get_physical_index()] |= 1; // final blit runs on the generic stream
-				blit_needs_sync = several(touched[resources[itr->second]->get_physical_index()]);
-			}
-		}
-		for (unsigned pass_index : pass_stack)
-		{
-			bool shared = false;
-			for (unsigned r : pass_reads_physical[pass_index])
-				shared = shared || several(touched[r]);
-			for (unsigned w : pass_writes_physical[pass_index])
-				shared = shared || several(touched[w]);
-			// The front's stream alternates with the frame's parity (HIP::Device): what two front passes of different frames share (the
-			// G-buffer targets a producer pass rewrites three frames after the lighting pass read them) is ordered by events too.
-			pass_needs_sync[pass_index] = shared || (pass_stream[pass_index] == 2 && device && device->front_alternates());
-		}
-	}
-
-	// What the front writes and the back reads exists twice and alternates per frame (like an image with history), so the
-	// front of frame N+1 never waits for the back of frame N to finish reading: write-after-read across frames disappears.
-	// Only resources with a single writer qualify (every byte the back reads is rewritten by the front each frame).
-	physical_buffer_double.assign(physical_dimensions.size(), false);
-	{
-		std::vector<unsigned> writers(physical_dimensions.size(), 0);
-		std::vector<uint8_t> reader_streams(physical_dimensions.size(), 0);
-		for (unsigned pass_index : pass_stack)
-		{
-			for (unsigned w : pass_writes_physical[pass_index])
-				writers[w]++;
-			for (unsigned r : pass_reads_physical[pass_index])
-				reader_streams[r] |= uint8_t(1u << pass_stream[pass_index]);
-		}
-		if (swapchain_physical_index == RenderResource::Unused)
-		{
-			auto itr = resource_to_index.find(backbuffer_source);
-			if (itr != resource_to_index.end() && resources[itr->second]->get_physical_index() != RenderResource::Unused)
-				reader_streams[resources[itr->second]->get_physical_index()] |= 1;
-		}
-		bool has_tail = false;
-		for (unsigned pass_index : pass_stack)
-			has_tail = has_tail || pass_stream[pass_index] == 3;
-		for (unsigned pass_index : pass_stack)
-		{
-			// ... and what the back hands to the tail (`tonemapped`), for the same reason one stage further down the frame
-			const bool hands_to_tail = has_tail && pass_stream[pass_index] == 0;
-			if (front[pass_index] || hands_to_tail)
-				for (unsigned w : pass_writes_physical[pass_index])
-				{
-					const uint8_t others = reader_streams[w] & ~uint8_t(1u << pass_stream[pass_index]);
-					if (writers[w] == 1 && (front[pass_index] ? others != 0 : (others & uint8_t(1u << 3)) != 0))
-						physical_buffer_double[w] = true;
-				}
-		}
-	}
+StreamType RenderGraph::get_pass_stream(unsigned pass_index) const
+{
+	const auto itr = std::find(pass_stack.begin(), pass_stack.end(), pass_index);
+	const size_t position = size_t(itr - pass_stack.begin());
+	return position < stream_plan.pass_stream.size() ? stream_plan.pass_stream[position] : StreamType::Generic;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1365,28 +1159,29 @@ void RenderGraph::build_aliases()
 		return;
 
 	std::vector<Range> ranges(count);
-	auto reader = [&](const RenderTextureResource *res, unsigned position, unsigned stream) {
+	auto reader = [&](const RenderTextureResource *res, unsigned position, StreamType stream) {
 		if (!res || res->get_physical_index() == RenderResource::Unused)
 			return;
 		auto &r = ranges[res->get_physical_index()];
 		r.first_read = std::min(r.first_read, position);
 		r.last_read = std::max(r.last_read, position);
-		r.streams |= uint8_t(1u << stream);
+		r.streams |= stream_bit(stream);
 	};
-	auto writer = [&](const RenderTextureResource *res, unsigned position, unsigned stream, bool block) {
+	auto writer = [&](const RenderTextureResource *res, unsigned position, StreamType stream, bool block) {
 		if (!res || res->get_physical_index() == RenderResource::Unused)
 			return;
 		auto &r = ranges[res->get_physical_index()];
 		r.first_write = std::min(r.first_write, position);
 		r.last_write = std::max(r.last_write, position);
 		r.block_alias = r.block_alias || block;
-		r.streams |= uint8_t(1u << stream);
+		r.streams |= stream_bit(stream);
 	};
 
-	for (unsigned pass_index : pass_stack)
+	for (size_t stack_index = 0; stack_index < pass_stack.size(); stack_index++)
 	{
+		const unsigned pass_index = pass_stack[stack_index];
 		auto &pass = *passes[pass_index];
-		const unsigned stream = pass_stream[pass_index];
+		const StreamType stream = stream_plan.pass_stream[stack_index];
 		const unsigned position = pass_physical_pass[pass_index];
 		for (auto *in : pass.get_color_inputs()) reader(in, position, stream);
 		for (auto *in : pass.get_color_scale_inputs()) reader(in, position, stream);
@@ -1402,18 +1197,11 @@ void RenderGraph::build_aliases()
 		for (auto *out : pass.get_storage_texture_outputs()) writer(out, position, stream, true);
 	}
 
-	unsigned blit_source = RenderResource::Unused;
-	if (swapchain_physical_index == RenderResource::Unused)
-	{
-		auto itr = resource_to_index.find(backbuffer_source);
-		if (itr != resource_to_index.end())
-			blit_source = resources[itr->second]->get_physical_index();
-	}
 	auto eligible = [&](unsigned i) {
 		const uint8_t s = ranges[i].streams;
 		return physical_dimensions[i].buffer_info.size == 0 && !physical_image_has_history[i] && i != swapchain_physical_index &&
 		       (physical_dimensions[i].flags & ATTACHMENT_INFO_INTERNAL_RETAINED_BIT) == 0 &&
-		       i != blit_source && !physical_buffer_double[i] && s != 0 && (s & (s - 1)) == 0;
+		       i != blit_source_physical_index && !stream_plan.physical_buffer_double[i] && s != 0 && (s & (s - 1)) == 0;
 	};
 
 	std::vector<std::vector<unsigned>> sharing(count); // owner -> images living in its allocation (owner first)
@@ -1446,158 +1234,17 @@ void RenderGraph::build_aliases()
 void RenderGraph::enqueue_render_passes(HIP::Device &device_, TaskComposer &composer)
 {
 	GRANITE_SCOPED_TIMELINE_EVENT("enqueue-render-passes");
-	const size_t ring_slot = size_t(frame_counter++ % EventRing);
-	if (pass_done_event.size() < (passes.size() + 1) * EventRing)
-		pass_done_event.resize((passes.size() + 1) * EventRing, nullptr);
-	if (physical_sync.size() != physical_dimensions.size())
-	{
-		physical_sync.assign(physical_dimensions.size(), {});
-		for (auto &v : physical_sync_alternate)
-			v.assign(physical_dimensions.size(), {});
-	}
-
-	static const bool sync_debug = getenv("GRANITE_SYNC_DEBUG") != nullptr;
-	const uint64_t this_frame = frame_counter - 1;
-	// The runs published under the device's frame fences stay named for EventRing frames on the assumption that the device's ring and this
-	// one advance together: one next_frame_context() per enqueued frame.  A caller that rotates the device faster only makes waits
-	// stricter (a fence re-recorded early is a later point of its stream), i.e. costs barrier packets, never correctness: say so once.
-	if (sync_debug && last_device_frame != 0 && device_.get_frame_number() != last_device_frame + 1)
-	{
-		static bool told = false;
-		if (!told)
-			fprintf(stderr, "[sync] the device advanced %llu frame contexts between two enqueued frames: published fences are re-recorded early (stricter waits)\n",
-			        (unsigned long long)(device_.get_frame_number() - last_device_frame));
-		told = true;
-	}
-	last_device_frame = device_.get_frame_number();
-	int current_pass = -1;
-	std::vector<void *> waited;
-	const uint64_t device_completed = device_.get_completed_frame();
-	auto wait_for = [&](hipStream_t stream, void *event, const char *kind = "", unsigned resource = 0, int src_pass = -1, uint64_t src_frame = 0,
-	                    uint64_t src_device_frame = 0) {
-		if (!event || std::find(waited.begin(), waited.end(), event) != waited.end())
-			return;
-		// recorded in a frame the host has already waited for (frame pacing: three frames back with the default lead): complete, no call at all
-		// -- the write-after-read dependencies on the rotating copies' previous users are all of this kind
-		if (src_device_frame != 0 && src_device_frame <= device_completed)
-			return;
-		waited.push_back(event);
-		// The host runs one to two frames ahead of the GPU (Device::next_frame_context), so most cross-stream dependencies (anything on work of two
-		// frames ago, usually the cluster build as well) are already complete when they are looked at: no barrier packet
-		// is needed then, and each one costs the command processor several microseconds between two kernels.
-		if (hipEventQuery(static_cast<hipEvent_t>(event)) == hipSuccess)
-			return;
-		if (sync_debug)
-			fprintf(stderr, "[sync] frame %llu pass %s waits %s on %s: pass %s of frame %llu\n", (unsigned long long)this_frame,
-			        current_pass >= 0 ? passes[current_pass]->get_name().c_str() : "blit", kind, physical_dimensions[resource].name.c_str(),
-			        src_pass >= 0 && src_pass < int(passes.size()) ? passes[src_pass]->get_name().c_str() : "?", (unsigned long long)src_frame);
-		if (hipStreamWaitEvent(stream, static_cast<hipEvent_t>(event), 0) != hipSuccess)
-			throw std::runtime_error("cross-queue dependency failed");
-	};
-	// RAW / WAW / WAR against accesses recorded on the other stream.
-	// (An access of the same stream type is ordered by the stream itself -- unless the type's stream alternates with the frame's parity, the
-	// front's, and the access was recorded in a frame of the other parity: the device says, frame numbers being the device's.)
-	const uint64_t device_frame = device_.get_frame_number();
-	auto in_order_with = [&](int stream_index, int other_index, uint64_t other_device_frame) {
-		return other_index == stream_index && device_.same_stream(HIP::CommandBuffer::Type(stream_index), device_frame, other_device_frame);
-	};
-	auto acquire = [&](hipStream_t stream, int stream_index, const std::vector<unsigned> &reads, const std::vector<unsigned> &writes) {
-		for (unsigned r : reads)
-			if (physical_sync[r].last_write && !in_order_with(stream_index, physical_sync[r].write_stream, physical_sync[r].write_device_frame))
-				wait_for(stream, physical_sync[r].last_write, "RAW", r, physical_sync[r].write_pass, physical_sync[r].write_frame, physical_sync[r].write_device_frame);
-		for (unsigned w : writes)
-		{
-			if (physical_sync[w].last_write && !in_order_with(stream_index, physical_sync[w].write_stream, physical_sync[w].write_device_frame))
-				wait_for(stream, physical_sync[w].last_write, "WAW", w, physical_sync[w].write_pass, physical_sync[w].write_frame, physical_sync[w].write_device_frame);
-			for (int other = 0; other < StreamCount; other++)
-				if (!in_order_with(stream_index, other, physical_sync[w].read_device_frame[other]))
-					wait_for(stream, physical_sync[w].last_read[other], "WAR", w, physical_sync[w].read_pass[other], physical_sync[w].read_frame[other],
-					         physical_sync[w].read_device_frame[other]);
-		}
-	};
-	// One event per RUN of consecutive passes on the same stream (not per pass): the accesses of every pass of the run are
-	// published under the run's event, which is recorded once, after the run's last pass and before any pass of another
-	// stream is enqueued.  Fewer packets between kernels: each event record / wait costs the command processor several
-	// microseconds (measured: 23 us of a 283 us frame with one record per pass).
-	auto ensure_event = [&](void *&event) {
-		if (!event)
-		{
-			hipEvent_t e;
-			// ordering between streams of this device only: no system-scope fence (GRANITE_SYNC_EVENT_SYSTEM_FENCE=1 restores it)
-			static const unsigned flags = hipEventDisableTiming | (getenv("GRANITE_SYNC_EVENT_SYSTEM_FENCE") ? 0u : unsigned(hipEventDisableSystemFence));
-			if (hipEventCreateWithFlags(&e, flags) != hipSuccess)
-				throw std::runtime_error("hipEventCreate failed");
-			event = e;
-		}
-	};
-	auto release = [&](int stream_index, void *event, const std::vector<unsigned> &reads, const std::vector<unsigned> &writes) {
-		for (unsigned r : reads)
-		{
-			physical_sync[r].last_read[stream_index] = event;
-			physical_sync[r].read_pass[stream_index] = current_pass;
-			physical_sync[r].read_frame[stream_index] = this_frame;
-			physical_sync[r].read_device_frame[stream_index] = device_frame;
-		}
-		for (unsigned w : writes)
-		{
-			physical_sync[w].last_write = event;
-			physical_sync[w].write_stream = stream_index;
-			physical_sync[w].write_pass = current_pass;
-			physical_sync[w].write_frame = this_frame;
-			physical_sync[w].write_device_frame = device_frame;
-			for (auto &read : physical_sync[w].last_read)
-				read = nullptr;
-		}
-	};
-
-	static const HIP::CommandBuffer::Type stream_types[StreamCount] = {HIP::CommandBuffer::Type::Generic, HIP::CommandBuffer::Type::AsyncCompute,
-	                                                                    HIP::CommandBuffer::Type::Front, HIP::CommandBuffer::Type::Tail};
-	static_assert(int(HIP::CommandBuffer::Type::Count) == StreamCount, "one hazard-tracking slot per executor stream");
-	int run_stream = -1;        // stream of the run being enqueued
-	unsigned run_slot = 0;      // index of the run within the frame (event ring row)
-	bool run_published = false; // a pass of the run published accesses under the run's event
-	static_assert(unsigned(EventRing) == HIP::Device::FrameFenceRing, "a run published under a device fence must stay named for as long as one under the graph's own events");
-	// The last run a frame puts on a stream publishes under the DEVICE's fence of that stream and frame (the staging ring's, same depth as
-	// EventRing) and records it here: the fence next_frame_context() would otherwise record right behind the run's own event.
-	// Which run that is: a dry pass over the frame's passes (need_render_pass is asked once per pass and frame).
-	std::vector<char> pass_runs(pass_stack.size(), 0);
-	int last_run_of_stream[StreamCount] = {-1, -1, -1, -1};
-	{
-		int stream_of_run = -1, run = 0;
-		for (size_t i = 0; i < pass_stack.size(); i++)
-		{
-			auto &pass = *passes[pass_stack[i]];
-			pass_runs[i] = !(pass.may_not_need_render_pass() && !pass.need_render_pass());
-			if (!pass_runs[i])
-				continue;
-			if (int(get_pass_stream(pass_stack[i])) != stream_of_run)
-			{
-				stream_of_run = int(get_pass_stream(pass_stack[i]));
-				run++;
-			}
-			last_run_of_stream[stream_of_run] = run;
-		}
-	}
 	const bool blit_follows = swapchain_attachment && swapchain_physical_index == RenderResource::Unused;
-	auto run_event = [&]() -> void * {
-		// (the final blit goes behind the generic stream's last run: that run keeps its own event, the fence is recorded behind the blit)
-		if (int(run_slot) == last_run_of_stream[run_stream] && !(blit_follows && stream_types[run_stream] == HIP::CommandBuffer::Type::Generic))
-			return device_.frame_fence(stream_types[run_stream]);
-		void *&event = pass_done_event[run_slot * EventRing + ring_slot];
-		ensure_event(event);
-		return event;
-	};
-	auto close_run = [&]() {
-		if (run_stream >= 0 && run_published)
-		{
-			void *event = run_event();
-			if (event == device_.frame_fence(stream_types[run_stream]))
-				device_.record_frame_fence(stream_types[run_stream]);
-			else if (hipEventRecord(static_cast<hipEvent_t>(event), static_cast<hipStream_t>(device_.get_stream(stream_types[run_stream]))) != hipSuccess)
-				throw std::runtime_error("hipEventRecord failed");
-		}
-		run_published = false;
-	};
+	hazards.begin_frame(device_, pass_stack.size(), blit_follows);
+	// Which passes run this frame (need_render_pass is asked once per pass and frame), told to the tracker before the first is enqueued.
+	std::vector<char> pass_runs(pass_stack.size(), 0);
+	for (size_t i = 0; i < pass_stack.size(); i++)
+	{
+		auto &pass = *passes[pass_stack[i]];
+		pass_runs[i] = !(pass.may_not_need_render_pass() && !pass.need_render_pass());
+		if (pass_runs[i])
+			hazards.expect_pass(stream_plan.pass_stream[i]);
+	}
 
 	for (size_t stack_index = 0; stack_index < pass_stack.size(); stack_index++)
 	{
@@ -1607,15 +1254,10 @@ void RenderGraph::enqueue_render_passes(HIP::Device &device_, TaskComposer &comp
 			continue;
 		pass.prepare_render_pass(composer);
 
-		auto type = stream_types[get_pass_stream(pass_index)];
+		const StreamType type = stream_plan.pass_stream[stack_index];
+		const auto &accesses = stream_plan.passes[stack_index];
 		auto stream = static_cast<hipStream_t>(device_.get_stream(type));
-		if (int(get_pass_stream(pass_index)) != run_stream)
-		{
-			close_run();
-			run_stream = int(get_pass_stream(pass_index));
-			run_slot++; // rows 1 .. (number of runs <= number of passes); row 0 belongs to the final blit
-			waited.clear();
-		}
+		hazards.enter_pass(type, int(stack_index));
 		// Measurement hook (tests/test_gpu_graph_random.py shows that the waits matter): frames are WRONG with it, so
 		// honouring it is announced on stderr instead of corrupting output silently through an inherited environment.
 		static const bool no_cross_sync = []() {
@@ -1625,10 +1267,9 @@ void RenderGraph::enqueue_render_passes(HIP::Device &device_, TaskComposer &comp
 				                "DISABLED, rendered frames are not valid.\n");
 			return off;
 		}();
-		const bool sync = uses_async_stream && pass_needs_sync[pass_index] && !no_cross_sync;
-		current_pass = int(pass_index);
+		const bool sync = stream_plan.uses_async_stream && stream_plan.pass_needs_sync[stack_index] && !no_cross_sync;
 		if (sync)
-			acquire(stream, int(type), pass_reads_physical[pass_index], pass_writes_physical[pass_index]);
+			hazards.acquire(accesses.reads, accesses.writes);
 
 		HIP::CommandBuffer cmd{device_, stream, type};
 
@@ -1667,44 +1308,31 @@ void RenderGraph::enqueue_render_passes(HIP::Device &device_, TaskComposer &comp
 			pending_timestamps.push_back(ts);
 		}
 		if (sync)
-		{
-			release(int(type), run_event(), pass_reads_physical[pass_index], pass_writes_physical[pass_index]);
-			run_published = true;
-		}
+			hazards.release(accesses.reads, accesses.writes);
 	}
-	close_run();
 
 	// Backbuffer could not alias the swapchain image: final blit.  Same geometry only; R8G8B8A8 UNORM <-> SRGB is a byte
 	// copy (the stored bytes are the gamma-space colour either way -- e.g. the un-sharpened FSR output, aa.cpp:80-84.  The
 	// reference's scale pass, render_graph.cpp:2557-2566, would sample the UNORM view and let the sRGB store encode again).
-	if (swapchain_attachment && swapchain_physical_index == RenderResource::Unused)
+	if (blit_follows)
 	{
-		const unsigned src_index = resources[resource_to_index[backbuffer_source]]->get_physical_index();
+		hazards.enter_blit(); // a run of its own behind the last run of passes, which is recorded here
+		const unsigned src_index = blit_source_physical_index;
 		auto &src = get_physical_texture_resource(src_index);
 		auto rgba8 = [](VkFormat f) { return f == VK_FORMAT_R8G8B8A8_UNORM || f == VK_FORMAT_R8G8B8A8_SRGB; };
 		const bool same_texels = src.get_format() == swapchain_attachment->get_format() || (rgba8(src.get_format()) && rgba8(swapchain_attachment->get_format()));
 		if (src.get_width() != swapchain_attachment->get_width() || src.get_height() != swapchain_attachment->get_height() || !same_texels)
 			throw std::logic_error("Backbuffer source does not match the swapchain; scaling blits are not implemented.");
-		HIP::CommandBuffer cmd{device_, device_.get_stream(HIP::CommandBuffer::Type::Generic), HIP::CommandBuffer::Type::Generic};
-		auto stream = static_cast<hipStream_t>(cmd.get_stream());
+		HIP::CommandBuffer cmd{device_, device_.get_stream(StreamType::Generic), StreamType::Generic};
 		const std::vector<unsigned> reads = {src_index}, none;
-		const bool sync = uses_async_stream && blit_needs_sync;
-		current_pass = -1;
+		const bool sync = stream_plan.uses_async_stream && stream_plan.blit_needs_sync;
 		if (sync)
-		{
-			waited.clear();
-			acquire(stream, int(HIP::CommandBuffer::Type::Generic), reads, none);
-		}
+			hazards.acquire(reads, none);
 		cmd.copy_image(*swapchain_attachment, src);
 		if (sync)
-		{
-			void *&event = pass_done_event[0 * EventRing + ring_slot]; // row 0 is reserved for the blit
-			ensure_event(event);
-			release(int(HIP::CommandBuffer::Type::Generic), event, reads, none);
-			if (hipEventRecord(static_cast<hipEvent_t>(event), stream) != hipSuccess)
-				throw std::runtime_error("hipEventRecord failed");
-		}
+			hazards.release(reads, none);
 	}
+	hazards.end_frame();
 
 	device_.next_frame_context();
 }
@@ -1817,7 +1445,7 @@ std::string RenderGraph::dump_json() const
 		first = false;
 		os << "{\"name\":\"" << pass.get_name() << "\",\"queue\":" << unsigned(pass.get_queue())
 		   << ",\"physical_pass\":" << int(get_physical_pass_index(pass_index))
-		   << ",\"stream\":" << (get_pass_stream(pass_index) == 0 ? "\"generic\"" : get_pass_stream(pass_index) == 1 ? "\"async\"" : get_pass_stream(pass_index) == 2 ? "\"front\"" : "\"tail\"")
+		   << ",\"stream\":" << "\"" << stream_name(get_pass_stream(pass_index)) << "\""
 		   << ",\"writes\":[";
 		bool f2 = true;
 		auto emit = [&](const RenderResource *r) {

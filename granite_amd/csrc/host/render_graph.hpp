@@ -19,6 +19,7 @@
 #include <unordered_map>
 #include <unordered_set>
 #include <vector>
+#include "frame_schedule.hpp"
 #include "hip_device.hpp"
 
 namespace Granite
@@ -411,11 +412,12 @@ public:
 	unsigned get_physical_pass_index(unsigned pass_index) const { return pass_index < pass_physical_pass.size() ? pass_physical_pass[pass_index] : unsigned(RenderResource::Unused); }
 	unsigned get_physical_pass_count() const { return physical_pass_count; }
 	unsigned get_physical_alias(unsigned index) const { return index < physical_aliases.size() ? physical_aliases[index] : unsigned(RenderResource::Unused); }
-	// 0 = generic stream (the back of the frame), 1 = async compute (passes the front does not wait for within a frame:
-	// explicit ASYNC_COMPUTE passes and input-free front passes such as the cluster build), 2 = the rest of the front,
-	// 3 = the tail (what follows the frame's last pass with a tie to the next frame and reads one image of it).
-	unsigned get_pass_stream(unsigned pass_index) const { return pass_index < pass_stream.size() ? pass_stream[pass_index] : 0u; }
-	bool physical_buffer_is_double_buffered(unsigned index) const { return index < physical_buffer_double.size() && physical_buffer_double[index]; }
+	// The stream a baked pass runs on (frame_schedule.hpp: StreamType); generic for a pass that was culled.
+	StreamType get_pass_stream(unsigned pass_index) const;
+	bool physical_buffer_is_double_buffered(unsigned index) const
+	{
+		return index < stream_plan.physical_buffer_double.size() && stream_plan.physical_buffer_double[index];
+	}
 	void bake();
 	void reset();
 	void log();
@@ -516,51 +518,19 @@ private:
 	std::vector<PassTimestamp> pending_timestamps;
 	std::vector<void *> event_pool;
 
-	// Cross-stream ordering.  Filled by bake(): the physical resources each pass reads / writes and the stream it runs
-	// on.  At execution every pass that shares a resource with a pass on the OTHER stream waits on that pass's "done"
-	// event (RAW, WAW and WAR); the state survives across frames, which is what lets frame N+1's hoisted passes start
-	// as soon as frame N's readers of their outputs have finished.  With a single stream in use nothing is recorded.
+	// Executor scheduling (frame_schedule.hpp).  Filled by bake(): the stream each pass runs on, the physical resources it reads / writes
+	// and the hand-over rings; at execution the hazard tracker orders the streams against each other.
 	bool hoist_independent_compute = true;
 	// The passes behind the last pass of the frame that leaves anything to the next frame (history, feedback) and that take ONE image from
 	// what precedes them -- post-tonemap anti-aliasing reading `tonemapped` -- run on a stream of their own: frame N's tail beside frame
 	// N + 1's resolve / bloom / tonemap (reference ordering kept: scene_viewer_application.cpp:1230-1261, smaa.cpp:95-208).  The image
 	// handed over exists in HandOverCopies rotating copies like a front-to-back resource.
 	bool split_tail = true;
-	bool uses_async_stream = false;
-	std::vector<uint8_t> pass_stream;
-	std::vector<bool> pass_needs_sync; // touches a physical resource that the other stream also touches
-	bool blit_needs_sync = false;
-	std::vector<std::vector<unsigned>> pass_reads_physical, pass_writes_physical;
-	// hipEvent_t ring per pass: a sync entry must keep naming the record of the frame it was made in (the alternate copy
-	// of a double-buffered buffer was last read two frames ago), so the event of frame f is slot f % EventRing.  The
-	// host never runs more than Device::StagingFrames - 1 frames ahead, so a slot is complete long before its reuse.
-	enum { EventRing = 4 };
-	std::vector<void *> pass_done_event;
-	uint64_t frame_counter = 0;
-	uint64_t last_device_frame = 0; // Device::get_frame_number() at the last enqueue (the two rings advance in lockstep)
-	enum { StreamCount = 4 }; // generic (back), async compute, front, tail: HIP::CommandBuffer::Type
-	struct PhysicalSync
-	{
-		void *last_write = nullptr;
-		int write_stream = -1;
-		void *last_read[StreamCount] = {};
-		// who recorded those events (pass index, frame), for GRANITE_SYNC_DEBUG=1 traces
-		int write_pass = -1, read_pass[StreamCount] = {-1, -1, -1, -1};
-		uint64_t write_frame = 0, read_frame[StreamCount] = {};
-		// the device's frame number at those records: which of a type's alternating streams they went to (HIP::Device::same_stream)
-		uint64_t write_device_frame = 0, read_device_frame[StreamCount] = {};
-	};
-	std::vector<PhysicalSync> physical_sync;
-	// Buffers written by a hoisted pass exist twice and alternate per frame (like an image with history), so the
-	// hoisted pass of frame N+1 never waits for frame N's consumers: write-after-read across frames disappears.
-	std::vector<bool> physical_buffer_double;
-	// HandOverCopies - 1 spare copies per resource; every frame the current copy goes to the back of the ring and the oldest
-	// spare becomes current.  Three copies: the producer of frame N+1 writes what the consumers of frame N-2 read last, so
-	// a back-of-frame that runs late (it shares the chip with the next frame's lighting) never stalls the front.
-	enum { HandOverCopies = 3 };
+	StreamPlan stream_plan;
+	HazardTracker hazards;
+	unsigned blit_source_physical_index = RenderResource::Unused; // the backbuffer source where it is not the swapchain image itself
 	std::vector<HIP::BufferHandle> physical_buffers_alternate[HandOverCopies - 1];
 	std::vector<HIP::ImageHandle> physical_images_alternate[HandOverCopies - 1];
-	std::vector<PhysicalSync> physical_sync_alternate[HandOverCopies - 1];
 	void build_stream_assignment();
 	void build_physical_passes();
 	void build_aliases();

@@ -47,6 +47,9 @@ struct Execution
 	RenderGraph *graph = nullptr;
 	const unsigned *frame = nullptr;
 	bool force_graphics = false; // every pass on the graphics queue: the serial reference run
+	// the backbuffer source in another format than the swapchain and written on the async compute queue: the frame ends in the
+	// executor's final blit, which has to wait for another stream
+	bool blit = false;
 };
 
 static void mix_pass(RenderGraph &graph, HIP::CommandBuffer &cmd, const std::vector<RenderTextureResource *> &outs,
@@ -141,10 +144,13 @@ static std::string declare_random(RenderGraph &graph, unsigned seed, bool alias,
 				mix_pass(*exec->graph, cmd, outs, ins, *exec->frame * 1000u + i, feedback);
 			});
 	}
-	auto &final_pass = graph.add_pass("final", RENDER_GRAPH_QUEUE_GRAPHICS_BIT);
+	const bool blit = exec && exec->blit;
+	auto &final_pass = graph.add_pass("final", blit ? RENDER_GRAPH_QUEUE_ASYNC_COMPUTE_BIT : RENDER_GRAPH_QUEUE_GRAPHICS_BIT);
 	AttachmentInfo back;
 	std::vector<RenderTextureResource *> final_ins, final_outs;
-	final_outs.push_back(&final_pass.add_color_output("back", back));
+	if (blit)
+		back.format = VK_FORMAT_R8G8B8A8_UNORM;
+	final_outs.push_back(blit ? &final_pass.add_storage_texture_output("back", back) : &final_pass.add_color_output("back", back));
 	decl += ",{\"name\":\"final\",\"queue\":1,\"reads\":[";
 	const unsigned taps = 1 + pick(3);
 	std::vector<std::string> seen;
@@ -179,7 +185,7 @@ static void random_graph(unsigned seed, bool alias)
 
 // Runs the random graph of `seed` for four frames without any host synchronisation in between and returns one hash per frame
 // of the swapchain image.  serial = every pass on the graphics queue, nothing hoisted, nothing aliased: one in-order stream.
-static std::vector<uint64_t> execute_random(HIP::Device &device, unsigned seed, bool serial)
+static std::vector<uint64_t> execute_random(HIP::Device &device, unsigned seed, bool serial, bool blit)
 {
 	RenderGraph graph;
 	unsigned frame = 0;
@@ -187,6 +193,7 @@ static std::vector<uint64_t> execute_random(HIP::Device &device, unsigned seed, 
 	exec.graph = &graph;
 	exec.frame = &frame;
 	exec.force_graphics = serial;
+	exec.blit = blit;
 	graph.set_device(&device);
 	declare_random(graph, seed, !serial, &exec);
 	if (serial)
@@ -196,6 +203,9 @@ static std::vector<uint64_t> execute_random(HIP::Device &device, unsigned seed, 
 	for (unsigned i = 0; i < 4; i++)
 		swapchain.push_back(device.create_image(1280, 720, VK_FORMAT_R8G8B8A8_SRGB, "swapchain-" + std::to_string(i)));
 	TaskComposer composer;
+	// tests/hip_stub's call trace is compared per graph (tests/test_executor_call_stream_cpu.py): say where one begins and what was baked
+	if (getenv("HIP_STUB_TRACE"))
+		fprintf(stderr, "=== case execute-%s%u %s\n=== graph %s\n", blit ? "blit-" : "", seed, serial ? "serial" : "pipelined", graph.dump_json().c_str());
 	for (frame = 0; frame < 4; frame++)
 	{
 		graph.setup_attachments(device, swapchain[frame].get());
@@ -229,13 +239,14 @@ int main(int argc, char **argv)
 		}
 		return 0;
 	}
-	if (argc >= 3 && std::string(argv[1]) == "--execute")
+	if (argc >= 3 && (std::string(argv[1]) == "--execute" || std::string(argv[1]) == "--execute-blit"))
 	{
+		const bool blit = std::string(argv[1]) == "--execute-blit";
 		HIP::Device device(0);
 		const unsigned n = unsigned(atoi(argv[2]));
 		for (unsigned seed = 0; seed < n; seed++)
 		{
-			const auto pipelined = execute_random(device, seed, false), serial = execute_random(device, seed, true);
+			const auto pipelined = execute_random(device, seed, false, blit), serial = execute_random(device, seed, true, blit);
 			printf("{\"case\":\"execute-%u\",\"pipelined\":[", seed);
 			for (size_t i = 0; i < pipelined.size(); i++)
 				printf("%s\"%016llx\"", i ? "," : "", (unsigned long long)pipelined[i]);

@@ -35,17 +35,29 @@ thread_local hipError_t last_error = hipSuccess;
 
 // HIP_STUB_TRACE=1: one line per stream call on stderr -- "L s<stream> <kernel>", "R s<stream> e<event>", "W s<stream> e<event>", and the host's
 // "Q s0 e<event>" (hipEventQuery) / "S s0 e<event>" (hipEventSynchronize) -- the order
-// in which a frame hands its work to the runtime (streams and events numbered in creation order).
+// in which a frame hands its work to the runtime (streams and events numbered in the order they are first named; a destroyed one gives its
+// number up, so that a new object at a reused address is a new number), and "G s<stream>" per hipGraphLaunch.
 const bool tracing = getenv("HIP_STUB_TRACE") != nullptr;
 std::mutex trace_lock;
-std::map<const void *, int> stream_ids, event_ids;
-std::map<const void *, std::string> kernel_names;
-int id_of(std::map<const void *, int> &ids, const void *p)
+struct Ids
 {
-	auto it = ids.find(p);
-	if (it == ids.end())
-		it = ids.emplace(p, int(ids.size())).first;
+	std::map<const void *, int> of;
+	int next = 0;
+} stream_ids, event_ids;
+std::map<const void *, std::string> kernel_names;
+int id_of(Ids &ids, const void *p)
+{
+	auto it = ids.of.find(p);
+	if (it == ids.of.end())
+		it = ids.of.emplace(p, ids.next++).first;
 	return it->second;
+}
+void forget(Ids &ids, const void *p)
+{
+	if (!tracing)
+		return;
+	std::lock_guard<std::mutex> holder{trace_lock};
+	ids.of.erase(p);
 }
 void trace(const char *what, const void *stream, const void *event, const void *kernel)
 {
@@ -127,11 +139,11 @@ hipError_t hipStreamCreateWithPriority(hipStream_t *s, unsigned, int priority)
 	*s = reinterpret_cast<hipStream_t>(st);
 	return hipSuccess;
 }
-hipError_t hipStreamDestroy(hipStream_t s) { delete reinterpret_cast<Stream *>(s); return hipSuccess; }
+hipError_t hipStreamDestroy(hipStream_t s) { forget(stream_ids, s); delete reinterpret_cast<Stream *>(s); return hipSuccess; }
 hipError_t hipStreamSynchronize(hipStream_t) { counters.syncs++; return hipSuccess; }
 hipError_t hipEventCreate(hipEvent_t *e) { *e = reinterpret_cast<hipEvent_t>(new Event); return hipSuccess; }
 hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { return hipEventCreate(e); }
-hipError_t hipEventDestroy(hipEvent_t e) { delete reinterpret_cast<Event *>(e); return hipSuccess; }
+hipError_t hipEventDestroy(hipEvent_t e) { forget(event_ids, e); delete reinterpret_cast<Event *>(e); return hipSuccess; }
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t s)
 {
 	counters.event_records++;
@@ -198,7 +210,7 @@ void __hipUnregisterFatBinary(void **) {}
 hipError_t hipStreamBeginCapture(hipStream_t, hipStreamCaptureMode) { return hipSuccess; }
 hipError_t hipStreamEndCapture(hipStream_t, hipGraph_t *g) { *g = reinterpret_cast<hipGraph_t>(new int(0)); return hipSuccess; }
 hipError_t hipGraphInstantiate(hipGraphExec_t *e, hipGraph_t, hipGraphNode_t *, char *, size_t) { *e = reinterpret_cast<hipGraphExec_t>(new int(0)); return hipSuccess; }
-hipError_t hipGraphLaunch(hipGraphExec_t, hipStream_t) { counters.graph_launches++; return hipSuccess; }
+hipError_t hipGraphLaunch(hipGraphExec_t, hipStream_t s) { counters.graph_launches++; trace("G", s, nullptr, nullptr); return hipSuccess; }
 hipError_t hipGraphDestroy(hipGraph_t g) { delete reinterpret_cast<int *>(g); return hipSuccess; }
 hipError_t hipGraphExecDestroy(hipGraphExec_t e) { delete reinterpret_cast<int *>(e); return hipSuccess; }
 }

@@ -18,6 +18,8 @@ LIB_PATH = os.path.join(_HERE, os.environ.get("GRANITE_LIB_DIR", "lib"), "libgra
 POST_AA_NONE, POST_AA_FXAA = 0, 1
 POST_AA_SMAA_LOW, POST_AA_SMAA_MEDIUM, POST_AA_SMAA_HIGH, POST_AA_SMAA_ULTRA = 2, 3, 4, 5
 POST_AA_TAA_LOW, POST_AA_TAA_MEDIUM, POST_AA_TAA_HIGH = 6, 7, 8
+# gra_config::ambient_occlusion: "ssao-main" copies an uploaded image in (what True means), or computes FidelityFX CACAO from the G-buffer
+AMBIENT_OCCLUSION_UPLOAD, AMBIENT_OCCLUSION_CACAO = 1, 2
 
 
 class Config(C.Structure):
@@ -221,11 +223,13 @@ class Application:
                  frame_time: float = synth.FRAME_TIME, timestamps: bool = False, strip_index: int = 0, strip_count: int = 1,
                  alias_images: bool = True, depth_hierarchy: int = 0,
                  resolution_scale: float = 1.0, resolution_scale_sharpen: bool = True, fsr_fp16: bool = True,
-                 ambient_occlusion: bool = False, hdr10: bool = False, ssr: bool = False, aa_bench: bool = False,
+                 ambient_occlusion=False, hdr10: bool = False, ssr: bool = False, aa_bench: bool = False,
                  output_gather_rgba: bool = False, rt_fp16: bool = True, taa_history_reach_rows: int = 0):
         """taa_history_reach_rows > 0 (row bands + TAA): the history bands exchange boundary rows with their neighbours only; a pixel
         that reaches further makes the next render / sync / read raise.  rt_fp16 = False: viewer_config renderTargetFp16 = false (the reference's default): emissive / HDR-main and the TAA colour
-        output are B10G11R11_UFLOAT_PACK32; the emissive upload is then (h, w) uint32 words (oracle.pack_b10g11r11)."""
+        output are B10G11R11_UFLOAT_PACK32; the emissive upload is then (h, w) uint32 words (oracle.pack_b10g11r11).
+        ambient_occlusion: False, True (= AMBIENT_OCCLUSION_UPLOAD: "ssao-output-main" is what upload_ambient_occlusion brought, white
+        before that) or AMBIENT_OCCLUSION_CACAO (computed from depth and normals every frame)."""
         self.lib = load_library()
         cfg = Config()
         cfg.device, cfg.width, cfg.height = device, width, height
@@ -317,7 +321,7 @@ class Application:
         self._check(self.lib.gra_upload_aa_bench_images(self.handle, a.ctypes.data, b.ctypes.data, a.shape[1], a.shape[0]))
 
     def upload_ambient_occlusion(self, ao: np.ndarray):
-        """Render-sized uint8 image for "ssao-output-main" (needs ambient_occlusion=True)."""
+        """Render-sized uint8 image for "ssao-output-main" (needs ambient_occlusion=True; refused where the pass computes it)."""
         a = np.ascontiguousarray(ao, np.uint8)
         self._check(self.lib.gra_upload_ambient_occlusion(self.handle, a.ctypes.data))
 

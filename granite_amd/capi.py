@@ -194,6 +194,57 @@ class PushOceanMipmap(C.Structure):
     _fields_ = [("result_mod", C.c_float * 4), ("inv_resolution", C.c_float * 2), ("count", C.c_uint32 * 2), ("lod", C.c_float)]
 
 
+# gr_cacao_*: FFX_CACAO_Quality values taken, limits, and the VkFormat values of two intermediates no Image argument takes
+CACAO_QUALITY_HIGH, CACAO_QUALITY_HIGHEST = 3, 4
+CACAO_MAX_BLUR_PASSES = 8
+CACAO_MAX_EXTENT = 16384
+CACAO_FORMAT_R8G8B8A8_SNORM, CACAO_FORMAT_R32_UINT = 38, 98
+CACAO_INTERMEDIATE_COUNT = 7
+
+
+class CacaoSettings(C.Structure):
+    """gr_cacao_settings: FFX_CACAO_Settings."""
+    _fields_ = [("radius", C.c_float), ("shadow_multiplier", C.c_float), ("shadow_power", C.c_float), ("shadow_clamp", C.c_float),
+                ("horizon_angle_threshold", C.c_float), ("fade_out_from", C.c_float), ("fade_out_to", C.c_float), ("quality_level", C.c_uint32),
+                ("adaptive_quality_limit", C.c_float), ("blur_pass_count", C.c_uint32), ("sharpness", C.c_float),
+                ("temporal_supersampling_angle_offset", C.c_float), ("temporal_supersampling_radius_offset", C.c_float),
+                ("detail_shadow_strength", C.c_float), ("generate_normals", C.c_uint32), ("bilateral_sigma_squared", C.c_float),
+                ("bilateral_similarity_distance_sigma", C.c_float)]
+
+
+class CacaoConstants(C.Structure):
+    """gr_cacao_constants: FFX_CACAO_Constants, the shaders' constant buffer."""
+    _f2 = C.c_float * 2
+    _fields_ = [("DepthUnpackConsts", _f2), ("CameraTanHalfFOV", _f2), ("NDCToViewMul", _f2), ("NDCToViewAdd", _f2), ("DepthBufferUVToViewMul", _f2),
+                ("DepthBufferUVToViewAdd", _f2), ("EffectRadius", C.c_float), ("EffectShadowStrength", C.c_float), ("EffectShadowPow", C.c_float),
+                ("EffectShadowClamp", C.c_float), ("EffectFadeOutMul", C.c_float), ("EffectFadeOutAdd", C.c_float),
+                ("EffectHorizonAngleThreshold", C.c_float), ("EffectSamplingRadiusNearLimitRec", C.c_float), ("DepthPrecisionOffsetMod", C.c_float),
+                ("NegRecEffectRadius", C.c_float), ("LoadCounterAvgDiv", C.c_float), ("AdaptiveSampleCountLimit", C.c_float), ("InvSharpness", C.c_float),
+                ("PassIndex", C.c_int32), ("BilateralSigmaSquared", C.c_float), ("BilateralSimilarityDistanceSigma", C.c_float),
+                ("PatternRotScaleMatrices", (C.c_float * 4) * 5), ("NormalsUnpackMul", C.c_float), ("NormalsUnpackAdd", C.c_float),
+                ("DetailAOStrength", C.c_float), ("Dummy0", C.c_float), ("SSAOBufferDimensions", _f2), ("SSAOBufferInverseDimensions", _f2),
+                ("DepthBufferDimensions", _f2), ("DepthBufferInverseDimensions", _f2), ("DepthBufferOffset", C.c_int32 * 2),
+                ("PerPassFullResUVOffset", _f2), ("InputOutputBufferDimensions", _f2), ("InputOutputBufferInverseDimensions", _f2),
+                ("ImportanceMapDimensions", _f2), ("ImportanceMapInverseDimensions", _f2), ("DeinterleavedDepthBufferDimensions", _f2),
+                ("DeinterleavedDepthBufferInverseDimensions", _f2), ("DeinterleavedDepthBufferOffset", _f2),
+                ("DeinterleavedDepthBufferNormalisedOffset", _f2), ("NormalsWorldToViewspaceMatrix", (C.c_float * 4) * 4)]
+
+
+class CacaoBufferSizes(C.Structure):
+    """gr_cacao_buffer_sizes: FFX_CACAO_BufferSizeInfo."""
+    _fields_ = [(name, C.c_uint32) for name in (
+        "inputOutputBufferWidth", "inputOutputBufferHeight", "ssaoBufferWidth", "ssaoBufferHeight", "depthBufferXOffset", "depthBufferYOffset",
+        "depthBufferWidth", "depthBufferHeight", "deinterleavedDepthBufferXOffset", "deinterleavedDepthBufferYOffset",
+        "deinterleavedDepthBufferWidth", "deinterleavedDepthBufferHeight", "importanceMapWidth", "importanceMapHeight",
+        "downsampledSsaoBufferWidth", "downsampledSsaoBufferHeight")]
+
+
+class CacaoIntermediate(C.Structure):
+    """gr_cacao_intermediate: one intermediate of the workspace."""
+    _fields_ = [("name", C.c_char * 32), ("format", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("layers", C.c_uint32),
+                ("mips", C.c_uint32), ("mip_offset", C.c_uint64 * 4), ("bytes", C.c_uint64)]
+
+
 class TimingEntry(C.Structure):
     _fields_ = [("name", C.c_char_p), ("count", C.c_uint64), ("total_ms", C.c_double)]
 
@@ -489,6 +540,20 @@ def load_library() -> C.CDLL:
         "gr_ocean_generate_fft": (C.c_int, [vp, vp, vp, vp, P(PushOceanGenerate), C.c_uint32, P(C.c_float)]),
         "gr_ocean_bake_maps": (C.c_int, [vp, vp, P(Image), P(Image), P(Image), P(Image), P(PushOceanBake)]),
         "gr_ocean_mipmap": (C.c_int, [vp, vp, P(Image), P(Image), P(PushOceanMipmap)]),
+        "gr_cacao_reference_settings": (None, [P(CacaoSettings)]),
+        "gr_cacao_update_buffer_sizes": (C.c_int, [C.c_uint32, C.c_uint32, P(CacaoBufferSizes)]),
+        "gr_cacao_update_constants": (C.c_int, [vp, P(CacaoConstants), P(CacaoSettings), P(CacaoBufferSizes), P(C.c_float), P(C.c_float)]),
+        "gr_cacao_workspace_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+        "gr_cacao_workspace_describe": (C.c_int, [C.c_uint32, C.c_uint32, P(CacaoIntermediate), C.c_uint32]),
+        "gr_cacao_prepare_depths": (C.c_int, [vp, vp, P(Image), vp, P(CacaoConstants)]),
+        "gr_cacao_prepare_normals": (C.c_int, [vp, vp, P(Image), vp, P(CacaoConstants)]),
+        "gr_cacao_generate_base": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, P(CacaoConstants)]),
+        "gr_cacao_importance_generate": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, P(CacaoConstants)]),
+        "gr_cacao_importance_postprocess_a": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, P(CacaoConstants)]),
+        "gr_cacao_importance_postprocess_b": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, P(CacaoConstants)]),
+        "gr_cacao_generate": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, P(CacaoConstants), C.c_uint32]),
+        "gr_cacao_blur": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32, P(CacaoConstants), C.c_uint32]),
+        "gr_cacao_apply": (C.c_int, [vp, vp, vp, P(Image), P(CacaoConstants), C.c_uint32]),
         "gr_fsr_sharpen": (C.c_int, [vp, vp, P(Image), P(Image), C.c_float]),
         "gr_mip_chain_offset": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
         "gr_mip_chain_size": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
@@ -514,7 +579,44 @@ EXPORTED_SYMBOLS = [
     "gr_cube_chain_bytes", "gr_cube_chain_offset", "gr_env_equirect_to_cube", "gr_env_specular", "gr_env_diffuse",
     "gr_fft_describe", "gr_fft_plan_create", "gr_fft_plan_destroy", "gr_fft_plan_iterations", "gr_fft_execute", "gr_fft_execute_iteration",
     "gr_ocean_generate_fft", "gr_ocean_bake_maps", "gr_ocean_mipmap",
+    "gr_cacao_reference_settings", "gr_cacao_update_buffer_sizes", "gr_cacao_update_constants", "gr_cacao_workspace_bytes", "gr_cacao_workspace_describe",
+    "gr_cacao_prepare_depths", "gr_cacao_prepare_normals", "gr_cacao_generate_base", "gr_cacao_importance_generate",
+    "gr_cacao_importance_postprocess_a", "gr_cacao_importance_postprocess_b", "gr_cacao_generate", "gr_cacao_blur", "gr_cacao_apply",
 ]
+
+
+def cacao_reference_settings() -> CacaoSettings:
+    """The FFX_CACAO_Settings setup_ffx_cacao installs (renderer/post/ssao.cpp:73-91)."""
+    s = CacaoSettings()
+    load_library().gr_cacao_reference_settings(C.byref(s))
+    return s
+
+
+def cacao_constants(width: int, height: int, projection, view, settings: Optional[CacaoSettings] = None, ctx: Optional["Context"] = None):
+    """The four per-pass constant blocks (a ctypes array of CacaoConstants) for a width x height frame; projection and view are 16 floats
+    each, column-major (RenderParameters::projection and ::view).  Raises on settings the kernels do not take."""
+    lib = load_library()
+    settings = settings or cacao_reference_settings()
+    sizes = CacaoBufferSizes()
+    constants = (CacaoConstants * 4)()
+    proj = (C.c_float * 16)(*[float(v) for v in np.asarray(projection, np.float32).reshape(16)])
+    to_view = (C.c_float * 16)(*[float(v) for v in np.asarray(view, np.float32).reshape(16)])
+    code = lib.gr_cacao_update_buffer_sizes(width, height, C.byref(sizes))
+    if code == 0:
+        code = lib.gr_cacao_update_constants(ctx.handle if ctx else None, constants, C.byref(settings), C.byref(sizes), proj, to_view)
+    if code != 0:
+        message = lib.gr_last_error(ctx.handle).decode() if ctx else "width, height or settings the SSAO kernels do not take"
+        raise GraniteHipError(f"gr_cacao_update_constants failed ({code}): {message}")
+    return constants
+
+
+def cacao_workspace_describe(width: int, height: int) -> Optional[list]:
+    """[{name, format, width, height, layers, mips, mip_offset, bytes}] of the workspace, or None for a size that is refused."""
+    out = (CacaoIntermediate * CACAO_INTERMEDIATE_COUNT)()
+    if load_library().gr_cacao_workspace_describe(width, height, out, CACAO_INTERMEDIATE_COUNT) != 0:
+        return None
+    return [{"name": d.name.decode(), "format": d.format, "width": d.width, "height": d.height, "layers": d.layers, "mips": d.mips,
+             "mip_offset": list(d.mip_offset)[:d.mips], "bytes": d.bytes} for d in out]
 
 
 def fft_options(nx, ny=1, nz=1, dimensions=1, mode=FFT_FORWARD_C2C, data_type=FFT_FP32, input_resource=FFT_RESOURCE_BUFFER,
@@ -887,6 +989,33 @@ class Context:
     def ocean_mipmap(self, src: DeviceImage, out: DeviceImage, push: PushOceanMipmap, stream=None):
         """gr_ocean_mipmap: one LinearWrap tap per texel of `out` (push.count texels) from `src`, times push.result_mod."""
         self.check(self.lib.gr_ocean_mipmap(self.handle, stream, src.desc, out.desc, C.byref(push)))
+
+    # ---- SSAO: FidelityFX CACAO --------------------------------------------------------------------------------------------------------
+    def cacao_workspace(self, width: int, height: int) -> DeviceBuffer:
+        """A workspace for a width x height frame (gr_alloc returns 256-byte aligned memory)."""
+        nbytes = self.lib.gr_cacao_workspace_bytes(width, height)
+        if nbytes == 0:
+            raise GraniteHipError(f"gr_cacao_workspace_bytes: {width} x {height} is not a size the SSAO pass takes")
+        return DeviceBuffer(self, nbytes)
+
+    def cacao(self, depth: DeviceImage, normal: DeviceImage, out: DeviceImage, workspace, constants, quality: int = CACAO_QUALITY_HIGHEST,
+              blur_passes: int = 2, stream=None):
+        """The sequence of FFX_CACAO_GraniteDraw on one stream: depth D32_SFLOAT and normal A2B10G10R10 -> out R8_UNORM.  workspace: a
+        DeviceBuffer or a 256-byte aligned device pointer of gr_cacao_workspace_bytes; constants: cacao_constants(...)."""
+        lib, h = self.lib, self.handle
+        ws = workspace.ptr if isinstance(workspace, DeviceBuffer) else workspace
+        w, hgt = depth.width, depth.height
+        self.check(lib.gr_cacao_prepare_depths(h, stream, depth.desc, ws, constants))
+        self.check(lib.gr_cacao_prepare_normals(h, stream, normal.desc, ws, constants))
+        if quality == CACAO_QUALITY_HIGHEST:
+            self.check(lib.gr_cacao_generate_base(h, stream, ws, w, hgt, constants))
+            self.check(lib.gr_cacao_importance_generate(h, stream, ws, w, hgt, constants))
+            self.check(lib.gr_cacao_importance_postprocess_a(h, stream, ws, w, hgt, constants))
+            self.check(lib.gr_cacao_importance_postprocess_b(h, stream, ws, w, hgt, constants))
+        self.check(lib.gr_cacao_generate(h, stream, ws, w, hgt, constants, quality))
+        if blur_passes:
+            self.check(lib.gr_cacao_blur(h, stream, ws, w, hgt, constants, blur_passes))
+        self.check(lib.gr_cacao_apply(h, stream, ws, out.desc, constants, 1 if blur_passes else 0))
 
     def blit(self, src: DeviceImage, out: DeviceImage, linear: bool, stream=None):
         self.check(self.lib.gr_blit(self.handle, stream, src.desc, out.desc, int(linear)))

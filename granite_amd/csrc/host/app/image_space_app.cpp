@@ -6,6 +6,7 @@
 #include <hip/hip_runtime_api.h>
 #include "../gtx.hpp"
 #include "../post/spd.hpp"
+#include "../post/ssao.hpp"
 #include "../post/ssr.hpp"
 #include <chrono>
 #include <cmath>
@@ -49,6 +50,10 @@ ImageSpaceApplication::ImageSpaceApplication(const gra_config &config_) : config
 		throw std::logic_error("aa_bench is a graph of its own: no lighting, bloom, hdr10, SSR, depth hierarchy or row bands.");
 	if (config.resolution_scale < 0.0f || config.resolution_scale > 1.0f)
 		throw std::logic_error("resolution_scale must be in (0, 1].");
+	if (config.ambient_occlusion < 0 || config.ambient_occlusion > GRA_AMBIENT_OCCLUSION_CACAO)
+		throw std::logic_error("ambient_occlusion must be 0, 1 (GRA_AMBIENT_OCCLUSION_UPLOAD) or 2 (GRA_AMBIENT_OCCLUSION_CACAO).");
+	if (config.ambient_occlusion == GRA_AMBIENT_OCCLUSION_CACAO && config.strip_count > 1)
+		throw std::logic_error("Computed ambient occlusion (GRA_AMBIENT_OCCLUSION_CACAO) is not tiled into row bands (strip_count > 1).");
 	render_width = config.width;
 	render_height = config.height;
 	if (scaled())
@@ -407,6 +412,8 @@ void ImageSpaceApplication::upload_ambient_occlusion(const void *ao_r8)
 {
 	if (!config.ambient_occlusion || !config.enable_lighting)
 		throw std::logic_error("This graph has no ambient-occlusion input (config.ambient_occlusion).");
+	if (config.ambient_occlusion == GRA_AMBIENT_OCCLUSION_CACAO)
+		throw std::logic_error("This graph computes its ambient occlusion (GRA_AMBIENT_OCCLUSION_CACAO): an uploaded image would never be read.");
 	if (!ao_r8)
 		throw std::logic_error("upload_ambient_occlusion: null image");
 	auto &device = get_device();
@@ -645,11 +652,15 @@ void ImageSpaceApplication::add_main_pass_deferred(const std::string &tag)
 	});
 
 	ssao_output = nullptr;
-	if (config.ambient_occlusion)
+	if (config.ambient_occlusion == GRA_AMBIENT_OCCLUSION_CACAO)
 	{
-		// setup_ffx_cacao(graph, context, "ssao-output-<tag>", depth, normal) (scene_viewer_application.cpp:950-954; output
-		// declared at ssao.cpp:48-58: R8_UNORM storage image the size of the depth input).  CACAO itself exists only as
-		// SPIR-V blobs in the reference; the pass here copies the uploaded image in (white = unoccluded until one arrives).
+		// scene_viewer_application.cpp:950-954: FidelityFX CACAO on the G-buffer's depth and normals (host/post/ssao.cpp)
+		setup_ffx_cacao(graph, context, tagcat("ssao-output", tag), tagcat("depth-transient", tag), tagcat("normal", tag), nullptr, tagcat("ssao", tag));
+	}
+	else if (config.ambient_occlusion)
+	{
+		// The same pass and output declaration (ssao.cpp:48-58: R8_UNORM storage image the size of the depth input) with the effect
+		// left out: the pass copies the uploaded image in (white = unoccluded until one arrives).
 		auto &ssao = graph.add_pass(tagcat("ssao", tag), RENDER_GRAPH_QUEUE_COMPUTE_BIT);
 		AttachmentInfo ao;
 		ao.format = VK_FORMAT_R8_UNORM;

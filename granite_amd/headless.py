@@ -20,7 +20,8 @@ frames, wait idle; `averageFrameTimeUs` = wall time / frames.  --stat keys: aver
 with --timestamp, performance{pass: timePerAccumulationUs, timePerFrameContextUs, accumulationsPerFrameContext}.
 --config understands the viewer_config keys that select image-space work (read_config, scene_viewer_application.cpp:
 163-260): renderer, hdrBloom, hdrBloomDynamicExposure, clusteredLights, postAA, resolutionScale, resolutionScaleSharpen,
-hdr10, ssao (as the lighting pass's ambient-occlusion input), ssr; keys that concern geometry or shadow passes are accepted and
+hdr10, ssao (the lighting pass's ambient-occlusion input: white until an image is uploaded, or, with --ssao-compute, FidelityFX CACAO
+computed from the G-buffer's depth and normals as setup_ffx_cacao does), ssr; keys that concern geometry or shadow passes are accepted and
 ignored, a forward renderer or MSAA is refused (no G-buffer for this executor to consume).
 
 --video-encode-path records every timed frame as the reference's runner does (application_headless.cpp:225-275, 348-372): each
@@ -180,6 +181,8 @@ def parse_args(argv):
     ap.add_argument("--lights", type=int, default=-1, help="synthetic scene: number of positional lights (default 4096)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--video-encode-path", default="")
+    ap.add_argument("--ssao-compute", action="store_true",
+                    help='a config\'s "ssao": true computes FidelityFX CACAO from depth and normals instead of taking an uploaded image')
     for ignored in ("--fs-assets", "--fs-builtin", "--fs-cache"):
         ap.add_argument(ignored, default="")
     return ap.parse_args(argv)
@@ -233,6 +236,8 @@ def main(argv=None) -> int:
             print("[ERROR]: Failed to read config file. Assuming defaults.", file=sys.stderr)   # read_config :168-171
     try:
         kw = viewer_config_to_kwargs(doc)
+        if args.ssao_compute and kw["ambient_occlusion"]:
+            kw["ambient_occlusion"] = gapp.AMBIENT_OCCLUSION_CACAO
     except ConfigError as e:
         print(f"[ERROR]: {e}", file=sys.stderr)
         return 1

@@ -69,9 +69,14 @@ typedef struct gra_config
 	int32_t resolution_scale_sharpen;
 	int32_t fsr_fp32;
 	/* viewer_config "ssao" on the deferred path (scene_viewer_application.cpp:950-980,1571): the lighting pass takes the
-	 * R8_UNORM texture "ssao-output-main" as LightingParameters::ambient_occlusion.  Its producer in Granite is FFX CACAO,
-	 * shipped as SPIR-V blobs only; the harness fills the texture from gra_upload_ambient_occlusion like the G-buffer. */
+	 * R8_UNORM texture "ssao-output-main" as LightingParameters::ambient_occlusion.  Its producer in Granite is FidelityFX CACAO
+	 * (setup_ffx_cacao).  GRA_AMBIENT_OCCLUSION_UPLOAD (1): the pass "ssao-main" fills the texture from
+	 * gra_upload_ambient_occlusion like the G-buffer (white until an image arrives).  GRA_AMBIENT_OCCLUSION_CACAO (2): "ssao-main" computes
+	 * it from the G-buffer's depth and normals every frame (host/post/ssao.cpp, csrc/cacao.hip) with the reference's settings; an upload
+	 * is refused, and so are row bands (strip_count > 1). */
 	int32_t ambient_occlusion;
+#define GRA_AMBIENT_OCCLUSION_UPLOAD 1
+#define GRA_AMBIENT_OCCLUSION_CACAO 2
 	/* HDR10 output (setup_hdr10_pq_encoding, renderer/post/hdr.cpp:595-658): the backbuffer is A2B10G10R10_UNORM_PACK32 and the
 	 * frame ends lighting -> "ui" (an R8G8B8A8_SRGB layer cleared to transparent: (0, 0, 0, 1) = scene fully visible) -> "pq10"
 	 * with ST.2020 primaries, maxContentLightLevel 1000, hdr / ui pre-exposure 500 / 400 (scene_viewer_application.cpp:1283-1285).
@@ -147,7 +152,8 @@ int gra_set_lights(gra_app *app, const gra_light_desc *lights, uint32_t count);
 int gra_upload_gbuffer(gra_app *app, const void *emissive_rgba16f, const void *albedo_rgba8, const void *normal_a2b10g10r10,
                        const void *pbr_rg8, const void *depth_d32f, const void *motion_vectors_rg16f);
 
-/* Render-sized R8_UNORM ambient-occlusion image (host pointer, tightly packed); needs config.ambient_occlusion. */
+/* Render-sized R8_UNORM ambient-occlusion image (host pointer, tightly packed); needs config.ambient_occlusion ==
+ * GRA_AMBIENT_OCCLUSION_UPLOAD (declared below the aa_bench upload). */
 /* The two input images of the aa_bench graph: R8G8B8A8_SRGB, tightly packed, any size (both the same). */
 int gra_upload_aa_bench_images(gra_app *app, const void *rgba8_first, const void *rgba8_second, uint32_t width, uint32_t height);
 int gra_upload_ambient_occlusion(gra_app *app, const void *ao_r8);

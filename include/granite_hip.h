@@ -988,6 +988,140 @@ int gr_ocean_bake_maps(gr_ctx *ctx, gr_stream stream, const gr_image *height, co
  * (2 gid + 1) * inv_resolution, times result_mod. */
 int gr_ocean_mipmap(gr_ctx *ctx, gr_stream stream, const gr_image *in, const gr_image *out, const gr_push_ocean_mipmap *push);
 
+/* ---- SSAO: FidelityFX CACAO as the reference runs it (renderer/post/ssao.cpp, renderer/post/ffx-cacao) -----------------------------------
+ * One configuration and its non-adaptive sibling: native resolution, normals from the G-buffer, quality HIGHEST (adaptive, shader level 3)
+ * or HIGH (shader level 2), 0 .. 8 blur passes.  One entry point per shader of FFX_CACAO_GraniteDraw (ffx_cacao_impl.cpp:767-1026); the
+ * four per-pass dispatches of a stage are one launch.  Every intermediate lives in one caller-owned workspace of gr_cacao_workspace_bytes
+ * bytes, 256-byte aligned, laid out as gr_cacao_workspace_describe says: layers and mips tightly packed, mip k of an extent n is
+ * max(1, n >> k).  Sampler models, rounding rules and store conversions: granite_amd/csrc/cacao_core.hpp, DESIGN.md 7.11.
+ * Refused with GR_ERR_INVALID_ARGUMENT (a wrong image format alone: GR_ERR_UNSUPPORTED_FORMAT) before anything is launched: null
+ * pointers, a workspace that is not 256-byte aligned, a width or height of 0 or above GR_CACAO_MAX_EXTENT, images that do not have the
+ * size of the call, constants whose buffer dimensions are not those of width x height, and what each entry point names. */
+#define GR_CACAO_QUALITY_HIGH 3u    /* FFX_CACAO_QUALITY_HIGH: shader level 2, 12 tap pairs */
+#define GR_CACAO_QUALITY_HIGHEST 4u /* FFX_CACAO_QUALITY_HIGHEST: shader level 3, adaptive, 5 + 1 .. 32 tap pairs */
+#define GR_CACAO_MAX_BLUR_PASSES 8u
+#define GR_CACAO_MAX_EXTENT 16384u
+#define GR_CACAO_FORMAT_R8G8B8A8_SNORM 38u /* VkFormat values of two intermediates that no gr_image argument takes */
+#define GR_CACAO_FORMAT_R32_UINT 98u
+typedef struct gr_cacao_settings /* FFX_CACAO_Settings, ffx_cacao.h:52-70 */
+{
+	float radius;
+	float shadow_multiplier;
+	float shadow_power;
+	float shadow_clamp;
+	float horizon_angle_threshold;
+	float fade_out_from;
+	float fade_out_to;
+	uint32_t quality_level; /* GR_CACAO_QUALITY_* */
+	float adaptive_quality_limit;
+	uint32_t blur_pass_count;
+	float sharpness;
+	float temporal_supersampling_angle_offset;  /* unused, as in the reference */
+	float temporal_supersampling_radius_offset; /* unused, as in the reference */
+	float detail_shadow_strength;
+	uint32_t generate_normals; /* must be 0 */
+	float bilateral_sigma_squared;
+	float bilateral_similarity_distance_sigma;
+} gr_cacao_settings;
+typedef struct gr_cacao_constants /* FFX_CACAO_Constants, ffx_cacao.h:95-154 = ffx_cacao_bindings.hlsl:27-87 */
+{
+	float DepthUnpackConsts[2];
+	float CameraTanHalfFOV[2];
+	float NDCToViewMul[2];
+	float NDCToViewAdd[2];
+	float DepthBufferUVToViewMul[2];
+	float DepthBufferUVToViewAdd[2];
+	float EffectRadius;
+	float EffectShadowStrength;
+	float EffectShadowPow;
+	float EffectShadowClamp;
+	float EffectFadeOutMul;
+	float EffectFadeOutAdd;
+	float EffectHorizonAngleThreshold;
+	float EffectSamplingRadiusNearLimitRec;
+	float DepthPrecisionOffsetMod;
+	float NegRecEffectRadius;
+	float LoadCounterAvgDiv;
+	float AdaptiveSampleCountLimit;
+	float InvSharpness;
+	int32_t PassIndex;
+	float BilateralSigmaSquared;
+	float BilateralSimilarityDistanceSigma;
+	float PatternRotScaleMatrices[5][4];
+	float NormalsUnpackMul;
+	float NormalsUnpackAdd;
+	float DetailAOStrength;
+	float Dummy0;
+	float SSAOBufferDimensions[2];
+	float SSAOBufferInverseDimensions[2];
+	float DepthBufferDimensions[2];
+	float DepthBufferInverseDimensions[2];
+	int32_t DepthBufferOffset[2];
+	float PerPassFullResUVOffset[2];
+	float InputOutputBufferDimensions[2];
+	float InputOutputBufferInverseDimensions[2];
+	float ImportanceMapDimensions[2];
+	float ImportanceMapInverseDimensions[2];
+	float DeinterleavedDepthBufferDimensions[2];
+	float DeinterleavedDepthBufferInverseDimensions[2];
+	float DeinterleavedDepthBufferOffset[2];
+	float DeinterleavedDepthBufferNormalisedOffset[2];
+	float NormalsWorldToViewspaceMatrix[4][4];
+} gr_cacao_constants;
+typedef struct gr_cacao_buffer_sizes /* FFX_CACAO_BufferSizeInfo, ffx_cacao.h:159-183 */
+{
+	uint32_t inputOutputBufferWidth, inputOutputBufferHeight;
+	uint32_t ssaoBufferWidth, ssaoBufferHeight;
+	uint32_t depthBufferXOffset, depthBufferYOffset;
+	uint32_t depthBufferWidth, depthBufferHeight;
+	uint32_t deinterleavedDepthBufferXOffset, deinterleavedDepthBufferYOffset;
+	uint32_t deinterleavedDepthBufferWidth, deinterleavedDepthBufferHeight;
+	uint32_t importanceMapWidth, importanceMapHeight;
+	uint32_t downsampledSsaoBufferWidth, downsampledSsaoBufferHeight;
+} gr_cacao_buffer_sizes;
+typedef struct gr_cacao_intermediate
+{
+	char name[32];          /* the reference's texture name (ffx_cacao_impl.cpp:71-79) */
+	uint32_t format;        /* gr_format or GR_CACAO_FORMAT_* */
+	uint32_t width, height; /* of mip 0 */
+	uint32_t layers, mips;
+	uint64_t mip_offset[4]; /* bytes from the workspace's start to layer 0 of mip k; layer l follows at l * mip width * mip height * texel size */
+	uint64_t bytes;
+} gr_cacao_intermediate;
+#define GR_CACAO_INTERMEDIATE_COUNT 7u
+/* Host-only.  The settings setup_ffx_cacao installs (renderer/post/ssao.cpp:73-91). */
+void gr_cacao_reference_settings(gr_cacao_settings *settings);
+/* Host-only.  FFX_CACAO_UpdateBufferSizeInfo with useDownsampledSsao = false. */
+int gr_cacao_update_buffer_sizes(uint32_t width, uint32_t height, gr_cacao_buffer_sizes *sizes);
+/* Host-only.  FFX_CACAO_UpdateConstants + FFX_CACAO_UpdatePerPassConstants for the four passes (ffx_cacao.cpp:108-269).  proj and
+ * normals_to_view are column-major 4x4 matrices in memory, RenderParameters::projection and ::view.  ctx may be NULL (it only receives the
+ * message).  Refused: generate_normals != 0, a quality_level other than GR_CACAO_QUALITY_HIGH / HIGHEST, blur_pass_count above 8. */
+int gr_cacao_update_constants(gr_ctx *ctx, gr_cacao_constants constants[4], const gr_cacao_settings *settings, const gr_cacao_buffer_sizes *sizes,
+                              const float proj[16], const float normals_to_view[16]);
+/* Host-only.  0 for a width or height of 0 or above GR_CACAO_MAX_EXTENT. */
+size_t gr_cacao_workspace_bytes(uint32_t width, uint32_t height);
+/* Host-only.  Fills out[0 .. GR_CACAO_INTERMEDIATE_COUNT): deinterleaved depths (R16_SFLOAT, 4 layers, 4 mips), deinterleaved normals
+ * (R8G8B8A8_SNORM, 4 layers), SSAO ping and pong (R8G8_UNORM, 4 layers), importance map and its pong (R8_UNORM), load counter (R32_UINT). */
+int gr_cacao_workspace_describe(uint32_t width, uint32_t height, gr_cacao_intermediate *out, uint32_t capacity);
+/* ClearLoadCounter + PrepareNativeDepthsAndMips: depth D32_SFLOAT width x height. */
+int gr_cacao_prepare_depths(gr_ctx *ctx, gr_stream stream, const gr_image *depth, void *workspace, const gr_cacao_constants *constants);
+/* PrepareNativeNormalsFromInputNormals: normal A2B10G10R10_UNORM_PACK32 width x height.  A texel past an odd extent reads as zero. */
+int gr_cacao_prepare_normals(gr_ctx *ctx, gr_stream stream, const gr_image *normal, void *workspace, const gr_cacao_constants *constants);
+/* GenerateQ3Base x 4: depths and normals -> SSAO pong (obscurance, weight / 20). */
+int gr_cacao_generate_base(gr_ctx *ctx, gr_stream stream, void *workspace, uint32_t width, uint32_t height, const gr_cacao_constants constants[4]);
+/* GenerateImportanceMap (pong -> importance), PostprocessImportanceMapA (importance -> its pong), PostprocessImportanceMapB (-> importance,
+ * and the load counter: integer atomic adds of every texel with x % 3 + y % 3 == 0). */
+int gr_cacao_importance_generate(gr_ctx *ctx, gr_stream stream, void *workspace, uint32_t width, uint32_t height, const gr_cacao_constants *constants);
+int gr_cacao_importance_postprocess_a(gr_ctx *ctx, gr_stream stream, void *workspace, uint32_t width, uint32_t height, const gr_cacao_constants *constants);
+int gr_cacao_importance_postprocess_b(gr_ctx *ctx, gr_stream stream, void *workspace, uint32_t width, uint32_t height, const gr_cacao_constants *constants);
+/* GenerateQ2 x 4 (quality GR_CACAO_QUALITY_HIGH) or GenerateQ3 x 4 (HIGHEST; reads pong, importance and the load counter) -> SSAO ping
+ * (occlusion, packed edges).  Any other quality is refused. */
+int gr_cacao_generate(gr_ctx *ctx, gr_stream stream, void *workspace, uint32_t width, uint32_t height, const gr_cacao_constants constants[4], uint32_t quality);
+/* EdgeSensitiveBlur<blur_passes> x 4: ping -> pong.  blur_passes 1 .. 8; 0 has no dispatch and is refused. */
+int gr_cacao_blur(gr_ctx *ctx, gr_stream stream, void *workspace, uint32_t width, uint32_t height, const gr_cacao_constants *constants, uint32_t blur_passes);
+/* Apply: SSAO pong (from_pong != 0: after a blur) or ping -> out, R8_UNORM width x height. */
+int gr_cacao_apply(gr_ctx *ctx, gr_stream stream, const void *workspace, const gr_image *out, const gr_cacao_constants *constants, uint32_t from_pong);
+
 /* Fill with a 32-bit pattern (count dwords): attachment clears to a colour. */
 int gr_fill_u32(gr_ctx *ctx, gr_stream stream, void *dst, uint32_t value, size_t count);
 /* Executor self-test operation (no counterpart in the reference): out[i] = hash(i, salt, one dword of each of up to four
@@ -1092,7 +1226,25 @@ GR_ASSERT_SIZE(gr_push_ocean_mipmap, 36);     /* mipmap.comp:17-23, ocean.cpp:55
 GR_ASSERT_OFFSET(gr_push_ocean_mipmap, inv_resolution, 16);
 GR_ASSERT_OFFSET(gr_push_ocean_mipmap, count, 24);
 GR_ASSERT_OFFSET(gr_push_ocean_mipmap, lod, 32);
-GR_STATIC_ASSERT(GR_TRANSFORMS_OFFSET_SHADOW == GR_MAX_LIGHTS_BINDLESS * 48u, "ClustererBindlessTransforms: lights[4096] of 48 B");
+GR_ASSERT_SIZE(gr_cacao_constants, 384);      /* ffx_cacao.h:95-154, ffx_cacao_bindings.hlsl:27-87 */
+GR_ASSERT_OFFSET(gr_cacao_constants, EffectRadius, 48);
+GR_ASSERT_OFFSET(gr_cacao_constants, InvSharpness, 96);
+GR_ASSERT_OFFSET(gr_cacao_constants, PassIndex, 100);
+GR_ASSERT_OFFSET(gr_cacao_constants, PatternRotScaleMatrices, 112);
+GR_ASSERT_OFFSET(gr_cacao_constants, NormalsUnpackMul, 192);
+GR_ASSERT_OFFSET(gr_cacao_constants, SSAOBufferDimensions, 208);
+GR_ASSERT_OFFSET(gr_cacao_constants, DepthBufferOffset, 240);
+GR_ASSERT_OFFSET(gr_cacao_constants, PerPassFullResUVOffset, 248);
+GR_ASSERT_OFFSET(gr_cacao_constants, InputOutputBufferDimensions, 256);
+GR_ASSERT_OFFSET(gr_cacao_constants, ImportanceMapDimensions, 272);
+GR_ASSERT_OFFSET(gr_cacao_constants, DeinterleavedDepthBufferDimensions, 288);
+GR_ASSERT_OFFSET(gr_cacao_constants, DeinterleavedDepthBufferNormalisedOffset, 312);
+GR_ASSERT_OFFSET(gr_cacao_constants, NormalsWorldToViewspaceMatrix, 320);
+GR_ASSERT_SIZE(gr_cacao_settings, 68);        /* ffx_cacao.h:52-70 */
+GR_ASSERT_OFFSET(gr_cacao_settings, quality_level, 28);
+GR_ASSERT_OFFSET(gr_cacao_settings, generate_normals, 56);
+GR_ASSERT_SIZE(gr_cacao_buffer_sizes, 64);    /* ffx_cacao.h:159-183 */
+GR_STATIC_ASSERT(GR_TRANSFORMS_OFFSET_SHADOW ==GR_MAX_LIGHTS_BINDLESS * 48u, "ClustererBindlessTransforms: lights[4096] of 48 B");
 GR_STATIC_ASSERT(GR_TRANSFORMS_OFFSET_MODEL + GR_MAX_LIGHTS_BINDLESS * 48u == GR_TRANSFORMS_OFFSET_TYPE_MASK, "ClustererBindlessTransforms: model[4096] of 48 B");
 GR_STATIC_ASSERT(GR_TRANSFORMS_OFFSET_TYPE_MASK + GR_MAX_LIGHTS_BINDLESS / 8u == GR_TRANSFORMS_OFFSET_DECALS, "ClustererBindlessTransforms: type_mask[128]");
 #undef GR_ASSERT_SIZE

@@ -1,0 +1,143 @@
+"""CPU: granite_amd/csrc/cacao_core.hpp built for the host (tests/cpp/cacao_core_host.cpp under tests/cpp/hip_emu.hpp, -ffp-contract=off) --
+the kernel text the device build compiles -- and held to tests/cacao_ref.py stage by stage, each stage fed the reference's stored inputs,
+with the bounds of tests/cacao_chain.py.  The same cases run on the device in tests/test_gpu_cacao.py.  The stand-alone program of the same
+file is run once under AddressSanitizer and UndefinedBehaviorSanitizer: the blur's LDS indexing and the guarded stores are what it is for."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import cacao_cases as cc
+import cacao_chain as chain
+import cacao_ref as cr
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SOURCE = os.path.join(ROOT, "tests", "cpp", "cacao_core_host.cpp")
+FLAGS = ["-std=c++20", "-Wall", "-Werror", "-Wno-unused-function", "-ffp-contract=off", "-pthread"]
+
+
+def ptr(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+class HostBackend:
+    def __init__(self, lib):
+        self.lib = lib
+
+    def layout(self, w, h):
+        offsets = np.zeros(11, np.uint64)
+        self.lib.cacao_host_layout(w, h, ptr(offsets))
+        return chain.Layout(w, h, offsets)
+
+    def run(self, stage, guarded, constants, width, height, **a):
+        lib = self.lib
+        # the workspace proper must be 256-byte aligned, as the launchers ask
+        store = np.zeros(guarded.size + 512, np.uint8)
+        shift = (-(store.ctypes.data + chain.GUARD)) % 256
+        view = store[shift:shift + guarded.size]
+        view[:] = guarded
+        ws = C.c_void_p(view.ctypes.data + chain.GUARD)
+        constants = np.ascontiguousarray(constants)
+        out = None
+        if stage == "prepare_depths":
+            rows = chain.padded(a["depth"], 3, np.float32(7.0))
+            lib.cacao_host_prepare_depths(ptr(rows), width, height, rows.strides[0], ws, ptr(constants))
+        elif stage == "prepare_normals":
+            rows = chain.padded(a["normal"], 5, np.uint32(0xffffffff))
+            lib.cacao_host_prepare_normals(ptr(rows), width, height, rows.strides[0], ws, ptr(constants))
+        elif stage == "generate_base":
+            lib.cacao_host_generate(ws, width, height, ptr(constants), 0)
+        elif stage == "generate":
+            lib.cacao_host_generate(ws, width, height, ptr(constants), 3 if a["quality"] == cr.QUALITY_HIGHEST else 2)
+        elif stage.startswith("importance_"):
+            lib.cacao_host_importance(ws, width, height, ptr(constants), ("importance_generate", "importance_postprocess_a", "importance_postprocess_b").index(stage))
+        elif stage == "blur":
+            lib.cacao_host_blur(ws, width, height, ptr(constants), a["blur_passes"])
+        elif stage == "apply":
+            out = np.full((height, width + 7), chain.FILL, np.uint8)
+            lib.cacao_host_apply(ws, ptr(out), width, height, out.strides[0], ptr(constants), a["from_pong"])
+        else:
+            raise KeyError(stage)
+        return (view.copy(), out) if out is not None else view.copy()
+
+
+@pytest.fixture(scope="module")
+def host(tmp_path_factory):
+    lib = tmp_path_factory.mktemp("cacao_core") / "libcacao_core_host.so"
+    subprocess.check_call(["g++", "-O1", *FLAGS, "-shared", "-fPIC", "-o", str(lib), SOURCE])
+    return C.CDLL(str(lib))
+
+
+@pytest.mark.parametrize("quality", cc.QUALITIES, ids=lambda q: f"q{q}")
+@pytest.mark.parametrize("case", cc.CASES, ids=cc.case_id)
+def test_stages_against_reference(host, case, quality):
+    chain.check_stages(HostBackend(host), case, quality)
+
+
+@pytest.mark.parametrize("case", [c for c in cc.CASES if c[:2] == (130, 98)], ids=cc.case_id)
+def test_lod_flags_are_the_references(host, case):
+    """the header's own flag (a tap's lod within 2^-10 of a mip switch) against cacao_ref's, where they are not a last bit of log2 apart"""
+    w, h, cam_name, variant, _ = case
+    quality = cr.QUALITY_HIGH
+    ref = chain.reference(case, quality)
+    backend = HostBackend(host)
+    layout = backend.layout(w, h)
+    buf = np.zeros(layout.bytes + 256, np.uint8)
+    shift = (-buf.ctypes.data) % 256
+    ws = buf[shift:shift + layout.bytes]
+    layout.put(ws, "depth_mips", ref["depth_mips"])
+    layout.put(ws, "normals", ref["normals"])
+    flags = np.zeros((cr.PASSES, layout.hh, layout.hw), np.uint8)
+    constants = np.ascontiguousarray(cc.constants(w, h, cam_name, variant, quality))
+    host.cacao_host_generate_flags(ptr(ws), w, h, ptr(constants), 2, ptr(flags))
+    differing = np.count_nonzero(flags.astype(bool) != ref["info"]["flag"])
+    # a flag is itself a comparison of log2's result with a threshold: the two may disagree on a texel whose lod sits on the flag's own edge
+    assert differing <= max(1, int(0.1 * ref["info"]["flag"].sum())), f"{differing} texels flagged differently"
+
+
+def test_constants_are_the_references_bytes(host):
+    """the header's restatement of FFX_CACAO_UpdateBufferSizeInfo / UpdateConstants / UpdatePerPassConstants against the bytes the reference's
+    own ffx_cacao.cpp wrote; PatternRotScaleMatrices may differ by 1 ulp (cosf / sinf belong to the math library of the day)"""
+    g = cc.golden()
+    checked = 0
+    for w, h in cc.SIZES:
+        sizes = np.zeros(16, np.uint32)
+        host.cacao_host_buffer_sizes(w, h, ptr(sizes))
+        assert np.array_equal(sizes, g[f"{w}x{h}/sizes"])
+        for cam_name in cc.CAMERAS:
+            for variant in cc.SETTINGS:
+                for quality in cc.QUALITIES:
+                    k = cc.key(w, h, cam_name, variant, quality)
+                    got = np.zeros(4, cr.CONSTANTS_DTYPE)
+                    host.cacao_host_constants(ptr(got), ptr(g[k + "/settings"]), w, h, ptr(g[k + "/proj"]), ptr(g[k + "/view"]))
+                    want = g[k + "/constants"].view(cr.CONSTANTS_DTYPE).reshape(4)
+                    for name in cr.CONSTANTS_DTYPE.names:
+                        if name == "PatternRotScaleMatrices":
+                            ulps = np.abs(got[name].view(np.int32).astype(np.int64) - want[name].view(np.int32).astype(np.int64))
+                            assert ulps.max() <= 1, (k, name, int(ulps.max()))
+                        else:
+                            assert got[name].tobytes() == want[name].tobytes(), (k, name, got[name], want[name])
+                    checked += 1
+    assert checked == len(cc.SIZES) * len(cc.CAMERAS) * len(cc.SETTINGS) * len(cc.QUALITIES)
+    settings = np.zeros(17, np.uint32)
+    host.cacao_host_settings(ptr(settings))
+    assert np.array_equal(settings, cc.settings_words("reference", cr.QUALITY_HIGHEST))
+
+
+def test_unorm8_load_is_the_quotient(host):
+    """the division-free v / 255 of the header against the IEEE quotient, all 256 inputs"""
+    host.cacao_host_unorm8.restype = C.c_float
+    got = np.array([host.cacao_host_unorm8(v) for v in range(256)], np.float32)
+    assert np.array_equal(got.view(np.uint32), (np.arange(256, dtype=np.float32) / np.float32(255.0)).view(np.uint32))
+
+
+def test_stand_alone_program_under_sanitizers(tmp_path):
+    """the whole pass at 61 x 45, 16 x 16 and 130 x 98 on exactly sized heap blocks, -fsanitize=address,undefined"""
+    exe = tmp_path / "cacao_core_host_asan"
+    subprocess.check_call(["g++", "-O1", "-g", *FLAGS, "-DCACAO_HOST_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
+                           "-o", str(exe), SOURCE])
+    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert "cacao_core_host: done" in run.stdout and "runtime error" not in run.stderr

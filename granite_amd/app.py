@@ -331,7 +331,7 @@ class Application:
         self._check(self.lib.gra_upload_gbuffer_gtx(self.handle, *paths))
 
     def decode_gtx(self, src: str, dst: str):
-        """Decode the block-compressed .gtx `src` (BC1-BC7) on the device, every level and layer, into the uncompressed .gtx `dst`."""
+        """Decode the block-compressed .gtx `src` (BC1-BC7 or ASTC LDR) on the device, every level and layer, into the uncompressed .gtx `dst`."""
         self._check(self.lib.gra_gtx_decode(self.handle, str(src).encode(), str(dst).encode()))
 
     def bake_environment(self, equirect: str, cube: Optional[str] = None, reflection: Optional[str] = None, irradiance: Optional[str] = None,

@@ -49,7 +49,38 @@ FORMAT_BC6H_UFLOAT_BLOCK = 143
 FORMAT_BC6H_SFLOAT_BLOCK = 144
 FORMAT_BC7_UNORM_BLOCK = 145
 FORMAT_BC7_SRGB_BLOCK = 146
-BLOCK_FORMATS = (131, 132, 133, 134, 135, 136, 137, 138, 139, 141, 143, 144, 145, 146)
+BLOCK_FORMATS = (131, 132, 133, 134, 135, 136, 137, 138, 139, 141, 143, 144, 145, 146)  # BC1-BC7: 4 x 4 texels a block
+# ASTC LDR, 2-D footprints, 16 bytes a block (the SFLOAT forms are not handled)
+FORMAT_ASTC_4x4_UNORM_BLOCK = 157
+FORMAT_ASTC_4x4_SRGB_BLOCK = 158
+FORMAT_ASTC_5x4_UNORM_BLOCK = 159
+FORMAT_ASTC_5x4_SRGB_BLOCK = 160
+FORMAT_ASTC_5x5_UNORM_BLOCK = 161
+FORMAT_ASTC_5x5_SRGB_BLOCK = 162
+FORMAT_ASTC_6x5_UNORM_BLOCK = 163
+FORMAT_ASTC_6x5_SRGB_BLOCK = 164
+FORMAT_ASTC_6x6_UNORM_BLOCK = 165
+FORMAT_ASTC_6x6_SRGB_BLOCK = 166
+FORMAT_ASTC_8x5_UNORM_BLOCK = 167
+FORMAT_ASTC_8x5_SRGB_BLOCK = 168
+FORMAT_ASTC_8x6_UNORM_BLOCK = 169
+FORMAT_ASTC_8x6_SRGB_BLOCK = 170
+FORMAT_ASTC_8x8_UNORM_BLOCK = 171
+FORMAT_ASTC_8x8_SRGB_BLOCK = 172
+FORMAT_ASTC_10x5_UNORM_BLOCK = 173
+FORMAT_ASTC_10x5_SRGB_BLOCK = 174
+FORMAT_ASTC_10x6_UNORM_BLOCK = 175
+FORMAT_ASTC_10x6_SRGB_BLOCK = 176
+FORMAT_ASTC_10x8_UNORM_BLOCK = 177
+FORMAT_ASTC_10x8_SRGB_BLOCK = 178
+FORMAT_ASTC_10x10_UNORM_BLOCK = 179
+FORMAT_ASTC_10x10_SRGB_BLOCK = 180
+FORMAT_ASTC_12x10_UNORM_BLOCK = 181
+FORMAT_ASTC_12x10_SRGB_BLOCK = 182
+FORMAT_ASTC_12x12_UNORM_BLOCK = 183
+FORMAT_ASTC_12x12_SRGB_BLOCK = 184
+ASTC_FOOTPRINTS = ((4, 4), (5, 4), (5, 5), (6, 5), (6, 6), (8, 5), (8, 6), (8, 8), (10, 5), (10, 6), (10, 8), (10, 10), (12, 10), (12, 12))
+ASTC_FORMATS = {157 + i: ASTC_FOOTPRINTS[i // 2] for i in range(28)}  # format -> (block width, block height)
 
 FORMAT_BPP = {
     FORMAT_R8_UNORM: 1,
@@ -525,6 +556,8 @@ def load_library() -> C.CDLL:
         "gr_video_yuv_plan": (C.c_int, [P(Image), C.c_uint32, P(Image), P(VideoYuvInfo), P(VideoYuvPlan)]),
         "gr_texture_decoded_format": (C.c_uint32, [C.c_uint32]),
         "gr_texture_block_bytes": (C.c_uint32, [C.c_uint32]),
+        "gr_texture_block_dim": (C.c_int, [C.c_uint32, P(C.c_uint32), P(C.c_uint32)]),
+        "gr_texture_block_info": (C.c_int, [C.c_uint32, P(C.c_uint32), P(C.c_uint32)]),
         "gr_texture_decode": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint32, P(Image)]),
         "gr_cube_chain_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32]),
         "gr_cube_chain_offset": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32]),
@@ -575,7 +608,7 @@ EXPORTED_SYMBOLS = [
     "gr_smaa_set_luts", "gr_fxaa", "gr_blit", "gr_smaa_edge_detection", "gr_smaa_blend_weight", "gr_smaa_neighbor_blend", "gr_taa_resolve",
     "gr_hiz", "gr_mip_chain_offset", "gr_mip_chain_size", "gr_fsr_upscale", "gr_fsr_sharpen", "gr_fill_byte", "gr_fill_u32", "gr_pq10_encode", "gr_get_device_info", "gr_spd_downsample", "gr_debug_mix", "gr_pack_b10g11r11",
     "gr_video_scale", "gr_video_scale_plan", "gr_video_scaler_weights", "gr_video_yuv_to_rgb", "gr_video_yuv_plan",
-    "gr_texture_decoded_format", "gr_texture_block_bytes", "gr_texture_decode",
+    "gr_texture_decoded_format", "gr_texture_block_bytes", "gr_texture_block_dim", "gr_texture_block_info", "gr_texture_decode",
     "gr_cube_chain_bytes", "gr_cube_chain_offset", "gr_env_equirect_to_cube", "gr_env_specular", "gr_env_diffuse",
     "gr_fft_describe", "gr_fft_plan_create", "gr_fft_plan_destroy", "gr_fft_plan_iterations", "gr_fft_execute", "gr_fft_execute_iteration",
     "gr_ocean_generate_fft", "gr_ocean_bake_maps", "gr_ocean_mipmap",
@@ -936,9 +969,20 @@ class Context:
                                            quality))
 
     def texture_decode(self, block_format: int, blocks, block_row_pitch: int, out, stream=None):
-        """gr_texture_decode: one level of one layer of BC1-BC7 blocks (device pointer) into `out` (DeviceImage or Image)."""
+        """gr_texture_decode: one level of one layer of BC1-BC7 or ASTC LDR blocks (device pointer; ceil(w / bw) blocks a row, bw x bh
+        texels a block as texture_block_info gives them) into `out` (DeviceImage or Image) of the decoded format."""
         desc = out.desc if isinstance(out, DeviceImage) else out
         self.check(self.lib.gr_texture_decode(self.handle, stream, int(block_format), blocks, int(block_row_pitch), C.byref(desc)))
+
+    @staticmethod
+    def texture_block_info(block_format: int):
+        """(block width, block height, bytes per block, decoded format) of a format gr_texture_decode takes; ValueError otherwise."""
+        lib = load_library()
+        w, h, nbytes, decoded = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        if lib.gr_texture_block_dim(int(block_format), C.byref(w), C.byref(h)) < 0 or \
+                lib.gr_texture_block_info(int(block_format), C.byref(nbytes), C.byref(decoded)) < 0:
+            raise ValueError(f"format {block_format} is not a block format gr_texture_decode takes")
+        return w.value, h.value, nbytes.value, decoded.value
 
     # ---- environment baking: cubes are DeviceBuffers holding an RGBA16F chain in GTX payload layout (gr_cube_chain_bytes) ----------
     def env_equirect_to_cube(self, equirect: DeviceImage, cube: DeviceBuffer, size: int, levels: int, stream=None):

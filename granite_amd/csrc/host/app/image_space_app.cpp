@@ -470,7 +470,7 @@ void ImageSpaceApplication::upload_gbuffer_gtx(const char *const paths[6])
 		auto &img = images[i];
 		if (img.type != 1 || img.layers != 1 || img.depth != 1)
 			throw std::runtime_error(std::string(paths[i]) + ": a 2-D single-layer image is expected for " + slots[i].what + ".");
-		// a block-compressed file stands for its decoded format (albedo as BC1/2/3/7, pbr as BC5, emissive as BC6H into RGBA16F targets)
+		// a block-compressed file stands for its decoded format (albedo as BC1/2/3/7 or ASTC, pbr as BC5, emissive as BC6H into RGBA16F targets)
 		const VkFormat decoded = compressed_format_to_decoded_format(img.format);
 		compressed[i] = decoded != VK_FORMAT_UNDEFINED;
 		const VkFormat format = compressed[i] ? decoded : img.format;
@@ -495,7 +495,7 @@ void ImageSpaceApplication::upload_gbuffer_gtx(const char *const paths[6])
 		if (!*targets[i])
 			throw std::logic_error(std::string("This graph has no ") + slots[i].what + " attachment.");
 		const GtxImage &img = images[i];
-		const uint32_t pitch = img.level_blocks_x(0) * gr_texture_block_bytes(uint32_t(img.format));
+		const uint32_t pitch = img.level_blocks_x(0) * vk_format_payload_block_size(img.format);
 		const size_t bytes = size_t(pitch) * img.level_blocks_y(0);
 		void *blocks = nullptr;
 		if (gr_alloc(ctx, bytes, &blocks) < 0)

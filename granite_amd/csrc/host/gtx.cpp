@@ -12,7 +12,7 @@ static const char GtxMagic[16] = "GRANITE TEXFMT1";
 size_t GtxImage::level_size(uint32_t level) const
 {
 	const uint32_t d = (depth >> level) ? (depth >> level) : 1u;
-	return size_t(level_blocks_x(level)) * level_blocks_y(level) * d * layers * vk_format_block_size(format);
+	return size_t(level_blocks_x(level)) * level_blocks_y(level) * d * layers * vk_format_payload_block_size(format);
 }
 
 size_t GtxImage::level_offset(uint32_t level) const
@@ -73,7 +73,7 @@ GtxImage gtx_parse(const void *data, size_t size)
 
 	if (img.type > 2) // VK_IMAGE_TYPE_1D / 2D / 3D
 		throw std::runtime_error("GTX: unknown image type.");
-	if (!vk_format_block_size(img.format))
+	if (!vk_format_payload_block_size(img.format))
 		throw std::runtime_error("GTX: format " + std::to_string(unsigned(img.format)) + " is not one the executor handles.");
 	if (!img.width || !img.height || !img.depth || !img.layers || !img.levels || img.levels > 16)
 		throw std::runtime_error("GTX: empty or implausible dimensions.");
@@ -95,7 +95,7 @@ GtxImage gtx_parse(const void *data, size_t size)
 
 std::vector<uint8_t> gtx_serialize(const GtxImage &image)
 {
-	if (!vk_format_block_size(image.format))
+	if (!vk_format_payload_block_size(image.format))
 		throw std::runtime_error("GTX: cannot serialise this format.");
 	const size_t payload_size = image.required_payload_size();
 	if (image.payload.size() != payload_size)

@@ -8,8 +8,9 @@
 // Header, 64 bytes, little endian: magic[16] = "GRANITE TEXFMT1\0"; u32 type (VkImageType), format (VkFormat), width,
 // height, depth, layers, levels, flags; u64 payload_size; u64 reserved.  Payload: mip levels in order, each starting at
 // a 16-byte aligned offset; inside a level the array layers (and depth slices) follow each other, rows tightly packed.
-// A block-compressed level holds ceil(w / 4) x ceil(h / 4) blocks per layer, rows of blocks tightly packed.
-// Only formats the executor knows (vk_format_block_size: its uncompressed formats and BC1-BC7 without SNORM) are accepted.
+// A block-compressed level holds ceil(w / bw) x ceil(h / bh) blocks per layer (4 x 4 texels for BC, the footprint for ASTC), rows of
+// blocks tightly packed.
+// Only formats the executor knows (vk_format_payload_block_size: its uncompressed formats, BC1-BC7 without SNORM, ASTC LDR) are accepted.
 #pragma once
 #include <cstddef>
 #include <cstdint>

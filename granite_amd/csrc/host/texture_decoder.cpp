@@ -7,7 +7,8 @@ namespace Granite
 {
 VkFormat compressed_format_to_decoded_format(VkFormat format)
 {
-	return VkFormat(gr_texture_decoded_format(uint32_t(format)));
+	uint32_t block_bytes = 0, decoded = 0;
+	return gr_texture_block_info(uint32_t(format), &block_bytes, &decoded) < 0 ? VK_FORMAT_UNDEFINED : VkFormat(decoded);
 }
 
 namespace
@@ -49,7 +50,9 @@ GtxImage decode_compressed_image(gr_ctx *ctx, gr_stream stream, const GtxImage &
 			throw std::runtime_error(gr_last_error(ctx));
 	};
 	check(gr_upload(ctx, stream, blocks.ptr, compressed.payload.data(), compressed.payload.size()));
-	const uint32_t block_bytes = gr_texture_block_bytes(uint32_t(compressed.format)), texel_bytes = vk_format_block_size(decoded);
+	uint32_t block_bytes = 0, decoded_again = 0;
+	check(gr_texture_block_info(uint32_t(compressed.format), &block_bytes, &decoded_again));
+	const uint32_t texel_bytes = vk_format_block_size(decoded);
 	for (uint32_t level = 0; level < compressed.levels; level++)
 	{
 		const uint32_t width = compressed.level_width(level), height = compressed.level_height(level);

@@ -7,7 +7,8 @@
 namespace Granite
 {
 // texture_decoder.cpp:28-129 for the formats handled here: BC1/2/3/7 -> R8G8B8A8_UNORM / _SRGB, BC4 -> R8_UNORM, BC5 -> R8G8_UNORM,
-// BC6H -> R16G16B16A16_SFLOAT; VK_FORMAT_UNDEFINED for everything else (the SNORM forms included).
+// BC6H -> R16G16B16A16_SFLOAT, ASTC LDR -> R8G8B8A8_UNORM / _SRGB; VK_FORMAT_UNDEFINED for everything else (the SNORM forms, ETC2 / EAC
+// and the ASTC SFLOAT forms included).
 VkFormat compressed_format_to_decoded_format(VkFormat format);
 
 // decode_compressed_image (texture_decoder.cpp:1290-1424): one upload of the whole payload, one gr_texture_decode per level and layer

@@ -48,7 +48,36 @@ enum VkFormat : uint32_t
 	VK_FORMAT_BC6H_UFLOAT_BLOCK = 143,
 	VK_FORMAT_BC6H_SFLOAT_BLOCK = 144,
 	VK_FORMAT_BC7_UNORM_BLOCK = 145,
-	VK_FORMAT_BC7_SRGB_BLOCK = 146
+	VK_FORMAT_BC7_SRGB_BLOCK = 146,
+	// ASTC LDR, 2-D footprints: .gtx payloads and inputs of Granite::decode_compressed_image only
+	VK_FORMAT_ASTC_4x4_UNORM_BLOCK = 157,
+	VK_FORMAT_ASTC_4x4_SRGB_BLOCK = 158,
+	VK_FORMAT_ASTC_5x4_UNORM_BLOCK = 159,
+	VK_FORMAT_ASTC_5x4_SRGB_BLOCK = 160,
+	VK_FORMAT_ASTC_5x5_UNORM_BLOCK = 161,
+	VK_FORMAT_ASTC_5x5_SRGB_BLOCK = 162,
+	VK_FORMAT_ASTC_6x5_UNORM_BLOCK = 163,
+	VK_FORMAT_ASTC_6x5_SRGB_BLOCK = 164,
+	VK_FORMAT_ASTC_6x6_UNORM_BLOCK = 165,
+	VK_FORMAT_ASTC_6x6_SRGB_BLOCK = 166,
+	VK_FORMAT_ASTC_8x5_UNORM_BLOCK = 167,
+	VK_FORMAT_ASTC_8x5_SRGB_BLOCK = 168,
+	VK_FORMAT_ASTC_8x6_UNORM_BLOCK = 169,
+	VK_FORMAT_ASTC_8x6_SRGB_BLOCK = 170,
+	VK_FORMAT_ASTC_8x8_UNORM_BLOCK = 171,
+	VK_FORMAT_ASTC_8x8_SRGB_BLOCK = 172,
+	VK_FORMAT_ASTC_10x5_UNORM_BLOCK = 173,
+	VK_FORMAT_ASTC_10x5_SRGB_BLOCK = 174,
+	VK_FORMAT_ASTC_10x6_UNORM_BLOCK = 175,
+	VK_FORMAT_ASTC_10x6_SRGB_BLOCK = 176,
+	VK_FORMAT_ASTC_10x8_UNORM_BLOCK = 177,
+	VK_FORMAT_ASTC_10x8_SRGB_BLOCK = 178,
+	VK_FORMAT_ASTC_10x10_UNORM_BLOCK = 179,
+	VK_FORMAT_ASTC_10x10_SRGB_BLOCK = 180,
+	VK_FORMAT_ASTC_12x10_UNORM_BLOCK = 181,
+	VK_FORMAT_ASTC_12x10_SRGB_BLOCK = 182,
+	VK_FORMAT_ASTC_12x12_UNORM_BLOCK = 183,
+	VK_FORMAT_ASTC_12x12_SRGB_BLOCK = 184
 };
 
 enum VkImageUsageFlagBits : uint32_t
@@ -136,9 +165,24 @@ static inline unsigned vk_format_block_size(VkFormat format)
 	}
 }
 
-// Texels per block: 4 x 4 for the BC formats above, 1 x 1 for everything else (vulkan/texture/texture_format.cpp format_block_dim).
+static inline bool vk_format_is_astc_ldr(VkFormat format) { return format >= VK_FORMAT_ASTC_4x4_UNORM_BLOCK && format <= VK_FORMAT_ASTC_12x12_SRGB_BLOCK; }
+
+// Bytes per block of a .gtx payload: vk_format_block_size, and 16 for the ASTC LDR formats.  vk_format_block_size itself keeps 0 for
+// ASTC: it is also the texel size the image-argument contract knows a format by, and no image argument takes an ASTC format.
+static inline unsigned vk_format_payload_block_size(VkFormat format) { return vk_format_is_astc_ldr(format) ? 16u : vk_format_block_size(format); }
+
+// Texels per block: 4 x 4 for the BC formats above, the footprint for ASTC, 1 x 1 for everything else (vulkan/texture/texture_format.cpp
+// format_block_dim).
 static inline void vk_format_block_dim(VkFormat format, unsigned &width, unsigned &height)
 {
+	if (vk_format_is_astc_ldr(format))
+	{
+		static const unsigned char dims[14][2] = {{4, 4}, {5, 4}, {5, 5}, {6, 5}, {6, 6}, {8, 5}, {8, 6}, {8, 8}, {10, 5}, {10, 6}, {10, 8}, {10, 10}, {12, 10}, {12, 12}};
+		const unsigned index = (unsigned(format) - unsigned(VK_FORMAT_ASTC_4x4_UNORM_BLOCK)) / 2;
+		width = dims[index][0];
+		height = dims[index][1];
+		return;
+	}
 	const bool block = format >= VK_FORMAT_BC1_RGB_UNORM_BLOCK && format <= VK_FORMAT_BC7_SRGB_BLOCK && vk_format_block_size(format) != 0; // not SNORM
 	width = height = block ? 4u : 1u;
 }

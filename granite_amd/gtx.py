@@ -41,15 +41,22 @@ class GtxFile:
 
 
 def block_bytes(fmt: int) -> int:
-    """Bytes per texel, or per 4 x 4 block of a BC format."""
+    """Bytes per texel, or per block of a BC or ASTC format."""
+    if fmt in capi.ASTC_FORMATS:
+        return 16
     return capi.load_library().gr_texture_block_bytes(fmt) or capi.FORMAT_BPP[fmt]
+
+
+def block_dim(fmt: int):
+    """(width, height) of a block in texels: 4 x 4 for BC, the footprint for ASTC, 1 x 1 otherwise."""
+    return capi.ASTC_FORMATS.get(fmt, (4, 4) if fmt in capi.BLOCK_FORMATS else (1, 1))
 
 
 def level_blocks(info: GtxInfo, level: int):
     """(blocks per row, rows of blocks, bytes per block) of a level; a block is one texel unless the format is block-compressed."""
-    dim = 4 if info.format in capi.BLOCK_FORMATS else 1
+    bw, bh = block_dim(info.format)
     w, h = max(info.width >> level, 1), max(info.height >> level, 1)
-    return (w + dim - 1) // dim, (h + dim - 1) // dim, block_bytes(info.format)
+    return (w + bw - 1) // bw, (h + bh - 1) // bh, block_bytes(info.format)
 
 
 def level_size(info: GtxInfo, level: int) -> int:
@@ -98,7 +105,7 @@ def write(path: str, fmt: int, levels: List[np.ndarray], flags: int = 0, layers:
     """levels[l]: array whose bytes are level l (all layers), level 0 first; shape[-3:-1] or [0:2] of level 0 gives h, w.
     A block-compressed format takes raw blocks and needs size = (width, height) in texels."""
     first = np.ascontiguousarray(levels[0])
-    if fmt in capi.BLOCK_FORMATS and size is None:
+    if (fmt in capi.BLOCK_FORMATS or fmt in capi.ASTC_FORMATS) and size is None:
         raise GtxError("a block-compressed format needs size=(width, height)")
     h, w = (size[1], size[0]) if size is not None else (first.shape[1], first.shape[2]) if layers > 1 else (first.shape[0], first.shape[1])
     info = GtxInfo(1, fmt, w, h, 1, layers, len(levels), flags, 0)

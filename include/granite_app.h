@@ -173,10 +173,11 @@ int gra_gtx_write(const char *path, const gra_gtx_info *info, const void *payloa
  * emissive / HDR R16G16B16A16_SFLOAT, albedo R8G8B8A8_SRGB or _UNORM, normal A2B10G10R10_UNORM_PACK32, pbr R8G8_UNORM,
  * depth D32_SFLOAT or R32_SFLOAT, motion vectors R16G16_SFLOAT; sizes must equal the configured frame.  NULL = unchanged.
  * A block-compressed file is accepted where its decoded format (gr_texture_decoded_format) is the attachment's own -- albedo as
- * BC1 / BC2 / BC3 / BC7, pbr as BC5, emissive as BC6H with RGBA16F targets: its blocks are uploaded and decoded into the attachment. */
+ * BC1 / BC2 / BC3 / BC7 or ASTC LDR, pbr as BC5, emissive as BC6H with RGBA16F targets: its blocks are uploaded and decoded into the
+ * attachment. */
 int gra_upload_gbuffer_gtx(gra_app *app, const char *emissive, const char *albedo, const char *normal, const char *pbr,
                            const char *depth, const char *motion_vectors);
-/* Decodes a block-compressed .gtx (BC1-BC7; no SNORM, no 3-D) on the application's device, every level and layer
+/* Decodes a block-compressed .gtx (BC1-BC7 without SNORM, ASTC LDR; no 3-D) on the application's device, every level and layer
  * (Granite::decode_compressed_image, one gr_texture_decode each), and writes an uncompressed .gtx of the decoded format with the
  * same extents, layers, levels and flags. */
 int gra_gtx_decode(gra_app *app, const char *src_path, const char *dst_path);

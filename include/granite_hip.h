@@ -71,7 +71,36 @@ typedef enum gr_format
 	GR_FORMAT_BC6H_UFLOAT_BLOCK = 143,
 	GR_FORMAT_BC6H_SFLOAT_BLOCK = 144,
 	GR_FORMAT_BC7_UNORM_BLOCK = 145,
-	GR_FORMAT_BC7_SRGB_BLOCK = 146
+	GR_FORMAT_BC7_SRGB_BLOCK = 146,
+	/* ASTC LDR, 2-D footprints, 16 bytes a block: inputs of gr_texture_decode only.  The SFLOAT (HDR) forms are absent. */
+	GR_FORMAT_ASTC_4x4_UNORM_BLOCK = 157,
+	GR_FORMAT_ASTC_4x4_SRGB_BLOCK = 158,
+	GR_FORMAT_ASTC_5x4_UNORM_BLOCK = 159,
+	GR_FORMAT_ASTC_5x4_SRGB_BLOCK = 160,
+	GR_FORMAT_ASTC_5x5_UNORM_BLOCK = 161,
+	GR_FORMAT_ASTC_5x5_SRGB_BLOCK = 162,
+	GR_FORMAT_ASTC_6x5_UNORM_BLOCK = 163,
+	GR_FORMAT_ASTC_6x5_SRGB_BLOCK = 164,
+	GR_FORMAT_ASTC_6x6_UNORM_BLOCK = 165,
+	GR_FORMAT_ASTC_6x6_SRGB_BLOCK = 166,
+	GR_FORMAT_ASTC_8x5_UNORM_BLOCK = 167,
+	GR_FORMAT_ASTC_8x5_SRGB_BLOCK = 168,
+	GR_FORMAT_ASTC_8x6_UNORM_BLOCK = 169,
+	GR_FORMAT_ASTC_8x6_SRGB_BLOCK = 170,
+	GR_FORMAT_ASTC_8x8_UNORM_BLOCK = 171,
+	GR_FORMAT_ASTC_8x8_SRGB_BLOCK = 172,
+	GR_FORMAT_ASTC_10x5_UNORM_BLOCK = 173,
+	GR_FORMAT_ASTC_10x5_SRGB_BLOCK = 174,
+	GR_FORMAT_ASTC_10x6_UNORM_BLOCK = 175,
+	GR_FORMAT_ASTC_10x6_SRGB_BLOCK = 176,
+	GR_FORMAT_ASTC_10x8_UNORM_BLOCK = 177,
+	GR_FORMAT_ASTC_10x8_SRGB_BLOCK = 178,
+	GR_FORMAT_ASTC_10x10_UNORM_BLOCK = 179,
+	GR_FORMAT_ASTC_10x10_SRGB_BLOCK = 180,
+	GR_FORMAT_ASTC_12x10_UNORM_BLOCK = 181,
+	GR_FORMAT_ASTC_12x10_SRGB_BLOCK = 182,
+	GR_FORMAT_ASTC_12x12_UNORM_BLOCK = 183,
+	GR_FORMAT_ASTC_12x12_SRGB_BLOCK = 184
 } gr_format;
 
 /* A 2-D attachment as the executor sees it: what Vulkan::ImageView is to the reference's callbacks.
@@ -810,21 +839,33 @@ int gr_video_yuv_to_rgb(gr_ctx *ctx, gr_stream stream, const gr_image *planes, u
 int gr_video_yuv_plan(const gr_image *planes, uint32_t num_planes, const gr_image *out, const gr_video_yuv_info *info,
                       struct gr_video_yuv_plan *plan);
 
-/* ---- Block-compressed texture decode (vulkan/texture/texture_decoder.cpp, assets/shaders/decode/{s3tc,rgtc,bc7,bc6}.comp) ---- */
+/* ---- Block-compressed texture decode (vulkan/texture/texture_decoder.cpp, assets/shaders/decode/{s3tc,rgtc,bc7,bc6,astc}.comp) ---- */
 
 /* Host-only. Decoded format of a block format as compressed_format_to_decoded_format (texture_decoder.cpp:28-129):
  * BC1/2/3/7 -> R8G8B8A8_UNORM or _SRGB (same bytes; the view differs), BC4 -> R8_UNORM, BC5 -> R8G8_UNORM,
  * BC6H -> R16G16B16A16_SFLOAT.  GR_FORMAT_UNDEFINED for anything else. */
 uint32_t gr_texture_decoded_format(uint32_t block_format);
-/* Host-only. Bytes per 4x4 block (8 or 16), 0 if not a block format handled here. */
+/* Host-only. Bytes per 4x4 block (8 or 16), 0 if not a block format handled here.
+ * These two queries answer for BC1-BC7 only, as they always have: they give GR_FORMAT_UNDEFINED / 0 for every other number, the ASTC
+ * formats included.  gr_texture_block_dim and gr_texture_block_info below answer for every format gr_texture_decode takes. */
 uint32_t gr_texture_block_bytes(uint32_t block_format);
-/* One level of one layer.  `blocks`: device pointer, ceil(w/4) x ceil(h/4) blocks, rows `block_row_pitch_bytes` apart
- * (>= ceil(w/4) * block bytes).  out->width/height are texel extents (at most 65536), out->format must be gr_texture_decoded_format().
+/* Host-only. Texels per block: 4 x 4 for BC1-BC7, the footprint (4 x 4 ... 12 x 12) for ASTC.  GR_ERR_UNSUPPORTED_FORMAT for a format
+ * gr_texture_decode does not take, GR_ERR_INVALID_ARGUMENT for a NULL pointer. */
+int gr_texture_block_dim(uint32_t block_format, uint32_t *width, uint32_t *height);
+/* Host-only. Bytes per block and the decoded format (what out->format of gr_texture_decode must be) of BC1-BC7 and of the ASTC LDR
+ * formats: ASTC _UNORM -> R8G8B8A8_UNORM, _SRGB -> R8G8B8A8_SRGB, 16 bytes.  Same codes as gr_texture_block_dim. */
+int gr_texture_block_info(uint32_t block_format, uint32_t *block_bytes, uint32_t *decoded_format);
+/* One level of one layer.  `blocks`: device pointer, ceil(w/bw) x ceil(h/bh) blocks of bw x bh texels (gr_texture_block_dim), rows
+ * `block_row_pitch_bytes` apart (>= ceil(w/bw) * block bytes).  out->width/height are texel extents (at most 65536), out->format must
+ * be the decoded format (gr_texture_block_info).
  * Texels outside out->width x out->height are not written.  Any out pitch >= the row's bytes and any byte alignment of
  * either pointer; everything else is refused with GR_ERR_INVALID_ARGUMENT / GR_ERR_UNSUPPORTED_FORMAT before a launch.
  * width or height 0 returns GR_OK without launching.
  * BC1 RGB stores alpha 255 everywhere, BC1 RGBA stores the punch-through texel as (0, 0, 0, 0); BC2 / BC3 colours are always four-colour;
- * BC6H stores alpha 0x3C00; reserved BC6H / BC7 modes store what the shaders store (zero endpoints); _SRGB formats store the _UNORM bytes. */
+ * BC6H stores alpha 0x3C00; reserved BC6H / BC7 modes store what the shaders store (zero endpoints); _SRGB formats store the _UNORM bytes.
+ * ASTC decodes as astc.comp does in its 8-bit mode: endpoints interpolated in 16 bits as (c << 8) | 0x80 and the top byte stored, for
+ * UNORM and SRGB alike; the error colour (0xff, 0, 0xff, 0xff) for an illegal block and, texel by texel, for the texels of a partition
+ * whose endpoint mode is an HDR one; a void extent stores the top bytes of its colour whether or not its HDR flag is set. */
 int gr_texture_decode(gr_ctx *ctx, gr_stream stream, uint32_t block_format, const void *blocks,
                       uint32_t block_row_pitch_bytes, const gr_image *out);
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""gtx_decode.py src.gtx dst.gtx: decode a block-compressed (BC1-BC7) .gtx on the GPU into an uncompressed one."""
+"""gtx_decode.py src.gtx dst.gtx: decode a block-compressed (BC1-BC7 or ASTC LDR) .gtx on the GPU into an uncompressed one."""
 import os
 import sys
 

@@ -90,13 +90,25 @@ class OceanConfig(C.Structure):
     _fields_ = [("fft_resolution", C.c_uint32), ("displacement_downsample", C.c_uint32), ("grid_count", C.c_uint32), ("grid_resolution", C.c_uint32),
                 ("ocean_size", C.c_float * 2), ("wind_velocity", C.c_float * 2), ("normal_mod", C.c_float), ("amplitude", C.c_float),
                 ("heightmap", C.c_uint32), ("lod_bias", C.c_float), ("force_mipmap_shader", C.c_uint32), ("through_render_graph", C.c_uint32),
-                ("freq_band_modulation", C.c_uint32), ("frequency_bands", C.c_float * 8)]
+                ("freq_band_modulation", C.c_uint32), ("frequency_bands", C.c_float * 8),
+                ("lod_update", C.c_uint32), ("fixed_position", C.c_uint32), ("center_position", C.c_float * 3)]
 
 
 class OceanResourceInfo(C.Structure):
     """gra_ocean_resource_info."""
     _fields_ = [("exists", C.c_uint32), ("is_image", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("format", C.c_uint32),
                 ("levels", C.c_uint32), ("size_bytes", C.c_uint64)]
+
+
+class OceanDrawInfo(C.Structure):
+    """gra_ocean_draw_info."""
+    _fields_ = [("data", C.c_float * 16), ("lods", C.c_uint32), ("lod_stride", C.c_uint32), ("border_count", C.c_uint32), ("index_type", C.c_uint32)]
+
+
+class OceanMeshInfo(C.Structure):
+    """gra_ocean_mesh_info."""
+    _fields_ = [("exists", C.c_uint32), ("on_device", C.c_uint32), ("vertex_count", C.c_uint32), ("vertex_stride", C.c_uint32),
+                ("index_count", C.c_uint32), ("index_stride", C.c_uint32)]
 
 
 class Timestamp(C.Structure):
@@ -114,7 +126,7 @@ EXPORTED_SYMBOLS = [
     "gra_video_begin", "gra_video_frame_layout", "gra_video_read_frame", "gra_video_end",
     "gra_video_play_begin", "gra_video_play_layout", "gra_video_play_frame", "gra_video_play_read_rgb", "gra_video_play_end",
     "gra_ocean_default_config", "gra_ocean_create", "gra_ocean_update", "gra_ocean_describe", "gra_ocean_read", "gra_ocean_distribution",
-    "gra_ocean_parameters", "gra_ocean_destroy",
+    "gra_ocean_parameters", "gra_ocean_destroy", "gra_ocean_set_camera", "gra_ocean_draw_info", "gra_ocean_mesh_describe", "gra_ocean_mesh_read",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -202,6 +214,10 @@ def load_library() -> C.CDLL:
         "gra_ocean_distribution": (C.c_int, [vp, C.c_uint32, vp]),
         "gra_ocean_parameters": (C.c_int, [vp, vp]),
         "gra_ocean_destroy": (None, [vp]),
+        "gra_ocean_set_camera": (C.c_int, [vp, P(C.c_float), P(C.c_float)]),
+        "gra_ocean_draw_info": (C.c_int, [vp, P(OceanDrawInfo)]),
+        "gra_ocean_mesh_describe": (C.c_int, [vp, C.c_uint32, P(OceanMeshInfo)]),
+        "gra_ocean_mesh_read": (C.c_int, [vp, C.c_uint32, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)

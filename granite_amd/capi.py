@@ -225,6 +225,39 @@ class PushOceanMipmap(C.Structure):
     _fields_ = [("result_mod", C.c_float * 4), ("inv_resolution", C.c_float * 2), ("count", C.c_uint32 * 2), ("lod", C.c_float)]
 
 
+class PushOceanUpdateLod(C.Structure):
+    """gr_push_ocean_update_lod: update_lod.comp's Registers (std140, 64 bytes)."""
+    _fields_ = [("shifted_camera_pos", C.c_float * 3), ("max_lod", C.c_float), ("image_offset", C.c_int32 * 2), ("num_threads", C.c_int32 * 2),
+                ("grid_base", C.c_float * 2), ("grid_size", C.c_float * 2), ("lod_bias", C.c_float), ("padding", C.c_uint32 * 3)]
+
+
+class PushOceanCull(C.Structure):
+    """gr_push_ocean_cull: cull_blocks.comp's Registers (std140, 96 bytes)."""
+    _fields_ = [("world_offset", C.c_float * 3), ("padding0", C.c_uint32), ("image_offset", C.c_int32 * 2), ("num_threads", C.c_uint32 * 2),
+                ("inv_num_threads", C.c_float * 2), ("grid_base", C.c_float * 2), ("grid_size", C.c_float * 2), ("grid_resolution", C.c_float * 2),
+                ("heightmap_range", C.c_float * 2), ("guard_band", C.c_float), ("lod_stride", C.c_uint32), ("max_lod", C.c_float),
+                ("handle_edge_lods", C.c_int32), ("padding1", C.c_uint32 * 2)]
+
+
+class OceanPatch(C.Structure):
+    """gr_ocean_patch: PatchData of ocean.inc."""
+    _fields_ = [("offsets", C.c_float * 2), ("inner_lod", C.c_float), ("padding", C.c_float), ("lods", C.c_float * 4)]
+
+
+class OceanIndirectDraw(C.Structure):
+    """gr_ocean_indirect_draw: IndirectDraw of ocean.inc."""
+    _fields_ = [("index_count", C.c_uint32), ("instance_count", C.c_uint32), ("first_index", C.c_uint32), ("vertex_offset", C.c_int32),
+                ("first_instance", C.c_uint32), ("padding0", C.c_uint32), ("padding1", C.c_uint32), ("padding2", C.c_uint32)]
+
+
+class OceanBuffer(C.Structure):
+    """gr_ocean_buffer: a storage buffer, device pointer and size."""
+    _fields_ = [("ptr", C.c_void_p), ("size_bytes", C.c_uint64)]
+
+
+OCEAN_MAX_LOD_INDIRECT = 8
+
+
 # gr_cacao_*: FFX_CACAO_Quality values taken, limits, and the VkFormat values of two intermediates no Image argument takes
 CACAO_QUALITY_HIGH, CACAO_QUALITY_HIGHEST = 3, 4
 CACAO_MAX_BLUR_PASSES = 8
@@ -573,6 +606,9 @@ def load_library() -> C.CDLL:
         "gr_ocean_generate_fft": (C.c_int, [vp, vp, vp, vp, P(PushOceanGenerate), C.c_uint32, P(C.c_float)]),
         "gr_ocean_bake_maps": (C.c_int, [vp, vp, P(Image), P(Image), P(Image), P(Image), P(PushOceanBake)]),
         "gr_ocean_mipmap": (C.c_int, [vp, vp, P(Image), P(Image), P(PushOceanMipmap)]),
+        "gr_ocean_update_lod": (C.c_int, [vp, vp, P(Image), P(PushOceanUpdateLod)]),
+        "gr_ocean_init_counter_buffer": (C.c_int, [vp, vp, P(OceanBuffer), P(C.c_uint32)]),
+        "gr_ocean_cull_blocks": (C.c_int, [vp, vp, P(Image), C.c_uint32, P(OceanBuffer), P(OceanBuffer), P(PushOceanCull), P(C.c_float)]),
         "gr_cacao_reference_settings": (None, [P(CacaoSettings)]),
         "gr_cacao_update_buffer_sizes": (C.c_int, [C.c_uint32, C.c_uint32, P(CacaoBufferSizes)]),
         "gr_cacao_update_constants": (C.c_int, [vp, P(CacaoConstants), P(CacaoSettings), P(CacaoBufferSizes), P(C.c_float), P(C.c_float)]),
@@ -611,7 +647,7 @@ EXPORTED_SYMBOLS = [
     "gr_texture_decoded_format", "gr_texture_block_bytes", "gr_texture_block_dim", "gr_texture_block_info", "gr_texture_decode",
     "gr_cube_chain_bytes", "gr_cube_chain_offset", "gr_env_equirect_to_cube", "gr_env_specular", "gr_env_diffuse",
     "gr_fft_describe", "gr_fft_plan_create", "gr_fft_plan_destroy", "gr_fft_plan_iterations", "gr_fft_execute", "gr_fft_execute_iteration",
-    "gr_ocean_generate_fft", "gr_ocean_bake_maps", "gr_ocean_mipmap",
+    "gr_ocean_generate_fft", "gr_ocean_bake_maps", "gr_ocean_mipmap", "gr_ocean_update_lod", "gr_ocean_init_counter_buffer", "gr_ocean_cull_blocks",
     "gr_cacao_reference_settings", "gr_cacao_update_buffer_sizes", "gr_cacao_update_constants", "gr_cacao_workspace_bytes", "gr_cacao_workspace_describe",
     "gr_cacao_prepare_depths", "gr_cacao_prepare_normals", "gr_cacao_generate_base", "gr_cacao_importance_generate",
     "gr_cacao_importance_postprocess_a", "gr_cacao_importance_postprocess_b", "gr_cacao_generate", "gr_cacao_blur", "gr_cacao_apply",
@@ -1033,6 +1069,22 @@ class Context:
     def ocean_mipmap(self, src: DeviceImage, out: DeviceImage, push: PushOceanMipmap, stream=None):
         """gr_ocean_mipmap: one LinearWrap tap per texel of `out` (push.count texels) from `src`, times push.result_mod."""
         self.check(self.lib.gr_ocean_mipmap(self.handle, stream, src.desc, out.desc, C.byref(push)))
+
+    # ---- ocean: the LOD update's dispatches ------------------------------------------------------------------------------------------
+    def ocean_update_lod(self, lod_image: DeviceImage, push: PushOceanUpdateLod, stream=None):
+        """gr_ocean_update_lod: the R16F LOD map of a num_threads x num_threads grid."""
+        self.check(self.lib.gr_ocean_update_lod(self.handle, stream, lod_image.desc, C.byref(push)))
+
+    def ocean_init_counter_buffer(self, counters: "DeviceBuffer", counts16, stream=None):
+        """gr_ocean_init_counter_buffer: eight indirect draws, index_count from the first eight of the sixteen counts."""
+        counts = (C.c_uint32 * 16)(*[int(v) for v in counts16])
+        self.check(self.lib.gr_ocean_init_counter_buffer(self.handle, stream, C.byref(OceanBuffer(counters.ptr, counters.nbytes)), counts))
+
+    def ocean_cull_blocks(self, lod_image: DeviceImage, wrap: int, patches: "DeviceBuffer", counters: "DeviceBuffer", push: PushOceanCull, frustum, stream=None):
+        """gr_ocean_cull_blocks: one patch per block in view, appended to its LOD's bucket.  frustum: 24 floats, six planes."""
+        planes = (C.c_float * 24)(*[float(v) for v in frustum])
+        self.check(self.lib.gr_ocean_cull_blocks(self.handle, stream, lod_image.desc, int(wrap), C.byref(OceanBuffer(patches.ptr, patches.nbytes)),
+                                                 C.byref(OceanBuffer(counters.ptr, counters.nbytes)), C.byref(push), planes))
 
     # ---- SSAO: FidelityFX CACAO --------------------------------------------------------------------------------------------------------
     def cacao_workspace(self, width: int, height: int) -> DeviceBuffer:

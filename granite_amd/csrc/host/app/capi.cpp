@@ -315,7 +315,11 @@ int gra_ocean_create(gra_app *app, const gra_ocean_config *config, gra_ocean **o
 		c.lod_bias = config->lod_bias;
 		auto handle = std::make_unique<gra_ocean>();
 		handle->app = app;
-		handle->ocean = std::make_unique<Ocean>(c, config->force_mipmap_shader != 0); // refuses before anything is allocated
+		OceanLodRequest lod;
+		lod.lod_update = config->lod_update != 0;
+		lod.fixed_position = config->fixed_position != 0;
+		lod.center_position = vec3(config->center_position[0], config->center_position[1], config->center_position[2]);
+		handle->ocean = std::make_unique<Ocean>(c, config->force_mipmap_shader != 0, lod); // refuses before anything is allocated
 		auto &device = app->app->get_device();
 		if (!device.get_context())
 			throw std::logic_error("gra_ocean_create: the application has no device");
@@ -337,8 +341,16 @@ int gra_ocean_create(gra_app *app, const gra_ocean_config *config, gra_ocean **o
 			dim.height = n;
 			dim.format = VK_FORMAT_R16G16B16A16_SFLOAT;
 			graph.set_backbuffer_dimensions(dim);
+			if (lod.lod_update)
+				handle->ocean->add_lod_update_pass(graph); // before the FFT update, as add_render_passes has them
 			handle->ocean->add_fft_update_pass(graph);
 			auto &present = graph.add_pass("ocean-present", RENDER_GRAPH_QUEUE_COMPUTE_BIT);
+			if (lod.lod_update)
+			{
+				present.add_texture_input(Ocean::ResourceNames[GRA_OCEAN_LODS]);
+				present.add_storage_read_only_input(Ocean::ResourceNames[GRA_OCEAN_LOD_COUNTER]);
+				present.add_storage_read_only_input(Ocean::ResourceNames[GRA_OCEAN_LOD_DATA]);
+			}
 			for (unsigned i = 0; i < Ocean::ResourceCount; i++)
 			{
 				if (i <= GRA_OCEAN_DISPLACEMENT_FFT_INPUT || i == GRA_OCEAN_SPD_COUNTER)
@@ -377,6 +389,8 @@ int gra_ocean_update(gra_ocean *ocean, double elapsed_time)
 		else
 		{
 			HIP::CommandBuffer cmd(device, device.get_stream(HIP::CommandBuffer::Type::Generic), HIP::CommandBuffer::Type::Generic);
+			if (ocean->ocean->has_lod_update())
+				ocean->ocean->update_lod_pass(cmd);
 			ocean->ocean->update_fft_pass(cmd);
 		}
 		device.wait_idle();
@@ -387,7 +401,7 @@ int gra_ocean_update(gra_ocean *ocean, double elapsed_time)
 int gra_ocean_describe(gra_ocean *ocean, uint32_t which, gra_ocean_resource_info *info)
 {
 	return ocean_guarded(ocean, [&]() {
-		if (!info || which >= Ocean::ResourceCount)
+		if (!info || which >= Ocean::TotalResourceCount)
 			throw std::logic_error("gra_ocean_describe: null info or unknown resource");
 		if (ocean->graph && !ocean->updated)
 			throw std::logic_error("gra_ocean_describe: a graph's resources exist after the first update");
@@ -413,7 +427,7 @@ int gra_ocean_describe(gra_ocean *ocean, uint32_t which, gra_ocean_resource_info
 int gra_ocean_read(gra_ocean *ocean, uint32_t which, uint32_t level, void *out, uint64_t size)
 {
 	return ocean_guarded(ocean, [&]() {
-		if (!out || which >= Ocean::ResourceCount)
+		if (!out || which >= Ocean::TotalResourceCount)
 			throw std::logic_error("gra_ocean_read: null output or unknown resource");
 		if (!ocean->updated)
 			throw std::logic_error("gra_ocean_read: nothing has been computed yet");
@@ -467,6 +481,99 @@ int gra_ocean_parameters(gra_ocean *ocean, float *out8)
 		const vec2 world = ocean->ocean->heightmap_world_size(), normal = ocean->ocean->normalmap_world_size(), wind = ocean->ocean->get_wind_direction();
 		const float values[8] = {world.x, world.y, normal.x, normal.y, wind.x, wind.y, ocean->ocean->get_phillips_L(), ocean->ocean->get_config().amplitude};
 		memcpy(out8, values, sizeof(values));
+	});
+}
+
+int gra_ocean_set_camera(gra_ocean *ocean, const float position[3], const float planes[24])
+{
+	return ocean_guarded(ocean, [&]() {
+		if (!position || !planes)
+			throw std::logic_error("gra_ocean_set_camera: null position or planes");
+		vec4 p[6];
+		for (unsigned i = 0; i < 6; i++)
+			p[i] = vec4(planes[4 * i], planes[4 * i + 1], planes[4 * i + 2], planes[4 * i + 3]);
+		ocean->ocean->set_camera(vec3(position[0], position[1], position[2]), p);
+	});
+}
+
+int gra_ocean_draw_info(gra_ocean *ocean, struct gra_ocean_draw_info *out)
+{
+	return ocean_guarded(ocean, [&]() {
+		if (!out)
+			throw std::logic_error("gra_ocean_draw_info: null output");
+		const OceanDrawInfo info = ocean->ocean->get_lod().get_draw_info();
+		static_assert(sizeof(out->data) == sizeof(info.data), "gra_ocean_draw_info carries OceanData");
+		memcpy(out->data, &info.data, sizeof(out->data));
+		out->lods = info.lods;
+		out->lod_stride = info.lod_stride;
+		out->border_count = info.border_count;
+		out->index_type = info.index_type;
+	});
+}
+
+// The mesh `which` names: host copies, and the device buffers where the ocean made them.
+struct ocean_mesh
+{
+	const void *vertices = nullptr, *indices = nullptr;
+	uint32_t vertex_count = 0, vertex_stride = 0, index_count = 0;
+	HIP::Buffer *vbo = nullptr, *ibo = nullptr;
+};
+static ocean_mesh find_ocean_mesh(gra_ocean *ocean, uint32_t which)
+{
+	ocean_mesh m;
+	const OceanLod &lod = ocean->ocean->get_lod();
+	if (which == GRA_OCEAN_MESH_BORDER)
+	{
+		const OceanBorderMesh &border = lod.get_border_mesh();
+		m = {border.positions.data(), border.indices.data(), uint32_t(border.positions.size()), uint32_t(sizeof(vec3)), uint32_t(border.indices.size()),
+		     ocean->ocean->get_border_vbo(), ocean->ocean->get_border_ibo()};
+	}
+	else if (which < lod.get_lod_count())
+	{
+		const OceanLodMesh &mesh = lod.get_lod_mesh(which);
+		m = {mesh.vertices.data(), mesh.indices.data(), uint32_t(mesh.vertices.size()), uint32_t(sizeof(OceanVertex)), uint32_t(mesh.indices.size()),
+		     ocean->ocean->get_lod_vbo(which), ocean->ocean->get_lod_ibo(which)};
+	}
+	return m;
+}
+
+int gra_ocean_mesh_describe(gra_ocean *ocean, uint32_t which, gra_ocean_mesh_info *info)
+{
+	return ocean_guarded(ocean, [&]() {
+		if (!info)
+			throw std::logic_error("gra_ocean_mesh_describe: null info");
+		const ocean_mesh m = find_ocean_mesh(ocean, which);
+		*info = {};
+		info->exists = m.vertex_count != 0 ? 1u : 0u;
+		info->on_device = m.vbo && m.ibo ? 1u : 0u;
+		info->vertex_count = m.vertex_count;
+		info->vertex_stride = m.vertex_stride;
+		info->index_count = m.index_count;
+		info->index_stride = uint32_t(sizeof(uint16_t));
+	});
+}
+
+int gra_ocean_mesh_read(gra_ocean *ocean, uint32_t which, void *vbo_out, void *ibo_out)
+{
+	return ocean_guarded(ocean, [&]() {
+		const ocean_mesh m = find_ocean_mesh(ocean, which);
+		if (!vbo_out || !ibo_out || m.vertex_count == 0)
+			throw std::logic_error("gra_ocean_mesh_read: null output or a mesh that does not exist");
+		const size_t vertex_bytes = size_t(m.vertex_count) * m.vertex_stride, index_bytes = size_t(m.index_count) * sizeof(uint16_t);
+		if (m.vbo && m.ibo)
+		{
+			gr_ctx *ctx = ocean->app->app->get_device().get_context();
+			if (m.vbo->get_size() != vertex_bytes || m.ibo->get_size() != index_bytes)
+				throw std::logic_error("gra_ocean_mesh_read: a device buffer does not have its mesh's size");
+			if (gr_download(ctx, nullptr, vbo_out, m.vbo->get_device_pointer(), vertex_bytes) < 0 ||
+			    gr_download(ctx, nullptr, ibo_out, m.ibo->get_device_pointer(), index_bytes) < 0 || gr_sync(ctx, nullptr) < 0)
+				throw std::runtime_error(gr_last_error(ctx));
+		}
+		else
+		{
+			memcpy(vbo_out, m.vertices, vertex_bytes);
+			memcpy(ibo_out, m.indices, index_bytes);
+		}
 	});
 }
 

@@ -23,8 +23,18 @@ enum : unsigned
 	NormalOutput,
 	SpdCounter,
 	GradientJacobian,
-	HeightDisplacement
+	HeightDisplacement,
+	Lods,
+	LodCounter,
+	LodData
 };
+
+OceanLodRequest checked(const OceanConfig &config, const OceanLodRequest &request)
+{
+	if (request.lod_update)
+		OceanLod::check_lod_update(config);
+	return request;
+}
 
 std::vector<gr_image> level_views(const HIP::Image &image, unsigned levels)
 {
@@ -35,14 +45,16 @@ std::vector<gr_image> level_views(const HIP::Image &image, unsigned levels)
 }
 } // namespace
 
-const char *const Ocean::ResourceNames[Ocean::ResourceCount] = {
+const char *const Ocean::ResourceNames[Ocean::TotalResourceCount] = {
 	"ocean-height-fft-input",  "ocean-normal-fft-input",  "ocean-displacement-fft-input",
 	"ocean-height-fft-output", "ocean-displacement-fft-output", "ocean-normal-fft-output",
 	"ocean-spd-counter",       "ocean-gradient-jacobian-output", "ocean-height-displacement-output",
+	"ocean-lods",              "ocean-lod-counter",       "ocean-lod-data",
 };
 
-Ocean::Ocean(const OceanConfig &config, bool force_mipmap_shader_)
-	: parameters(derive_ocean_parameters(config)), force_mipmap_shader(force_mipmap_shader_)
+Ocean::Ocean(const OceanConfig &config, bool force_mipmap_shader_, const OceanLodRequest &lod_request_)
+	: parameters(derive_ocean_parameters(config)), force_mipmap_shader(force_mipmap_shader_), lod_request(checked(config, lod_request_)),
+	  lod(parameters.config, lod_request_.fixed_position, lod_request_.center_position)
 {
 	for (auto &f : frequency_bands)
 		f = 1.0f;
@@ -81,6 +93,54 @@ void Ocean::on_device_created(HIP::Device &device_)
 	if (!planned)
 		throw std::runtime_error(std::string("Ocean: failed to plan FFT: ") + gr_last_error(device->get_context()));
 	init_distributions(device_);
+	if (lod_request.lod_update)
+		build_buffers(device_);
+}
+
+void Ocean::build_buffers(HIP::Device &device_)
+{
+	gr_ctx *ctx = device_.get_context();
+	auto upload = [&](const void *data, size_t size, VkBufferUsageFlags usage, const char *name) {
+		auto buffer = device_.create_buffer(size, usage, name);
+		if (gr_upload(ctx, nullptr, buffer->get_device_pointer(), data, size) < 0 || gr_sync(ctx, nullptr) < 0)
+			throw std::runtime_error(std::string("Ocean: mesh upload: ") + gr_last_error(ctx));
+		return buffer;
+	};
+	for (unsigned i = 0; i < lod.get_lod_count(); i++)
+	{
+		const OceanLodMesh &mesh = lod.get_lod_mesh(i);
+		lod_vbos.push_back(upload(mesh.vertices.data(), mesh.vertices.size() * sizeof(OceanVertex), VK_BUFFER_USAGE_VERTEX_BUFFER_BIT, "ocean-lod-vbo"));
+		lod_ibos.push_back(upload(mesh.indices.data(), mesh.indices.size() * sizeof(uint16_t), VK_BUFFER_USAGE_INDEX_BUFFER_BIT, "ocean-lod-ibo"));
+	}
+	const OceanBorderMesh &border = lod.get_border_mesh();
+	if (!border.positions.empty())
+	{
+		border_vbo = upload(border.positions.data(), border.positions.size() * sizeof(vec3), VK_BUFFER_USAGE_VERTEX_BUFFER_BIT, "ocean-border-vbo");
+		border_ibo = upload(border.indices.data(), border.indices.size() * sizeof(uint16_t), VK_BUFFER_USAGE_INDEX_BUFFER_BIT, "ocean-border-ibo");
+	}
+}
+
+void Ocean::add_lod_update_pass(RenderGraph &graph_)
+{
+	if (!lod_request.lod_update)
+		throw std::logic_error("Ocean: add_lod_update_pass on an ocean created without a LOD request.");
+	graph = &graph_;
+	const unsigned count = parameters.config.grid_count;
+	auto &update_lod = graph_.add_pass("ocean-update-lods", RENDER_GRAPH_QUEUE_COMPUTE_BIT);
+	AttachmentInfo lod_attachment;
+	lod_attachment.format = VK_FORMAT_R16_SFLOAT;
+	lod_attachment.size_x = lod_attachment.size_y = float(count);
+	lod_attachment.size_class = SizeClass::Absolute;
+	graph_textures[Lods] = &update_lod.add_storage_texture_output(ResourceNames[Lods], lod_attachment);
+
+	BufferInfo lod_info_counter, lod_info;
+	lod_info_counter.size = OceanLod::MaxLODIndirect * sizeof(gr_ocean_indirect_draw);
+	lod_info_counter.usage = VK_BUFFER_USAGE_STORAGE_BUFFER_BIT | VK_BUFFER_USAGE_INDIRECT_BUFFER_BIT;
+	graph_buffers[LodCounter] = &update_lod.add_storage_output(ResourceNames[LodCounter], lod_info_counter);
+	lod_info.size = VkDeviceSize(count) * count * OceanLod::MaxLODIndirect * sizeof(gr_ocean_patch);
+	lod_info.usage = VK_BUFFER_USAGE_STORAGE_BUFFER_BIT;
+	graph_buffers[LodData] = &update_lod.add_storage_output(ResourceNames[LodData], lod_info);
+	update_lod.set_build_render_pass([this](HIP::CommandBuffer &cmd) { update_lod_pass(cmd); });
 }
 
 void Ocean::init_distributions(HIP::Device &device_)
@@ -165,23 +225,32 @@ void Ocean::create_resources(HIP::Device &device_)
 	if (config.heightmap)
 		own_images[HeightDisplacement] =
 				device_.create_image(n, n, VK_FORMAT_R16G16B16A16_SFLOAT, ResourceNames[HeightDisplacement], std::max(parameters.vertex_levels(), 1u));
+	if (lod_request.lod_update)
+	{
+		const unsigned count = config.grid_count;
+		own_images[Lods] = device_.create_image(count, count, VK_FORMAT_R16_SFLOAT, ResourceNames[Lods]);
+		own_buffers[LodCounter] = device_.create_buffer(OceanLod::MaxLODIndirect * sizeof(gr_ocean_indirect_draw),
+		                                                VK_BUFFER_USAGE_STORAGE_BUFFER_BIT | VK_BUFFER_USAGE_INDIRECT_BUFFER_BIT, ResourceNames[LodCounter]);
+		own_buffers[LodData] = device_.create_buffer(size_t(count) * count * OceanLod::MaxLODIndirect * sizeof(gr_ocean_patch), VK_BUFFER_USAGE_STORAGE_BUFFER_BIT,
+		                                             ResourceNames[LodData]);
+	}
 }
 
 HIP::Buffer *Ocean::get_buffer(unsigned which)
 {
-	if (which >= ResourceCount)
+	if (which >= TotalResourceCount)
 		return nullptr;
 	if (graph)
-		return graph->maybe_get_physical_buffer_resource(graph_buffers[which]);
+		return graph_buffers[which] ? graph->maybe_get_physical_buffer_resource(graph_buffers[which]) : nullptr;
 	return own_buffers[which].get();
 }
 
 HIP::Image *Ocean::get_image(unsigned which)
 {
-	if (which >= ResourceCount)
+	if (which >= TotalResourceCount)
 		return nullptr;
 	if (graph)
-		return graph->maybe_get_physical_texture_resource(graph_textures[which]);
+		return graph_textures[which] ? graph->maybe_get_physical_texture_resource(graph_textures[which]) : nullptr;
 	return own_images[which].get();
 }
 
@@ -352,5 +421,42 @@ void Ocean::update_fft_pass(HIP::CommandBuffer &cmd)
 	compute_fft(cmd);
 	bake_maps(cmd);
 	generate_mipmaps(cmd);
+}
+
+void Ocean::build_lod_map(HIP::CommandBuffer &cmd)
+{
+	const gr_image image = get_image(Lods)->get_level_view(0);
+	const gr_push_ocean_update_lod push = lod.update_lod_push();
+	cmd.check(gr_ocean_update_lod(cmd.get_context(), cmd.get_stream(), &image, &push), "ocean update lod");
+}
+
+void Ocean::init_counter_buffer(HIP::CommandBuffer &cmd)
+{
+	HIP::Buffer *buffer = get_buffer(LodCounter);
+	const gr_ocean_buffer counters = {buffer->get_device_pointer(), buffer->get_size()};
+	uint32_t vertex_counts[16];
+	lod.get_counts(vertex_counts);
+	cmd.check(gr_ocean_init_counter_buffer(cmd.get_context(), cmd.get_stream(), &counters, vertex_counts), "ocean init counter buffer");
+}
+
+void Ocean::cull_blocks(HIP::CommandBuffer &cmd)
+{
+	const gr_image image = get_image(Lods)->get_level_view(0);
+	HIP::Buffer *lod_buffer = get_buffer(LodData), *lod_counter_buffer = get_buffer(LodCounter);
+	const gr_ocean_buffer patches = {lod_buffer->get_device_pointer(), lod_buffer->get_size()};
+	const gr_ocean_buffer counters = {lod_counter_buffer->get_device_pointer(), lod_counter_buffer->get_size()};
+	const gr_push_ocean_cull push = lod.cull_push();
+	cmd.check(gr_ocean_cull_blocks(cmd.get_context(), cmd.get_stream(), &image, lod.get_wrap(), &patches, &counters, &push, lod.get_frustum()),
+	          "ocean cull blocks");
+}
+
+// Three launches in stream order; the order stands in for the reference's barrier between the first two and the cull.
+void Ocean::update_lod_pass(HIP::CommandBuffer &cmd)
+{
+	if (!device || !lod_request.lod_update)
+		throw std::logic_error("Ocean: update_lod_pass before on_device_created, or on an ocean created without a LOD request.");
+	build_lod_map(cmd);
+	init_counter_buffer(cmd);
+	cull_blocks(cmd);
 }
 } // namespace Granite

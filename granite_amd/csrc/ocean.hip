@@ -7,6 +7,13 @@
 //                     the mirrored row backwards -- whole 128-byte lines either way -- and stores 64 consecutive half2.
 //   k_ocean_bake      one lane per texel of the height map, rows along x; the taps at texel centres snap to single texels.
 //   k_ocean_mipmap    one lane per output texel, rows along x; four texels a tap.
+//
+// And that of Ocean::update_lod_pass: ocean/update_lod.comp, ocean/init_counter_buffer.comp and ocean/cull_blocks.comp, one launch each,
+// one wave64 per 8 x 8 group of the shaders.
+//   k_ocean_update_lod    one lane per block of the grid; one fp16 store each.
+//   k_ocean_init_counters one lane per dword of the eight draw records.
+//   k_ocean_cull          one lane per block.  The append is aggregated per wave: per LOD present in the wave one ballot, one
+//                         agent-scope add of the lane count by the first lane, each lane's slot from its rank in the ballot.
 #include "ctx.hpp"
 #include "ocean_core.hpp"
 
@@ -89,6 +96,85 @@ uint32_t log2_of(uint32_t v)
 }
 // What both image entry points ask of an image beyond the contract: texel indices stay below 2^31.
 constexpr uint32_t MAX_EXTENT = 32768u;
+
+// ---- the LOD update ------------------------------------------------------------------------------------------------------------
+constexpr uint32_t TILE = 8u; // the shaders' 8 x 8 group: one wave64
+
+struct UpdateLodLaunch
+{
+	UpdateLodArgs u;
+	uint8_t *out;
+	uint32_t pitch;
+};
+
+__global__ __launch_bounds__(TILE * TILE) void k_ocean_update_lod(UpdateLodLaunch a)
+{
+	const int x = int(blockIdx.x * TILE + (threadIdx.x & (TILE - 1u))), y = int(blockIdx.y * TILE + threadIdx.x / TILE);
+	if (x >= a.u.n || y >= a.u.n)
+		return;
+	int ix, iy;
+	const uint16_t bits = update_lod_texel(a.u, x, y, ix, iy); // ix, iy < n: the image is n x n
+	*reinterpret_cast<uint16_t *>(a.out + size_t(iy) * a.pitch + size_t(ix) * 2u) = bits;
+}
+
+struct InitCountersLaunch
+{
+	uint32_t *draws;
+	uint32_t counts[MAX_LOD_INDIRECT];
+};
+
+__global__ __launch_bounds__(64) void k_ocean_init_counters(InitCountersLaunch a)
+{
+	const uint32_t word = threadIdx.x; // 8 records of 8 dwords
+	a.draws[word] = (word & 7u) == 0u ? a.counts[word >> 3] : 0u;
+}
+
+struct CullLaunch
+{
+	CullArgs c;
+	Patch *patches;
+	uint32_t *draws;
+	uint32_t num_lods; // int(max_lod) + 1
+};
+
+__global__ __launch_bounds__(TILE * TILE) void k_ocean_cull(CullLaunch a)
+{
+	const uint32_t lane = threadIdx.x;
+	const int x = int(blockIdx.x * TILE + (lane & (TILE - 1u))), y = int(blockIdx.y * TILE + lane / TILE);
+	Patch patch = {};
+	int lod = -1; // no lane leaves before the ballots
+	if (x < a.c.n && y < a.c.n && box_in_frustum(a.c, x, y))
+		lod = cull_patch(a.c, x, y, patch);
+	for (uint32_t l = 0; l < a.num_lods; l++)
+	{
+		const unsigned long long mask = __ballot(lod == int(l));
+		if (mask == 0ull)
+			continue;
+		const uint32_t first = uint32_t(__ffsll(mask)) - 1u;
+		uint32_t base = 0;
+		if (lane == first)
+			base = __hip_atomic_fetch_add(&a.draws[l * 8u + 1u], uint32_t(__popcll(mask)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		base = uint32_t(__shfl(int(base), int(first)));
+		if (lod == int(l))
+		{
+			const uint32_t slot = base + uint32_t(__popcll(mask & ((1ull << lane) - 1ull)));
+			if (slot < a.c.lod_stride) // holds whenever the counters began at init_counter_buffer's zero
+				a.patches[size_t(a.c.lod_stride) * l + slot] = patch;
+		}
+	}
+}
+
+// What the three entry points ask of num_threads and max_lod; the text of the rule broken, or nullptr.
+const char *grid_rule(int32_t nx, int32_t ny, float max_lod)
+{
+	if (nx != ny)
+		return "num_threads is not square";
+	if (nx < 4 || nx > 128 || !power_of_two(uint32_t(nx)))
+		return "num_threads is not a power of two in 4 .. 128";
+	if (!(max_lod >= 0.0f && max_lod <= float(MAX_LOD_INDIRECT - 1u)) || max_lod != floorf(max_lod))
+		return "max_lod is not an integer in 0 .. 7";
+	return nullptr;
+}
 
 Texture texture_of(const gr_image *img) { return {static_cast<const uint8_t *>(img->ptr), int(img->width), int(img->height), img->pitch_bytes}; }
 } // namespace
@@ -212,6 +298,114 @@ extern "C" int gr_ocean_mipmap(gr_ctx *ctx, gr_stream stream, const gr_image *in
 		hipLaunchKernelGGL(k_ocean_mipmap<2>, grid, dim3(GROUP), 0, s, a);
 	else
 		hipLaunchKernelGGL(k_ocean_mipmap<4>, grid, dim3(GROUP), 0, s, a);
+	GR_CHECK_LAUNCH(ctx);
+	return GR_OK;
+}
+
+extern "C" int gr_ocean_update_lod(gr_ctx *ctx, gr_stream stream, const gr_image *lod_image, const gr_push_ocean_update_lod *push)
+{
+	if (!ctx)
+		return GR_ERR_INVALID_ARGUMENT;
+	GR_CHECK_ARG(ctx, push);
+	if (const char *rule = grid_rule(push->num_threads[0], push->num_threads[1], push->max_lod))
+		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_ocean_update_lod: %s (%d x %d, max_lod %g)", rule, push->num_threads[0], push->num_threads[1], double(push->max_lod));
+	const uint32_t n = uint32_t(push->num_threads[0]);
+	GR_CHECK_IMAGE(ctx, lod_image, GR_FORMAT_R16_SFLOAT, n, n);
+
+	UpdateLodLaunch a = {};
+	memcpy(a.u.camera, push->shifted_camera_pos, sizeof(a.u.camera));
+	a.u.max_lod = push->max_lod;
+	a.u.offset_x = push->image_offset[0];
+	a.u.offset_y = push->image_offset[1];
+	a.u.n = int(n);
+	a.u.base_x = push->grid_base[0];
+	a.u.base_y = push->grid_base[1];
+	a.u.size_x = push->grid_size[0];
+	a.u.size_y = push->grid_size[1];
+	a.u.lod_bias = push->lod_bias;
+	a.out = static_cast<uint8_t *>(lod_image->ptr);
+	a.pitch = lod_image->pitch_bytes;
+	hipStream_t s = gr_to_stream(stream);
+	gr_scoped_timing timing{ctx, s, "ocean_update_lod"};
+	hipLaunchKernelGGL(k_ocean_update_lod, dim3(gr_div_up(n, TILE), gr_div_up(n, TILE)), dim3(TILE * TILE), 0, s, a);
+	GR_CHECK_LAUNCH(ctx);
+	return GR_OK;
+}
+
+extern "C" int gr_ocean_init_counter_buffer(gr_ctx *ctx, gr_stream stream, const gr_ocean_buffer *counters, const uint32_t *counts16)
+{
+	if (!ctx)
+		return GR_ERR_INVALID_ARGUMENT;
+	GR_CHECK_ARG(ctx, counters && counters->ptr);
+	GR_CHECK_ARG(ctx, counts16);
+	if (counters->size_bytes < MAX_LOD_INDIRECT * sizeof(gr_ocean_indirect_draw) || (reinterpret_cast<uintptr_t>(counters->ptr) & 3u))
+		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_ocean_init_counter_buffer: counters has %llu bytes, below 8 * 32, or is not 4-byte aligned",
+		                 static_cast<unsigned long long>(counters->size_bytes));
+	InitCountersLaunch a = {};
+	a.draws = static_cast<uint32_t *>(counters->ptr);
+	memcpy(a.counts, counts16, sizeof(a.counts)); // NUM_COUNTERS = 8: the shader reads the first eight of the sixteen
+	hipStream_t s = gr_to_stream(stream);
+	gr_scoped_timing timing{ctx, s, "ocean_init_counter_buffer"};
+	hipLaunchKernelGGL(k_ocean_init_counters, dim3(1), dim3(64), 0, s, a);
+	GR_CHECK_LAUNCH(ctx);
+	return GR_OK;
+}
+
+extern "C" int gr_ocean_cull_blocks(gr_ctx *ctx, gr_stream stream, const gr_image *lod_image, uint32_t wrap, const gr_ocean_buffer *patches,
+                                    const gr_ocean_buffer *counters, const gr_push_ocean_cull *push, const float *frustum)
+{
+	if (!ctx)
+		return GR_ERR_INVALID_ARGUMENT;
+	GR_CHECK_ARG(ctx, push);
+	GR_CHECK_ARG(ctx, frustum);
+	GR_CHECK_ARG(ctx, patches && patches->ptr);
+	GR_CHECK_ARG(ctx, counters && counters->ptr);
+	if (push->num_threads[0] > 128u || push->num_threads[1] > 128u)
+		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_ocean_cull_blocks: num_threads is not a power of two in 4 .. 128 (%u x %u)", push->num_threads[0], push->num_threads[1]);
+	if (const char *rule = grid_rule(int32_t(push->num_threads[0]), int32_t(push->num_threads[1]), push->max_lod))
+		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_ocean_cull_blocks: %s (%u x %u, max_lod %g)", rule, push->num_threads[0], push->num_threads[1], double(push->max_lod));
+	const uint32_t n = push->num_threads[0], num_lods = uint32_t(push->max_lod) + 1u;
+	GR_CHECK_IMAGE(ctx, lod_image, GR_FORMAT_R16_SFLOAT, n, n);
+	if (push->lod_stride < n * n)
+		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_ocean_cull_blocks: lod_stride %u is below num_threads.x * num_threads.y = %u", push->lod_stride, n * n);
+	if (patches->size_bytes < uint64_t(push->lod_stride) * num_lods * sizeof(gr_ocean_patch) || (reinterpret_cast<uintptr_t>(patches->ptr) & 15u))
+		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_ocean_cull_blocks: patches has %llu bytes, below lod_stride * (max_lod + 1) * 32 = %llu, or is not 16-byte aligned",
+		                 static_cast<unsigned long long>(patches->size_bytes), static_cast<unsigned long long>(uint64_t(push->lod_stride) * num_lods * sizeof(gr_ocean_patch)));
+	if (counters->size_bytes < MAX_LOD_INDIRECT * sizeof(gr_ocean_indirect_draw) || (reinterpret_cast<uintptr_t>(counters->ptr) & 3u))
+		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_ocean_cull_blocks: counters has %llu bytes, below 8 * 32, or is not 4-byte aligned",
+		                 static_cast<unsigned long long>(counters->size_bytes));
+	const size_t image_bytes = size_t(lod_image->pitch_bytes) * lod_image->height;
+	if (gr_images_overlap(patches->ptr, size_t(patches->size_bytes), lod_image->ptr, image_bytes) ||
+	    gr_images_overlap(counters->ptr, size_t(counters->size_bytes), lod_image->ptr, image_bytes) ||
+	    gr_images_overlap(patches->ptr, size_t(patches->size_bytes), counters->ptr, size_t(counters->size_bytes)))
+		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_ocean_cull_blocks: patches, counters and the LOD image overlap");
+
+	CullLaunch a = {};
+	memcpy(a.c.world_offset, push->world_offset, sizeof(a.c.world_offset));
+	a.c.offset_x = push->image_offset[0];
+	a.c.offset_y = push->image_offset[1];
+	a.c.n = int(n);
+	a.c.base_x = push->grid_base[0];
+	a.c.base_y = push->grid_base[1];
+	a.c.size_x = push->grid_size[0];
+	a.c.size_y = push->grid_size[1];
+	a.c.resolution_x = push->grid_resolution[0];
+	a.c.resolution_y = push->grid_resolution[1];
+	a.c.range_lo = push->heightmap_range[0];
+	a.c.range_hi = push->heightmap_range[1];
+	a.c.guard_band = push->guard_band;
+	a.c.lod_stride = push->lod_stride;
+	a.c.max_lod = push->max_lod;
+	a.c.handle_edge_lods = push->handle_edge_lods != 0 ? 1u : 0u;
+	a.c.wrap = wrap != 0u ? 1u : 0u;
+	memcpy(a.c.frustum, frustum, sizeof(a.c.frustum));
+	a.c.lods = texture_of(lod_image);
+	a.patches = static_cast<Patch *>(patches->ptr);
+	a.draws = static_cast<uint32_t *>(counters->ptr);
+	a.num_lods = num_lods;
+	hipStream_t s = gr_to_stream(stream);
+	gr_scoped_timing timing{ctx, s, "ocean_cull_blocks"};
+	hipLaunchKernelGGL(k_ocean_cull, dim3(gr_div_up(n, TILE), gr_div_up(n, TILE)), dim3(TILE * TILE), 0, s, a);
 	GR_CHECK_LAUNCH(ctx);
 	return GR_OK;
 }

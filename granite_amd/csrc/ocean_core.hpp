@@ -1,5 +1,6 @@
 // Follows MIT-licensed work (Granite, (c) 2017-2026 Hans-Kristian Arntzen): see THIRD_PARTY_NOTICES.md at the repository root.
-// The ocean's FFT update, the per-lane arithmetic: ocean/generate_fft.comp, ocean/bake_maps.comp and ocean/mipmap.comp.  Shared by the
+// The ocean's two compute passes, the per-lane arithmetic: ocean/generate_fft.comp, ocean/bake_maps.comp and ocean/mipmap.comp of the
+// FFT update, ocean/update_lod.comp and ocean/cull_blocks.comp of the LOD update.  Shared by the
 // gfx950 kernels (ocean.hip) and by a host build the CPU tests hold to the executed shaders (tests/cpp/ocean_core_host.cpp): the
 // kernels add the mapping of bins and texels to lanes, nothing else.  Both builds compile this header with -ffp-contract=off and with
 // correctly rounded fp32 sqrt and division: generate_bin quantises an angular velocity with round(), and a last-bit difference in
@@ -202,5 +203,118 @@ template <int C> OCEAN_HD void mipmap_texel(const MipmapArgs &a, uint32_t x, uin
 	const Texel<C> t = sample_wrap<C>(a.in, u, v, 0, 0);
 	for (int c = 0; c < C; c++)
 		out[c] = uint16_t(float_to_half(a.result_mod[c] * t.v[c]));
+}
+
+// ---- update_lod.comp -----------------------------------------------------------------------------------------------------------
+// The LOD pass.  Sums are written in the shaders' operation order: dot() adds its products left to right.
+constexpr uint32_t MAX_LOD_INDIRECT = 8u;
+struct UpdateLodArgs
+{
+	float camera[3]; // shifted_camera_pos
+	float max_lod;
+	int offset_x, offset_y; // image_offset
+	int n;                  // num_threads, square and a power of two
+	float base_x, base_y, size_x, size_y;
+	float lod_bias;
+};
+OCEAN_HD float square_dist(const UpdateLodArgs &a, float px, float pz)
+{
+	const float dx = a.camera[0] - px, dy = a.camera[1] - 0.0f, dz = a.camera[2] - pz;
+	return (dx * dx + dy * dy) + dz * dz;
+}
+// Block (x, y): the texel it stores to, (id + image_offset) & (n - 1), and the R16F bits of its LOD.
+OCEAN_HD uint16_t update_lod_texel(const UpdateLodArgs &a, int x, int y, int &image_x, int &image_y)
+{
+	const float x00 = a.base_x + float(x) * a.size_x, y00 = a.base_y + float(y) * a.size_y;
+	const float x10 = x00 + 1.0f * a.size_x, y10 = y00 + 0.0f * a.size_y;
+	const float x01 = x00 + 0.0f * a.size_x, y01 = y00 + 1.0f * a.size_y;
+	const float x11 = x00 + 1.0f * a.size_x, y11 = y00 + 1.0f * a.size_y;
+	const float xc = x00 + 0.5f * a.size_x, yc = y00 + 0.5f * a.size_y;
+	float d = square_dist(a, xc, yc);
+	d = fminf(d, square_dist(a, x00, y00));
+	d = fminf(d, square_dist(a, x10, y10));
+	d = fminf(d, square_dist(a, x01, y01));
+	d = fminf(d, square_dist(a, x11, y11));
+	float lod = 0.5f * log2f(d + 1.0f) + a.lod_bias;
+	lod = fminf(fmaxf(lod, 0.0f), a.max_lod);
+	image_x = (x + a.offset_x) & (a.n - 1);
+	image_y = (y + a.offset_y) & (a.n - 1);
+	return uint16_t(float_to_half(lod));
+}
+
+// ---- cull_blocks.comp ----------------------------------------------------------------------------------------------------------
+struct Patch // PatchData of ocean.inc
+{
+	float offsets[2], inner_lod, padding, lods[4];
+};
+struct CullArgs
+{
+	float world_offset[3];
+	int offset_x, offset_y; // image_offset
+	int n;                  // num_threads, square and a power of two
+	float base_x, base_y, size_x, size_y, resolution_x, resolution_y;
+	float range_lo, range_hi, guard_band;
+	uint32_t lod_stride;
+	float max_lod;
+	uint32_t handle_edge_lods, wrap;
+	float frustum[6][4];
+	Texture lods; // R16F, n x n
+};
+// frustum_cull: the block's box, widened by the guard band and the heightmap range, against six planes; the corner farthest along
+// a plane's normal decides, and the first plane that has it behind ends the test.
+OCEAN_HD bool box_in_frustum(const CullArgs &a, int x, int y)
+{
+	const float min_x = a.base_x + float(x) * a.size_x, min_z = a.base_y + float(y) * a.size_y;
+	const float max_x = min_x + a.size_x, max_z = min_z + a.size_y;
+	const float lo[3] = {(min_x - a.guard_band) + a.world_offset[0], a.range_lo + a.world_offset[1], (min_z - a.guard_band) + a.world_offset[2]};
+	const float hi[3] = {(max_x + a.guard_band) + a.world_offset[0], a.range_hi + a.world_offset[1], (max_z + a.guard_band) + a.world_offset[2]};
+	for (int i = 0; i < 6; i++)
+	{
+		const float *p = a.frustum[i];
+		const float cx = p[0] > 0.0f ? hi[0] : lo[0], cy = p[1] > 0.0f ? hi[1] : lo[1], cz = p[2] > 0.0f ? hi[2] : lo[2];
+		if (((cx * p[0] + cy * p[1]) + cz * p[2]) + 1.0f * p[3] < 0.0f)
+			return false;
+	}
+	return true;
+}
+// A nearest tap at texel coordinate c of the n x n LOD image: NearestWrap (c mod n; & (n - 1) is Euclidean on two's complement) or
+// NearestClamp.  For a power-of-two n and |c| < 2^20 this is the texel that uv = (c + 0.5) / n selects.
+OCEAN_HD float lod_tap(const CullArgs &a, int cx, int cy)
+{
+	if (a.wrap)
+	{
+		cx &= a.n - 1;
+		cy &= a.n - 1;
+	}
+	else
+	{
+		cx = cx < 0 ? 0 : (cx > a.n - 1 ? a.n - 1 : cx);
+		cy = cy < 0 ? 0 : (cy > a.n - 1 ? a.n - 1 : cy);
+	}
+	return half_to_float(*reinterpret_cast<const uint16_t *>(a.lods.ptr + size_t(cy) * a.lods.pitch + size_t(cx) * 2u));
+}
+// Block (x, y) that passed the box test: its patch and its bucket.  The bucket is the shader's int(min(inner, min of the four)), kept
+// inside 0 .. max_lod whatever the image holds (the shader indexes with it unchecked; an image of update_lod's never leaves the range).
+OCEAN_HD int cull_patch(const CullArgs &a, int x, int y, Patch &patch)
+{
+	const int cx = x + a.offset_x, cy = y + a.offset_y;
+	const float centre = lod_tap(a, cx, cy);
+	float l[4] = {lod_tap(a, cx - 1, cy), lod_tap(a, cx + 1, cy), lod_tap(a, cx, cy - 1), lod_tap(a, cx, cy + 1)};
+	for (float &v : l)
+		v = fmaxf(v, centre);
+	if (a.handle_edge_lods)
+	{
+		if (x == 0)
+			l[0] = a.max_lod;
+		if (x == a.n - 1)
+			l[1] = a.max_lod;
+		if (y == 0)
+			l[2] = a.max_lod;
+		if (y == a.n - 1)
+			l[3] = a.max_lod;
+	}
+	const float least = fminf(centre, fminf(fminf(l[0], l[2]), fminf(l[1], l[3])));
+	patch = {{float(cx) * a.resolution_x, float(cy) * a.resolution_y}, centre, 0.0f, {l[0], l[1], l[2], l[3]}};
+	return least >= 0.0f ? (least > a.max_lod ? int(a.max_lod) : int(least)) : 0;
 }
 } // namespace gr_ocean

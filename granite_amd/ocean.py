@@ -1,9 +1,15 @@
-"""The ocean's FFT update on an Application's device (gra_ocean_* of include/granite_app.h).
+"""The ocean's FFT and LOD updates on an Application's device (gra_ocean_* of include/granite_app.h).
 
     ocean = Ocean(app, fft_resolution=128, grid_count=4, grid_resolution=32, ocean_size=(128, 128))
     ocean.update(1.5)
     heights = ocean.read("ocean-height-fft-output")              # (128, 128) fp16 bits
     coarse = ocean.read("ocean-gradient-jacobian-output", 3)     # (16, 16, 4)
+
+    ocean = Ocean(app, lod_update=1, grid_count=16, grid_resolution=32, fft_resolution=128, ocean_size=(256, 256))
+    ocean.set_camera((3.0, 5.0, -2.0), planes)                   # planes: six (x, y, z, w), inside where dot >= 0
+    ocean.update(0.0)                                            # both passes
+    draws = ocean.read("ocean-lod-counter").reshape(8, 8)        # eight indirect draws
+    vertices, indices = ocean.mesh(0)                            # the finest LOD mesh; ocean.mesh("border")
 
 Keyword arguments are the fields of gra_ocean_config; what is left out keeps the reference's default."""
 import ctypes as C
@@ -16,6 +22,10 @@ from . import capi
 RESOURCES = ["ocean-height-fft-input", "ocean-normal-fft-input", "ocean-displacement-fft-input", "ocean-height-fft-output",
              "ocean-displacement-fft-output", "ocean-normal-fft-output", "ocean-spd-counter", "ocean-gradient-jacobian-output",
              "ocean-height-displacement-output"]
+# ids 9 .. 11: they exist only in an ocean created with lod_update
+LOD_RESOURCES = ["ocean-lods", "ocean-lod-counter", "ocean-lod-data"]
+ALL_RESOURCES = RESOURCES + LOD_RESOURCES
+MESH_BORDER = 0xffffffff
 DISTRIBUTIONS = ["height", "displacement", "normal"]
 _CHANNELS = {capi.FORMAT_R16_SFLOAT: 1, capi.FORMAT_R16G16_SFLOAT: 2, capi.FORMAT_R16G16B16A16_SFLOAT: 4}
 
@@ -29,7 +39,7 @@ class Ocean:
         for key, value in config.items():
             if key not in dict(cfg._fields_):
                 raise TypeError(f"Ocean: unknown configuration field {key!r}")
-            if key in ("ocean_size", "wind_velocity", "frequency_bands"):
+            if key in ("ocean_size", "wind_velocity", "frequency_bands", "center_position"):
                 getattr(cfg, key)[:] = [float(v) for v in value]
             else:
                 setattr(cfg, key, value)
@@ -43,7 +53,7 @@ class Ocean:
 
     def describe(self, name: str) -> "_app.OceanResourceInfo":
         info = _app.OceanResourceInfo()
-        self.app._check(self.lib.gra_ocean_describe(self.handle, RESOURCES.index(name), C.byref(info)))
+        self.app._check(self.lib.gra_ocean_describe(self.handle, ALL_RESOURCES.index(name), C.byref(info)))
         return info
 
     def read(self, name: str, level: int = 0) -> np.ndarray:
@@ -56,8 +66,35 @@ class Ocean:
         else:
             w, h, c = max(info.width >> level, 1), max(info.height >> level, 1), _CHANNELS[info.format]
             out = np.empty((h, w) if c == 1 else (h, w, c), np.uint16)
-        self.app._check(self.lib.gra_ocean_read(self.handle, RESOURCES.index(name), int(level), out.ctypes.data, out.nbytes))
+        self.app._check(self.lib.gra_ocean_read(self.handle, ALL_RESOURCES.index(name), int(level), out.ctypes.data, out.nbytes))
         return out
+
+    def set_camera(self, position, planes):
+        """The camera of the next update's LOD pass: position (3 floats) and six planes (6 x 4 floats)."""
+        pos = (C.c_float * 3)(*[float(v) for v in position])
+        pl = (C.c_float * 24)(*[float(v) for v in np.asarray(planes, np.float32).reshape(24)])
+        self.app._check(self.lib.gra_ocean_set_camera(self.handle, pos, pl))
+
+    def draw_info(self) -> "_app.OceanDrawInfo":
+        info = _app.OceanDrawInfo()
+        self.app._check(self.lib.gra_ocean_draw_info(self.handle, C.byref(info)))
+        return info
+
+    def mesh_info(self, which) -> "_app.OceanMeshInfo":
+        info = _app.OceanMeshInfo()
+        self.app._check(self.lib.gra_ocean_mesh_describe(self.handle, MESH_BORDER if which == "border" else int(which), C.byref(info)))
+        return info
+
+    def mesh(self, which):
+        """which = 0 .. lods - 1 -> (vertices (k, 8) uint8: pos[4], weights[4]; indices uint16); "border" -> (positions (k, 3) float32, indices)"""
+        info = self.mesh_info(which)
+        if not info.exists:
+            raise capi.GraniteHipError(f"mesh {which!r} does not exist in this configuration")
+        vertices = np.empty((info.vertex_count, 3), np.float32) if which == "border" else np.empty((info.vertex_count, 8), np.uint8)
+        indices = np.empty(info.index_count, np.uint16)
+        assert vertices.nbytes == info.vertex_count * info.vertex_stride and info.index_stride == 2
+        self.app._check(self.lib.gra_ocean_mesh_read(self.handle, MESH_BORDER if which == "border" else int(which), vertices.ctypes.data, indices.ctypes.data))
+        return vertices, indices
 
     def distribution(self, name: str) -> np.ndarray:
         """(N, N, 2) float32: the Phillips distribution the update animates."""

@@ -209,13 +209,21 @@ typedef struct gra_fft_request
 	int32_t output_offset[2];
 } gra_fft_request;
 int gra_fft_transform(gra_app *app, const gra_fft_request *request);
-/* ---- the ocean's FFT update (Granite::Ocean, host/ocean.hpp) -------------------------------------------------------------------
+/* ---- the ocean's FFT and LOD updates (Granite::Ocean, host/ocean.hpp) ----------------------------------------------------------
  * gra_ocean_create derives the constructor's values, generates the three Phillips distributions and uploads them, plans the three
  * FFTs and allocates the pass's nine resources; it fails (gra_last_error) for an fft_resolution that is no power of two, for
  * fft_resolution >> displacement_downsample below 64, for a zero grid_count or grid_resolution and for a zero wind velocity, before
  * anything is allocated.  With through_render_graph the pass is added to a render graph of the ocean's own (add_fft_update_pass),
  * baked and executed by the graph; otherwise update_fft_pass runs directly on the generic stream.  Either way gra_ocean_update
- * returns after the pass has completed.  time = fmod(elapsed_time, 256), period = 256 / (2 pi), both narrowed to float. */
+ * returns after the pass has completed.  time = fmod(elapsed_time, 256), period = 256 / (2 pi), both narrowed to float.
+ *
+ * With lod_update the ocean also owns the reference's second per-frame pass, `ocean-update-lods` (add_lod_update_pass / update_lod_pass):
+ * gra_ocean_update then runs both passes, and both are complete on return.  It adds the resources ocean-lods (R16_SFLOAT, grid_count
+ * squared), ocean-lod-counter (eight 32-byte indirect draws) and ocean-lod-data (grid_count^2 * 8 patches of 32 bytes), ids 9 .. 11 of
+ * gra_ocean_describe / gra_ocean_read; without lod_update they do not exist.  gra_ocean_create refuses lod_update without a heightmap and
+ * with a grid_count or grid_resolution that is not a power of two in 4 .. 128, before anything is allocated.  With fixed_position the
+ * grid stays around center_position (the reference's scene node): no image offset, clamped LOD taps, no edge LODs, no border mesh.
+ * A configuration whose last three fields are zero is the ocean of before they existed. */
 #define GRA_OCEAN_HEIGHT_FFT_INPUT 0u
 #define GRA_OCEAN_NORMAL_FFT_INPUT 1u
 #define GRA_OCEAN_DISPLACEMENT_FFT_INPUT 2u
@@ -225,7 +233,12 @@ int gra_fft_transform(gra_app *app, const gra_fft_request *request);
 #define GRA_OCEAN_SPD_COUNTER 6u
 #define GRA_OCEAN_GRADIENT_JACOBIAN_OUTPUT 7u
 #define GRA_OCEAN_HEIGHT_DISPLACEMENT_OUTPUT 8u
-#define GRA_OCEAN_RESOURCE_COUNT 9u
+#define GRA_OCEAN_RESOURCE_COUNT 9u /* of the FFT update */
+#define GRA_OCEAN_LODS 9u
+#define GRA_OCEAN_LOD_COUNTER 10u
+#define GRA_OCEAN_LOD_DATA 11u
+#define GRA_OCEAN_TOTAL_RESOURCE_COUNT 12u
+#define GRA_OCEAN_MESH_BORDER 0xffffffffu /* gra_ocean_mesh_*: the border mesh, after the plane grid when there is no heightmap */
 #define GRA_OCEAN_DISTRIBUTION_HEIGHT 0u
 #define GRA_OCEAN_DISTRIBUTION_DISPLACEMENT 1u
 #define GRA_OCEAN_DISTRIBUTION_NORMAL 2u
@@ -240,6 +253,9 @@ typedef struct gra_ocean_config /* OceanConfig, renderer/ocean.hpp:40-75, and tw
 	uint32_t through_render_graph; /* run the pass inside a RenderGraph */
 	uint32_t freq_band_modulation;
 	float frequency_bands[8];
+	uint32_t lod_update;      /* the LOD update, its three resources and the meshes on the device */
+	uint32_t fixed_position;  /* the grid stays around center_position */
+	float center_position[3];
 } gra_ocean_config;
 typedef struct gra_ocean gra_ocean;
 typedef struct gra_ocean_resource_info
@@ -258,6 +274,32 @@ int gra_ocean_read(gra_ocean *ocean, uint32_t which, uint32_t level, void *out, 
 int gra_ocean_distribution(gra_ocean *ocean, uint32_t which, void *out);
 /* Heightmap and normal map world sizes, wind direction, Phillips L and the normalised amplitude: 8 floats. */
 int gra_ocean_parameters(gra_ocean *ocean, float *out8);
+/* Stands in for the reference's camera refresh and visibility frustum: position, and six planes (x, y, z, w; a point is inside where
+ * dot(plane.xyz, point) + plane.w >= 0) for the next gra_ocean_update.  Before the first call the camera is at the origin and every
+ * block is in view.  Fails for non-finite input and for a position whose snapped grid coordinate lies beyond +-2^20 blocks. */
+int gra_ocean_set_camera(gra_ocean *ocean, const float position[3], const float planes[24]);
+/* What a rasteriser needs beside the buffers and maps (renderer/ocean.cpp:826-860, 1082-1092).  The structure shares its name with the
+ * call that fills it, so it is a tag without a typedef: `struct gra_ocean_draw_info info;`. */
+struct gra_ocean_draw_info
+{
+	float data[16];        /* OceanData, std140: world_offset at 0, coord_offset at 4, inv_heightmap_size at 6, inv_ocean_grid_size at 8,
+	                          normal_uv_scale at 10, integer_to_world_mod at 12, heightmap_range at 14 */
+	uint32_t lods;         /* buckets in use and LOD meshes */
+	uint32_t lod_stride;   /* bytes between two buckets of ocean-lod-data */
+	uint32_t border_count; /* indices of the border mesh */
+	uint32_t index_type;   /* 0: VK_INDEX_TYPE_UINT16, restart index 0xffff */
+};
+int gra_ocean_draw_info(gra_ocean *ocean, struct gra_ocean_draw_info *out);
+typedef struct gra_ocean_mesh_info
+{
+	uint32_t exists, on_device; /* on_device: read from the ocean's vertex and index buffers (lod_update), else from the host's copy */
+	uint32_t vertex_count, vertex_stride, index_count, index_stride;
+} gra_ocean_mesh_info;
+/* which = 0 .. lods - 1: a LOD mesh, vertices of uint8 pos[4] + uint8 weights[4]; GRA_OCEAN_MESH_BORDER: positions of three floats.
+ * Both have 16-bit indices in triangle strips.  gra_ocean_mesh_read fills vertex_count * vertex_stride and index_count * index_stride
+ * bytes. */
+int gra_ocean_mesh_describe(gra_ocean *ocean, uint32_t which, gra_ocean_mesh_info *info);
+int gra_ocean_mesh_read(gra_ocean *ocean, uint32_t which, void *vbo_out, void *ibo_out);
 void gra_ocean_destroy(gra_ocean *ocean);
 
 /* Writes a graph texture (all its mip levels) or, with name == NULL, the last rendered backbuffer as .gtx. */

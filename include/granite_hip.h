@@ -1029,6 +1029,71 @@ int gr_ocean_bake_maps(gr_ctx *ctx, gr_stream stream, const gr_image *height, co
  * (2 gid + 1) * inv_resolution, times result_mod. */
 int gr_ocean_mipmap(gr_ctx *ctx, gr_stream stream, const gr_image *in, const gr_image *out, const gr_push_ocean_mipmap *push);
 
+/* ---- ocean: the LOD update (renderer/ocean.cpp Ocean::update_lod_pass, assets/shaders/ocean/{update_lod,init_counter_buffer,cull_blocks}.comp) ----
+ * One entry point per dispatch; push blocks are byte-identical to the shaders' std140 blocks.  All three refuse, before a launch: null
+ * pointers; num_threads that is not square, not a power of two or outside 4 .. 128; a LOD image that is not R16_SFLOAT of exactly
+ * num_threads; max_lod that is not an integer in 0 .. 7. */
+typedef struct gr_push_ocean_update_lod /* update_lod.comp Registers, ocean.cpp:285-294 */
+{
+	float shifted_camera_pos[3];
+	float max_lod;
+	int32_t image_offset[2];
+	int32_t num_threads[2];
+	float grid_base[2];
+	float grid_size[2];
+	float lod_bias;
+	uint32_t padding[3];
+} gr_push_ocean_update_lod;
+typedef struct gr_push_ocean_cull /* cull_blocks.comp Registers, ocean.cpp:335-349 */
+{
+	float world_offset[3];
+	uint32_t padding0;
+	int32_t image_offset[2];
+	uint32_t num_threads[2];
+	float inv_num_threads[2]; /* accepted and unused: the taps address texels */
+	float grid_base[2];
+	float grid_size[2];
+	float grid_resolution[2];
+	float heightmap_range[2];
+	float guard_band;
+	uint32_t lod_stride; /* patches per LOD bucket */
+	float max_lod;
+	int32_t handle_edge_lods;
+	uint32_t padding1[2];
+} gr_push_ocean_cull;
+typedef struct gr_ocean_patch /* PatchData, ocean.inc */
+{
+	float offsets[2];
+	float inner_lod;
+	float padding;
+	float lods[4]; /* -x, +x, -y, +y */
+} gr_ocean_patch;
+typedef struct gr_ocean_indirect_draw /* IndirectDraw, ocean.inc */
+{
+	uint32_t index_count, instance_count, first_index;
+	int32_t vertex_offset;
+	uint32_t first_instance, padding0, padding1, padding2;
+} gr_ocean_indirect_draw;
+typedef struct gr_ocean_buffer /* a storage buffer: device pointer and size */
+{
+	void *ptr;
+	uint64_t size_bytes;
+} gr_ocean_buffer;
+/* lod_image(id + image_offset & (num_threads - 1)) = clamp(0.5 log2(d2 + 1) + lod_bias, 0, max_lod), d2 the least squared distance from
+ * shifted_camera_pos to the block's centre and four corners at height 0. */
+int gr_ocean_update_lod(gr_ctx *ctx, gr_stream stream, const gr_image *lod_image, const gr_push_ocean_update_lod *push);
+/* Eight gr_ocean_indirect_draw: index_count from the first eight of counts16 (sixteen uint32_t in host memory, the shader's uniform
+ * block), everything else zero.  Refused: counters below 8 * 32 bytes. */
+int gr_ocean_init_counter_buffer(gr_ctx *ctx, gr_stream stream, const gr_ocean_buffer *counters, const uint32_t *counts16);
+/* Per block that passes the box test against frustum (six float[4] planes in host memory): one gr_ocean_patch appended at
+ * lod_stride * lod + slot, slot from counters[lod].instance_count.  wrap: the five nearest taps use NearestWrap (non-zero) or
+ * NearestClamp (0).  Slots inside one 8 x 8 group are in row order; the order across groups is arbitrary.  Also refused: lod_stride <
+ * num_threads.x * num_threads.y; patches below lod_stride * (max_lod + 1) * 32 bytes; counters below 8 * 32 bytes; buffers that overlap
+ * each other or the image.  A bucket is kept inside 0 .. max_lod and a slot at or past lod_stride is not written, whatever the image and
+ * the counters hold. */
+int gr_ocean_cull_blocks(gr_ctx *ctx, gr_stream stream, const gr_image *lod_image, uint32_t wrap, const gr_ocean_buffer *patches,
+                         const gr_ocean_buffer *counters, const gr_push_ocean_cull *push, const float *frustum);
+
 /* ---- SSAO: FidelityFX CACAO as the reference runs it (renderer/post/ssao.cpp, renderer/post/ffx-cacao) -----------------------------------
  * One configuration and its non-adaptive sibling: native resolution, normals from the G-buffer, quality HIGHEST (adaptive, shader level 3)
  * or HIGH (shader level 2), 0 .. 8 blur passes.  One entry point per shader of FFX_CACAO_GraniteDraw (ffx_cacao_impl.cpp:767-1026); the
@@ -1267,6 +1332,29 @@ GR_ASSERT_SIZE(gr_push_ocean_mipmap, 36);     /* mipmap.comp:17-23, ocean.cpp:55
 GR_ASSERT_OFFSET(gr_push_ocean_mipmap, inv_resolution, 16);
 GR_ASSERT_OFFSET(gr_push_ocean_mipmap, count, 24);
 GR_ASSERT_OFFSET(gr_push_ocean_mipmap, lod, 32);
+GR_ASSERT_SIZE(gr_push_ocean_update_lod, 64); /* update_lod.comp:6-15, ocean.cpp:285-294 */
+GR_ASSERT_OFFSET(gr_push_ocean_update_lod, max_lod, 12);
+GR_ASSERT_OFFSET(gr_push_ocean_update_lod, image_offset, 16);
+GR_ASSERT_OFFSET(gr_push_ocean_update_lod, num_threads, 24);
+GR_ASSERT_OFFSET(gr_push_ocean_update_lod, grid_base, 32);
+GR_ASSERT_OFFSET(gr_push_ocean_update_lod, grid_size, 40);
+GR_ASSERT_OFFSET(gr_push_ocean_update_lod, lod_bias, 48);
+GR_ASSERT_SIZE(gr_push_ocean_cull, 96);       /* cull_blocks.comp:6-20, ocean.cpp:335-349 */
+GR_ASSERT_OFFSET(gr_push_ocean_cull, image_offset, 16);
+GR_ASSERT_OFFSET(gr_push_ocean_cull, num_threads, 24);
+GR_ASSERT_OFFSET(gr_push_ocean_cull, inv_num_threads, 32);
+GR_ASSERT_OFFSET(gr_push_ocean_cull, grid_base, 40);
+GR_ASSERT_OFFSET(gr_push_ocean_cull, grid_size, 48);
+GR_ASSERT_OFFSET(gr_push_ocean_cull, grid_resolution, 56);
+GR_ASSERT_OFFSET(gr_push_ocean_cull, heightmap_range, 64);
+GR_ASSERT_OFFSET(gr_push_ocean_cull, guard_band, 72);
+GR_ASSERT_OFFSET(gr_push_ocean_cull, lod_stride, 76);
+GR_ASSERT_OFFSET(gr_push_ocean_cull, max_lod, 80);
+GR_ASSERT_OFFSET(gr_push_ocean_cull, handle_edge_lods, 84);
+GR_ASSERT_SIZE(gr_ocean_patch, 32);           /* ocean.inc:4-10 */
+GR_ASSERT_OFFSET(gr_ocean_patch, lods, 16);
+GR_ASSERT_SIZE(gr_ocean_indirect_draw, 32);   /* ocean.inc:12-22 */
+GR_ASSERT_OFFSET(gr_ocean_indirect_draw, instance_count, 4);
 GR_ASSERT_SIZE(gr_cacao_constants, 384);      /* ffx_cacao.h:95-154, ffx_cacao_bindings.hlsl:27-87 */
 GR_ASSERT_OFFSET(gr_cacao_constants, EffectRadius, 48);
 GR_ASSERT_OFFSET(gr_cacao_constants, InvSharpness, 96);

@@ -10,6 +10,13 @@ entry point (gr_timing_*), summed per stage over 10 updates.  The brackets seria
 than the wall clock of an update whose launches overlap their latencies.
 
     timeout -k 10 300 python tools/ocean_time.py > profiles/ocean_time.txt
+
+`python tools/ocean_time.py lod` times the LOD update instead, at the default configuration (grid_count 64, grid_resolution 128, ocean_size
+1024, lod_bias -3.5; camera near the origin, every block in view): gr_ocean_update_lod, gr_ocean_init_counter_buffer and
+gr_ocean_cull_blocks chained on one stream as Granite::Ocean::update_lod_pass chains them, 30 back-to-back passes between two
+synchronisations, three rounds, each launch alone the same way, and the FFT update beside it from the same run.
+
+    timeout -k 10 300 python tools/ocean_time.py lod > profiles/ocean_lod_time.txt
 """
 import ctypes as C
 import os
@@ -25,6 +32,42 @@ from granite_amd import capi, fft  # noqa: E402
 
 N, SHIFT, VERTEX_LEVELS = 1024, 1, 7  # log2(grid_resolution 128) levels of the height / displacement chain
 R16F, RG16F, RGBA16F = capi.FORMAT_R16_SFLOAT, capi.FORMAT_R16G16_SFLOAT, capi.FORMAT_R16G16B16A16_SFLOAT
+
+
+def lod_pass(gr):
+    """-> (stages of the LOD update at the default configuration, the buffers that keep them alive)"""
+    count, resolution, size, bias = 64, 128, 1024.0, -3.5
+    lods = resolution.bit_length() - 1
+    block = size / count
+    update = capi.PushOceanUpdateLod((1.3, 4.0, -2.1), float(lods - 1), (-32, -32), (count, count), (-32 * block, -32 * block), (block, block), bias)
+    cull = capi.PushOceanCull()
+    cull.image_offset[:] = [-32, -32]
+    cull.num_threads[:] = [count, count]
+    cull.inv_num_threads[:] = [1.0 / count, 1.0 / count]
+    cull.grid_base[:] = [-32 * block, -32 * block]
+    cull.grid_size[:] = [block, block]
+    cull.grid_resolution[:] = [resolution, resolution]
+    cull.heightmap_range[:] = [-10.0, 10.0]
+    cull.guard_band, cull.lod_stride, cull.max_lod, cull.handle_edge_lods = 5.0, count * count, float(lods - 1), 1
+    image = capi.DeviceImage(gr, count, count, R16F)
+    patches, counters = capi.DeviceBuffer(gr, count * count * 8 * 32), capi.DeviceBuffer(gr, 8 * 32)
+    planes = [0.0, 0.0, 0.0, 1.0] * 6
+    # index counts of the seven LOD meshes: size * (2 * (size + 1) + 1)
+    counts = [(resolution >> l) * (2 * ((resolution >> l) + 1) + 1) for l in range(lods)] + [0] * (16 - lods)
+    stages = {
+        "update_lod": lambda: gr.ocean_update_lod(image, update),
+        "init_counters": lambda: gr.ocean_init_counter_buffer(counters, counts),
+        "cull_blocks": lambda: gr.ocean_cull_blocks(image, 1, patches, counters, cull, planes),
+    }
+
+    launches = list(stages.values())
+
+    def whole():
+        for call in launches:
+            call()
+
+    stages["lod pass"] = whole
+    return stages, (image, patches, counters)
 
 
 def main():
@@ -102,6 +145,18 @@ def main():
         "bake": texels * (2 + 8 + 8) + m * m * 4,
         "mips": int(texels * 8 * (1 + 2 * 1 / 3)) * 2 + int(texels * 4 * (1 + 2 * 1 / 3)),  # every level written once, all but the last read once
     }
+    if sys.argv[1:] == ["lod"]:
+        lod_stages, keep = lod_pass(gr)
+        for round_ in range(3):
+            for name, call in lod_stages.items():
+                print(f"{name:14s} round {round_}: {per_call_ms(gr, call, calls=30) * 1e3:8.1f} us a call, 30 back to back")
+            print(f"{'fft update':14s} round {round_}: {per_call_ms(gr, update, calls=30) * 1e3:8.1f} us a call, 30 back to back")
+        counters = keep[2].download(np.uint32).reshape(8, 8)
+        print(f"blocks kept per LOD: {counters[:, 1].tolist()} of {64 * 64}")
+        for plan in plans.values():
+            plan.close()
+        gr.close()
+        return
     stages = {"generate x 3": generate, "fft x 3": transforms, "bake": bake, "mips": mips, "update": update}
     scratch_a, scratch_b = capi.DeviceBuffer(gr, 64 << 20), capi.DeviceBuffer(gr, 64 << 20)
     for round_ in range(3):

@@ -85,6 +85,21 @@ class FftRequest(C.Structure):
                 ("image_width", C.c_uint32), ("image_height", C.c_uint32), ("image_byte_offset", C.c_uint64), ("output_offset", C.c_int32 * 2)]
 
 
+class MeshletInfo(C.Structure):
+    """gra_meshlet_info."""
+    _fields_ = [("style", C.c_uint32), ("stream_count", C.c_uint32), ("meshlet_count", C.c_uint32), ("payload_size_words", C.c_uint32),
+                ("total_primitives", C.c_uint32), ("total_vertices", C.c_uint32), ("chunk_count", C.c_uint32), ("padding", C.c_uint32)]
+
+
+class MeshletRequest(C.Structure):
+    """gra_meshlet_request."""
+    _fields_ = [("flags", C.c_uint32), ("target_style", C.c_uint32), ("runtime_style", C.c_uint32), ("primitive_offset", C.c_uint32),
+                ("vertex_offset", C.c_uint32), ("padding", C.c_uint32),
+                ("indices", C.c_void_p), ("positions", C.c_void_p), ("attributes", C.c_void_p), ("skin", C.c_void_p), ("indirect", C.c_void_p),
+                ("indices_bytes", C.c_uint64), ("positions_bytes", C.c_uint64), ("attributes_bytes", C.c_uint64), ("skin_bytes", C.c_uint64),
+                ("indirect_bytes", C.c_uint64)]
+
+
 class OceanConfig(C.Structure):
     """gra_ocean_config."""
     _fields_ = [("fft_resolution", C.c_uint32), ("displacement_downsample", C.c_uint32), ("grid_count", C.c_uint32), ("grid_resolution", C.c_uint32),
@@ -127,6 +142,7 @@ EXPORTED_SYMBOLS = [
     "gra_video_play_begin", "gra_video_play_layout", "gra_video_play_frame", "gra_video_play_read_rgb", "gra_video_play_end",
     "gra_ocean_default_config", "gra_ocean_create", "gra_ocean_update", "gra_ocean_describe", "gra_ocean_read", "gra_ocean_distribution",
     "gra_ocean_parameters", "gra_ocean_destroy", "gra_ocean_set_camera", "gra_ocean_draw_info", "gra_ocean_mesh_describe", "gra_ocean_mesh_read",
+    "gra_meshlet_describe", "gra_meshlet_decode",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -180,6 +196,8 @@ def load_library() -> C.CDLL:
         "gra_gtx_decode": (C.c_int, [vp, C.c_char_p, C.c_char_p]),
         "gra_environment_bake": (C.c_int, [vp, C.c_char_p, C.c_float] + [C.c_char_p] * 3),
         "gra_fft_transform": (C.c_int, [vp, P(FftRequest)]),
+        "gra_meshlet_describe": (C.c_int, [C.c_char_p, P(MeshletInfo), vp, C.c_size_t]),
+        "gra_meshlet_decode": (C.c_int, [vp, C.c_char_p, P(MeshletRequest), P(MeshletInfo)]),
         "gra_upload_gbuffer_gtx": (C.c_int, [vp] + [C.c_char_p] * 6),
         "gra_save_resource_gtx": (C.c_int, [vp, C.c_char_p, C.c_char_p]),
         "gra_reset_timestamps": (C.c_int, [vp]),
@@ -371,6 +389,13 @@ class Application:
             r.image_width, r.image_height, r.image_byte_offset = int(image[0]), int(image[1]), int(image[2])
         r.output_offset[:] = [int(output_offset[0]), int(output_offset[1])]
         self._check(self.lib.gra_fft_transform(self.handle, C.byref(r)))
+
+    def decode_meshlet(self, path: str, request: MeshletRequest) -> MeshletInfo:
+        """gra_meshlet_decode: the MESHLET4 file `path` decoded on the device into the host arrays `request` points at (granite_amd.meshlet.decode
+        builds the request and the arrays)."""
+        info = MeshletInfo()
+        self._check(self.lib.gra_meshlet_decode(self.handle, str(path).encode(), C.byref(request), C.byref(info)))
+        return info
 
     def save_gtx(self, path: str, name: Optional[str] = None):
         """Write graph texture `name` (None = the last backbuffer) as .gtx."""

@@ -258,6 +258,24 @@ class OceanBuffer(C.Structure):
 OCEAN_MAX_LOD_INDIRECT = 8
 
 
+# gr_meshlet_decode: decode flags, mesh styles, and the argument blocks
+MESHLET_DECODE_UNROLLED_MESH, MESHLET_DECODE_INDEX_16 = 1, 2
+MESHLET_STYLE_WIREFRAME, MESHLET_STYLE_TEXTURED, MESHLET_STYLE_SKINNED = 0, 1, 2
+
+
+class PushMeshletDecode(C.Structure):
+    """gr_push_meshlet_decode: the Registers block of decode/meshlet_decode.comp."""
+    _fields_ = [("primitive_offset", C.c_uint32), ("vertex_offset", C.c_uint32), ("meshlet_count", C.c_uint32), ("wg_offset", C.c_uint32)]
+
+
+class MeshletDecodeArgs(C.Structure):
+    """gr_meshlet_decode_args: device pointers, capacities in elements."""
+    _fields_ = [("streams", C.c_void_p), ("payload", C.c_void_p), ("payload_words", C.c_uint32), ("stream_count", C.c_uint32), ("offsets", C.c_void_p),
+                ("indices", C.c_void_p), ("index_capacity", C.c_uint64), ("positions", C.c_void_p), ("position_capacity", C.c_uint64),
+                ("attributes", C.c_void_p), ("attribute_capacity", C.c_uint64), ("skin", C.c_void_p), ("skin_capacity", C.c_uint64),
+                ("target_style", C.c_uint32), ("flags", C.c_uint32)]
+
+
 # gr_cacao_*: FFX_CACAO_Quality values taken, limits, and the VkFormat values of two intermediates no Image argument takes
 CACAO_QUALITY_HIGH, CACAO_QUALITY_HIGHEST = 3, 4
 CACAO_MAX_BLUR_PASSES = 8
@@ -609,6 +627,7 @@ def load_library() -> C.CDLL:
         "gr_ocean_update_lod": (C.c_int, [vp, vp, P(Image), P(PushOceanUpdateLod)]),
         "gr_ocean_init_counter_buffer": (C.c_int, [vp, vp, P(OceanBuffer), P(C.c_uint32)]),
         "gr_ocean_cull_blocks": (C.c_int, [vp, vp, P(Image), C.c_uint32, P(OceanBuffer), P(OceanBuffer), P(PushOceanCull), P(C.c_float)]),
+        "gr_meshlet_decode": (C.c_int, [vp, vp, P(MeshletDecodeArgs), P(PushMeshletDecode)]),
         "gr_cacao_reference_settings": (None, [P(CacaoSettings)]),
         "gr_cacao_update_buffer_sizes": (C.c_int, [C.c_uint32, C.c_uint32, P(CacaoBufferSizes)]),
         "gr_cacao_update_constants": (C.c_int, [vp, P(CacaoConstants), P(CacaoSettings), P(CacaoBufferSizes), P(C.c_float), P(C.c_float)]),
@@ -648,6 +667,7 @@ EXPORTED_SYMBOLS = [
     "gr_cube_chain_bytes", "gr_cube_chain_offset", "gr_env_equirect_to_cube", "gr_env_specular", "gr_env_diffuse",
     "gr_fft_describe", "gr_fft_plan_create", "gr_fft_plan_destroy", "gr_fft_plan_iterations", "gr_fft_execute", "gr_fft_execute_iteration",
     "gr_ocean_generate_fft", "gr_ocean_bake_maps", "gr_ocean_mipmap", "gr_ocean_update_lod", "gr_ocean_init_counter_buffer", "gr_ocean_cull_blocks",
+    "gr_meshlet_decode",
     "gr_cacao_reference_settings", "gr_cacao_update_buffer_sizes", "gr_cacao_update_constants", "gr_cacao_workspace_bytes", "gr_cacao_workspace_describe",
     "gr_cacao_prepare_depths", "gr_cacao_prepare_normals", "gr_cacao_generate_base", "gr_cacao_importance_generate",
     "gr_cacao_importance_postprocess_a", "gr_cacao_importance_postprocess_b", "gr_cacao_generate", "gr_cacao_blur", "gr_cacao_apply",
@@ -1085,6 +1105,12 @@ class Context:
         planes = (C.c_float * 24)(*[float(v) for v in frustum])
         self.check(self.lib.gr_ocean_cull_blocks(self.handle, stream, lod_image.desc, int(wrap), C.byref(OceanBuffer(patches.ptr, patches.nbytes)),
                                                  C.byref(OceanBuffer(counters.ptr, counters.nbytes)), C.byref(push), planes))
+
+    # ---- mesh decode --------------------------------------------------------------------------------------------------------------------
+    def meshlet_decode(self, args: MeshletDecodeArgs, primitive_offset: int, vertex_offset: int, meshlet_count: int, wg_offset: int = 0, stream=None):
+        """gr_meshlet_decode: one launch that expands MESHLET4 streams into index, position, attribute and skin buffers."""
+        push = PushMeshletDecode(int(primitive_offset), int(vertex_offset), int(meshlet_count), int(wg_offset))
+        self.check(self.lib.gr_meshlet_decode(self.handle, stream, C.byref(args), C.byref(push)))
 
     # ---- SSAO: FidelityFX CACAO --------------------------------------------------------------------------------------------------------
     def cacao_workspace(self, width: int, height: int) -> DeviceBuffer:

@@ -9,6 +9,7 @@
 #include "../fft/fft.hpp"
 #include "../ocean.hpp"
 #include "../post/hdr.hpp"
+#include "../mesh/meshlet.hpp"
 #include <cstdio>
 #include <cstring>
 
@@ -88,6 +89,42 @@ static void fill_gtx_info(gra_gtx_info *info, const GtxImage &img)
 	info->flags = img.flags;
 	info->payload_size = img.payload.size();
 }
+
+// A MESHLET4 file in 4-byte aligned memory and the view over it; throws with create_mesh_view's reason.
+struct meshlet_file
+{
+	std::vector<uint32_t> words;
+	Meshlet::MeshView view = {};
+	explicit meshlet_file(const char *path)
+	{
+		FILE *f = fopen(path, "rb");
+		if (!f)
+			throw std::runtime_error(std::string("cannot open ") + path);
+		fseek(f, 0, SEEK_END);
+		const long size = ftell(f);
+		fseek(f, 0, SEEK_SET);
+		words.resize((size_t(size > 0 ? size : 0) + 3) / 4);
+		const bool ok = size >= 0 && fread(words.data(), 1, size_t(size), f) == size_t(size);
+		fclose(f);
+		if (!ok)
+			throw std::runtime_error(std::string("cannot read ") + path);
+		std::string why;
+		view = Meshlet::create_mesh_view(words.data(), size_t(size), &why);
+		if (!view.format_header)
+			throw std::runtime_error(std::string(path) + ": " + why);
+	}
+	void describe(gra_meshlet_info *info) const
+	{
+		*info = {};
+		info->style = uint32_t(view.format_header->style);
+		info->stream_count = view.format_header->stream_count;
+		info->meshlet_count = view.format_header->meshlet_count;
+		info->payload_size_words = view.format_header->payload_size_words;
+		info->total_primitives = view.total_primitives;
+		info->total_vertices = view.total_vertices;
+		info->chunk_count = view.num_bounds_256;
+	}
+};
 
 extern "C" {
 
@@ -583,6 +620,91 @@ void gra_ocean_destroy(gra_ocean *ocean)
 		return;
 	ocean->app->app->get_device().wait_idle();
 	delete ocean;
+}
+
+int gra_meshlet_describe(const char *path, gra_meshlet_info *info, char *error, size_t error_size)
+{
+	return guarded_message(error, error_size, [&]() {
+		if (!path || !info)
+			throw std::logic_error("gra_meshlet_describe: null argument");
+		meshlet_file(path).describe(info);
+	});
+}
+
+int gra_meshlet_decode(gra_app *app, const char *path, const gra_meshlet_request *request, gra_meshlet_info *result)
+{
+	return guarded(app, [&]() {
+		if (!path || !request)
+			throw std::logic_error("gra_meshlet_decode: null path or request");
+		gr_ctx *ctx = app->app->get_device().get_context();
+		if (!ctx)
+			throw std::logic_error("gra_meshlet_decode: the application has no device");
+		const meshlet_file file(path);
+		const Meshlet::MeshView &view = file.view;
+		if (request->target_style > uint32_t(view.format_header->style))
+			throw std::logic_error("gra_meshlet_decode: target_style is above the file's style");
+		if (request->runtime_style > 1u || (request->flags & ~(GR_MESHLET_DECODE_UNROLLED_MESH | GR_MESHLET_DECODE_INDEX_16)))
+			throw std::logic_error("gra_meshlet_decode: unknown runtime_style or flags");
+		const uint64_t index_bytes = (request->flags & GR_MESHLET_DECODE_UNROLLED_MESH) ? 4 : ((request->flags & GR_MESHLET_DECODE_INDEX_16) ? 2 : 1);
+		const uint64_t primitives = uint64_t(request->primitive_offset) + view.total_primitives, vertices = uint64_t(request->vertex_offset) + view.total_vertices;
+		const auto runtime_style = request->runtime_style ? Meshlet::RuntimeStyle::Meshlet : Meshlet::RuntimeStyle::MDI;
+		struct Array
+		{
+			const char *name;
+			void *host;
+			uint64_t bytes, least;
+			bool needed;
+			void *device = nullptr;
+		} arrays[5] = {{"indices", request->indices, request->indices_bytes, primitives * 3 * index_bytes, true},
+		               {"positions", request->positions, request->positions_bytes, vertices * 12, true},
+		               {"attributes", request->attributes, request->attributes_bytes, vertices * 16, request->target_style >= 1u},
+		               {"skin", request->skin, request->skin_bytes, vertices * 8, request->target_style >= 2u},
+		               {"indirect", request->indirect, request->indirect_bytes, view.num_bounds_256 * Meshlet::indirect_stride(runtime_style), false}};
+		struct Release
+		{
+			gr_ctx *ctx;
+			Array *arrays;
+			~Release()
+			{
+				for (int i = 0; i < 5; i++)
+					if (arrays[i].device)
+						gr_free(ctx, arrays[i].device);
+			}
+		} release{ctx, arrays};
+		auto check = [&](int code) {
+			if (code < 0)
+				throw std::runtime_error(gr_last_error(ctx));
+		};
+		for (Array &a : arrays)
+		{
+			if (!a.host && !a.needed)
+				continue;
+			if (a.bytes < a.least || (!a.host && a.bytes))
+				throw std::logic_error(std::string("gra_meshlet_decode: ") + a.name + " is null or smaller than the decode needs");
+			check(gr_alloc(ctx, a.bytes ? a.bytes : 16, &a.device)); // a mesh of empty meshlets still names its buffers
+			if (a.bytes)
+				check(gr_upload(ctx, nullptr, a.device, a.host, a.bytes));
+		}
+		Meshlet::DecodeInfo info;
+		info.ibo = {arrays[0].device, arrays[0].bytes};
+		for (int i = 0; i < 3; i++)
+			info.streams[i] = {arrays[1 + i].device, arrays[1 + i].bytes};
+		info.indirect = {arrays[4].device, arrays[4].bytes};
+		info.flags = request->flags;
+		info.target_style = Meshlet::MeshStyle(request->target_style);
+		info.runtime_style = runtime_style;
+		info.push.primitive_offset = request->primitive_offset;
+		info.push.vertex_offset = request->vertex_offset;
+		std::string why;
+		if (view.format_header->meshlet_count && !Meshlet::decode_mesh(ctx, nullptr, info, view, &why))
+			throw std::runtime_error(why);
+		for (Array &a : arrays)
+			if (a.device && a.bytes)
+				check(gr_download(ctx, nullptr, a.host, a.device, a.bytes));
+		check(gr_sync(ctx, nullptr));
+		if (result)
+			file.describe(result);
+	});
 }
 
 int gra_fft_transform(gra_app *app, const gra_fft_request *request)

@@ -302,6 +302,40 @@ int gra_ocean_mesh_describe(gra_ocean *ocean, uint32_t which, gra_ocean_mesh_inf
 int gra_ocean_mesh_read(gra_ocean *ocean, uint32_t which, void *vbo_out, void *ibo_out);
 void gra_ocean_destroy(gra_ocean *ocean);
 
+/* ---- MESHLET4 mesh files (host/mesh/meshlet.hpp; vulkan/mesh/meshlet.hpp) ----
+ * gra_meshlet_describe needs no device: it maps the file through Granite::Meshlet::create_mesh_view and fails, with the view's reason
+ * in `error`, for a file the view refuses. */
+typedef struct gra_meshlet_info
+{
+	uint32_t style;        /* 0 Wireframe, 1 Textured, 2 Skinned */
+	uint32_t stream_count; /* 2, 4, 6 */
+	uint32_t meshlet_count;
+	uint32_t payload_size_words;
+	uint32_t total_primitives;
+	uint32_t total_vertices;
+	uint32_t chunk_count; /* ceil(meshlet_count / 8) */
+	uint32_t padding;
+} gra_meshlet_info;
+int gra_meshlet_describe(const char *path, gra_meshlet_info *info, char *error, size_t error_size);
+/* Decodes the file on the application's device (Granite::Meshlet::decode_mesh, one gr_meshlet_decode launch) into host arrays.  Each
+ * array that is not NULL is uploaded first and downloaded afterwards, so bytes the decode does not write come back as they went in.
+ * Sizes in bytes, with P = primitive_offset + total_primitives and V = vertex_offset + total_vertices as the least element counts:
+ * indices P * 3 * (4 with GR_MESHLET_DECODE_UNROLLED_MESH, 2 with GR_MESHLET_DECODE_INDEX_16, else 1); positions V * 12; attributes
+ * V * 16 (target_style >= 1); skin V * 8 (target_style 2); indirect, optional, chunk_count * (128 for the Meshlet runtime style: eight
+ * {primitive_offset, vertex_offset, primitive_count, vertex_count}; 12 for MDI: {indexCount, firstIndex, vertexOffset}).  A larger
+ * array is taken whole: what lies past the last element is not written.  Fails for an array the style needs that is NULL or too small. */
+typedef struct gra_meshlet_request
+{
+	uint32_t flags;         /* GR_MESHLET_DECODE_* */
+	uint32_t target_style;  /* not above the file's */
+	uint32_t runtime_style; /* 0 MDI, 1 Meshlet */
+	uint32_t primitive_offset, vertex_offset;
+	uint32_t padding;
+	void *indices, *positions, *attributes, *skin, *indirect;
+	uint64_t indices_bytes, positions_bytes, attributes_bytes, skin_bytes, indirect_bytes;
+} gra_meshlet_request;
+int gra_meshlet_decode(gra_app *app, const char *path, const gra_meshlet_request *request, gra_meshlet_info *result);
+
 /* Writes a graph texture (all its mip levels) or, with name == NULL, the last rendered backbuffer as .gtx. */
 int gra_save_resource_gtx(gra_app *app, const char *name, const char *path);
 

@@ -276,6 +276,55 @@ class MeshletDecodeArgs(C.Structure):
                 ("target_style", C.c_uint32), ("flags", C.c_uint32)]
 
 
+# gr_meshlet_cull: flags and the records of meshlet_cull.comp
+MESHLET_CULL_ORTHO, MESHLET_CULL_SKINNED, MESHLET_CULL_FORCE_VISIBLE = 1, 2, 4
+
+
+class PushMeshletCull(C.Structure):
+    """gr_push_meshlet_cull: the Registers block of meshlet_cull.comp."""
+    _fields_ = [("offset", C.c_uint32), ("count", C.c_uint32), ("mdi_count_offset", C.c_uint32), ("draw_indirect_offset", C.c_uint32)]
+
+
+class MeshletTask(C.Structure):
+    """gr_meshlet_task: MeshAssetDrawTaskInfo."""
+    _fields_ = [("aabb_instance", C.c_uint32), ("occluder_state_offset", C.c_uint32), ("node_instance", C.c_uint32), ("mesh_index_count", C.c_uint32),
+                ("material_flags", C.c_uint32)]
+
+
+class MeshletAABB(C.Structure):
+    _fields_ = [("lo", C.c_float * 3), ("pad0", C.c_float), ("hi", C.c_float * 3), ("pad1", C.c_float)]
+
+
+class MeshletBound(C.Structure):
+    """gr_meshlet_bound: Meshlet::Bound."""
+    _fields_ = [("center", C.c_float * 3), ("radius", C.c_float), ("cone_axis_cutoff", C.c_float * 4)]
+
+
+class MatAffine(C.Structure):
+    """gr_mat_affine: three rows of a 3 x 4 matrix."""
+    _fields_ = [("rows", (C.c_float * 4) * 3)]
+
+
+class MeshletDraw(C.Structure):
+    """gr_meshlet_draw: RuntimeHeaderDecodedMDI."""
+    _fields_ = [("index_count", C.c_uint32), ("first_index", C.c_uint32), ("vertex_offset", C.c_int32)]
+
+
+class MeshletFrustum(C.Structure):
+    """gr_meshlet_frustum: the std140 Frustum block of inc/meshlet_ubos.h, 224 bytes."""
+    _fields_ = [("viewport", C.c_float * 4), ("planes", (C.c_float * 4) * 6), ("view", C.c_float * 16), ("viewport_scale_bias", C.c_float * 4),
+                ("hiz_resolution", C.c_int32 * 2), ("winding", C.c_float), ("hiz_min_lod", C.c_int32), ("hiz_max_lod", C.c_int32), ("pad", C.c_uint32 * 3)]
+
+
+class MeshletCullArgs(C.Structure):
+    """gr_meshlet_cull_args: device pointers, counts in elements."""
+    _fields_ = [("tasks", C.c_void_p), ("task_count", C.c_uint32), ("aabb_count", C.c_uint32), ("aabbs", C.c_void_p), ("transforms", C.c_void_p),
+                ("bounds", C.c_void_p), ("transform_count", C.c_uint32), ("bound_count", C.c_uint32), ("draws", C.c_void_p), ("draw_count", C.c_uint32),
+                ("occluder_count", C.c_uint32), ("occluders", C.c_void_p), ("output", C.c_void_p), ("output_dwords", C.c_uint64), ("chain", C.c_void_p),
+                ("chain_width", C.c_uint32), ("chain_height", C.c_uint32), ("chain_levels", C.c_uint32), ("phase", C.c_uint32), ("flags", C.c_uint32),
+                ("camera_position", C.c_float * 3), ("frustum", MeshletFrustum)]
+
+
 # gr_cacao_*: FFX_CACAO_Quality values taken, limits, and the VkFormat values of two intermediates no Image argument takes
 CACAO_QUALITY_HIGH, CACAO_QUALITY_HIGHEST = 3, 4
 CACAO_MAX_BLUR_PASSES = 8
@@ -628,6 +677,7 @@ def load_library() -> C.CDLL:
         "gr_ocean_init_counter_buffer": (C.c_int, [vp, vp, P(OceanBuffer), P(C.c_uint32)]),
         "gr_ocean_cull_blocks": (C.c_int, [vp, vp, P(Image), C.c_uint32, P(OceanBuffer), P(OceanBuffer), P(PushOceanCull), P(C.c_float)]),
         "gr_meshlet_decode": (C.c_int, [vp, vp, P(MeshletDecodeArgs), P(PushMeshletDecode)]),
+        "gr_meshlet_cull": (C.c_int, [vp, vp, P(MeshletCullArgs), P(PushMeshletCull)]),
         "gr_cacao_reference_settings": (None, [P(CacaoSettings)]),
         "gr_cacao_update_buffer_sizes": (C.c_int, [C.c_uint32, C.c_uint32, P(CacaoBufferSizes)]),
         "gr_cacao_update_constants": (C.c_int, [vp, P(CacaoConstants), P(CacaoSettings), P(CacaoBufferSizes), P(C.c_float), P(C.c_float)]),
@@ -667,7 +717,7 @@ EXPORTED_SYMBOLS = [
     "gr_cube_chain_bytes", "gr_cube_chain_offset", "gr_env_equirect_to_cube", "gr_env_specular", "gr_env_diffuse",
     "gr_fft_describe", "gr_fft_plan_create", "gr_fft_plan_destroy", "gr_fft_plan_iterations", "gr_fft_execute", "gr_fft_execute_iteration",
     "gr_ocean_generate_fft", "gr_ocean_bake_maps", "gr_ocean_mipmap", "gr_ocean_update_lod", "gr_ocean_init_counter_buffer", "gr_ocean_cull_blocks",
-    "gr_meshlet_decode",
+    "gr_meshlet_decode", "gr_meshlet_cull",
     "gr_cacao_reference_settings", "gr_cacao_update_buffer_sizes", "gr_cacao_update_constants", "gr_cacao_workspace_bytes", "gr_cacao_workspace_describe",
     "gr_cacao_prepare_depths", "gr_cacao_prepare_normals", "gr_cacao_generate_base", "gr_cacao_importance_generate",
     "gr_cacao_importance_postprocess_a", "gr_cacao_importance_postprocess_b", "gr_cacao_generate", "gr_cacao_blur", "gr_cacao_apply",
@@ -1111,6 +1161,11 @@ class Context:
         """gr_meshlet_decode: one launch that expands MESHLET4 streams into index, position, attribute and skin buffers."""
         push = PushMeshletDecode(int(primitive_offset), int(vertex_offset), int(meshlet_count), int(wg_offset))
         self.check(self.lib.gr_meshlet_decode(self.handle, stream, C.byref(args), C.byref(push)))
+
+    def meshlet_cull(self, args: MeshletCullArgs, offset: int, count: int, mdi_count_offset: int, draw_indirect_offset: int, stream=None):
+        """gr_meshlet_cull: one launch that culls `count` tasks from `offset` on and appends the surviving chunks' draw records."""
+        push = PushMeshletCull(int(offset), int(count), int(mdi_count_offset), int(draw_indirect_offset))
+        self.check(self.lib.gr_meshlet_cull(self.handle, stream, C.byref(args), C.byref(push)))
 
     # ---- SSAO: FidelityFX CACAO --------------------------------------------------------------------------------------------------------
     def cacao_workspace(self, width: int, height: int) -> DeviceBuffer:

@@ -13,6 +13,7 @@ from typing import Dict, Optional
 import numpy as np
 
 from . import app as gapp
+from . import capi
 from .capi import MESHLET_DECODE_INDEX_16, MESHLET_DECODE_UNROLLED_MESH
 
 MAGIC = b"MESHLET4"
@@ -98,3 +99,58 @@ def decode(application: "gapp.Application", path: str, target_style: Optional[in
         setattr(r, key + "_bytes", a.nbytes)
     application.decode_meshlet(path, r)
     return out
+
+
+class CullScene:
+    """The buffers gr_meshlet_cull reads and writes, uploaded from arrays: tasks (T, 5) uint32, aabbs (A, 8) float32, transforms (N, 12)
+    float32, bounds (B, 8) float32, draws (B, 3) uint32, occluders (O,) uint32, output (D,) uint32 as it is before the first launch (count
+    words zero), and optionally the HiZ chain (flat float32, or a capi.DeviceBuffer that gr_hiz wrote) with its width, height and levels."""
+
+    def __init__(self, ctx: "capi.Context", tasks, aabbs, transforms, bounds, draws, occluders, output, chain=None, chain_width=0, chain_height=0, chain_levels=0):
+        self.ctx = ctx
+        arrays = {"tasks": (tasks, np.uint32, 5), "aabbs": (aabbs, np.float32, 8), "transforms": (transforms, np.float32, 12), "bounds": (bounds, np.float32, 8),
+                  "draws": (draws, np.uint32, 3), "occluders": (occluders, np.uint32, 1), "output": (output, np.uint32, 1)}
+        self.counts, self.buffers = {}, {}
+        for key, (array, dtype, width) in arrays.items():
+            a = np.ascontiguousarray(array, dtype).reshape(-1, width)
+            self.counts[key] = len(a)
+            self.buffers[key] = capi.DeviceBuffer(ctx, max(a.nbytes, 16))
+            if a.nbytes:
+                self.buffers[key].upload(a)
+        if chain is not None and not isinstance(chain, capi.DeviceBuffer):
+            chain = capi.DeviceBuffer(ctx, max(np.asarray(chain).nbytes, 16)).upload(np.ascontiguousarray(chain, np.float32))
+        self.chain, self.chain_shape = chain, (int(chain_width), int(chain_height), int(chain_levels))
+
+    def reset(self, occluders, output):
+        """the occluder words and the output buffer as they are before a launch"""
+        for key, array in (("occluders", occluders), ("output", output)):
+            a = np.ascontiguousarray(array, np.uint32).ravel()
+            assert len(a) == self.counts[key]
+            if a.nbytes:
+                self.buffers[key].upload(a)
+
+    def args(self, frustum, camera_position, phase: int, flags: int) -> "capi.MeshletCullArgs":
+        a = capi.MeshletCullArgs()
+        for key, count in (("tasks", "task_count"), ("aabbs", "aabb_count"), ("transforms", "transform_count"), ("bounds", "bound_count"), ("draws", "draw_count"),
+                           ("occluders", "occluder_count")):
+            setattr(a, key, self.buffers[key].ptr)
+            setattr(a, count, self.counts[key])
+        a.output, a.output_dwords = self.buffers["output"].ptr, self.counts["output"]
+        if self.chain is not None:
+            a.chain = self.chain.ptr
+            a.chain_width, a.chain_height, a.chain_levels = self.chain_shape
+        a.phase, a.flags = int(phase), int(flags)
+        a.camera_position[:] = [float(v) for v in camera_position]
+        C.memmove(C.byref(a.frustum), np.ascontiguousarray(frustum, np.uint32).ctypes.data, 224)
+        return a
+
+    def download(self):
+        """(output dwords, occluder words)"""
+        self.ctx.sync()
+        return self.buffers["output"].download(np.uint32, self.counts["output"]), self.buffers["occluders"].download(np.uint32, self.counts["occluders"])
+
+
+def cull(scene: CullScene, frustum, camera_position, phase: int, flags: int, offset: int, count: int, mdi_count_offset: int, draw_indirect_offset: int, stream=None):
+    """One gr_meshlet_cull launch over `count` tasks from `offset`: survivors are appended as five-dword draw records at
+    output[draw_indirect_offset + 5 * slot] behind the count word output[mdi_count_offset].  frustum: the 224-byte block as 56 uint32."""
+    scene.ctx.meshlet_cull(scene.args(frustum, camera_position, phase, flags), offset, count, mdi_count_offset, draw_indirect_offset, stream)

@@ -1149,6 +1149,96 @@ typedef struct gr_meshlet_decode_args /* every pointer is a device pointer */
  * wg_offset at or past the last group, returns GR_OK without launching. */
 int gr_meshlet_decode(gr_ctx *ctx, gr_stream stream, const gr_meshlet_decode_args *args, const gr_push_meshlet_decode *push);
 
+/* ---- meshlet culling (renderer/scene_renderer.cpp build_mdi_culling_pass, assets/shaders/meshlet_cull.comp) -------------------------------
+ * One launch tests `count` tasks of up to 32 chunks each: the task's AABB against the frustum, every chunk's bounding sphere and normal
+ * cone against the frustum and the camera (inc/meshlet_render.h), in phase 2 both against the depth hierarchy, and compacts the
+ * survivors into five-dword records {index_count, 1, first_index, vertex_offset, task_index} (VkDrawIndexedIndirectCommand) at
+ * output[draw_indirect_offset + 5 * slot], slot from an atomic add on output[mdi_count_offset].  The records of one task are contiguous
+ * and in chunk order; the order of tasks among each other is whatever the atomics give and is not specified.  The caller zeroes the
+ * count word.  A record that would end past output_dwords is not written; the count still includes it.
+ *   phase 0 (CullingPhase::OneShot)              no occluder word is read or written
+ *   phase 1 (First, MotionVector)                reads: a task is skipped when its word is 0, a chunk when its bit is clear
+ *   phase 2 (Second)                             writes: 0 for an invisible task, else the chunks visible now; chunks whose old bit was set
+ *                                                are not drawn again unless FORCE_VISIBLE; adds the HiZ tests
+ * The chain is the one gr_hiz writes with output_downsample = 1 (R32_SFLOAT, gr_mip_chain_offset(chain_width, chain_height, 4, level)).
+ * Every index read from device data is held to the element count given here; what falls outside is not visible and is not read.
+ * Arithmetic and its order: granite_amd/csrc/meshlet_cull.hpp. */
+#define GR_MESHLET_CULL_ORTHO 1u         /* constant_id 0: projection[3].w == 1 */
+#define GR_MESHLET_CULL_SKINNED 2u       /* constant_id 1: no per-chunk test, the AABB test only */
+#define GR_MESHLET_CULL_FORCE_VISIBLE 4u /* constant_id 2, phase 2 only: draw what phase 1 drew as well */
+typedef struct gr_push_meshlet_cull /* meshlet_cull.comp:23-29, scene_renderer.cpp:983-989 */
+{
+	uint32_t offset;               /* first task */
+	uint32_t count;                /* tasks */
+	uint32_t mdi_count_offset;     /* dword of the count word in the output buffer */
+	uint32_t draw_indirect_offset; /* dword of the first record */
+} gr_push_meshlet_cull;
+typedef struct gr_meshlet_task /* MeshAssetDrawTaskInfo, inc/meshlet_render_types.h:15-22 */
+{
+	uint32_t aabb_instance;
+	uint32_t occluder_state_offset;
+	uint32_t node_instance;
+	uint32_t mesh_index_count; /* first chunk (a multiple of 32) + chunks - 1 */
+	uint32_t material_flags;
+} gr_meshlet_task;
+typedef struct gr_meshlet_aabb /* inc/meshlet_render_types.h:4-7 */
+{
+	float lo[3], pad0, hi[3], pad1;
+} gr_meshlet_aabb;
+typedef struct gr_meshlet_bound /* Meshlet::Bound, vulkan/mesh/meshlet.hpp:79-84; inc/meshlet_render_types.h:9-13 */
+{
+	float center[3];
+	float radius;
+	float cone_axis_cutoff[4];
+} gr_meshlet_bound;
+typedef struct gr_meshlet_draw /* RuntimeHeaderDecodedMDI, vulkan/mesh/meshlet.hpp:72-77; meshlet_cull.comp:16-21 */
+{
+	uint32_t index_count;
+	uint32_t first_index;
+	int32_t vertex_offset;
+} gr_meshlet_draw;
+typedef struct gr_meshlet_frustum /* inc/meshlet_ubos.h:4-14 (std140), renderer.cpp:540-572 */
+{
+	float viewport[4];
+	float planes[6][4];
+	float view[16]; /* column major */
+	float viewport_scale_bias[4];
+	int32_t hiz_resolution[2];
+	float winding;
+	int32_t hiz_min_lod;
+	int32_t hiz_max_lod;
+	uint32_t pad[3];
+} gr_meshlet_frustum;
+typedef struct gr_meshlet_cull_args /* every pointer is a device pointer; counts are in elements */
+{
+	const gr_meshlet_task *tasks;
+	uint32_t task_count;
+	uint32_t aabb_count;
+	const gr_meshlet_aabb *aabbs;           /* 16-byte aligned */
+	const gr_mat_affine *transforms;        /* mat_affine of inc/affine.h:4-7 (gr_mat_affine above); 16-byte aligned; not read when SKINNED */
+	const gr_meshlet_bound *bounds;         /* 16-byte aligned, one per chunk; not read when SKINNED */
+	uint32_t transform_count;
+	uint32_t bound_count;
+	const gr_meshlet_draw *draws;           /* one per chunk */
+	uint32_t draw_count;
+	uint32_t occluder_count;
+	uint32_t *occluders;                    /* phases 1 and 2 */
+	uint32_t *output;                       /* count words and records */
+	uint64_t output_dwords;
+	const void *chain;                      /* phase 2 */
+	uint32_t chain_width, chain_height, chain_levels;
+	uint32_t phase;                         /* 0, 1 or 2 */
+	uint32_t flags;                         /* GR_MESHLET_CULL_* */
+	float camera_position[3];
+	gr_meshlet_frustum frustum;
+} gr_meshlet_cull_args;
+/* ceil(count / 64) waves; count 0 returns GR_OK without a launch.  Refused with GR_ERR_INVALID_ARGUMENT before anything is launched, the
+ * message naming the field: a phase above 2, unknown flags, a null or misaligned pointer the phase and flags need (occluders in phases 1
+ * and 2, chain in phase 2, transforms and bounds unless SKINNED), in phase 2 a frustum whose hiz_resolution is not
+ * (chain_width, chain_height) << hiz_min_lod or whose hiz_max_lod is not chain_levels - 1 + hiz_min_lod, and mdi_count_offset or
+ * draw_indirect_offset outside output_dwords. */
+int gr_meshlet_cull(gr_ctx *ctx, gr_stream stream, const gr_meshlet_cull_args *args, const gr_push_meshlet_cull *push);
+
 /* ---- SSAO: FidelityFX CACAO as the reference runs it (renderer/post/ssao.cpp, renderer/post/ffx-cacao) -----------------------------------
  * One configuration and its non-adaptive sibling: native resolution, normals from the G-buffer, quality HIGHEST (adaptive, shader level 3)
  * or HIGH (shader level 2), 0 .. 8 blur passes.  One entry point per shader of FFX_CACAO_GraniteDraw (ffx_cacao_impl.cpp:767-1026); the
@@ -1416,6 +1506,26 @@ GR_ASSERT_OFFSET(gr_push_meshlet_decode, wg_offset, 12);
 GR_ASSERT_SIZE(gr_meshlet_stream, 16);        /* meshlet.hpp:47-57 */
 GR_ASSERT_OFFSET(gr_meshlet_stream, bits, 8);
 GR_ASSERT_SIZE(gr_meshlet_offsets, 12);       /* meshlet.cpp:209-214 */
+GR_ASSERT_SIZE(gr_push_meshlet_cull, 16);     /* meshlet_cull.comp:23-29 */
+GR_ASSERT_OFFSET(gr_push_meshlet_cull, mdi_count_offset, 8);
+GR_ASSERT_OFFSET(gr_push_meshlet_cull, draw_indirect_offset, 12);
+GR_ASSERT_SIZE(gr_meshlet_task, 20);          /* inc/meshlet_render_types.h:15-22 */
+GR_ASSERT_OFFSET(gr_meshlet_task, mesh_index_count, 12);
+GR_ASSERT_SIZE(gr_meshlet_aabb, 32);          /* inc/meshlet_render_types.h:4-7 */
+GR_ASSERT_OFFSET(gr_meshlet_aabb, hi, 16);
+GR_ASSERT_SIZE(gr_meshlet_bound, 32);         /* vulkan/mesh/meshlet.hpp:79-84 */
+GR_ASSERT_OFFSET(gr_meshlet_bound, cone_axis_cutoff, 16);
+GR_ASSERT_SIZE(gr_meshlet_draw, 12);          /* vulkan/mesh/meshlet.hpp:72-77 */
+GR_ASSERT_OFFSET(gr_meshlet_draw, vertex_offset, 8);
+GR_ASSERT_SIZE(gr_meshlet_frustum, 224);      /* inc/meshlet_ubos.h:4-14, std140 */
+GR_ASSERT_OFFSET(gr_meshlet_frustum, viewport, 0);
+GR_ASSERT_OFFSET(gr_meshlet_frustum, planes, 16);
+GR_ASSERT_OFFSET(gr_meshlet_frustum, view, 112);
+GR_ASSERT_OFFSET(gr_meshlet_frustum, viewport_scale_bias, 176);
+GR_ASSERT_OFFSET(gr_meshlet_frustum, hiz_resolution, 192);
+GR_ASSERT_OFFSET(gr_meshlet_frustum, winding, 200);
+GR_ASSERT_OFFSET(gr_meshlet_frustum, hiz_min_lod, 204);
+GR_ASSERT_OFFSET(gr_meshlet_frustum, hiz_max_lod, 208);
 GR_ASSERT_SIZE(gr_cacao_constants, 384);      /* ffx_cacao.h:95-154, ffx_cacao_bindings.hlsl:27-87 */
 GR_ASSERT_OFFSET(gr_cacao_constants, EffectRadius, 48);
 GR_ASSERT_OFFSET(gr_cacao_constants, InvSharpness, 96);

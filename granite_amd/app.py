@@ -32,7 +32,7 @@ class Config(C.Structure):
                 ("disable_image_aliasing", C.c_int32), ("depth_hierarchy", C.c_int32),
                 ("resolution_scale", C.c_float), ("resolution_scale_sharpen", C.c_int32), ("fsr_fp32", C.c_int32),
                 ("ambient_occlusion", C.c_int32), ("hdr10", C.c_int32), ("ssr", C.c_int32), ("aa_bench", C.c_int32), ("output_gather_rgba", C.c_int32),
-                ("hdr_packed_float", C.c_int32), ("taa_history_reach_rows", C.c_uint32)]
+                ("hdr_packed_float", C.c_int32), ("taa_history_reach_rows", C.c_uint32), ("volumetric_decals", C.c_int32)]
 
 
 # void (*gra_exchange_fn)(void *user, const char *tag, void *device_ptr, uint64_t chunk_bytes, uint32_t rank_count, void *stream)
@@ -142,7 +142,7 @@ EXPORTED_SYMBOLS = [
     "gra_video_play_begin", "gra_video_play_layout", "gra_video_play_frame", "gra_video_play_read_rgb", "gra_video_play_end",
     "gra_ocean_default_config", "gra_ocean_create", "gra_ocean_update", "gra_ocean_describe", "gra_ocean_read", "gra_ocean_distribution",
     "gra_ocean_parameters", "gra_ocean_destroy", "gra_ocean_set_camera", "gra_ocean_draw_info", "gra_ocean_mesh_describe", "gra_ocean_mesh_read",
-    "gra_meshlet_describe", "gra_meshlet_decode",
+    "gra_meshlet_describe", "gra_meshlet_decode", "gra_set_decal_texture", "gra_set_decals", "gra_get_decal_state",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -166,6 +166,9 @@ def load_library() -> C.CDLL:
         "gra_set_render_parameters": (C.c_int, [vp, vp]),
         "gra_get_render_parameters": (C.c_int, [vp, vp]),
         "gra_set_lights": (C.c_int, [vp, vp, C.c_uint32]),
+        "gra_set_decal_texture": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
+        "gra_set_decals": (C.c_int, [vp, vp, C.c_uint32]),
+        "gra_get_decal_state": (C.c_int, [vp, P(C.c_uint32), vp, vp, vp, vp]),
         "gra_upload_gbuffer": (C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
         "gra_render_frames": (C.c_int, [vp, C.c_uint32, C.c_int32]),
         "gra_sync": (C.c_int, [vp]),
@@ -258,12 +261,13 @@ class Application:
                  alias_images: bool = True, depth_hierarchy: int = 0,
                  resolution_scale: float = 1.0, resolution_scale_sharpen: bool = True, fsr_fp16: bool = True,
                  ambient_occlusion=False, hdr10: bool = False, ssr: bool = False, aa_bench: bool = False,
-                 output_gather_rgba: bool = False, rt_fp16: bool = True, taa_history_reach_rows: int = 0):
+                 output_gather_rgba: bool = False, rt_fp16: bool = True, taa_history_reach_rows: int = 0, volumetric_decals: bool = False):
         """taa_history_reach_rows > 0 (row bands + TAA): the history bands exchange boundary rows with their neighbours only; a pixel
         that reaches further makes the next render / sync / read raise.  rt_fp16 = False: viewer_config renderTargetFp16 = false (the reference's default): emissive / HDR-main and the TAA colour
         output are B10G11R11_UFLOAT_PACK32; the emissive upload is then (h, w) uint32 words (oracle.pack_b10g11r11).
         ambient_occlusion: False, True (= AMBIENT_OCCLUSION_UPLOAD: "ssao-output-main" is what upload_ambient_occlusion brought, white
-        before that) or AMBIENT_OCCLUSION_CACAO (computed from depth and normals every frame)."""
+        before that) or AMBIENT_OCCLUSION_CACAO (computed from depth and normals every frame).
+        volumetric_decals: the decals of set_decals are binned by the clusterer and applied to "albedo" by the G-buffer pass every frame."""
         self.lib = load_library()
         cfg = Config()
         cfg.device, cfg.width, cfg.height = device, width, height
@@ -287,6 +291,7 @@ class Application:
         cfg.output_gather_rgba = int(output_gather_rgba)
         cfg.hdr_packed_float = int(not rt_fp16)
         cfg.taa_history_reach_rows = int(taa_history_reach_rows)
+        cfg.volumetric_decals = int(volumetric_decals)
         if ssr:
             install_ssr_tables()
         self._exchange_ref = None
@@ -341,6 +346,27 @@ class Application:
     def set_lights(self, descs: np.ndarray):
         d = np.ascontiguousarray(descs, synth.LIGHT_DESC_DTYPE)
         self._check(self.lib.gra_set_lights(self.handle, d.ctypes.data if len(d) else None, len(d)))
+
+    def set_decal_texture(self, index: int, texture: dict):
+        """One decal texture (needs volumetric_decals): a dict of width, height, num_levels, format (capi.FORMAT_R8G8B8A8_SRGB or _UNORM) and
+        texels, the uint32 RGBA8 texels of every level, one level after another (synth.make_decal_texture)."""
+        texels = np.ascontiguousarray(texture["texels"], np.uint32)
+        self._check(self.lib.gra_set_decal_texture(self.handle, index, texture["width"], texture["height"], texture["num_levels"], texture["format"], texels.ctypes.data))
+
+    def set_decals(self, descs: np.ndarray):
+        """The scene's decals: synth.DECAL_DESC_DTYPE records, each the mat_affine rows of a unit box's world transform and a texture index."""
+        d = np.ascontiguousarray(descs, synth.DECAL_DESC_DTYPE)
+        self._check(self.lib.gra_set_decals(self.handle, d.ctypes.data if len(d) else None, len(d)))
+
+    def get_decal_state(self) -> dict:
+        """CPU-side decal state of the last frame's refresh, in sorted order: order, world_to_texture (n, 12), mvps (n, 16), ranges (n, 2)."""
+        count = C.c_uint32()
+        self._check(self.lib.gra_get_decal_state(self.handle, C.byref(count), None, None, None, None))
+        n = count.value
+        out = {"order": np.zeros(n, np.uint32), "world_to_texture": np.zeros((n, 12), np.float32), "mvps": np.zeros((n, 16), np.float32),
+               "ranges": np.zeros((n, 2), np.uint32)}
+        self._check(self.lib.gra_get_decal_state(self.handle, C.byref(count), *[out[k].ctypes.data for k in ("order", "world_to_texture", "mvps", "ranges")]))
+        return out
 
     def upload_gbuffer(self, gbuf: dict, motion_vectors=None):
         keep = [np.ascontiguousarray(gbuf[k]) if k in gbuf and gbuf[k] is not None else None

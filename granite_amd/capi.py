@@ -461,6 +461,21 @@ class PushSpotTransform(C.Structure):
 assert C.sizeof(PushSpotTransform) == 100
 
 
+class DecalTexture(C.Structure):
+    """gr_decal_texture: an RGBA8 mip chain in device memory, levels tightly packed one after another."""
+    _fields_ = [("levels", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("num_levels", C.c_uint32), ("format", C.c_uint32)]
+
+
+class DecalApplyArgs(C.Structure):
+    """gr_decal_apply_args."""
+    _fields_ = [("albedo", Image), ("depth", Image), ("inv_view_projection", C.c_float * 16), ("cluster", ClusterParams), ("transforms", C.c_void_p),
+                ("bitmask_decal", C.c_void_p), ("range_decal", C.c_void_p), ("textures", C.c_void_p), ("num_textures", C.c_uint32), ("pad0", C.c_uint32)]
+
+
+assert C.sizeof(DecalTexture) == 24 and C.sizeof(DecalApplyArgs) == 328
+MAX_DECALS_BINDLESS = 4096
+
+
 class PushClusterSetup(C.Structure):
     _fields_ = [("view", C.c_float * 16), ("num_lights", C.c_uint32)]
 
@@ -678,6 +693,8 @@ def load_library() -> C.CDLL:
         "gr_ocean_cull_blocks": (C.c_int, [vp, vp, P(Image), C.c_uint32, P(OceanBuffer), P(OceanBuffer), P(PushOceanCull), P(C.c_float)]),
         "gr_meshlet_decode": (C.c_int, [vp, vp, P(MeshletDecodeArgs), P(PushMeshletDecode)]),
         "gr_meshlet_cull": (C.c_int, [vp, vp, P(MeshletCullArgs), P(PushMeshletCull)]),
+        "gr_cluster_binning_decal": (C.c_int, [vp, vp, vp, vp, P(ClusterParams)]),
+        "gr_decal_apply": (C.c_int, [vp, vp, P(DecalApplyArgs)]),
         "gr_cacao_reference_settings": (None, [P(CacaoSettings)]),
         "gr_cacao_update_buffer_sizes": (C.c_int, [C.c_uint32, C.c_uint32, P(CacaoBufferSizes)]),
         "gr_cacao_update_constants": (C.c_int, [vp, P(CacaoConstants), P(CacaoSettings), P(CacaoBufferSizes), P(C.c_float), P(C.c_float)]),
@@ -717,7 +734,7 @@ EXPORTED_SYMBOLS = [
     "gr_cube_chain_bytes", "gr_cube_chain_offset", "gr_env_equirect_to_cube", "gr_env_specular", "gr_env_diffuse",
     "gr_fft_describe", "gr_fft_plan_create", "gr_fft_plan_destroy", "gr_fft_plan_iterations", "gr_fft_execute", "gr_fft_execute_iteration",
     "gr_ocean_generate_fft", "gr_ocean_bake_maps", "gr_ocean_mipmap", "gr_ocean_update_lod", "gr_ocean_init_counter_buffer", "gr_ocean_cull_blocks",
-    "gr_meshlet_decode", "gr_meshlet_cull",
+    "gr_meshlet_decode", "gr_meshlet_cull", "gr_cluster_binning_decal", "gr_decal_apply",
     "gr_cacao_reference_settings", "gr_cacao_update_buffer_sizes", "gr_cacao_update_constants", "gr_cacao_workspace_bytes", "gr_cacao_workspace_describe",
     "gr_cacao_prepare_depths", "gr_cacao_prepare_normals", "gr_cacao_generate_base", "gr_cacao_importance_generate",
     "gr_cacao_importance_postprocess_a", "gr_cacao_importance_postprocess_b", "gr_cacao_generate", "gr_cacao_blur", "gr_cacao_apply",

@@ -218,6 +218,35 @@ int gra_set_lights(gra_app *app, const gra_light_desc *lights, uint32_t count)
 	return guarded(app, [&]() { app->app->set_lights(lights, count); });
 }
 
+int gra_set_decal_texture(gra_app *app, uint32_t index, uint32_t width, uint32_t height, uint32_t levels, uint32_t format, const void *texels)
+{
+	return guarded(app, [&]() { app->app->set_decal_texture(index, width, height, levels, format, texels); });
+}
+
+int gra_set_decals(gra_app *app, const gra_decal_desc *decals, uint32_t count)
+{
+	return guarded(app, [&]() { app->app->set_decals(decals, count); });
+}
+
+int gra_get_decal_state(gra_app *app, uint32_t *count, uint32_t *order, float *world_to_texture, float *mvps, uint32_t *ranges)
+{
+	return guarded(app, [&]() {
+		auto &cluster = app->app->get_clusterer();
+		const auto &sorted = cluster.get_decal_order();
+		if (!count)
+			throw std::logic_error("gra_get_decal_state: null count");
+		*count = uint32_t(sorted.size());
+		if (order)
+			memcpy(order, sorted.data(), sorted.size() * sizeof(uint32_t));
+		if (world_to_texture)
+			memcpy(world_to_texture, cluster.get_packed_decal_transforms().data(), sorted.size() * sizeof(mat_affine));
+		if (mvps)
+			memcpy(mvps, cluster.get_packed_decal_mvps().data(), sorted.size() * sizeof(mat4));
+		if (ranges)
+			memcpy(ranges, cluster.get_decal_index_range().data(), sorted.size() * sizeof(uvec2));
+	});
+}
+
 int gra_upload_gbuffer(gra_app *app, const void *emissive, const void *albedo, const void *normal, const void *pbr, const void *depth,
                        const void *mv)
 {

@@ -48,6 +48,8 @@ ImageSpaceApplication::ImageSpaceApplication(const gra_config &config_) : config
 		throw std::logic_error("hdr_packed_float (renderTargetFp16 = false) is not available with ssr / hdr10 / aa_bench: those passes take the lit target as RGBA16F.");
 	if (config.aa_bench && (config.enable_lighting || config.hdr_bloom || config.hdr10 || config.ssr || config.strip_count > 1 || config.depth_hierarchy))
 		throw std::logic_error("aa_bench is a graph of its own: no lighting, bloom, hdr10, SSR, depth hierarchy or row bands.");
+	if (config.volumetric_decals && (!config.enable_lighting || config.aa_bench || config.strip_count > 1))
+		throw std::logic_error("volumetric_decals needs enable_lighting and is not available with aa_bench or row bands (strip_count > 1).");
 	if (config.resolution_scale < 0.0f || config.resolution_scale > 1.0f)
 		throw std::logic_error("resolution_scale must be in (0, 1].");
 	if (config.ambient_occlusion < 0 || config.ambient_occlusion > GRA_AMBIENT_OCCLUSION_CACAO)
@@ -74,6 +76,8 @@ ImageSpaceApplication::ImageSpaceApplication(const gra_config &config_) : config
 	cluster.set_resolution(config.cluster_res[0], config.cluster_res[1], config.cluster_res[2]);
 	cluster.set_base_render_context(&context);
 	cluster.set_scene_lights(&light_list);
+	cluster.set_enable_volumetric_decals(config.volumetric_decals != 0);
+	cluster.set_scene_decals(&decal_list);
 
 	lighting.directional.color = vec3(config.directional_color[0], config.directional_color[1], config.directional_color[2]);
 	lighting.directional.direction = vec3(config.directional_direction[0], config.directional_direction[1], config.directional_direction[2]);
@@ -382,6 +386,89 @@ void ImageSpaceApplication::set_lights(const gra_light_desc *descs, uint32_t cou
 	}
 }
 
+void ImageSpaceApplication::set_decal_texture(uint32_t index, uint32_t width, uint32_t height, uint32_t levels, uint32_t format, const void *texels)
+{
+	if (!config.volumetric_decals)
+		throw std::logic_error("gra_set_decal_texture: this application was created without volumetric_decals.");
+	if (index > decal_textures.size())
+		throw std::logic_error("gra_set_decal_texture: index " + std::to_string(index) + " leaves a gap: " + std::to_string(decal_textures.size()) + " textures are set.");
+	if (!texels || !width || !height || width > 16384 || height > 16384)
+		throw std::logic_error("gra_set_decal_texture: texels and a width and height of 1 .. 16384 are needed.");
+	if (format != VK_FORMAT_R8G8B8A8_SRGB && format != VK_FORMAT_R8G8B8A8_UNORM)
+		throw std::logic_error("gra_set_decal_texture: format must be R8G8B8A8_SRGB (43) or R8G8B8A8_UNORM (37).");
+	uint32_t full_chain = 1;
+	while ((std::max(width, height) >> full_chain) != 0)
+		full_chain++;
+	if (!levels || levels > full_chain)
+		throw std::logic_error("gra_set_decal_texture: levels must be 1 .. " + std::to_string(full_chain) + " for this size.");
+	size_t texel_count = 0;
+	for (uint32_t l = 0; l < levels; l++)
+		texel_count += size_t(std::max(width >> l, 1u)) * std::max(height >> l, 1u);
+	auto &device = get_device();
+	device.wait_idle(); // a frame in flight may still sample the texture this one replaces
+	DecalTexture texture;
+	texture.levels = device.create_buffer(texel_count * 4, VK_BUFFER_USAGE_STORAGE_BUFFER_BIT, "decal-texture-" + std::to_string(index));
+	if (gr_upload(device.get_context(), nullptr, texture.levels->get_device_pointer(), texels, texel_count * 4) < 0 || gr_sync(device.get_context(), nullptr) < 0)
+		throw std::runtime_error(gr_last_error(device.get_context()));
+	texture.width = width;
+	texture.height = height;
+	texture.num_levels = levels;
+	texture.format = format;
+	if (index == decal_textures.size())
+		decal_textures.push_back(std::move(texture));
+	else
+		decal_textures[index] = std::move(texture);
+}
+
+void ImageSpaceApplication::set_decals(const gra_decal_desc *descs, uint32_t count)
+{
+	if (!config.volumetric_decals)
+		throw std::logic_error("gra_set_decals: this application was created without volumetric_decals.");
+	if (count && !descs)
+		throw std::logic_error("gra_set_decals: null decals.");
+	for (uint32_t i = 0; i < count; i++)
+		if (descs[i].texture >= decal_textures.size())
+			throw std::logic_error("gra_set_decals: decal " + std::to_string(i) + " names texture " + std::to_string(descs[i].texture) + ", but only " +
+			                       std::to_string(decal_textures.size()) + " are set (gra_set_decal_texture).");
+	decal_transforms.resize(count);
+	decal_texture_index.resize(count);
+	decal_list.clear();
+	for (uint32_t i = 0; i < count; i++)
+	{
+		for (int r = 0; r < 3; r++)
+			decal_transforms[i][r] = vec4(descs[i].transform[4 * r + 0], descs[i].transform[4 * r + 1], descs[i].transform[4 * r + 2], descs[i].transform[4 * r + 3]);
+		decal_texture_index[i] = descs[i].texture;
+		decal_list.push_back({&decal_transforms[i]});
+	}
+}
+
+// lights/volumetric_decal.h as inc/render_target.h calls it while the G-buffer is written: here on the albedo and depth the pass has just
+// filled.  The texture table is this frame's, in the order the clusterer sorted the decals into (the reference allocates the bindless
+// descriptors per frame in that order, clusterer.cpp:1564-1573), and travels through the staging ring.
+void ImageSpaceApplication::apply_volumetric_decals(HIP::CommandBuffer &cmd, HIP::Image &albedo, HIP::Image &depth)
+{
+	const auto &order = cluster.get_decal_order();
+	if (order.empty())
+		return;
+	decal_table.resize(order.size());
+	for (size_t i = 0; i < order.size(); i++)
+	{
+		const DecalTexture &t = decal_textures[decal_texture_index[order[i]]];
+		decal_table[i] = {t.levels->get_device_pointer(), t.width, t.height, t.num_levels, t.format};
+	}
+	gr_decal_apply_args args = {};
+	args.albedo = albedo.get_view();
+	args.depth = depth.get_view();
+	memcpy(args.inv_view_projection, context.get_render_parameters().inv_view_projection.data(), sizeof(args.inv_view_projection));
+	args.cluster = cluster.get_cluster_parameters_bindless();
+	args.transforms = cluster.get_cluster_transform_buffer()->get_device_pointer();
+	args.bitmask_decal = static_cast<const uint32_t *>(cluster.get_cluster_bitmask_decal_buffer()->get_device_pointer());
+	args.range_decal = static_cast<const uint32_t *>(cluster.get_cluster_range_decal_buffer()->get_device_pointer());
+	args.textures = static_cast<const gr_decal_texture *>(cmd.stage(decal_table.data(), decal_table.size() * sizeof(gr_decal_texture)));
+	args.num_textures = uint32_t(decal_table.size());
+	cmd.check(gr_decal_apply(cmd.get_context(), cmd.get_stream(), &args), "decal_apply");
+}
+
 void ImageSpaceApplication::upload_gbuffer(const void *emissive, const void *albedo, const void *normal, const void *pbr, const void *depth,
                                            const void *mv)
 {
@@ -645,11 +732,16 @@ void ImageSpaceApplication::add_main_pass_deferred(const std::string &tag)
 				cmd.copy_image(target, *src);
 		};
 		fill(g_emissive, src_emissive, config.rmw_emissive != 0);
-		fill(g_albedo, src_albedo, false);
+		// with decals the base colour is rewritten from its source every frame: the apply below modifies it in place
+		fill(g_albedo, src_albedo, config.volumetric_decals != 0);
 		fill(g_normal, src_normal, false);
 		fill(g_pbr, src_pbr, false);
 		fill(g_depth, src_depth, false);
+		if (config.volumetric_decals)
+			apply_volumetric_decals(cmd, graph.get_physical_texture_resource(g_albedo), graph.get_physical_texture_resource(g_depth));
 	});
+	// Scene::add_render_pass_dependencies(graph, gbuffer, GEOMETRY_BIT): the decal masks, ranges and transforms, when decals are on
+	cluster.setup_render_pass_dependencies(graph, gbuffer, RenderPassCreator::GEOMETRY_BIT);
 
 	ssao_output = nullptr;
 	if (config.ambient_occlusion == GRA_AMBIENT_OCCLUSION_CACAO)

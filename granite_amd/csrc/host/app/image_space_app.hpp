@@ -32,6 +32,8 @@ public:
 	~ImageSpaceApplication();
 
 	void set_lights(const gra_light_desc *descs, uint32_t count);
+	void set_decals(const gra_decal_desc *descs, uint32_t count);
+	void set_decal_texture(uint32_t index, uint32_t width, uint32_t height, uint32_t levels, uint32_t format, const void *texels);
 	void upload_gbuffer(const void *emissive, const void *albedo, const void *normal, const void *pbr, const void *depth, const void *mv);
 	void render_frame();
 	void wait_idle()
@@ -149,6 +151,18 @@ private:
 	std::vector<std::unique_ptr<PositionalLight>> light_objects;
 	std::vector<mat_affine> light_transforms;
 	PositionalLightList light_list;
+	// Volumetric decals (config.volumetric_decals): node transforms, the texture each one names, and the textures' mip chains.
+	struct DecalTexture
+	{
+		HIP::BufferHandle levels;
+		uint32_t width = 0, height = 0, num_levels = 0, format = 0;
+	};
+	std::vector<mat_affine> decal_transforms;
+	std::vector<uint32_t> decal_texture_index;
+	VolumetricDecalList decal_list;
+	std::vector<DecalTexture> decal_textures;
+	std::vector<gr_decal_texture> decal_table; // this frame's table, in the clusterer's sorted order
+	void apply_volumetric_decals(HIP::CommandBuffer &cmd, HIP::Image &albedo, HIP::Image &depth);
 	HIP::ImageHandle src_emissive, src_albedo, src_normal, src_pbr, src_depth, src_mv, src_ao;
 	// scene_viewer_application.cpp:881-883: renderTargetFp16 ? R16G16B16A16_SFLOAT : B10G11R11_UFLOAT_PACK32
 	VkFormat hdr_target_format() const { return config.hdr_packed_float ? VK_FORMAT_B10G11R11_UFLOAT_PACK32 : VK_FORMAT_R16G16B16A16_SFLOAT; }

@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <algorithm>
 #include <cstring>
+#include <limits>
 
 namespace Granite
 {
@@ -44,6 +45,14 @@ void LightClusterer::setup_render_pass_dependencies(RenderGraph &, RenderPass &t
 		target.add_storage_read_only_input("cluster-range");
 		target.add_storage_read_only_input("cluster-transforms");
 	}
+	// The reference binds the decal buffers globally and declares nothing (render_context / global bindings); this executor orders passes
+	// by their declared resources, so the pass that applies decals while it writes the G-buffer takes them as inputs.
+	if ((dep_flags & RenderPassCreator::GEOMETRY_BIT) != 0 && enable_volumetric_decals)
+	{
+		target.add_storage_read_only_input("cluster-bitmask-decal");
+		target.add_storage_read_only_input("cluster-range-decal");
+		target.add_storage_read_only_input("cluster-transforms");
+	}
 }
 
 void LightClusterer::setup_render_pass_resources(RenderGraph &graph)
@@ -56,6 +65,15 @@ void LightClusterer::setup_render_pass_resources(RenderGraph &graph)
 	if (!bindless.light_ranges)
 		bindless.light_ranges = graph.get_device().create_buffer(MaxLightsBindless * sizeof(uvec2), VK_BUFFER_USAGE_STORAGE_BUFFER_BIT,
 		                                                         "cluster-light-ranges");
+	if (!enable_volumetric_decals)
+		return;
+	bindless.bitmask_buffer_decal = &graph.get_physical_buffer_resource(graph.get_buffer_resource("cluster-bitmask-decal"));
+	bindless.range_buffer_decal = &graph.get_physical_buffer_resource(graph.get_buffer_resource("cluster-range-decal"));
+	if (!bindless.decal_ranges)
+	{
+		bindless.decal_ranges = graph.get_device().create_buffer(MaxDecalsBindless * sizeof(uvec2), VK_BUFFER_USAGE_STORAGE_BUFFER_BIT, "cluster-decal-ranges");
+		bindless.decal_mvps = graph.get_device().create_buffer(MaxDecalsBindless * sizeof(mat4), VK_BUFFER_USAGE_STORAGE_BUFFER_BIT, "cluster-decal-mvps");
+	}
 }
 
 // ---- per-frame CPU refresh (clusterer.cpp:656-703,781-827,1133-1176; threaded_scene.cpp:141-150) -----------------------
@@ -76,6 +94,13 @@ void LightClusterer::refresh(const RenderContext &context_, TaskComposer &)
 {
 	GRANITE_SCOPED_TIMELINE_EVENT("clusterer-refresh");
 	const RenderParameters &rp = context_.get_render_parameters();
+	refresh_lights(rp);
+	if (enable_volumetric_decals)
+		refresh_decals(rp); // after the lights: both ways of refreshing them write the whole parameter block
+}
+
+void LightClusterer::refresh_lights(const RenderParameters &rp)
+{
 	{
 		std::unique_lock<std::mutex> holder{ahead.lock};
 		wait_for_workers(holder);
@@ -95,6 +120,125 @@ void LightClusterer::refresh(const RenderContext &context_, TaskComposer &)
 	}
 	GRANITE_SCOPED_TIMELINE_EVENT("light-sort-and-pack");
 	sort_and_pack(rp, sort_state, packed);
+}
+
+// ---- decals (clusterer.cpp:1124-1131 sort_decals, :1348-1389 ranges, :1403-1411 mvps; scene.cpp:733-736 world_to_texture) -------------
+static mat4 to_mat4(const mat_affine &m)
+{
+	mat4 r(0.0f);
+	for (int c = 0; c < 4; c++)
+		r[c] = vec4(m[0][c], m[1][c], m[2][c], c == 3 ? 1.0f : 0.0f);
+	return r;
+}
+
+// muglm::inverse(mat4) (math/muglm/muglm.cpp:146-201) in fp32, operation for operation: what scene.cpp:733-736 takes of a decal's world
+// transform.  host/math.cpp's inverse() works in double and differs from it in the last bits; a decal's world_to_texture is the reference's.
+static mat4 inverse_fp32(const mat4 &m)
+{
+	const float c00 = m[2][2] * m[3][3] - m[3][2] * m[2][3], c02 = m[1][2] * m[3][3] - m[3][2] * m[1][3], c03 = m[1][2] * m[2][3] - m[2][2] * m[1][3];
+	const float c04 = m[2][1] * m[3][3] - m[3][1] * m[2][3], c06 = m[1][1] * m[3][3] - m[3][1] * m[1][3], c07 = m[1][1] * m[2][3] - m[2][1] * m[1][3];
+	const float c08 = m[2][1] * m[3][2] - m[3][1] * m[2][2], c10 = m[1][1] * m[3][2] - m[3][1] * m[1][2], c11 = m[1][1] * m[2][2] - m[2][1] * m[1][2];
+	const float c12 = m[2][0] * m[3][3] - m[3][0] * m[2][3], c14 = m[1][0] * m[3][3] - m[3][0] * m[1][3], c15 = m[1][0] * m[2][3] - m[2][0] * m[1][3];
+	const float c16 = m[2][0] * m[3][2] - m[3][0] * m[2][2], c18 = m[1][0] * m[3][2] - m[3][0] * m[1][2], c19 = m[1][0] * m[2][2] - m[2][0] * m[1][2];
+	const float c20 = m[2][0] * m[3][1] - m[3][0] * m[2][1], c22 = m[1][0] * m[3][1] - m[3][0] * m[1][1], c23 = m[1][0] * m[2][1] - m[2][0] * m[1][1];
+	const float fac[6][4] = {{c00, c00, c02, c03}, {c04, c04, c06, c07}, {c08, c08, c10, c11}, {c12, c12, c14, c15}, {c16, c16, c18, c19}, {c20, c20, c22, c23}};
+	float vec[4][4];
+	for (int r = 0; r < 4; r++)
+	{
+		vec[r][0] = m[1][r];
+		vec[r][1] = vec[r][2] = vec[r][3] = m[0][r];
+	}
+	mat4 inv(0.0f);
+	for (int i = 0; i < 4; i++)
+	{
+		const float sign_a = (i & 1) ? -1.0f : 1.0f, sign_b = -sign_a;
+		inv[0][i] = (vec[1][i] * fac[0][i] - vec[2][i] * fac[1][i] + vec[3][i] * fac[2][i]) * sign_a;
+		inv[1][i] = (vec[0][i] * fac[0][i] - vec[2][i] * fac[3][i] + vec[3][i] * fac[4][i]) * sign_b;
+		inv[2][i] = (vec[0][i] * fac[1][i] - vec[1][i] * fac[3][i] + vec[3][i] * fac[5][i]) * sign_a;
+		inv[3][i] = (vec[0][i] * fac[2][i] - vec[1][i] * fac[4][i] + vec[2][i] * fac[5][i]) * sign_b;
+	}
+	const float d0 = m[0][0] * inv[0][0], d1 = m[0][1] * inv[1][0], d2 = m[0][2] * inv[2][0], d3 = m[0][3] * inv[3][0];
+	const float one_over_determinant = 1.0f / ((d0 + d1) + (d2 + d3));
+	for (int c = 0; c < 4; c++)
+		inv[c] = inv[c] * one_over_determinant;
+	return inv;
+}
+
+static vec2 decal_z_range(const RenderParameters &rp, const mat_affine &transform)
+{
+	float lo = std::numeric_limits<float>::infinity();
+	float hi = -lo;
+	for (unsigned i = 0; i < 8; i++)
+	{
+		// AABB::get_corner(i) of VolumetricDecal::get_static_aabb(): bit k picks +0.5 on axis k
+		const vec4 texel(i & 1u ? 0.5f : -0.5f, i & 2u ? 0.5f : -0.5f, i & 4u ? 0.5f : -0.5f, 1.0f);
+		// SIMD::mul(vec4, mat_affine, vec4) is one dpps per row on the reference's x86 path: (x0 y0 + x1 y1) + (x2 y2 + x3 y3)
+		auto row = [&](const vec4 &r) { return (r.x * texel.x + r.y * texel.y) + (r.z * texel.z + r.w * texel.w); };
+		const vec3 world(row(transform[0]), row(transform[1]), row(transform[2]));
+		const float z = dot(world - rp.camera_position, rp.camera_front);
+		lo = std::min(lo, z);
+		hi = std::max(hi, z);
+	}
+	return vec2(lo, hi);
+}
+
+// transform->get_aabb().get_center() of a decal: SIMD::transform_aabb of the unit box (scene.cpp:773) -- per row the translation first, then
+// the three columns in order, each taking the box's high or low end by the sign of its entry -- and minimum + (maximum - minimum) * 0.5.
+// Mathematically the translation; in fp32 not the same number, and the sort is by this one.
+static vec3 decal_aabb_center(const mat_affine &m)
+{
+	float lo[3], hi[3];
+	for (int r = 0; r < 3; r++)
+	{
+		const float row[4] = {m[r].x, m[r].y, m[r].z, m[r].w};
+		hi[r] = lo[r] = row[3];
+		for (int c = 0; c < 3; c++)
+		{
+			const bool positive = row[c] > 0.0f;
+			hi[r] = hi[r] + row[c] * (positive ? 0.5f : -0.5f);
+			lo[r] = lo[r] + row[c] * (positive ? -0.5f : 0.5f);
+		}
+	}
+	return vec3(lo[0] + (hi[0] - lo[0]) * 0.5f, lo[1] + (hi[1] - lo[1]) * 0.5f, lo[2] + (hi[2] - lo[2]) * 0.5f);
+}
+
+void LightClusterer::refresh_decals(const RenderParameters &rp)
+{
+	GRANITE_SCOPED_TIMELINE_EVENT("decal-sort-and-pack");
+	const size_t total = scene_decals ? scene_decals->size() : 0;
+	decals.order.resize(total);
+	decals.keys.resize(total);
+	for (size_t i = 0; i < total; i++)
+	{
+		decals.order[i] = uint32_t(i);
+		decals.keys[i] = dot(rp.camera_front, decal_aabb_center(*(*scene_decals)[i].transform));
+	}
+	std::stable_sort(decals.order.begin(), decals.order.end(), [this](uint32_t a, uint32_t b) { return decals.keys[a] < decals.keys[b]; });
+	const size_t count = std::min(total, size_t(MaxDecalsBindless));
+	decals.order.resize(count);
+
+	auto &p = packed.parameters;
+	p.num_decals = int32_t(count);
+	p.num_decals_32 = (p.num_decals + 31) / 32;
+	p.decals_texture_offset = 0; // the owner's texture table starts at decal 0 (the reference: first descriptor of the frame's allocation, :1564-1573)
+
+	decals.world_to_texture.resize(count);
+	decals.mvps.resize(count);
+	decals.volume_index_range.resize(std::max(count, size_t(1)));
+	if (count == 0)
+		decals.volume_index_range[0] = uvec2(~0u, 0u); // the z-range kernel still runs, so that the range buffer reads "empty"
+	for (size_t i = 0; i < count; i++)
+	{
+		const mat_affine &world = *(*scene_decals)[decals.order[i]].transform;
+		const mat4 world4 = to_mat4(world);
+		const mat4 inv = inverse_fp32(world4);
+		mat_affine w2t;
+		for (int r = 0; r < 3; r++)
+			w2t[r] = vec4(inv[0][r], inv[1][r], inv[2][r], inv[3][r]);
+		decals.world_to_texture[i] = w2t;
+		decals.mvps[i] = rp.view_projection * world4;
+		decals.volume_index_range[i] = compute_uint_range(rp, decal_z_range(rp, world));
+	}
 }
 
 void LightClusterer::sort_and_pack(const RenderParameters &rp, SortState &sort, PackedLights &out) const
@@ -360,20 +504,35 @@ uvec2 LightClusterer::compute_uint_range(const RenderParameters &rp, vec2 range)
 }
 
 // ---- GPU build (clusterer.cpp:1178-1207,1277-1346,1463-1573) ----------------------------------------------------------------
-void LightClusterer::update_bindless_data(HIP::CommandBuffer &cmd)
+// The decals' part of the frame's one upload: world_to_texture rows into the transforms buffer, the mvps and the slice intervals.
+unsigned LightClusterer::decal_updates(HIP::CommandBuffer::BufferUpdate *updates) const
+{
+	if (!enable_volumetric_decals)
+		return 0;
+	const size_t count = decals.world_to_texture.size();
+	updates[0] = {bindless.transforms_buffer, GR_TRANSFORMS_OFFSET_DECALS, count * sizeof(mat_affine), decals.world_to_texture.data()};
+	updates[1] = {bindless.decal_mvps.get(), 0, count * sizeof(mat4), decals.mvps.data()};
+	updates[2] = {bindless.decal_ranges.get(), 0, decals.volume_index_range.size() * sizeof(uvec2), decals.volume_index_range.data()};
+	return 3;
+}
+
+// Returns whether the decals' arrays went along.
+bool LightClusterer::update_bindless_data(HIP::CommandBuffer &cmd)
 {
 	// The reference records three cmd.update_buffer here and a fourth (the per-light slice intervals) before the z-range
 	// dispatch (clusterer.cpp:1178-1207,1302).  All four are staged now and uploaded by ONE kernel: nothing on the GPU
 	// reads any of them before this point, and a copy-engine transfer in the middle of the pass costs more than the pass.
 	uint32_t count = uint32_t(packed.parameters.num_lights);
 	auto &ranges = packed.volume_index_range;
-	const HIP::CommandBuffer::BufferUpdate updates[] = {
+	HIP::CommandBuffer::BufferUpdate updates[7] = {
 		{bindless.transforms_buffer, GR_TRANSFORMS_OFFSET_LIGHTS, count * sizeof(PositionalFragmentInfo), packed.lights.data()},
 		{bindless.transforms_buffer, GR_TRANSFORMS_OFFSET_MODEL, count * sizeof(mat_affine), packed.model.data()},
 		{bindless.transforms_buffer, GR_TRANSFORMS_OFFSET_TYPE_MASK, packed.parameters.num_lights_32 * sizeof(uint32_t), packed.type_mask},
 		{bindless.light_ranges.get(), 0, ranges.size() * sizeof(uvec2), ranges.data()},
 	};
-	cmd.update_buffers(updates, 4);
+	const unsigned extra = decal_updates(updates + 4);
+	cmd.update_buffers(updates, 4 + extra);
+	return extra != 0;
 }
 
 void LightClusterer::update_bindless_mask_buffer_gpu(HIP::CommandBuffer &cmd)
@@ -432,11 +591,42 @@ void LightClusterer::update_bindless_range_buffer_gpu(HIP::CommandBuffer &cmd)
 
 void LightClusterer::build_cluster_bindless_gpu(HIP::CommandBuffer &cmd)
 {
+	decals_uploaded = false;
+	build_cluster_lights_gpu(cmd);
+	if (enable_volumetric_decals)
+		build_cluster_decals_gpu(cmd, decals_uploaded);
+}
+
+// clusterer.cpp:1371-1461: the decals' masks and ranges, after the lights' on the same stream.
+void LightClusterer::build_cluster_decals_gpu(HIP::CommandBuffer &cmd, bool uploaded)
+{
+	if (!uploaded) // the lights' arrays were read from the staging ring by gr_cluster_front: the decals' are this frame's one upload
+	{
+		HIP::CommandBuffer::BufferUpdate updates[3];
+		cmd.update_buffers(updates, decal_updates(updates));
+	}
+	cmd.barrier(VK_PIPELINE_STAGE_2_COPY_BIT, VK_ACCESS_TRANSFER_WRITE_BIT, VK_PIPELINE_STAGE_COMPUTE_SHADER_BIT, VK_ACCESS_2_SHADER_STORAGE_READ_BIT);
+	if (packed.parameters.num_decals > 0)
+		cmd.check(gr_cluster_binning_decal(cmd.get_context(), cmd.get_stream(), static_cast<const float *>(bindless.decal_mvps->get_device_pointer()),
+		                                   static_cast<uint32_t *>(bindless.bitmask_buffer_decal->get_device_pointer()), &packed.parameters),
+		          "cluster_binning_decal");
+	// Runs without decals too, over the single (~0u, 0) entry: the range buffer must read "empty" (clusterer.cpp:1384-1388).
+	gr_push_z_range push = {};
+	push.num_volumes = uint32_t(decals.volume_index_range.size());
+	push.num_volumes_128 = (push.num_volumes + 127) / 128;
+	push.num_ranges = resolution_z;
+	cmd.check(gr_cluster_z_range(cmd.get_context(), cmd.get_stream(), static_cast<const uint32_t *>(bindless.decal_ranges->get_device_pointer()),
+	                             static_cast<uint32_t *>(bindless.range_buffer_decal->get_device_pointer()), &push),
+	          "cluster_z_range (decals)");
+}
+
+void LightClusterer::build_cluster_lights_gpu(HIP::CommandBuffer &cmd)
+{
 	uint32_t local_count = uint32_t(packed.parameters.num_lights);
 	static const bool separate = getenv("GRANITE_CLUSTER_SEPARATE_LAUNCHES") != nullptr; // A/B: the reference's dispatch-by-dispatch form
 	if (separate || local_count == 0 || packed.volume_index_range.empty())
 	{
-		update_bindless_data(cmd); // reads this frame's slot of the pinned staging ring: launched directly
+		decals_uploaded = update_bindless_data(cmd); // reads this frame's slot of the pinned staging ring: launched directly
 		cmd.barrier(VK_PIPELINE_STAGE_2_COPY_BIT, VK_ACCESS_TRANSFER_WRITE_BIT, VK_PIPELINE_STAGE_COMPUTE_SHADER_BIT, VK_ACCESS_2_SHADER_STORAGE_READ_BIT);
 		update_bindless_mask_buffer_gpu(cmd);
 		update_bindless_range_buffer_gpu(cmd);
@@ -456,7 +646,7 @@ void LightClusterer::build_cluster_bindless_gpu(HIP::CommandBuffer &cmd)
 	const bool read_staged = local_count <= read_staged_below;
 	if (!read_staged)
 	{
-		update_bindless_data(cmd);
+		decals_uploaded = update_bindless_data(cmd);
 		cmd.barrier(VK_PIPELINE_STAGE_2_COPY_BIT, VK_ACCESS_TRANSFER_WRITE_BIT, VK_PIPELINE_STAGE_COMPUTE_SHADER_BIT, VK_ACCESS_2_SHADER_STORAGE_READ_BIT);
 	}
 	if ((resolution_z & 63) != 0)

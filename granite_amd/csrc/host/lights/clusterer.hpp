@@ -1,7 +1,8 @@
 // Follows MIT-licensed work (Granite, (c) 2017-2026 Hans-Kristian Arntzen; FidelityFX parts (c) 2021 Advanced Micro Devices, Inc.): see
 // THIRD_PARTY_NOTICES.md at the repository root.
 // LightClusterer — the bindless clustered-light path of renderer/lights/clusterer.{hpp,cpp} on the HIP executor.
-// Shadows, decals, volumetric diffuse / fog and the legacy (non-bindless) clusterer need scene geometry and are out of
+// Volumetric decals are the clusterer's second client (set_enable_volumetric_decals): they need no scene geometry, a decal is a unit box
+// under a transform.  Shadows, volumetric diffuse / fog and the legacy (non-bindless) clusterer need scene geometry and are out of
 // scope; the class keeps the RenderPassCreator / PerFrameRefreshable surface used by the hot path.
 #pragma once
 #include <atomic>
@@ -50,10 +51,18 @@ struct PositionalLightInfo
 };
 using PositionalLightList = std::vector<PositionalLightInfo>;
 
+// One visible volumetric decal (renderer/scene.hpp VolumetricDecalInfo {decal, transform}): the world transform of its unit box.  Which
+// texture it samples is the owner's business: the clusterer hands back the order it sorted the list into (get_decal_order).
+struct VolumetricDecalInfo
+{
+	const mat_affine *transform;
+};
+using VolumetricDecalList = std::vector<VolumetricDecalInfo>;
+
 class LightClusterer : public RenderPassCreator, public PerFrameRefreshable
 {
 public:
-	enum { MaxLightsBindless = GR_MAX_LIGHTS_BINDLESS, MaxLightsGlobal = 32 };
+	enum { MaxLightsBindless = GR_MAX_LIGHTS_BINDLESS, MaxLightsGlobal = 32, MaxDecalsBindless = GR_MAX_DECALS_BINDLESS };
 
 	void set_resolution(unsigned x, unsigned y, unsigned z)
 	{
@@ -67,6 +76,12 @@ public:
 		invalidate_prefetch();
 		scene_lights = lights_;
 	}
+	// clusterer.hpp:84-85,107.  Off: nothing of the decal path is declared, packed, uploaded or launched.
+	void set_enable_volumetric_decals(bool enable) { enable_volumetric_decals = enable; }
+	bool clusterer_has_volumetric_decals() const { return enable_volumetric_decals; }
+	// Stand-in for the scene's decal list, as set_scene_lights is for its lights.  Sorted and packed by refresh() on the submitting
+	// thread; the prefetch workers never see it.
+	void set_scene_decals(const VolumetricDecalList *decals_) { scene_decals = decals_; }
 	~LightClusterer() override;
 
 	// The reference runs its per-frame refreshes as TaskComposer tasks on worker threads, beside command recording
@@ -90,6 +105,8 @@ public:
 	const HIP::Buffer *get_cluster_transform_buffer() const { return bindless.transforms_buffer; }
 	const HIP::Buffer *get_cluster_bitmask_buffer() const { return bindless.bitmask_buffer; }
 	const HIP::Buffer *get_cluster_range_buffer() const { return bindless.range_buffer; }
+	const HIP::Buffer *get_cluster_bitmask_decal_buffer() const { return bindless.bitmask_buffer_decal; }
+	const HIP::Buffer *get_cluster_range_decal_buffer() const { return bindless.range_buffer_decal; }
 	bool clusterer_has_volumetric_diffuse() const { return false; }
 
 	// Introspection for the parity tests: CPU-side packed state of the last refresh.
@@ -97,6 +114,11 @@ public:
 	const std::vector<mat_affine> &get_packed_models() const { return packed.model; }
 	const uint32_t *get_type_mask() const { return packed.type_mask; }
 	const std::vector<uvec2> &get_volume_index_range() const { return packed.volume_index_range; }
+	// Decals of the last refresh, in sorted order: entry i is scene decal get_decal_order()[i].
+	const std::vector<uint32_t> &get_decal_order() const { return decals.order; }
+	const std::vector<mat_affine> &get_packed_decal_transforms() const { return decals.world_to_texture; }
+	const std::vector<mat4> &get_packed_decal_mvps() const { return decals.mvps; }
+	const std::vector<uvec2> &get_decal_index_range() const { return decals.volume_index_range; }
 
 private:
 	const RenderContext *context = nullptr;
@@ -120,6 +142,21 @@ private:
 	PackedLights packed;
 	SortState sort_state;
 
+	// Decals (clusterer.cpp:1124-1131,1348-1389,1403-1411): sorted front to back, clipped to MaxDecalsBindless.
+	bool enable_volumetric_decals = false;
+	const VolumetricDecalList *scene_decals = nullptr;
+	struct
+	{
+		std::vector<uint32_t> order;
+		std::vector<float> keys;
+		std::vector<mat_affine> world_to_texture; // BindlessDecalTransform
+		std::vector<mat4> mvps;                   // view_projection x world
+		std::vector<uvec2> volume_index_range;    // at least one entry: (~0u, 0) without decals
+	} decals;
+	void refresh_decals(const RenderParameters &rp);
+	void refresh_lights(const RenderParameters &rp);
+	bool decals_uploaded = false; // this frame's decal arrays went along with the lights' upload
+
 	struct
 	{
 		const HIP::Buffer *bitmask_buffer = nullptr;
@@ -128,6 +165,10 @@ private:
 		const HIP::Buffer *transformed_spots = nullptr;
 		const HIP::Buffer *cull_data = nullptr;
 		HIP::BufferHandle light_ranges; // uvec2[MaxLightsBindless] upload target for the z-range kernel
+		const HIP::Buffer *bitmask_buffer_decal = nullptr;
+		const HIP::Buffer *range_buffer_decal = nullptr;
+		HIP::BufferHandle decal_ranges; // uvec2[MaxDecalsBindless]
+		HIP::BufferHandle decal_mvps;   // mat4[MaxDecalsBindless]: the reference creates a linked host buffer per frame (clusterer.cpp:1400-1412)
 	} bindless;
 
 	// One-frame-ahead refresh on helper threads: thread 0 sorts, then all of them pack chunks of PackChunk lights.
@@ -160,7 +201,10 @@ private:
 	uvec2 compute_uint_range(const RenderParameters &rp, vec2 range) const;
 	bool bindless_light_is_point(unsigned index) const { return (packed.type_mask[index >> 5] & (1u << (index & 31))) != 0; }
 	void build_cluster_bindless_gpu(HIP::CommandBuffer &cmd);
-	void update_bindless_data(HIP::CommandBuffer &cmd);
+	void build_cluster_lights_gpu(HIP::CommandBuffer &cmd);
+	void build_cluster_decals_gpu(HIP::CommandBuffer &cmd, bool uploaded);
+	unsigned decal_updates(HIP::CommandBuffer::BufferUpdate *updates) const;
+	bool update_bindless_data(HIP::CommandBuffer &cmd);
 	void update_bindless_mask_buffer_gpu(HIP::CommandBuffer &cmd);
 	void update_bindless_range_buffer_gpu(HIP::CommandBuffer &cmd);
 };

@@ -213,6 +213,48 @@ def make_lights(cam: Camera, count: int, spot_fraction: float = 0.25, z_lo: floa
     return descs
 
 
+DECAL_DESC_DTYPE = np.dtype([("transform", "<f4", 12), ("texture", "<u4")])  # gra_decal_desc
+
+
+def make_decal_texture(width: int, height: int, levels: int, srgb: bool = True, seed: int = SEED) -> dict:
+    """A decal texture for Application.set_decal_texture: random RGBA8 texels with partial alpha and a box-filtered mip chain, level i being
+    max(1, w >> i) x max(1, h >> i), all levels in one uint32 array."""
+    r = _rng(5, seed + 131 * width + 17 * height)
+    level = r.integers(0, 256, (height, width, 4)).astype(np.float64)
+    level[..., 3] = r.integers(64, 231, (height, width))
+    chain = []
+    for _ in range(levels):
+        c = np.clip(np.rint(level), 0, 255).astype(np.uint32)
+        chain.append((c[..., 0] | (c[..., 1] << 8) | (c[..., 2] << 16) | (c[..., 3] << 24)).reshape(-1))
+        h, w = level.shape[:2]
+        fh, fw = min(2, h), min(2, w)
+        level = level[:max(1, h >> 1) * fh, :max(1, w >> 1) * fw].reshape(max(1, h >> 1), fh, max(1, w >> 1), fw, 4).mean(axis=(1, 3))
+    return {"width": width, "height": height, "num_levels": levels, "format": 43 if srgb else 37, "texels": np.concatenate(chain).astype(np.uint32)}
+
+
+def make_decals(cam: Camera, count: int, num_textures: int, seed: int = SEED, size=(0.8, 2.5)) -> np.ndarray:
+    """Deterministic decals on the default synthetic surface (surface_view_z): unit boxes scaled to `size` world units, turned at random and
+    centred on the surface under a random screen position, so that each one reaches some pixels.  Returns DECAL_DESC_DTYPE records."""
+    r = _rng(6, seed)
+    out = np.zeros(count, DECAL_DESC_DTYPE)
+    for i in range(count):
+        u, v = r.uniform(0.05, 0.95, 2)
+        d = float(surface_view_z(u, v))
+        clip = np.array([2.0 * u - 1.0, 2.0 * v - 1.0, float(cam.depth_from_view_distance(np.float64(d))), 1.0])
+        p = cam.invVP @ clip
+        axis = r.normal(size=3)
+        axis /= np.linalg.norm(axis)
+        angle = r.uniform(0.0, math.pi)
+        k = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+        rot = np.eye(3) + math.sin(angle) * k + (1.0 - math.cos(angle)) * (k @ k)
+        m = np.zeros((3, 4))
+        m[:, :3] = rot @ np.diag(r.uniform(size[0], size[1], 3) * (1.0, 1.0, 3.0))
+        m[:, 3] = p[:3] / p[3]
+        out["transform"][i] = m.astype(np.float32).reshape(12)
+        out["texture"][i] = i % max(num_textures, 1)
+    return out
+
+
 def make_motion_vectors(width: int, height: int) -> np.ndarray:
     """Config 4: MV RG16F = 0 (camera reprojection branch) with a 10 % region of constant (2 px, 1 px)/resolution."""
     mv = np.zeros((height, width, 2), np.float32)

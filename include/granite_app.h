@@ -112,7 +112,19 @@ typedef struct gra_config
 	 * and the next gra_render_frame / gra_sync / read-back fails with an error that says so.  0 = whole bands are all-gathered
 	 * (any motion).  Every rank must be given the same value. */
 	uint32_t taa_history_reach_rows;
+	/* Volumetric decals (lights/volumetric_decal.h): the clusterer also bins the decals of gra_set_decals, and the G-buffer pass applies them
+	 * to base colour, from the world position alone, before lighting reads it.  The pass then rewrites "albedo" from the uploaded image every
+	 * frame, so decals do not accumulate.  Needs enable_lighting; not with strip_count > 1 or aa_bench.  0 = off: no graph, launch or byte
+	 * changes. */
+	int32_t volumetric_decals;
 } gra_config;
+
+/* One volumetric decal: the world transform of its unit box and the texture (gra_set_decal_texture) it projects along its z axis. */
+typedef struct gra_decal_desc
+{
+	float transform[12]; /* mat_affine rows */
+	uint32_t texture;
+} gra_decal_desc;
 
 /* Scene-level light description (one PositionalLight + its node transform). */
 typedef struct gra_light_desc
@@ -146,6 +158,16 @@ int gra_get_render_parameters(gra_app *app, float *params104);
 int gra_get_render_size(gra_app *app, uint32_t *width, uint32_t *height);
 
 int gra_set_lights(gra_app *app, const gra_light_desc *lights, uint32_t count);
+
+/* Decals (config.volumetric_decals).  A texture is width x height RGBA8 texels (format: VK_FORMAT_R8G8B8A8_SRGB 43 or _UNORM 37) with
+ * `levels` mip levels, level i = max(1, width >> i) x max(1, height >> i), tightly packed one after another in `texels` (host pointer).
+ * Indices are dense: index may be an existing one (replaced) or the next free one.  gra_set_decals replaces the list; a decal that names a
+ * texture that has not been set is refused, the message says which.  Beyond 4096 decals the farthest are dropped. */
+int gra_set_decal_texture(gra_app *app, uint32_t index, uint32_t width, uint32_t height, uint32_t levels, uint32_t format, const void *texels);
+int gra_set_decals(gra_app *app, const gra_decal_desc *decals, uint32_t count);
+/* CPU-side state of the last refresh, decals in sorted order: order[i] = index into the gra_set_decals list, 12 floats of world_to_texture,
+ * 16 of the mvp and the two slice-interval words per decal.  Any pointer may be NULL; *count is always written. */
+int gra_get_decal_state(gra_app *app, uint32_t *count, uint32_t *order, float *world_to_texture, float *mvps, uint32_t *ranges);
 
 /* Synthetic G-buffer (host pointers, tightly packed rows, width x height of the config).  Any pointer may be NULL to
  * leave that attachment unchanged.  Graphs without lighting take `emissive` as the HDR input. */

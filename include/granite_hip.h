@@ -1239,6 +1239,50 @@ typedef struct gr_meshlet_cull_args /* every pointer is a device pointer; counts
  * draw_indirect_offset outside output_dwords. */
 int gr_meshlet_cull(gr_ctx *ctx, gr_stream stream, const gr_meshlet_cull_args *args, const gr_push_meshlet_cull *push);
 
+/* ---- volumetric decals: the clusterer's second client (renderer/lights/clusterer.cpp:1348-1461,1564-1573) ----------------------------------
+ * A decal is the unit box under a transform, with a texture; it acts on base colour from the world position alone.  Arithmetic, the
+ * sampler and LOD model: granite_amd/csrc/decal_core.hpp, DESIGN.md 7.14. */
+#define GR_MAX_DECALS_BINDLESS 4096 /* CLUSTERER_MAX_DECALS */
+
+/* clusterer_bindless_binning_decal.comp in its SUBGROUPS form at 64 lanes (8 x 8 cell tile per wave, decals in lanes 0-31 of a chunk).
+ * mvps: column-major mat4[num_decals] on the device (view_projection x world).  bitmask[(y * res_x + x) * num_decals_32 + chunk]; no other
+ * word is written.  num_decals 0 returns GR_OK without a launch.  Refused with GR_ERR_INVALID_ARGUMENT: null pointers, a resolution that
+ * is not a positive multiple of 8, num_decals outside 0 .. GR_MAX_DECALS_BINDLESS, num_decals_32 that is not ceil(num_decals / 32).
+ * The decal z ranges are gr_cluster_z_range over a second pair of buffers. */
+int gr_cluster_binning_decal(gr_ctx *ctx, gr_stream stream, const float *mvps, uint32_t *bitmask, const gr_cluster_params *params);
+
+/* One decal texture: R8G8B8A8_SRGB or R8G8B8A8_UNORM; level i is max(1, width >> i) x max(1, height >> i) texels, levels tightly packed
+ * one after another from `levels` (device memory, 4-byte aligned).  The records live in device memory, so gr_decal_apply cannot look at them:
+ * it is the caller's contract that every record a decal can name has width and height of at least 1, num_levels of 1 .. the full chain's
+ * count (floor(log2(max(width, height))) + 1), one of the two formats, and `levels` covering all of its levels.  A record that breaks it
+ * makes the kernel read outside the texture (gra_set_decal_texture refuses such a texture before it reaches the device). */
+typedef struct gr_decal_texture
+{
+	const void *levels;
+	uint32_t width, height, num_levels, format;
+} gr_decal_texture;
+
+/* lights/volumetric_decal.h (apply_volumetric_decals) on a G-buffer already written: per pixel with depth != 0, the decals of the pixel's
+ * cluster cell and z slice in ascending index order, rgb = mix(rgb, decal.rgb, decal.a).  Alpha is never changed; a pixel no decal reaches
+ * is not written.  Decal i samples textures[cluster.decals_texture_offset + i]; an index outside [0, num_textures) skips the decal.
+ * cluster.num_decals 0 returns GR_OK without a launch.  Refused with GR_ERR_INVALID_ARGUMENT before anything is launched: an image that
+ * breaks the gr_image contract, albedo and depth of different sizes, a null transforms, bitmask_decal, range_decal or textures, a cluster
+ * block whose resolution, num_decals, num_decals_32 or z_max_index is out of range. */
+typedef struct gr_decal_apply_args
+{
+	gr_image albedo;               /* R8G8B8A8_SRGB, read-modify-write */
+	gr_image depth;                /* D32_SFLOAT, reverse-Z: 0 is the far plane */
+	float inv_view_projection[16]; /* column-major */
+	gr_cluster_params cluster;     /* UBO, by value */
+	const void *transforms;        /* GR_TRANSFORMS_SIZE bytes; world_to_texture rows at GR_TRANSFORMS_OFFSET_DECALS */
+	const uint32_t *bitmask_decal; /* gr_cluster_binning_decal's output */
+	const uint32_t *range_decal;   /* uvec2[z_max_index + 1] */
+	const gr_decal_texture *textures; /* device array */
+	uint32_t num_textures;
+	uint32_t pad0;
+} gr_decal_apply_args;
+int gr_decal_apply(gr_ctx *ctx, gr_stream stream, const gr_decal_apply_args *args);
+
 /* ---- SSAO: FidelityFX CACAO as the reference runs it (renderer/post/ssao.cpp, renderer/post/ffx-cacao) -----------------------------------
  * One configuration and its non-adaptive sibling: native resolution, normals from the G-buffer, quality HIGHEST (adaptive, shader level 3)
  * or HIGH (shader level 2), 0 .. 8 blur passes.  One entry point per shader of FFX_CACAO_GraniteDraw (ffx_cacao_impl.cpp:767-1026); the
@@ -1544,6 +1588,18 @@ GR_ASSERT_SIZE(gr_cacao_settings, 68);        /* ffx_cacao.h:52-70 */
 GR_ASSERT_OFFSET(gr_cacao_settings, quality_level, 28);
 GR_ASSERT_OFFSET(gr_cacao_settings, generate_normals, 56);
 GR_ASSERT_SIZE(gr_cacao_buffer_sizes, 64);    /* ffx_cacao.h:159-183 */
+GR_ASSERT_SIZE(gr_decal_texture, 24);
+GR_ASSERT_OFFSET(gr_decal_texture, width, 8);
+GR_ASSERT_OFFSET(gr_decal_texture, format, 20);
+GR_ASSERT_SIZE(gr_decal_apply_args, 328);
+GR_ASSERT_OFFSET(gr_decal_apply_args, depth, 24);
+GR_ASSERT_OFFSET(gr_decal_apply_args, inv_view_projection, 48);
+GR_ASSERT_OFFSET(gr_decal_apply_args, cluster, 112);
+GR_ASSERT_OFFSET(gr_decal_apply_args, transforms, 288);
+GR_ASSERT_OFFSET(gr_decal_apply_args, bitmask_decal, 296);
+GR_ASSERT_OFFSET(gr_decal_apply_args, range_decal, 304);
+GR_ASSERT_OFFSET(gr_decal_apply_args, textures, 312);
+GR_ASSERT_OFFSET(gr_decal_apply_args, num_textures, 320);
 GR_STATIC_ASSERT(GR_TRANSFORMS_OFFSET_SHADOW ==GR_MAX_LIGHTS_BINDLESS * 48u, "ClustererBindlessTransforms: lights[4096] of 48 B");
 GR_STATIC_ASSERT(GR_TRANSFORMS_OFFSET_MODEL + GR_MAX_LIGHTS_BINDLESS * 48u == GR_TRANSFORMS_OFFSET_TYPE_MASK, "ClustererBindlessTransforms: model[4096] of 48 B");
 GR_STATIC_ASSERT(GR_TRANSFORMS_OFFSET_TYPE_MASK + GR_MAX_LIGHTS_BINDLESS / 8u == GR_TRANSFORMS_OFFSET_DECALS, "ClustererBindlessTransforms: type_mask[128]");

@@ -1,0 +1,95 @@
+"""CPU: granite_amd/csrc/decal_core.hpp built for the host (tests/cpp/decal_core_host.cpp, a stand-alone program, -ffp-contract=off, walking
+tiles as the kernels of decal.hip do) and held to the reference's decal shaders executed on the CPU (tests/golden/decal_shader_v1.npz):
+binning masks word for word on every case, every word written exactly once; the apply as float colour before the 8-bit store, bit for bit.
+The program is built plainly and with -fsanitize=address,undefined and run directly (its own main; nothing is preloaded).  The same cases
+run on the device in tests/test_gpu_decals.py."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import decal_cases as dc
+import decal_ref as ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SOURCE = os.path.join(ROOT, "tests", "cpp", "decal_core_host.cpp")
+GOLDEN = dc.load_golden()
+
+
+def build(tmp, name, flags):
+    exe = tmp / name
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-ffp-contract=off", *flags, "-o", str(exe), SOURCE])
+    return str(exe)
+
+
+@pytest.fixture(scope="module")
+def plain(tmp_path_factory):
+    return build(tmp_path_factory.mktemp("decal_core"), "decal_core_host", [])
+
+
+@pytest.fixture(scope="module")
+def sanitized(tmp_path_factory):
+    return build(tmp_path_factory.mktemp("decal_core_san"), "decal_core_host_san", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+
+
+def counted(a):
+    a = np.ascontiguousarray(a).reshape(-1)
+    return [np.uint32(len(a)), a]
+
+
+def binning_bytes(case):
+    parts = [np.uint32(0), np.frombuffer(case["prm"].tobytes(), np.uint32), *counted(np.asarray(case["mvps"], np.float32))]
+    return b"".join(np.ascontiguousarray(p).tobytes() for p in parts)
+
+
+def apply_bytes(case):
+    parts = [np.uint32(1), np.frombuffer(case["prm"].tobytes(), np.uint32), np.uint32(case["width"]), np.uint32(case["height"]),
+             np.asarray(case["inv_view_projection"], np.float32), *counted(np.asarray(case["decal_rows"], np.float32)), *counted(case["bitmask_decal"]),
+             *counted(case["range_decal"]), np.asarray(case["albedo"], np.uint32), np.asarray(case["depth"], np.float32), ref.srgb_decode_table(),
+             np.uint32(len(case["textures"]))]
+    for t in case["textures"]:
+        parts += [np.uint32([t[f] for f in dc.TEXTURE_FIELDS]), *counted(np.asarray(t["texels"], np.uint32))]
+    return b"".join(np.ascontiguousarray(p).tobytes() for p in parts)
+
+
+def run(exe, tmp_path, data):
+    case = tmp_path / "case.bin"
+    case.write_bytes(data)
+    return subprocess.run([exe, str(case)], capture_output=True, check=True).stdout
+
+
+def check_binning(exe, tmp_path, name):
+    case = dc.golden_case(GOLDEN, name)
+    words = np.frombuffer(run(exe, tmp_path, binning_bytes(case)), np.uint32)
+    assert np.array_equal(words, GOLDEN[f"{name}/bitmask"]), f"{name}: host build against the executed shader"
+
+
+def check_apply(exe, tmp_path, name):
+    case = dc.golden_case(GOLDEN, name)
+    raw = run(exe, tmp_path, apply_bytes(case))
+    pixels = case["width"] * case["height"]
+    colour = np.frombuffer(raw[:pixels * 12], np.uint32).reshape(case["height"], case["width"], 3)
+    touched = np.frombuffer(raw[pixels * 12:], np.uint32).reshape(case["height"], case["width"]) != 0
+    assert np.array_equal(touched, GOLDEN[f"{name}/touched"]), name
+    assert np.array_equal(colour, GOLDEN[f"{name}/colour"].view(np.uint32)), f"{name}: host build against the executed shader"
+
+
+@pytest.mark.parametrize("name", dc.BINNING_CASES + list(dc.APPLY_CASES))
+def test_binning_against_the_golden(plain, tmp_path, name):
+    check_binning(plain, tmp_path, name)
+
+
+@pytest.mark.parametrize("name", dc.APPLY_CASES)
+def test_apply_against_the_golden(plain, tmp_path, name):
+    check_apply(plain, tmp_path, name)
+
+
+@pytest.mark.parametrize("name", ["cell_border/8x8", "near_straddle/32x16", "count_33/24x40", "count_70/24x40"])
+def test_binning_under_address_and_undefined_behaviour_sanitizers(sanitized, tmp_path, name):
+    check_binning(sanitized, tmp_path, name)
+
+
+@pytest.mark.parametrize("name", dc.APPLY_CASES)
+def test_apply_under_address_and_undefined_behaviour_sanitizers(sanitized, tmp_path, name):
+    check_apply(sanitized, tmp_path, name)

@@ -20,6 +20,7 @@ POST_AA_SMAA_LOW, POST_AA_SMAA_MEDIUM, POST_AA_SMAA_HIGH, POST_AA_SMAA_ULTRA = 2
 POST_AA_TAA_LOW, POST_AA_TAA_MEDIUM, POST_AA_TAA_HIGH = 6, 7, 8
 # gra_config::ambient_occlusion: "ssao-main" copies an uploaded image in (what True means), or computes FidelityFX CACAO from the G-buffer
 AMBIENT_OCCLUSION_UPLOAD, AMBIENT_OCCLUSION_CACAO = 1, 2
+SKY_OFF, SKY_ATMOSPHERE, SKY_CUBE = 0, 1, 2  # gra_config_ext.sky
 
 
 class Config(C.Structure):
@@ -33,6 +34,11 @@ class Config(C.Structure):
                 ("resolution_scale", C.c_float), ("resolution_scale_sharpen", C.c_int32), ("fsr_fp32", C.c_int32),
                 ("ambient_occlusion", C.c_int32), ("hdr10", C.c_int32), ("ssr", C.c_int32), ("aa_bench", C.c_int32), ("output_gather_rgba", C.c_int32),
                 ("hdr_packed_float", C.c_int32), ("taa_history_reach_rows", C.c_uint32), ("volumetric_decals", C.c_int32)]
+
+
+class ConfigExt(C.Structure):
+    """gra_config_ext: the settings that came after gra_config's layout was fixed, handed to gra_create_ext beside the config."""
+    _fields_ = [("struct_size", C.c_uint32), ("sky", C.c_int32)]
 
 
 # void (*gra_exchange_fn)(void *user, const char *tag, void *device_ptr, uint64_t chunk_bytes, uint32_t rank_count, void *stream)
@@ -143,6 +149,7 @@ EXPORTED_SYMBOLS = [
     "gra_ocean_default_config", "gra_ocean_create", "gra_ocean_update", "gra_ocean_describe", "gra_ocean_read", "gra_ocean_distribution",
     "gra_ocean_parameters", "gra_ocean_destroy", "gra_ocean_set_camera", "gra_ocean_draw_info", "gra_ocean_mesh_describe", "gra_ocean_mesh_read",
     "gra_meshlet_describe", "gra_meshlet_decode", "gra_set_decal_texture", "gra_set_decals", "gra_get_decal_state",
+    "gra_set_sky_cube", "gra_set_sky_cube_gtx", "gra_get_sky_state", "gra_create_ext",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -159,6 +166,7 @@ def load_library() -> C.CDLL:
     vp, P = C.c_void_p, C.POINTER
     sigs = {
         "gra_create": (vp, [P(Config), C.c_char_p, C.c_size_t]),
+        "gra_create_ext": (vp, [P(Config), P(ConfigExt), C.c_char_p, C.c_size_t]),
         "gra_destroy": (None, [vp]),
         "gra_last_error": (C.c_char_p, [vp]),
         "gra_set_camera": (C.c_int, [vp, vp, vp]),
@@ -169,6 +177,9 @@ def load_library() -> C.CDLL:
         "gra_set_decal_texture": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
         "gra_set_decals": (C.c_int, [vp, vp, C.c_uint32]),
         "gra_get_decal_state": (C.c_int, [vp, P(C.c_uint32), vp, vp, vp, vp]),
+        "gra_set_sky_cube": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp]),
+        "gra_set_sky_cube_gtx": (C.c_int, [vp, C.c_char_p, vp]),
+        "gra_get_sky_state": (C.c_int, [vp, vp, vp, vp, P(C.c_float), vp]),
         "gra_upload_gbuffer": (C.c_int, [vp, vp, vp, vp, vp, vp, vp]),
         "gra_render_frames": (C.c_int, [vp, C.c_uint32, C.c_int32]),
         "gra_sync": (C.c_int, [vp]),
@@ -261,13 +272,16 @@ class Application:
                  alias_images: bool = True, depth_hierarchy: int = 0,
                  resolution_scale: float = 1.0, resolution_scale_sharpen: bool = True, fsr_fp16: bool = True,
                  ambient_occlusion=False, hdr10: bool = False, ssr: bool = False, aa_bench: bool = False,
-                 output_gather_rgba: bool = False, rt_fp16: bool = True, taa_history_reach_rows: int = 0, volumetric_decals: bool = False):
+                 output_gather_rgba: bool = False, rt_fp16: bool = True, taa_history_reach_rows: int = 0, volumetric_decals: bool = False,
+                 sky: int = 0):
         """taa_history_reach_rows > 0 (row bands + TAA): the history bands exchange boundary rows with their neighbours only; a pixel
         that reaches further makes the next render / sync / read raise.  rt_fp16 = False: viewer_config renderTargetFp16 = false (the reference's default): emissive / HDR-main and the TAA colour
         output are B10G11R11_UFLOAT_PACK32; the emissive upload is then (h, w) uint32 words (oracle.pack_b10g11r11).
         ambient_occlusion: False, True (= AMBIENT_OCCLUSION_UPLOAD: "ssao-output-main" is what upload_ambient_occlusion brought, white
         before that) or AMBIENT_OCCLUSION_CACAO (computed from depth and normals every frame).
-        volumetric_decals: the decals of set_decals are binned by the clusterer and applied to "albedo" by the G-buffer pass every frame."""
+        volumetric_decals: the decals of set_decals are binned by the clusterer and applied to "albedo" by the G-buffer pass every frame.
+        sky: SKY_OFF, SKY_ATMOSPHERE (the procedural atmosphere lit by the directional light) or SKY_CUBE (the cube of set_sky_cube): the
+        G-buffer pass writes "emissive" where depth == 0 every frame."""
         self.lib = load_library()
         cfg = Config()
         cfg.device, cfg.width, cfg.height = device, width, height
@@ -298,7 +312,9 @@ class Application:
         self.config = cfg
         self.width, self.height = width, height
         err = C.create_string_buffer(512)
-        self.handle = self.lib.gra_create(cfg, err, 512)
+        # the settings of gra_config_ext travel only when one of them is set: without them the call is the one it always was
+        self.config_ext = ConfigExt(C.sizeof(ConfigExt), int(sky))
+        self.handle = self.lib.gra_create_ext(cfg, self.config_ext, err, 512) if sky else self.lib.gra_create(cfg, err, 512)
         if not self.handle:
             raise capi.GraniteHipError(f"gra_create failed: {err.value.decode()}")
         if device >= 0 and POST_AA_SMAA_LOW <= post_aa <= POST_AA_SMAA_ULTRA:
@@ -357,6 +373,29 @@ class Application:
         """The scene's decals: synth.DECAL_DESC_DTYPE records, each the mat_affine rows of a unit box's world transform and a texture index."""
         d = np.ascontiguousarray(descs, synth.DECAL_DESC_DTYPE)
         self._check(self.lib.gra_set_decals(self.handle, d.ctypes.data if len(d) else None, len(d)))
+
+    def set_sky_cube(self, cube, size: int = 0, levels: int = 0, color=(1.0, 1.0, 1.0)):
+        """The sky's cube (needs sky=SKY_CUBE): the uint16 words of an RGBA16F chain in the gr_env_* layout with its size and levels, or the
+        path of a cube .gtx as bake_environment writes it; `color` multiplies it."""
+        c = np.ascontiguousarray(color, np.float32)
+        if isinstance(cube, (str, os.PathLike)):
+            self._check(self.lib.gra_set_sky_cube_gtx(self.handle, str(cube).encode(), c.ctypes.data))
+            return
+        chain = np.ascontiguousarray(cube, np.uint16)
+        need = capi.load_library().gr_cube_chain_bytes(int(size), int(levels)) if 0 < size <= 16384 else 0
+        assert chain.nbytes >= need, (chain.nbytes, need)
+        self._check(self.lib.gra_set_sky_cube(self.handle, int(size), int(levels), chain.ctypes.data, c.ctypes.data))
+
+    def get_sky_state(self) -> dict:
+        """What the next frame's sky is drawn with: local_view_projection and inv_local_view_projection (16 floats each, column-major) and
+        the Skybox's push values color, camera_height, direction."""
+        out = {"local_view_projection": np.zeros(16, np.float32), "inv_local_view_projection": np.zeros(16, np.float32), "color": np.zeros(3, np.float32),
+               "direction": np.zeros(3, np.float32)}
+        height = C.c_float()
+        self._check(self.lib.gra_get_sky_state(self.handle, out["local_view_projection"].ctypes.data, out["inv_local_view_projection"].ctypes.data,
+                                               out["color"].ctypes.data, C.byref(height), out["direction"].ctypes.data))
+        out["camera_height"] = height.value
+        return out
 
     def get_decal_state(self) -> dict:
         """CPU-side decal state of the last frame's refresh, in sorted order: order, world_to_texture (n, 12), mvps (n, 16), ranges (n, 2)."""

@@ -476,6 +476,20 @@ assert C.sizeof(DecalTexture) == 24 and C.sizeof(DecalApplyArgs) == 328
 MAX_DECALS_BINDLESS = 4096
 
 
+class SkyArgs(C.Structure):
+    """gr_sky_args: the cube is absent when its ptr, size and levels are all 0."""
+    _fields_ = [("emissive", Image), ("depth", Image), ("inv_local_view_projection", C.c_float * 16), ("color", C.c_float * 3), ("camera_height", C.c_float),
+                ("sun_direction", C.c_float * 3), ("pad0", C.c_float), ("cube", Cube)]
+
+
+class SkyCubeParams(C.Structure):
+    """gr_sky_cube_params: volumetric_light_setup_sky.comp's UBO, less inv_resolution (1 / size, formed by the launcher)."""
+    _fields_ = [("sun_color", C.c_float * 3), ("camera_y", C.c_float), ("sun_direction", C.c_float * 3), ("pad0", C.c_float)]
+
+
+assert C.sizeof(SkyArgs) == 160 and C.sizeof(SkyCubeParams) == 32
+
+
 class PushClusterSetup(C.Structure):
     _fields_ = [("view", C.c_float * 16), ("num_lights", C.c_uint32)]
 
@@ -695,6 +709,8 @@ def load_library() -> C.CDLL:
         "gr_meshlet_cull": (C.c_int, [vp, vp, P(MeshletCullArgs), P(PushMeshletCull)]),
         "gr_cluster_binning_decal": (C.c_int, [vp, vp, vp, vp, P(ClusterParams)]),
         "gr_decal_apply": (C.c_int, [vp, vp, P(DecalApplyArgs)]),
+        "gr_sky_apply": (C.c_int, [vp, vp, P(SkyArgs)]),
+        "gr_sky_cube": (C.c_int, [vp, vp, vp, C.c_uint32, P(SkyCubeParams)]),
         "gr_cacao_reference_settings": (None, [P(CacaoSettings)]),
         "gr_cacao_update_buffer_sizes": (C.c_int, [C.c_uint32, C.c_uint32, P(CacaoBufferSizes)]),
         "gr_cacao_update_constants": (C.c_int, [vp, P(CacaoConstants), P(CacaoSettings), P(CacaoBufferSizes), P(C.c_float), P(C.c_float)]),
@@ -734,7 +750,7 @@ EXPORTED_SYMBOLS = [
     "gr_cube_chain_bytes", "gr_cube_chain_offset", "gr_env_equirect_to_cube", "gr_env_specular", "gr_env_diffuse",
     "gr_fft_describe", "gr_fft_plan_create", "gr_fft_plan_destroy", "gr_fft_plan_iterations", "gr_fft_execute", "gr_fft_execute_iteration",
     "gr_ocean_generate_fft", "gr_ocean_bake_maps", "gr_ocean_mipmap", "gr_ocean_update_lod", "gr_ocean_init_counter_buffer", "gr_ocean_cull_blocks",
-    "gr_meshlet_decode", "gr_meshlet_cull", "gr_cluster_binning_decal", "gr_decal_apply",
+    "gr_meshlet_decode", "gr_meshlet_cull", "gr_cluster_binning_decal", "gr_decal_apply", "gr_sky_apply", "gr_sky_cube",
     "gr_cacao_reference_settings", "gr_cacao_update_buffer_sizes", "gr_cacao_update_constants", "gr_cacao_workspace_bytes", "gr_cacao_workspace_describe",
     "gr_cacao_prepare_depths", "gr_cacao_prepare_normals", "gr_cacao_generate_base", "gr_cacao_importance_generate",
     "gr_cacao_importance_postprocess_a", "gr_cacao_importance_postprocess_b", "gr_cacao_generate", "gr_cacao_blur", "gr_cacao_apply",
@@ -1122,6 +1138,27 @@ class Context:
         """gr_env_diffuse: the irradiance cube (one level) of a cube."""
         assert src.nbytes >= self.lib.gr_cube_chain_bytes(src_size, src_levels) and out.nbytes >= self.lib.gr_cube_chain_bytes(out_size, 1)
         self.check(self.lib.gr_env_diffuse(self.handle, stream, C.byref(Cube(src.ptr, src_size, src_levels)), out.ptr, int(out_size)))
+
+    # ---- the sky pass ------------------------------------------------------------------------------------------------------------------
+    def sky_apply(self, emissive: DeviceImage, depth: DeviceImage, inv_local_view_projection, color, camera_height: float, sun_direction,
+                  cube: Optional[DeviceBuffer] = None, cube_size: int = 0, cube_levels: int = 0, stream=None):
+        """gr_sky_apply: the far pixels (depth == 0) of `emissive` get the atmosphere, or, with a cube, texture(cube, direction).rgb * color."""
+        args = SkyArgs()
+        args.emissive, args.depth = emissive.desc, depth.desc
+        args.inv_local_view_projection[:] = [float(v) for v in np.asarray(inv_local_view_projection, np.float32).reshape(16)]
+        args.color[:] = [float(v) for v in color]
+        args.camera_height = float(camera_height)
+        args.sun_direction[:] = [float(v) for v in sun_direction]
+        if cube is not None:
+            assert cube.nbytes >= self.lib.gr_cube_chain_bytes(cube_size, cube_levels) or not (0 < cube_size <= 16384), (cube.nbytes, cube_size, cube_levels)
+            args.cube = Cube(cube.ptr, int(cube_size), int(cube_levels))
+        self.check(self.lib.gr_sky_apply(self.handle, stream, C.byref(args)))
+
+    def sky_cube(self, out: DeviceBuffer, size: int, sun_color, camera_y: float, sun_direction, stream=None):
+        """gr_sky_cube: six faces of `size` RGBA16F texels of atmosphere (32 / 16 steps, alpha 1), level 0 of a gr_env_* chain."""
+        assert out.nbytes >= self.lib.gr_cube_chain_bytes(size, 1) or not (0 < size <= 16384), (out.nbytes, size)
+        params = SkyCubeParams((C.c_float * 3)(*[float(v) for v in sun_color]), float(camera_y), (C.c_float * 3)(*[float(v) for v in sun_direction]), 0.0)
+        self.check(self.lib.gr_sky_cube(self.handle, stream, out.ptr, int(size), C.byref(params)))
 
     # ---- FFT: a plan owns its scratch and twiddles and may be in flight on one stream at a time ---------------------------------
     def fft_plan(self, options: FftOptions):

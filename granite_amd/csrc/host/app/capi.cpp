@@ -130,12 +130,24 @@ extern "C" {
 
 gra_app *gra_create(const gra_config *config, char *error, size_t error_size)
 {
+	return gra_create_ext(config, nullptr, error, error_size);
+}
+
+gra_app *gra_create_ext(const gra_config *config, const gra_config_ext *ext, char *error, size_t error_size)
+{
 	try
 	{
 		if (!config)
 			throw std::logic_error("null config");
+		gra_config_ext settings = {};
+		if (ext)
+		{
+			if (ext->struct_size < sizeof(uint32_t))
+				throw std::logic_error("gra_config_ext.struct_size is smaller than the member itself.");
+			memcpy(&settings, ext, ext->struct_size < sizeof(settings) ? ext->struct_size : sizeof(settings));
+		}
 		auto *handle = new gra_app;
-		handle->app = std::make_unique<ImageSpaceApplication>(*config);
+		handle->app = std::make_unique<ImageSpaceApplication>(*config, settings);
 		return handle;
 	}
 	catch (const std::exception &e)
@@ -226,6 +238,46 @@ int gra_set_decal_texture(gra_app *app, uint32_t index, uint32_t width, uint32_t
 int gra_set_decals(gra_app *app, const gra_decal_desc *decals, uint32_t count)
 {
 	return guarded(app, [&]() { app->app->set_decals(decals, count); });
+}
+
+int gra_get_sky_state(gra_app *app, float local_view_projection16[16], float inv_local_view_projection16[16], float color[3], float *camera_height,
+                      float direction[3])
+{
+	return guarded(app, [&]() {
+		const RenderContext &context = app->app->get_context();
+		const auto &rp = context.get_render_parameters();
+		if (local_view_projection16)
+			memcpy(local_view_projection16, rp.local_view_projection.data(), 16 * sizeof(float));
+		if (inv_local_view_projection16)
+			memcpy(inv_local_view_projection16, rp.inv_local_view_projection.data(), 16 * sizeof(float));
+		const Skybox::RenderInfo info = app->app->get_skybox().get_render_info(context);
+		for (int i = 0; i < 3; i++)
+		{
+			if (color)
+				color[i] = info.color[i];
+			if (direction)
+				direction[i] = info.direction[i];
+		}
+		if (camera_height)
+			*camera_height = info.camera_height;
+	});
+}
+
+int gra_set_sky_cube(gra_app *app, uint32_t size, uint32_t levels, const void *rgba16f_chain, const float color[3])
+{
+	return guarded(app, [&]() { app->app->set_sky_cube(size, levels, rgba16f_chain, color); });
+}
+
+int gra_set_sky_cube_gtx(gra_app *app, const char *cube_gtx, const float color[3])
+{
+	return guarded(app, [&]() {
+		if (!cube_gtx)
+			throw std::logic_error("gra_set_sky_cube_gtx: null path");
+		const GtxImage image = gtx_load(cube_gtx);
+		if (image.format != VK_FORMAT_R16G16B16A16_SFLOAT || image.layers != 6 || image.depth != 1 || image.width != image.height)
+			throw std::logic_error(std::string("gra_set_sky_cube_gtx: ") + cube_gtx + " is not a square R16G16B16A16_SFLOAT image of 6 layers (a cube as gra_environment_bake writes it).");
+		app->app->set_sky_cube(image.width, image.levels, image.payload.data(), color);
+	});
 }
 
 int gra_get_decal_state(gra_app *app, uint32_t *count, uint32_t *order, float *world_to_texture, float *mvps, uint32_t *ranges)

@@ -35,7 +35,7 @@ static PostAAType to_post_aa_type(int32_t v)
 	}
 }
 
-ImageSpaceApplication::ImageSpaceApplication(const gra_config &config_) : config(config_)
+ImageSpaceApplication::ImageSpaceApplication(const gra_config &config_, const gra_config_ext &ext_) : config(config_), ext(ext_)
 {
 	if (config.device >= 0)
 		device_holder = std::make_unique<HIP::Device>(config.device);
@@ -50,6 +50,10 @@ ImageSpaceApplication::ImageSpaceApplication(const gra_config &config_) : config
 		throw std::logic_error("aa_bench is a graph of its own: no lighting, bloom, hdr10, SSR, depth hierarchy or row bands.");
 	if (config.volumetric_decals && (!config.enable_lighting || config.aa_bench || config.strip_count > 1))
 		throw std::logic_error("volumetric_decals needs enable_lighting and is not available with aa_bench or row bands (strip_count > 1).");
+	if (ext.sky < GRA_SKY_OFF || ext.sky > GRA_SKY_CUBE)
+		throw std::logic_error("sky must be 0 (GRA_SKY_OFF), 1 (GRA_SKY_ATMOSPHERE) or 2 (GRA_SKY_CUBE).");
+	if (ext.sky && (!config.enable_lighting || config.aa_bench || config.strip_count > 1))
+		throw std::logic_error("sky needs enable_lighting and is not available with aa_bench or row bands (strip_count > 1).");
 	if (config.resolution_scale < 0.0f || config.resolution_scale > 1.0f)
 		throw std::logic_error("resolution_scale must be in (0, 1].");
 	if (config.ambient_occlusion < 0 || config.ambient_occlusion > GRA_AMBIENT_OCCLUSION_CACAO)
@@ -442,6 +446,27 @@ void ImageSpaceApplication::set_decals(const gra_decal_desc *descs, uint32_t cou
 	}
 }
 
+void ImageSpaceApplication::set_sky_cube(uint32_t size, uint32_t levels, const void *rgba16f_chain, const float *color)
+{
+	if (ext.sky != GRA_SKY_CUBE)
+		throw std::logic_error("gra_set_sky_cube: this application was created without sky = 2 (GRA_SKY_CUBE).");
+	if (!rgba16f_chain || !color)
+		throw std::logic_error("gra_set_sky_cube: null chain or color.");
+	uint32_t full_chain = 0;
+	for (uint32_t n = size; n; n >>= 1)
+		full_chain++;
+	if (!size || size > 16384 || !levels || levels > full_chain)
+		throw std::logic_error("gra_set_sky_cube: size must be 1 .. 16384 and levels 1 .. " + std::to_string(full_chain) + " for this size.");
+	const size_t bytes = size_t(gr_cube_chain_bytes(size, levels));
+	auto &device = get_device();
+	device.wait_idle(); // a frame in flight may still sample the cube this one replaces
+	auto chain = device.create_buffer(bytes, VK_BUFFER_USAGE_STORAGE_BUFFER_BIT, "sky-cube");
+	if (gr_upload(device.get_context(), nullptr, chain->get_device_pointer(), rgba16f_chain, bytes) < 0 || gr_sync(device.get_context(), nullptr) < 0)
+		throw std::runtime_error(gr_last_error(device.get_context()));
+	skybox.set_image(std::move(chain), size, levels);
+	skybox.set_color(vec3(color[0], color[1], color[2]));
+}
+
 // lights/volumetric_decal.h as inc/render_target.h calls it while the G-buffer is written: here on the albedo and depth the pass has just
 // filled.  The texture table is this frame's, in the order the clusterer sorted the decals into (the reference allocates the bindless
 // descriptors per frame in that order, clusterer.cpp:1564-1573), and travels through the staging ring.
@@ -731,7 +756,8 @@ void ImageSpaceApplication::add_main_pass_deferred(const std::string &tag)
 			if (needs_fill(target) || always)
 				cmd.copy_image(target, *src);
 		};
-		fill(g_emissive, src_emissive, config.rmw_emissive != 0);
+		// with the sky on emissive is rewritten from its source every frame as well: the sky below writes its far pixels in place
+		fill(g_emissive, src_emissive, config.rmw_emissive != 0 || ext.sky != 0);
 		// with decals the base colour is rewritten from its source every frame: the apply below modifies it in place
 		fill(g_albedo, src_albedo, config.volumetric_decals != 0);
 		fill(g_normal, src_normal, false);
@@ -739,6 +765,9 @@ void ImageSpaceApplication::add_main_pass_deferred(const std::string &tag)
 		fill(g_depth, src_depth, false);
 		if (config.volumetric_decals)
 			apply_volumetric_decals(cmd, graph.get_physical_texture_resource(g_albedo), graph.get_physical_texture_resource(g_depth));
+		// the Skybox renderable of the G-buffer pass (scene_renderer.cpp:463-473): a quad at z = 0 under GREATER_OR_EQUAL, i.e. depth == 0
+		if (ext.sky)
+			skybox.render(cmd, context, graph.get_physical_texture_resource(g_emissive), graph.get_physical_texture_resource(g_depth));
 	});
 	// Scene::add_render_pass_dependencies(graph, gbuffer, GEOMETRY_BIT): the decal masks, ranges and transforms, when decals are on
 	cluster.setup_render_pass_dependencies(graph, gbuffer, RenderPassCreator::GEOMETRY_BIT);
@@ -984,6 +1013,8 @@ void ImageSpaceApplication::render_frame()
 	check_taa_history_reach();
 	if (video)
 		video_check_ring(); // a full ring fails the frame before any of its state advances
+	if (ext.sky == GRA_SKY_CUBE && !skybox.has_image())
+		throw std::logic_error("sky = 2 (GRA_SKY_CUBE) but no cube is set: call gra_set_sky_cube or gra_set_sky_cube_gtx before rendering a frame.");
 	if (need_bake)
 		bake_render_graph();
 

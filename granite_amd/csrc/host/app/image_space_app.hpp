@@ -19,6 +19,7 @@
 #include "../render_context.hpp"
 #include "../render_graph.hpp"
 #include "../renderer.hpp"
+#include "../sky.hpp"
 #include "../video/scaler.hpp"
 #include "../video/yuv_to_rgb.hpp"
 #include "video_ring.hpp"
@@ -28,11 +29,13 @@ namespace Granite
 class ImageSpaceApplication
 {
 public:
-	explicit ImageSpaceApplication(const gra_config &config);
+	explicit ImageSpaceApplication(const gra_config &config, const gra_config_ext &ext = {});
 	~ImageSpaceApplication();
 
 	void set_lights(const gra_light_desc *descs, uint32_t count);
 	void set_decals(const gra_decal_desc *descs, uint32_t count);
+	void set_sky_cube(uint32_t size, uint32_t levels, const void *rgba16f_chain, const float *color);
+	const Skybox &get_skybox() const { return skybox; }
 	void set_decal_texture(uint32_t index, uint32_t width, uint32_t height, uint32_t levels, uint32_t format, const void *texels);
 	void upload_gbuffer(const void *emissive, const void *albedo, const void *normal, const void *pbr, const void *depth, const void *mv);
 	void render_frame();
@@ -119,6 +122,7 @@ public:
 
 private:
 	gra_config config;
+	gra_config_ext ext; // settings that came after gra_config's layout was fixed (gra_create_ext)
 	unsigned render_width = 0, render_height = 0; // backbuffer size x resolution_scale
 	bool scaled() const { return config.resolution_scale > 0.0f && config.resolution_scale < 1.0f; }
 	VkFormat backbuffer_format() const { return config.hdr10 ? VK_FORMAT_A2B10G10R10_UNORM_PACK32 : VK_FORMAT_R8G8B8A8_SRGB; }
@@ -163,6 +167,8 @@ private:
 	std::vector<DecalTexture> decal_textures;
 	std::vector<gr_decal_texture> decal_table; // this frame's table, in the clusterer's sorted order
 	void apply_volumetric_decals(HIP::CommandBuffer &cmd, HIP::Image &albedo, HIP::Image &depth);
+	// The scene's background (ext.sky): the atmosphere lit by the directional light, or the cube of set_sky_cube.
+	Skybox skybox;
 	HIP::ImageHandle src_emissive, src_albedo, src_normal, src_pbr, src_depth, src_mv, src_ao;
 	// scene_viewer_application.cpp:881-883: renderTargetFp16 ? R16G16B16A16_SFLOAT : B10G11R11_UFLOAT_PACK32
 	VkFormat hdr_target_format() const { return config.hdr_packed_float ? VK_FORMAT_B10G11R11_UFLOAT_PACK32 : VK_FORMAT_R16G16B16A16_SFLOAT; }

@@ -131,39 +131,6 @@ static mat4 to_mat4(const mat_affine &m)
 	return r;
 }
 
-// muglm::inverse(mat4) (math/muglm/muglm.cpp:146-201) in fp32, operation for operation: what scene.cpp:733-736 takes of a decal's world
-// transform.  host/math.cpp's inverse() works in double and differs from it in the last bits; a decal's world_to_texture is the reference's.
-static mat4 inverse_fp32(const mat4 &m)
-{
-	const float c00 = m[2][2] * m[3][3] - m[3][2] * m[2][3], c02 = m[1][2] * m[3][3] - m[3][2] * m[1][3], c03 = m[1][2] * m[2][3] - m[2][2] * m[1][3];
-	const float c04 = m[2][1] * m[3][3] - m[3][1] * m[2][3], c06 = m[1][1] * m[3][3] - m[3][1] * m[1][3], c07 = m[1][1] * m[2][3] - m[2][1] * m[1][3];
-	const float c08 = m[2][1] * m[3][2] - m[3][1] * m[2][2], c10 = m[1][1] * m[3][2] - m[3][1] * m[1][2], c11 = m[1][1] * m[2][2] - m[2][1] * m[1][2];
-	const float c12 = m[2][0] * m[3][3] - m[3][0] * m[2][3], c14 = m[1][0] * m[3][3] - m[3][0] * m[1][3], c15 = m[1][0] * m[2][3] - m[2][0] * m[1][3];
-	const float c16 = m[2][0] * m[3][2] - m[3][0] * m[2][2], c18 = m[1][0] * m[3][2] - m[3][0] * m[1][2], c19 = m[1][0] * m[2][2] - m[2][0] * m[1][2];
-	const float c20 = m[2][0] * m[3][1] - m[3][0] * m[2][1], c22 = m[1][0] * m[3][1] - m[3][0] * m[1][1], c23 = m[1][0] * m[2][1] - m[2][0] * m[1][1];
-	const float fac[6][4] = {{c00, c00, c02, c03}, {c04, c04, c06, c07}, {c08, c08, c10, c11}, {c12, c12, c14, c15}, {c16, c16, c18, c19}, {c20, c20, c22, c23}};
-	float vec[4][4];
-	for (int r = 0; r < 4; r++)
-	{
-		vec[r][0] = m[1][r];
-		vec[r][1] = vec[r][2] = vec[r][3] = m[0][r];
-	}
-	mat4 inv(0.0f);
-	for (int i = 0; i < 4; i++)
-	{
-		const float sign_a = (i & 1) ? -1.0f : 1.0f, sign_b = -sign_a;
-		inv[0][i] = (vec[1][i] * fac[0][i] - vec[2][i] * fac[1][i] + vec[3][i] * fac[2][i]) * sign_a;
-		inv[1][i] = (vec[0][i] * fac[0][i] - vec[2][i] * fac[3][i] + vec[3][i] * fac[4][i]) * sign_b;
-		inv[2][i] = (vec[0][i] * fac[1][i] - vec[1][i] * fac[3][i] + vec[3][i] * fac[5][i]) * sign_a;
-		inv[3][i] = (vec[0][i] * fac[2][i] - vec[1][i] * fac[4][i] + vec[2][i] * fac[5][i]) * sign_b;
-	}
-	const float d0 = m[0][0] * inv[0][0], d1 = m[0][1] * inv[1][0], d2 = m[0][2] * inv[2][0], d3 = m[0][3] * inv[3][0];
-	const float one_over_determinant = 1.0f / ((d0 + d1) + (d2 + d3));
-	for (int c = 0; c < 4; c++)
-		inv[c] = inv[c] * one_over_determinant;
-	return inv;
-}
-
 static vec2 decal_z_range(const RenderParameters &rp, const mat_affine &transform)
 {
 	float lo = std::numeric_limits<float>::infinity();

@@ -90,6 +90,7 @@ inline mat4 operator*(const mat4 &a, const mat4 &b)
 }
 
 mat4 inverse(const mat4 &m);
+mat4 inverse_fp32(const mat4 &m); // muglm's own arithmetic, where a result has to equal the reference's bit for bit
 mat4 translate(const vec3 &v);
 mat4 scale(const vec3 &v);
 // muglm::perspective (math/muglm/muglm.cpp:319-337): reverse-Z, Vulkan clip space with Y flip.

@@ -28,6 +28,9 @@ struct RenderParameters
 	mat4 unjittered_view_projection;
 	mat4 unjittered_inv_view_projection;
 	mat4 unjittered_prev_view_projection;
+	// projection * (view with its translation zeroed) and its inverse: what skybox.vert turns a clip-space position into a direction with
+	mat4 local_view_projection;
+	mat4 inv_local_view_projection;
 	vec3 camera_position;
 	vec3 camera_front;
 	vec3 camera_right;
@@ -63,8 +66,13 @@ class RenderContext
 public:
 	// RenderContext::set_camera (render_context.cpp:53-86): inverses, camera basis, z_near / z_far from inv_projection.
 	void set_camera(const mat4 &projection, const mat4 &view);
-	// Harness hook: install precomputed parameters verbatim (keeps CPU oracle and device bit-identical inputs).
-	void set_render_parameters(const RenderParameters &params) { camera = params; }
+	// Harness hook: install precomputed parameters verbatim (keeps CPU oracle and device bit-identical inputs); the local view projection
+	// is formed from their projection and view, as set_camera forms it.
+	void set_render_parameters(const RenderParameters &params)
+	{
+		camera = params;
+		set_local_view_projection();
+	}
 	const RenderParameters &get_render_parameters() const { return camera; }
 
 	void set_frame_parameters(const FrameParameters &frame_) { frame = frame_; }
@@ -74,6 +82,8 @@ public:
 	const LightingParameters *get_lighting_parameters() const { return lighting; }
 
 private:
+	// render_context.cpp:62-67
+	void set_local_view_projection();
 	RenderParameters camera;
 	FrameParameters frame;
 	const LightingParameters *lighting = nullptr;

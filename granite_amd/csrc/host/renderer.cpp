@@ -109,6 +109,7 @@ void RenderContext::set_camera(const mat4 &projection, const mat4 &view)
 	camera.inv_view_projection = inverse(camera.view_projection);
 	camera.unjittered_view_projection = camera.view_projection;
 	camera.unjittered_inv_view_projection = camera.inv_view_projection;
+	set_local_view_projection();
 	camera.camera_position = camera.inv_view[3].xyz();
 	camera.camera_up = camera.inv_view[1].xyz();
 	camera.camera_right = camera.inv_view[0].xyz();
@@ -125,5 +126,16 @@ void RenderContext::set_camera(const mat4 &projection, const mat4 &view)
 	bool infinite_z = camera.inv_view_projection[3][3] == 0.0f;
 	camera.z_near = project(1.0f, 1.0f);
 	camera.z_far = project(infinite_z ? 1e-10f : 0.0f, 1.0f);
+}
+
+void RenderContext::set_local_view_projection()
+{
+	mat4 local_view = camera.view;
+	local_view[3].x = 0.0f;
+	local_view[3].y = 0.0f;
+	local_view[3].z = 0.0f;
+	camera.local_view_projection = camera.projection * local_view;
+	// the pixel directions of the sky come from this matrix and decide the earth test: it is the reference's, bit for bit
+	camera.inv_local_view_projection = inverse_fp32(camera.local_view_projection);
 }
 } // namespace Granite

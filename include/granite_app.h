@@ -119,6 +119,23 @@ typedef struct gra_config
 	int32_t volumetric_decals;
 } gra_config;
 
+/* Settings that came after gra_config's layout was fixed (its last member stays volumetric_decals): handed to gra_create_ext beside the
+ * config.  struct_size is sizeof(gra_config_ext) as the caller was compiled; members beyond it read as 0, so the structure can grow.
+ * sky -- the sky pass (Skybox, renderer/mesh_util.cpp:1046-1142): the G-buffer pass writes "emissive" where depth == 0, after the decals
+ * and before lighting, and then rewrites "emissive" from the uploaded image every frame.  GRA_SKY_ATMOSPHERE: the procedural Rayleigh /
+ * Mie atmosphere (the viewer's background for a scene without one), sun direction and colour those of gra_set_directional_light /
+ * the config, camera height camera_position.y.  GRA_SKY_CUBE: the cube of gra_set_sky_cube times its colour; a frame rendered before a
+ * cube is set fails with a message that says so.  Needs enable_lighting; not with strip_count > 1 or aa_bench.  0 = off: no graph,
+ * launch or byte changes. */
+typedef struct gra_config_ext
+{
+	uint32_t struct_size;
+	int32_t sky;
+} gra_config_ext;
+#define GRA_SKY_OFF 0
+#define GRA_SKY_ATMOSPHERE 1
+#define GRA_SKY_CUBE 2
+
 /* One volumetric decal: the world transform of its unit box and the texture (gra_set_decal_texture) it projects along its z axis. */
 typedef struct gra_decal_desc
 {
@@ -142,6 +159,8 @@ typedef struct gra_light_desc
 #define GRA_RENDER_PARAMS_FLOATS 104
 
 gra_app *gra_create(const gra_config *config, char *error, size_t error_size);
+/* gra_create with the settings of gra_config_ext; ext == NULL is gra_create. */
+gra_app *gra_create_ext(const gra_config *config, const gra_config_ext *ext, char *error, size_t error_size);
 void gra_destroy(gra_app *app);
 const char *gra_last_error(gra_app *app);
 
@@ -165,6 +184,16 @@ int gra_set_lights(gra_app *app, const gra_light_desc *lights, uint32_t count);
  * texture that has not been set is refused, the message says which.  Beyond 4096 decals the farthest are dropped. */
 int gra_set_decal_texture(gra_app *app, uint32_t index, uint32_t width, uint32_t height, uint32_t levels, uint32_t format, const void *texels);
 int gra_set_decals(gra_app *app, const gra_decal_desc *decals, uint32_t count);
+/* The sky's cube (gra_config_ext.sky == GRA_SKY_CUBE): an R16G16B16A16_SFLOAT chain of `levels` levels in the gr_env_* layout (host pointer,
+ * gr_cube_chain_bytes(size, levels) bytes), and the colour it is multiplied by.  The _gtx form takes a cube .gtx as gra_environment_bake
+ * writes it (6 layers, square, R16G16B16A16_SFLOAT, any number of levels of its chain). */
+int gra_set_sky_cube(gra_app *app, uint32_t size, uint32_t levels, const void *rgba16f_chain, const float color[3]);
+int gra_set_sky_cube_gtx(gra_app *app, const char *cube_gtx, const float color[3]);
+/* What the next frame's sky would be drawn with: RenderParameters::local_view_projection and its inverse (column-major), and the Skybox's
+ * push values (a cube: its colour, 0, 0; none: the directional light's colour, camera_position.y, the light's direction).  Any pointer
+ * may be NULL.  Needs no device. */
+int gra_get_sky_state(gra_app *app, float local_view_projection16[16], float inv_local_view_projection16[16], float color[3], float *camera_height,
+                      float direction[3]);
 /* CPU-side state of the last refresh, decals in sorted order: order[i] = index into the gra_set_decals list, 12 floats of world_to_texture,
  * 16 of the mvp and the two slice-interval words per decal.  Any pointer may be NULL; *count is always written. */
 int gra_get_decal_state(gra_app *app, uint32_t *count, uint32_t *order, float *world_to_texture, float *mvps, uint32_t *ranges);

@@ -1283,6 +1283,43 @@ typedef struct gr_decal_apply_args
 } gr_decal_apply_args;
 int gr_decal_apply(gr_ctx *ctx, gr_stream stream, const gr_decal_apply_args *args);
 
+/* ---- the sky pass (renderer/mesh_util.cpp:1046-1142 Skybox, skybox.vert / skybox.frag, lights/atmospheric_scatter.h) ------------------------
+ * The reference draws the skybox as a full-screen quad at z = 0 with depth test GREATER_OR_EQUAL against a depth buffer cleared to 0: it
+ * writes the emissive attachment exactly where depth == 0.  Arithmetic, the pixel's direction and the cube LOD model:
+ * granite_amd/csrc/sky_core.hpp, DESIGN.md 7.15.
+ * Where depth == 0.0f (a float compare: -0.0 is far) rgb is written: without a cube color * rayleigh_mie_scatter(normalize(direction),
+ * sun_direction, camera_height, 16, 8), with a cube texture(cube, direction).rgb * color through LinearClamp.  The alpha of an
+ * R16G16B16A16_SFLOAT texel keeps its value; a B10G11R11 store rounds as every attachment store of this library.  No other pixel is stored
+ * to.  The cube is absent when ptr, size and levels are all 0.
+ * Refused with GR_ERR_INVALID_ARGUMENT before anything is launched: an image that breaks the gr_image contract (emissive of another format
+ * than the two, depth that is not D32_SFLOAT or not of the emissive's size, null pointers); a cube with a null ptr, size 0 or above 16384,
+ * levels 0 or beyond the chain of the size, or a ptr that is not 16-byte aligned. */
+typedef struct gr_sky_args
+{
+	gr_image emissive;                   /* R16G16B16A16_SFLOAT or B10G11R11_UFLOAT_PACK32; far pixels are written */
+	gr_image depth;                      /* D32_SFLOAT, reverse-Z: 0 is the far plane */
+	float inv_local_view_projection[16]; /* column-major: inverse(projection * view with its translation zeroed) */
+	float color[3];
+	float camera_height;
+	float sun_direction[3];
+	float pad0;
+	gr_cube cube; /* optional: the gr_env_* chain layout */
+} gr_sky_args;
+int gr_sky_apply(gr_ctx *ctx, gr_stream stream, const gr_sky_args *args);
+
+/* lights/volumetric_light_setup_sky.comp: the atmosphere along base_dirs + pos_du * u + pos_dv * v of inc/cube_coordinates.h, 32 primary
+ * and 16 light steps, six faces of `size` texels in R16G16B16A16_SFLOAT with alpha 1: level 0 of the gr_env_* chain layout (6 * size^2 * 8
+ * bytes), which gr_env_diffuse / gr_env_specular read as a cube of one level.  inv_resolution is 1.0f / size.
+ * Refused with GR_ERR_INVALID_ARGUMENT before a launch: null pointers, size 0 or above 16384, out_chain not 16-byte aligned. */
+typedef struct gr_sky_cube_params
+{
+	float sun_color[3];
+	float camera_y;
+	float sun_direction[3];
+	float pad0;
+} gr_sky_cube_params;
+int gr_sky_cube(gr_ctx *ctx, gr_stream stream, void *out_chain, uint32_t size, const gr_sky_cube_params *params);
+
 /* ---- SSAO: FidelityFX CACAO as the reference runs it (renderer/post/ssao.cpp, renderer/post/ffx-cacao) -----------------------------------
  * One configuration and its non-adaptive sibling: native resolution, normals from the G-buffer, quality HIGHEST (adaptive, shader level 3)
  * or HIGH (shader level 2), 0 .. 8 blur passes.  One entry point per shader of FFX_CACAO_GraniteDraw (ffx_cacao_impl.cpp:767-1026); the
@@ -1600,6 +1637,16 @@ GR_ASSERT_OFFSET(gr_decal_apply_args, bitmask_decal, 296);
 GR_ASSERT_OFFSET(gr_decal_apply_args, range_decal, 304);
 GR_ASSERT_OFFSET(gr_decal_apply_args, textures, 312);
 GR_ASSERT_OFFSET(gr_decal_apply_args, num_textures, 320);
+GR_ASSERT_SIZE(gr_sky_args, 160);
+GR_ASSERT_OFFSET(gr_sky_args, depth, 24);
+GR_ASSERT_OFFSET(gr_sky_args, inv_local_view_projection, 48);
+GR_ASSERT_OFFSET(gr_sky_args, color, 112);
+GR_ASSERT_OFFSET(gr_sky_args, camera_height, 124);
+GR_ASSERT_OFFSET(gr_sky_args, sun_direction, 128);
+GR_ASSERT_OFFSET(gr_sky_args, cube, 144);
+GR_ASSERT_SIZE(gr_sky_cube_params, 32); /* volumetric_light_setup_sky.comp's UBO */
+GR_ASSERT_OFFSET(gr_sky_cube_params, camera_y, 12);
+GR_ASSERT_OFFSET(gr_sky_cube_params, sun_direction, 16);
 GR_STATIC_ASSERT(GR_TRANSFORMS_OFFSET_SHADOW ==GR_MAX_LIGHTS_BINDLESS * 48u, "ClustererBindlessTransforms: lights[4096] of 48 B");
 GR_STATIC_ASSERT(GR_TRANSFORMS_OFFSET_MODEL + GR_MAX_LIGHTS_BINDLESS * 48u == GR_TRANSFORMS_OFFSET_TYPE_MASK, "ClustererBindlessTransforms: model[4096] of 48 B");
 GR_STATIC_ASSERT(GR_TRANSFORMS_OFFSET_TYPE_MASK + GR_MAX_LIGHTS_BINDLESS / 8u == GR_TRANSFORMS_OFFSET_DECALS, "ClustererBindlessTransforms: type_mask[128]");

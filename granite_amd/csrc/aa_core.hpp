@@ -10,15 +10,8 @@
 // fast kernels below are built on that; `axis_taps_exact` is the host-side proof, per image size, that every such tap of a
 // launch does snap (the launchers fall back to the generic sampler kernels where it does not -- beyond ~16K pixels per axis).
 #pragma once
-#include <math.h>
-#include <stdint.h>
-#include <string.h>
+#include "core_base.hpp"
 
-#if defined(__HIPCC__)
-#define AA_HD __host__ __device__ __forceinline__
-#else
-#define AA_HD inline
-#endif
 // A value every lane of the wave holds alike (a wave index, a workgroup-wide count read from LDS): on the device it is moved to a
 // scalar register, so what is computed from it runs on the scalar unit.
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -36,30 +29,13 @@
 
 namespace aa
 {
-constexpr float SAMPLER_SNAP = 1.0f / 256.0f;
-
-AA_HD int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// f = unnormalised coordinate - 0.5: index of the first texel and weight of the second (oracle_common.h: linear_axis).
-AA_HD void linear_axis(float f, int &i0, float &weight)
-{
-	const float fl = floorf(f + SAMPLER_SNAP);
-	float a = f - fl;
-	if (a < SAMPLER_SNAP)
-		a = 0.0f;
-	i0 = int(fl);
-	weight = a;
-}
-
-// UNORM8 -> float, bit-identical to float(v) / 255.0f for v = 0..255 (device_common.hpp: unorm8_to_float).
-AA_HD float unorm8_decode(uint32_t v)
-{
-	const float f = float(v);
-	return fmaf(f, 0x1.010102p-8f, f * -0x1.fdfdfep-33f);
-}
+using gr_core::clampi;
+using gr_core::f3;
+using gr_core::linear_axis;
+using gr_core::unorm8_to_float;
 
 // UNORM8 store: NaN and negatives -> 0, >= 1 -> 255, otherwise floor(v * 255 + 0.5).
-AA_HD uint32_t unorm8_encode(float v)
+GR_HD uint32_t unorm8_encode(float v)
 {
 	if (!(v > 0.0f))
 		return 0u;
@@ -68,16 +44,12 @@ AA_HD uint32_t unorm8_encode(float v)
 	return uint32_t(int(v * 255.0f + 0.5f));
 }
 
-struct f3
-{
-	float x, y, z;
-};
 struct f4
 {
 	float x, y, z, w;
 };
 
-AA_HD float luma_of(float r, float g, float b, float wr, float wg, float wb) { return r * wr + g * wg + b * wb; }
+GR_HD float luma_of(float r, float g, float b, float wr, float wg, float wb) { return r * wr + g * wg + b * wb; }
 
 // ---- host-side proof that a launch's pixel-centre taps are texel fetches ---------------------------------------------------
 // For every pixel index p of an axis of n texels, with tc = (p + 0.5) * inv: the tap fma(inv, k, tc) (k = 0: tc itself) must
@@ -132,7 +104,7 @@ constexpr float FXAA_LUMA_R = 0.299f, FXAA_LUMA_G = 0.587f, FXAA_LUMA_B = 0.114f
 // Tile: f4 texel(int x, int y) = (r, g, b, luma) of the clamped texel, decoded once.  The pixel's own taps (centre and
 // corners) are texel fetches; the four taps along the edge direction are bilinear.
 template <typename Tile>
-AA_HD f3 fxaa_sample(const Tile &t, float u, float v, float fw, float fh)
+GR_HD f3 fxaa_sample(const Tile &t, float u, float v, float fw, float fh)
 {
 	int ix, iy;
 	float a, b;
@@ -148,7 +120,7 @@ AA_HD f3 fxaa_sample(const Tile &t, float u, float v, float fw, float fh)
 
 // Returns the packed RGBA8 (gamma-space bytes, alpha 255) of pixel (x, y).
 template <typename Tile>
-AA_HD uint32_t fxaa_pixel(const Tile &t, int x, int y, float inv_w, float inv_h, float fw, float fh)
+GR_HD uint32_t fxaa_pixel(const Tile &t, int x, int y, float inv_w, float inv_h, float fw, float fh)
 {
 	const float FXAA_REDUCE_MIN = 1.0f / 128.0f, FXAA_REDUCE_MUL = 1.0f / 8.0f, FXAA_SPAN_MAX = 8.0f;
 	const float u = (float(x) + 0.5f) * inv_w, v = (float(y) + 0.5f) * inv_h;
@@ -179,7 +151,7 @@ AA_HD uint32_t fxaa_pixel(const Tile &t, int x, int y, float inv_w, float inv_h,
 // A pixel whose four corner texels carry the same RGB bytes has dir = 0 exactly: all four edge taps land on the pixel centre,
 // rgbA = rgbB = the centre texel, and the pass copies it (alpha 255).  The kernels test this on the raw bytes before anything
 // is decoded.
-AA_HD bool fxaa_corners_equal(uint32_t nw, uint32_t ne, uint32_t sw, uint32_t se)
+GR_HD bool fxaa_corners_equal(uint32_t nw, uint32_t ne, uint32_t sw, uint32_t se)
 {
 	return (((nw ^ ne) | (nw ^ sw) | (nw ^ se)) & 0x00ffffffu) == 0u;
 }
@@ -189,7 +161,7 @@ constexpr float SMAA_LUMA_R = 0.2126f, SMAA_LUMA_G = 0.7152f, SMAA_LUMA_B = 0.07
 
 // Luma: float luma(int x, int y) of the clamped texel.  Returns the RG8 edge texel (0 where the shader discards).
 template <typename Luma>
-AA_HD uint32_t smaa_edges_pixel(const Luma &t, int x, int y, float threshold)
+GR_HD uint32_t smaa_edges_pixel(const Luma &t, int x, int y, float threshold)
 {
 	const float L = t.luma(x, y), Lleft = t.luma(x - 1, y), Ltop = t.luma(x, y - 1);
 	const float dxy_x = fabsf(L - Lleft), dxy_y = fabsf(L - Ltop);
@@ -214,7 +186,7 @@ AA_HD uint32_t smaa_edges_pixel(const Luma &t, int x, int y, float threshold)
 // Weights of the pixel and of its right / bottom neighbours are texel fetches; a pixel without weights copies its colour
 // texel.  Colour: uint32_t raw(int x, int y) of the clamped texel.  Only pixels with weights reach the bilinear taps.
 template <typename Color>
-AA_HD f4 smaa_blend_sample(const Color &c, float u, float v, float fw, float fh)
+GR_HD f4 smaa_blend_sample(const Color &c, float u, float v, float fw, float fh)
 {
 	int ix, iy;
 	float a, b;
@@ -222,7 +194,7 @@ AA_HD f4 smaa_blend_sample(const Color &c, float u, float v, float fw, float fh)
 	linear_axis(v * fh - 0.5f, iy, b);
 	auto dec = [&](int tx, int ty) {
 		const uint32_t t = c.raw(tx, ty);
-		return f4{unorm8_decode(t & 255u), unorm8_decode((t >> 8) & 255u), unorm8_decode((t >> 16) & 255u), unorm8_decode(t >> 24)};
+		return f4{unorm8_to_float(t & 255u), unorm8_to_float((t >> 8) & 255u), unorm8_to_float((t >> 16) & 255u), unorm8_to_float(t >> 24)};
 	};
 	const f4 t00 = dec(ix, iy);
 	f4 top = t00;
@@ -248,13 +220,13 @@ AA_HD f4 smaa_blend_sample(const Color &c, float u, float v, float fw, float fh)
 
 // w_c / w_r / w_b: raw weight texels of the pixel, its right and its bottom neighbour (clamped).
 template <typename Color>
-AA_HD uint32_t smaa_blend_pixel(const Color &c, uint32_t w_c, uint32_t w_r, uint32_t w_b, int x, int y, float rt_x, float rt_y, float fw, float fh)
+GR_HD uint32_t smaa_blend_pixel(const Color &c, uint32_t w_c, uint32_t w_r, uint32_t w_b, int x, int y, float rt_x, float rt_y, float fw, float fh)
 {
 	// a = (right.a, bottom.g, this.b, this.r) -- SMAA.hlsl:1262-1265
 	if (((w_r >> 24) | ((w_b >> 8) & 255u) | ((w_c >> 16) & 255u) | (w_c & 255u)) == 0u)
 		return c.raw(x, y);
-	const float ax = unorm8_decode(w_r >> 24), ay = unorm8_decode((w_b >> 8) & 255u);
-	const float az = unorm8_decode((w_c >> 16) & 255u), aw = unorm8_decode(w_c & 255u);
+	const float ax = unorm8_to_float(w_r >> 24), ay = unorm8_to_float((w_b >> 8) & 255u);
+	const float az = unorm8_to_float((w_c >> 16) & 255u), aw = unorm8_to_float(w_c & 255u);
 	const float tx = (float(x) + 0.5f) * rt_x, ty = (float(y) + 0.5f) * rt_y;
 	const bool hz = fmaxf(ax, az) > fmaxf(ay, aw);
 	float ox = 0.0f, oy = ay, oz = 0.0f, ow = aw;
@@ -281,73 +253,27 @@ AA_HD uint32_t smaa_blend_pixel(const Color &c, uint32_t w_c, uint32_t w_r, uint
 // ---- fp16 storage helpers ------------------------------------------------------------------------------------------------------
 // Two halves in a dword, as RGBA16F / RG16F texels hold them.  On the device the conversion rides in v_fma_mix_f32 (exact
 // conversion + one fused multiply-add); the host form states the same arithmetic.
+GR_HD float half_lo(uint32_t p) { return gr_core::half_to_float(p & 0xffffu); }
+GR_HD float half_hi(uint32_t p) { return gr_core::half_to_float(p >> 16); }
+GR_HD uint32_t pack_half2_rne(float lo, float hi) { return gr_core::float_to_half(lo) | (gr_core::float_to_half(hi) << 16); }
 #if defined(__HIP_DEVICE_COMPILE__)
-AA_HD float half_lo(uint32_t p) { return float(__builtin_bit_cast(_Float16, uint16_t(p & 0xffffu))); }
-AA_HD float half_hi(uint32_t p) { return float(__builtin_bit_cast(_Float16, uint16_t(p >> 16))); }
-AA_HD float mad_half_lo(uint32_t p, float w, float acc)
+GR_HD float mad_half_lo(uint32_t p, float w, float acc)
 {
 	float r;
 	asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel_hi:[1,0,0]" : "=v"(r) : "v"(p), "v"(w), "v"(acc));
 	return r;
 }
-AA_HD float mad_half_hi(uint32_t p, float w, float acc)
+GR_HD float mad_half_hi(uint32_t p, float w, float acc)
 {
 	float r;
 	asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(p), "v"(w), "v"(acc));
 	return r;
 }
-AA_HD uint32_t pack_half2_rne(float lo, float hi)
-{
-	return uint32_t(__builtin_bit_cast(uint16_t, _Float16(lo))) | (uint32_t(__builtin_bit_cast(uint16_t, _Float16(hi))) << 16);
-}
-AA_HD float approx_rcp(float v) { return __builtin_amdgcn_rcpf(v); }   // 1 ulp; used where the result is stored as fp16
-AA_HD float approx_sqrt(float v) { return __builtin_amdgcn_sqrtf(v); } // 1 ulp
+GR_HD float approx_rcp(float v) { return __builtin_amdgcn_rcpf(v); }   // 1 ulp; used where the result is stored as fp16
+GR_HD float approx_sqrt(float v) { return __builtin_amdgcn_sqrtf(v); } // 1 ulp
 #else
-inline float half_bits_to_float(uint32_t h)
-{
-	const uint32_t s = (h & 0x8000u) << 16, e = (h >> 10) & 0x1fu, m = h & 0x3ffu;
-	uint32_t u;
-	if (e == 0)
-	{
-		const float v = float(m) * 5.9604644775390625e-08f;
-		return s ? -v : v;
-	}
-	u = e == 31 ? (s | 0x7f800000u | (m << 13)) : (s | ((e + 112u) << 23) | (m << 13));
-	float f;
-	memcpy(&f, &u, 4);
-	return f;
-}
-inline uint32_t float_to_half_bits_rne(float f)
-{
-	uint32_t u;
-	memcpy(&u, &f, 4);
-	const uint32_t s = (u >> 16) & 0x8000u, a = u & 0x7fffffffu;
-	if (a >= 0x7f800000u)
-		return s | 0x7c00u | ((a > 0x7f800000u) ? (0x200u | ((a >> 13) & 0x3ffu)) : 0u);
-	if (a >= 0x477ff000u)
-		return s | 0x7c00u;
-	if (a < 0x38800000u)
-	{
-		if (a < 0x33000000u)
-			return s;
-		const uint32_t e = a >> 23, m = (a & 0x7fffffu) | 0x800000u, shift = 126u - e;
-		uint32_t q = m >> shift;
-		const uint32_t rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1u);
-		if (rem > half || (rem == half && (q & 1u)))
-			q++;
-		return s | q;
-	}
-	uint32_t q = (((a >> 23) - 112u) << 10) | ((a & 0x7fffffu) >> 13);
-	const uint32_t rem = a & 0x1fffu;
-	if (rem > 0x1000u || (rem == 0x1000u && (q & 1u)))
-		q++;
-	return s | q;
-}
-inline float half_lo(uint32_t p) { return half_bits_to_float(p & 0xffffu); }
-inline float half_hi(uint32_t p) { return half_bits_to_float(p >> 16); }
 inline float mad_half_lo(uint32_t p, float w, float acc) { return fmaf(half_lo(p), w, acc); }
 inline float mad_half_hi(uint32_t p, float w, float acc) { return fmaf(half_hi(p), w, acc); }
-inline uint32_t pack_half2_rne(float lo, float hi) { return float_to_half_bits_rne(lo) | (float_to_half_bits_rne(hi) << 16); }
 inline float approx_rcp(float v) { return 1.0f / v; }
 inline float approx_sqrt(float v) { return sqrtf(v); }
 #endif
@@ -361,7 +287,7 @@ struct u2
 // The resolve's result is stored as fp16 and compared at 3 ulp fp16: divisions and square roots on continuous paths use the
 // hardware reciprocal / root (1 ulp fp32), products of tap weights are formed first (w_x * w_y) and folded into one fma per
 // channel -- a few fp32 ulps.  What takes decisions (texel selection, the neighbourhood's nearest depth) is exact.
-AA_HD f3 taa_from_hdr(float r, float g, float b)
+GR_HD f3 taa_from_hdr(float r, float g, float b)
 {
 	r *= 8.0f;
 	g *= 8.0f;
@@ -372,7 +298,7 @@ AA_HD f3 taa_from_hdr(float r, float g, float b)
 	b *= s;
 	return {0.25f * r + 0.5f * g + 0.25f * b, 0.5f * g - 0.25f * r - 0.25f * b, 0.5f * r - 0.5f * b};
 }
-AA_HD f3 taa_to_hdr(f3 c)
+GR_HD f3 taa_to_hdr(f3 c)
 {
 	const float tmp = c.x - c.y;
 	const float r = fminf(fmaxf(tmp + c.z, 0.0f), 0.999f), g = fminf(fmaxf(c.x + c.y, 0.0f), 0.999f), b = fminf(fmaxf(tmp - c.z, 0.0f), 0.999f);
@@ -394,7 +320,7 @@ struct TaaPush
 // colour in fp32 as well; hist_row_first / hist_row_last = the first and last history row the pixel fetched (row bands: a rank
 // only holds the history rows around its band).
 template <int QUALITY, typename Tile, typename Mv, typename Hist>
-AA_HD void taa_pixel(const Tile &t, const Mv &mvs, const Hist &hist, int x, int y, int w, int h, const TaaPush &P, u2 &out_color, u2 &out_history,
+GR_HD void taa_pixel(const Tile &t, const Mv &mvs, const Hist &hist, int x, int y, int w, int h, const TaaPush &P, u2 &out_color, u2 &out_history,
                      f3 &out_color_f32, int &hist_row_first, int &hist_row_last)
 {
 	const float u = (float(x) + 0.5f) * P.rt[0], v = (float(y) + 0.5f) * P.rt[1];

@@ -94,7 +94,7 @@ __global__ __launch_bounds__(FAST_BW *FAST_BH) void k_fxaa_fast(const uint8_t *i
 			s_list[before + uint32_t(__popcll(mine & ((1ull << lane) - 1ull)))] = uint16_t(tid);
 	}
 	const auto decode = [](uint32_t t) {
-		const float r = aa::unorm8_decode(t & 255u), g = aa::unorm8_decode((t >> 8) & 255u), b = aa::unorm8_decode((t >> 16) & 255u);
+		const float r = aa::unorm8_to_float(t & 255u), g = aa::unorm8_to_float((t >> 8) & 255u), b = aa::unorm8_to_float((t >> 16) & 255u);
 		return make_float4(r, g, b, aa::luma_of(r, g, b, aa::FXAA_LUMA_R, aa::FXAA_LUMA_G, aa::FXAA_LUMA_B));
 	};
 	if (interior)
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(FAST_BW *FAST_BH) void k_smaa_edges_fast(const uint
 	{
 		const int ty = i / TW, tx = i - ty * TW;
 		const uint32_t t = load_rgba8_clamped(in, in_pitch, w, h, bx - 2 + tx, by - 2 + ty);
-		s_luma[i] = aa::luma_of(aa::unorm8_decode(t & 255u), aa::unorm8_decode((t >> 8) & 255u), aa::unorm8_decode((t >> 16) & 255u), aa::SMAA_LUMA_R,
+		s_luma[i] = aa::luma_of(aa::unorm8_to_float(t & 255u), aa::unorm8_to_float((t >> 8) & 255u), aa::unorm8_to_float((t >> 16) & 255u), aa::SMAA_LUMA_R,
 		                        aa::SMAA_LUMA_G, aa::SMAA_LUMA_B);
 	}
 	__syncthreads();

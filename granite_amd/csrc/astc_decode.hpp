@@ -19,12 +19,7 @@
 // and four offsets that decode_block() derives once.  The decoder is total: every shift and bit offset is bounded for any 16 bytes.
 #pragma once
 #include <cstdint>
-
-#if defined(__HIPCC__)
-#define GR_ASTC_FN __host__ __device__ inline __attribute__((always_inline))
-#else
-#define GR_ASTC_FN inline
-#endif
+#include "core_base.hpp"
 
 namespace gr_astc
 {
@@ -266,7 +261,7 @@ constexpr Tables build_tables()
 	return t;
 }
 
-GR_ASTC_FN const Tables &tables()
+GR_HD const Tables &tables()
 {
 	static constexpr Tables t = build_tables();
 	return t;
@@ -280,7 +275,7 @@ struct Payload
 };
 
 // n bits (0..16) from bit `off` (>= 0); bits at and above 128 read as 0.
-GR_ASTC_FN uint32_t bits(const Payload &p, int off, int n)
+GR_HD uint32_t bits(const Payload &p, int off, int n)
 {
 	if (n <= 0 || off >= 128)
 		return 0;
@@ -295,7 +290,7 @@ GR_ASTC_FN uint32_t bits(const Payload &p, int off, int n)
 }
 
 // The low n bits (0..128) kept.
-GR_ASTC_FN Payload keep_low(const Payload &p, int n)
+GR_HD Payload keep_low(const Payload &p, int n)
 {
 	Payload r;
 	r.lo = n >= 64 ? p.lo : n <= 0 ? 0 : p.lo & ((uint64_t(1) << n) - 1);
@@ -303,7 +298,7 @@ GR_ASTC_FN Payload keep_low(const Payload &p, int n)
 	return r;
 }
 
-GR_ASTC_FN uint64_t reverse64(uint64_t v)
+GR_HD uint64_t reverse64(uint64_t v)
 {
 	v = ((v >> 1) & 0x5555555555555555ull) | ((v & 0x5555555555555555ull) << 1);
 	v = ((v >> 2) & 0x3333333333333333ull) | ((v & 0x3333333333333333ull) << 2);
@@ -314,7 +309,7 @@ GR_ASTC_FN uint64_t reverse64(uint64_t v)
 }
 
 // Value `index` of an integer sequence that starts at bit `start`: trits in groups of five (8 shared bits), quints in groups of three (7).
-GR_ASTC_FN int sequence_value(const Payload &p, int start, int index, Quant q)
+GR_HD int sequence_value(const Payload &p, int start, int index, Quant q)
 {
 	const int b = q.bits;
 	if (q.trits)
@@ -356,20 +351,20 @@ struct Block
 	uint8_t error_partitions; // bit p: partition p has an HDR endpoint mode, its texels take the error colour
 };
 
-GR_ASTC_FN void set_constant(Block &b, uint32_t colour)
+GR_HD void set_constant(Block &b, uint32_t colour)
 {
 	b.flags = BLOCK_CONSTANT;
 	b.constant = colour;
 }
 
-GR_ASTC_FN int clamp255(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
+GR_HD int clamp255(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
 // clamp255(sum >> 1), clamped first.  Written the other way round, two of these next to each other in a word are selected as one
 // v_ashr_pk_u8_i32 on gfx950, whose result keeps the upper half of its destination register where the code around it expects zeros:
 // with a negative sum left in that register the blue and alpha bytes came out as 0xff on the device (the host build was right).
-GR_ASTC_FN int half_clamp255(int sum) { return (sum < 0 ? 0 : sum > 511 ? 511 : sum) >> 1; }
-GR_ASTC_FN uint32_t rgba(int r, int g, int b, int a) { return uint32_t(r) | (uint32_t(g) << 8) | (uint32_t(b) << 16) | (uint32_t(a) << 24); }
+GR_HD int half_clamp255(int sum) { return (sum < 0 ? 0 : sum > 511 ? 511 : sum) >> 1; }
+GR_HD uint32_t rgba(int r, int g, int b, int a) { return uint32_t(r) | (uint32_t(g) << 8) | (uint32_t(b) << 16) | (uint32_t(a) << 24); }
 // (a, b) -> b with a's top bit shifted in, a as a signed 6-bit offset.
-GR_ASTC_FN void bit_transfer_signed(int &a, int &b)
+GR_HD void bit_transfer_signed(int &a, int &b)
 {
 	b = (b >> 1) | (a & 0x80);
 	a = (a >> 1) & 0x3f;
@@ -378,7 +373,7 @@ GR_ASTC_FN void bit_transfer_signed(int &a, int &b)
 }
 
 // The LDR endpoint modes.  v: the mode's 2, 4, 6 or 8 unquantised values.  Returns false for an HDR mode (2, 3, 7, 11, 14, 15).
-GR_ASTC_FN bool endpoints_of_mode(int mode, const int v_in[8], uint32_t &e0, uint32_t &e1)
+GR_HD bool endpoints_of_mode(int mode, const int v_in[8], uint32_t &e0, uint32_t &e1)
 {
 	int v[8];
 	for (int i = 0; i < 8; i++)
@@ -460,7 +455,7 @@ GR_ASTC_FN bool endpoints_of_mode(int mode, const int v_in[8], uint32_t &e0, uin
 	}
 }
 
-GR_ASTC_FN uint32_t hash52(uint32_t p)
+GR_HD uint32_t hash52(uint32_t p)
 {
 	p ^= p >> 15;
 	p -= p << 17;
@@ -476,7 +471,7 @@ GR_ASTC_FN uint32_t hash52(uint32_t p)
 }
 
 // The specification's partition hash (astc_select_partition) up to the point where x and y enter.
-GR_ASTC_FN void partition_hash(Block &b, int seed, int partitions)
+GR_HD void partition_hash(Block &b, int seed, int partitions)
 {
 	const uint32_t rnum = hash52(uint32_t(seed + (partitions - 1) * 1024));
 	int sh1, sh2;
@@ -502,7 +497,7 @@ GR_ASTC_FN void partition_hash(Block &b, int seed, int partitions)
 }
 
 // Everything about a block that does not depend on the texel.  bw x bh: the footprint.
-GR_ASTC_FN void decode_block(const Payload &p, int bw, int bh, Block &b)
+GR_HD void decode_block(const Payload &p, int bw, int bh, Block &b)
 {
 	const uint32_t x = uint32_t(p.lo);
 	b.flags = 0;
@@ -667,7 +662,7 @@ GR_ASTC_FN void decode_block(const Payload &p, int bw, int bh, Block &b)
 
 // ---- the texel half ---------------------------------------------------------------------------------------------------------------
 
-GR_ASTC_FN int partition_of(const Block &b, int x, int y, bool small_block)
+GR_HD int partition_of(const Block &b, int x, int y, bool small_block)
 {
 	if (small_block)
 	{
@@ -686,7 +681,7 @@ GR_ASTC_FN int partition_of(const Block &b, int x, int y, bool small_block)
 }
 
 // Texel (x, y) of a bw x bh footprint, as the four bytes of R8G8B8A8.
-GR_ASTC_FN uint32_t decode_texel(const Block &b, int x, int y, int bw, int bh)
+GR_HD uint32_t decode_texel(const Block &b, int x, int y, int bw, int bh)
 {
 	if (b.flags & BLOCK_CONSTANT)
 		return b.constant;

@@ -11,12 +11,7 @@
 // The partition, anchor and weight tables are constants of the formats (Khronos Data Format Specification, BPTC chapter).
 #pragma once
 #include <cstdint>
-
-#if defined(__HIPCC__)
-#define GR_BC_FN __host__ __device__ inline __attribute__((always_inline))
-#else
-#define GR_BC_FN inline
-#endif
+#include "core_base.hpp"
 
 namespace gr_bc
 {
@@ -45,7 +40,7 @@ struct Payload
 };
 
 // n bits (0..32) of the payload from bit `off`; off + n <= 128.
-GR_BC_FN uint32_t bits(const Payload &p, int off, int n)
+GR_HD uint32_t bits(const Payload &p, int off, int n)
 {
 	if (n <= 0)
 		return 0;
@@ -59,14 +54,14 @@ GR_BC_FN uint32_t bits(const Payload &p, int off, int n)
 	return uint32_t(v) & (n >= 32 ? ~0u : ((1u << n) - 1u));
 }
 
-GR_BC_FN int sign_extend(uint32_t v, int n) { return n >= 32 ? int(v) : int(v << (32 - n)) >> (32 - n); }
+GR_HD int sign_extend(uint32_t v, int n) { return n >= 32 ? int(v) : int(v << (32 - n)) >> (32 - n); }
 // n / d rounded to nearest, halves up.
-GR_BC_FN uint32_t round_div(uint32_t n, uint32_t d) { return (2u * n + d) / (2u * d); }
+GR_HD uint32_t round_div(uint32_t n, uint32_t d) { return (2u * n + d) / (2u * d); }
 
 // ---- BC1 colour block (also the colour half of BC2 / BC3) --------------------------------------------------------------------
 
 // The four palette entries as R | G << 8 | B << 16 | 0xff << 24.  `punch_through` is what index 3 of the three-colour mode stores.
-GR_BC_FN void bc1_palette(uint32_t endpoints, bool always_four, uint32_t punch_through, uint32_t pal[4])
+GR_HD void bc1_palette(uint32_t endpoints, bool always_four, uint32_t punch_through, uint32_t pal[4])
 {
 	const uint32_t c0 = endpoints & 0xffffu, c1 = endpoints >> 16;
 	const uint32_t red0 = c0 >> 11, green0 = (c0 >> 5) & 63u, blue0 = c0 & 31u;
@@ -86,11 +81,11 @@ GR_BC_FN void bc1_palette(uint32_t endpoints, bool always_four, uint32_t punch_t
 	}
 }
 
-GR_BC_FN uint32_t select4(uint32_t i, const uint32_t pal[4]) { return (i & 2u) ? ((i & 1u) ? pal[3] : pal[2]) : ((i & 1u) ? pal[1] : pal[0]); }
+GR_HD uint32_t select4(uint32_t i, const uint32_t pal[4]) { return (i & 2u) ? ((i & 1u) ? pal[3] : pal[2]) : ((i & 1u) ? pal[1] : pal[0]); }
 
 // ---- RGTC channel block (BC4, both halves of BC5, the alpha half of BC3) -----------------------------------------------------
 
-GR_BC_FN uint32_t rgtc_value(uint32_t e0, uint32_t e1, uint32_t k)
+GR_HD uint32_t rgtc_value(uint32_t e0, uint32_t e1, uint32_t k)
 {
 	if (k < 2u)
 		return k ? e1 : e0;
@@ -102,12 +97,12 @@ GR_BC_FN uint32_t rgtc_value(uint32_t e0, uint32_t e1, uint32_t k)
 }
 
 // Texel `pixel` (0..15) of an RGTC block.
-GR_BC_FN uint32_t rgtc_texel(uint64_t block, int pixel) { return rgtc_value(uint32_t(block) & 0xffu, uint32_t(block >> 8) & 0xffu, uint32_t(block >> (16 + 3 * pixel)) & 7u); }
+GR_HD uint32_t rgtc_texel(uint64_t block, int pixel) { return rgtc_value(uint32_t(block) & 0xffu, uint32_t(block >> 8) & 0xffu, uint32_t(block >> (16 + 3 * pixel)) & 7u); }
 
 // ---- BPTC tables --------------------------------------------------------------------------------------------------------------
 
 // Subset of each texel, one bit per texel (two subsets) or two (three subsets), texel 0 in the low bits.
-GR_BC_FN uint32_t partition2(uint32_t shape)
+GR_HD uint32_t partition2(uint32_t shape)
 {
 	static constexpr uint16_t table[64] = {
 		0xcccc, 0x8888, 0xeeee, 0xecc8, 0xc880, 0xfeec, 0xfec8, 0xec80, 0xc800, 0xffec, 0xfe80, 0xe800, 0xffe8, 0xff00, 0xfff0, 0xf000,
@@ -117,7 +112,7 @@ GR_BC_FN uint32_t partition2(uint32_t shape)
 	return table[shape];
 }
 
-GR_BC_FN uint32_t partition3(uint32_t shape)
+GR_HD uint32_t partition3(uint32_t shape)
 {
 	static constexpr uint32_t table[64] = {
 		0xaa685050u, 0x6a5a5040u, 0x5a5a4200u, 0x5450a0a8u, 0xa5a50000u, 0xa0a05050u, 0x5555a0a0u, 0x5a5a5050u,
@@ -132,7 +127,7 @@ GR_BC_FN uint32_t partition3(uint32_t shape)
 }
 
 // Anchor texel of the second subset of a two-subset shape.
-GR_BC_FN int anchor2(uint32_t shape)
+GR_HD int anchor2(uint32_t shape)
 {
 	static constexpr uint8_t table[64] = {15, 15, 15, 15, 15, 15, 15, 15, 15, 15, 15, 15, 15, 15, 15, 15, 15, 2, 8, 2, 2, 8, 8, 15, 2, 8, 2, 2, 8, 8, 2, 2,
 	                                      15, 15, 6, 8, 2, 8, 15, 15, 2, 8, 2, 2, 2, 15, 15, 6, 6, 2, 6, 8, 15, 15, 2, 2, 15, 15, 15, 15, 15, 2, 2, 15};
@@ -140,7 +135,7 @@ GR_BC_FN int anchor2(uint32_t shape)
 }
 
 // Anchor texels of the second and third subset of a three-subset shape, second | third << 4.
-GR_BC_FN uint32_t anchor3(uint32_t shape)
+GR_HD uint32_t anchor3(uint32_t shape)
 {
 	static constexpr uint8_t second[64] = {3, 3, 15, 15, 8, 3, 15, 15, 8, 8, 6, 6, 6, 5, 3, 3, 3, 3, 8, 15, 3, 3, 6, 10, 5, 8, 8, 6, 8, 5, 15, 15,
 	                                       8, 15, 3, 5, 6, 10, 8, 15, 15, 3, 15, 5, 15, 15, 15, 15, 3, 15, 5, 5, 5, 8, 5, 10, 5, 10, 8, 13, 15, 12, 3, 3};
@@ -150,7 +145,7 @@ GR_BC_FN uint32_t anchor3(uint32_t shape)
 }
 
 // Interpolation weight of an n-bit index (n = 2, 3, 4): 0, 21, 43, 64 / 0, 9, ... 64 / 0, 4, 9, ... 64.
-GR_BC_FN uint32_t bptc_weight(int n, uint32_t index)
+GR_HD uint32_t bptc_weight(int n, uint32_t index)
 {
 	const uint32_t top = (1u << n) - 1u;
 	return (64u * index + top / 2u) / top;
@@ -178,11 +173,11 @@ constexpr Bc7Mode bc7_mode(int mode)
 	}
 }
 
-GR_BC_FN uint32_t select3(uint32_t s, uint32_t a, uint32_t b, uint32_t c) { return s == 0u ? a : s == 1u ? b : c; }
+GR_HD uint32_t select3(uint32_t s, uint32_t a, uint32_t b, uint32_t c) { return s == 0u ? a : s == 1u ? b : c; }
 
 // Rows [row0, row0 + ROWS) of a block of mode MODE as RGBA8 words.
 template <int MODE, int ROWS>
-GR_BC_FN void bc7_rows(const Payload &p, int row0, uint32_t (*words)[ROW_WORDS_MAX])
+GR_HD void bc7_rows(const Payload &p, int row0, uint32_t (*words)[ROW_WORDS_MAX])
 {
 	constexpr Bc7Mode m = bc7_mode(MODE);
 	constexpr int channels = m.alpha_bits ? 4 : 3;
@@ -307,7 +302,7 @@ GR_BC_FN void bc7_rows(const Payload &p, int row0, uint32_t (*words)[ROW_WORDS_M
 }
 
 template <int ROWS>
-GR_BC_FN void bc7_block_rows(const Payload &p, int row0, uint32_t (*words)[ROW_WORDS_MAX])
+GR_HD void bc7_block_rows(const Payload &p, int row0, uint32_t (*words)[ROW_WORDS_MAX])
 {
 	// the mode is the position of the lowest set bit of the first word; none in the low byte = reserved: all zero
 	const uint32_t low = uint32_t(p.lo) & 0xffu;
@@ -377,7 +372,7 @@ constexpr Bc6Mode bc6_mode(int low5)
 }
 
 template <bool SIGNED>
-GR_BC_FN int bc6_unquantize(int v, int n)
+GR_HD int bc6_unquantize(int v, int n)
 {
 	if (SIGNED)
 	{
@@ -405,7 +400,7 @@ GR_BC_FN int bc6_unquantize(int v, int n)
 
 // The interpolated 17-bit value to the bits of a half: scale by 31/64 (unsigned) or 31/32 with the sign in bit 15 (signed; no -0).
 template <bool SIGNED>
-GR_BC_FN uint32_t bc6_finish(int v)
+GR_HD uint32_t bc6_finish(int v)
 {
 	if (!SIGNED)
 		return uint32_t(v * 31) >> 6;
@@ -418,7 +413,7 @@ GR_BC_FN uint32_t bc6_finish(int v)
 }
 
 template <int LOW5, bool SIGNED, int ROWS>
-GR_BC_FN void bc6_rows(const Payload &p, int row0, uint32_t (*words)[ROW_WORDS_MAX])
+GR_HD void bc6_rows(const Payload &p, int row0, uint32_t (*words)[ROW_WORDS_MAX])
 {
 	constexpr Bc6Mode m = bc6_mode(LOW5);
 	constexpr int base_low = m.endpoint_bits < 10 ? m.endpoint_bits : 10;
@@ -486,7 +481,7 @@ GR_BC_FN void bc6_rows(const Payload &p, int row0, uint32_t (*words)[ROW_WORDS_M
 }
 
 template <bool SIGNED, int ROWS>
-GR_BC_FN void bc6_block_rows(const Payload &p, int row0, uint32_t (*words)[ROW_WORDS_MAX])
+GR_HD void bc6_block_rows(const Payload &p, int row0, uint32_t (*words)[ROW_WORDS_MAX])
 {
 	const uint32_t low5 = uint32_t(p.lo) & 31u;
 	switch ((low5 & 2u) ? low5 : (low5 & 1u))
@@ -521,7 +516,7 @@ GR_BC_FN void bc6_block_rows(const Payload &p, int row0, uint32_t (*words)[ROW_W
 
 // Rows [row0, row0 + ROWS) of the block, words[r] = the row's 4 texels as little-endian words (texel_bytes(KIND) each).
 template <int KIND, int ROWS>
-GR_BC_FN void decode_rows(const Payload &p, int row0, uint32_t (*words)[ROW_WORDS_MAX])
+GR_HD void decode_rows(const Payload &p, int row0, uint32_t (*words)[ROW_WORDS_MAX])
 {
 	if (KIND == KIND_BC7)
 		bc7_block_rows<ROWS>(p, row0, words);

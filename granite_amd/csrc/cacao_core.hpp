@@ -25,22 +25,15 @@
 //   - UNORM8 loads are v / 255, SNORM8 loads max(v / 127, -1), the 10-bit UNORM load v / 1023; UNORM8 stores are
 //     uint(saturate(c) * 255 + 0.5) as everywhere in this project, SNORM8 stores floor(clamp(c, -1, 1) * 127 + 0.5).
 #pragma once
-#include "env_core.hpp"
+#include "core_base.hpp"
 #include "../../include/granite_hip.h"
-
-#if defined(__HIPCC__)
-#define CACAO_HD __host__ __device__ __forceinline__
-#define CACAO_UNROLL _Pragma("unroll")
-#else
-#define CACAO_HD inline
-#define CACAO_UNROLL
-#endif
 
 namespace gr_cacao
 {
-using gr_env::clampi;
-using gr_env::half_to_float;
-using gr_env::linear_axis;
+using gr_core::clampi;
+using gr_core::float_to_half_pinned; // f32tof16 of a value that is an fp32 result first
+using gr_core::half_to_float;
+using gr_core::linear_axis;
 
 constexpr uint32_t PASSES = 4u, DEPTH_MIPS = 4u;
 constexpr int MAX_TAPS = 32, ADAPTIVE_BASE_TAPS = 5, ADAPTIVE_FLEXIBLE_TAPS = MAX_TAPS - ADAPTIVE_BASE_TAPS, Q2_TAPS = 12;
@@ -194,7 +187,7 @@ inline void update_per_pass_constants(gr_cacao_constants &c, const gr_cacao_buff
 }
 
 // ---- the workspace --------------------------------------------------------------------------------------------------------------
-CACAO_HD uint32_t mip_extent(uint32_t size, uint32_t k)
+GR_HD uint32_t mip_extent(uint32_t size, uint32_t k)
 {
 	const uint32_t n = size >> k;
 	return n ? n : 1u;
@@ -250,30 +243,16 @@ inline Workspace workspace_layout(uint32_t width, uint32_t height)
 }
 
 // ---- small arithmetic -------------------------------------------------------------------------------------------------------------
-CACAO_HD float saturate(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
-// v / 255 for an integer v in [0, 255], bit for bit (device_common.hpp's unorm8_to_float, tests/test_oracle_kat.py; checked again for all
-// 256 inputs by tests/test_cacao_core_cpu.py): 1 / 255 split into its fp32 rounding and the remainder, one rounding at the end.
-CACAO_HD float unorm8(uint32_t v)
-{
-	const float f = float(v);
-	return fmaf(f, 0x1.010102p-8f, f * -0x1.fdfdfep-33f);
-}
+GR_HD float saturate(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
+// v / 255 for an integer v in [0, 255], bit for bit (checked again for all 256 inputs by tests/test_cacao_core_cpu.py)
+GR_HD float unorm8(uint32_t v) { return gr_core::unorm8_to_float(v); }
 // k / 3 for k in 0 .. 3, bit for bit, without the division
 static_assert(2.0f * (1.0f / 3.0f) == 2.0f / 3.0f && 3.0f * (1.0f / 3.0f) == 1.0f, "k * (1 / 3) is k / 3 for the four edge levels");
-CACAO_HD float third(uint32_t k) { return float(k) * (1.0f / 3.0f); }
-CACAO_HD float snorm8(uint32_t v) { return fmaxf(float(int8_t(v)) / 127.0f, -1.0f); }
-CACAO_HD uint32_t to_unorm8(float c) { return uint32_t(saturate(c) * 255.0f + 0.5f); }
-CACAO_HD uint32_t to_snorm8(float c) { return uint32_t(int32_t(floorf(fminf(fmaxf(c, -1.0f), 1.0f) * 127.0f + 0.5f))) & 0xffu; }
-// f32tof16 of a value that is an fp32 result first.  On the device the value is pinned in a register before the conversion, so that
-// the compiler cannot fuse the operation before it into one mixed-precision instruction that rounds once (ocean_core.hpp).
-CACAO_HD uint32_t float_to_half(float f)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-	asm("" : "+v"(f));
-#endif
-	return gr_env::float_to_half(f);
-}
-CACAO_HD int mirrori(int i, int n)
+GR_HD float third(uint32_t k) { return float(k) * (1.0f / 3.0f); }
+GR_HD float snorm8(uint32_t v) { return fmaxf(float(int8_t(v)) / 127.0f, -1.0f); }
+GR_HD uint32_t to_unorm8(float c) { return uint32_t(saturate(c) * 255.0f + 0.5f); }
+GR_HD uint32_t to_snorm8(float c) { return uint32_t(int32_t(floorf(fminf(fmaxf(c, -1.0f), 1.0f) * 127.0f + 0.5f))) & 0xffu; }
+GR_HD int mirrori(int i, int n)
 {
 	const int period = 2 * n;
 	int m = i % period;
@@ -281,10 +260,10 @@ CACAO_HD int mirrori(int i, int n)
 		m += period;
 	return m < n ? m : period - 1 - m;
 }
-CACAO_HD float dot4(float ax, float ay, float az, float aw, float bx, float by, float bz, float bw) { return ax * bx + ay * by + az * bz + aw * bw; }
+GR_HD float dot4(float ax, float ay, float az, float aw, float bx, float by, float bz, float bw) { return ax * bx + ay * by + az * bz + aw * bw; }
 
 // Linear filtering of one channel; fetch(x, y) takes texel indices already wrapped.
-template <bool MIRROR, typename Fetch> CACAO_HD float sample_linear(Fetch fetch, int w, int h, float u, float v)
+template <bool MIRROR, typename Fetch> GR_HD float sample_linear(Fetch fetch, int w, int h, float u, float v)
 {
 	int ix, iy;
 	float a, b;
@@ -305,10 +284,10 @@ template <bool MIRROR, typename Fetch> CACAO_HD float sample_linear(Fetch fetch,
 	return t;
 }
 
-CACAO_HD float view_depth(const gr_cacao_constants &c, float screen_depth) { return c.DepthUnpackConsts[0] / (c.DepthUnpackConsts[1] - screen_depth); }
+GR_HD float view_depth(const gr_cacao_constants &c, float screen_depth) { return c.DepthUnpackConsts[0] / (c.DepthUnpackConsts[1] - screen_depth); }
 
 // FFX_CACAO_MipSmartAverage.  (-1 / EffectRadius * EffectRadius is what the shader says.)
-CACAO_HD float mip_smart_average(const gr_cacao_constants &c, float d0, float d1, float d2, float d3)
+GR_HD float mip_smart_average(const gr_cacao_constants &c, float d0, float d1, float d2, float d3)
 {
 	const float closest = fminf(fminf(d0, d1), fminf(d2, d3));
 	const float falloff = -1.0f / c.EffectRadius * c.EffectRadius;
@@ -319,7 +298,7 @@ CACAO_HD float mip_smart_average(const gr_cacao_constants &c, float d0, float d1
 }
 
 // FFX_CACAO_Prepare_LoadNormal of one A2B10G10R10 word (0 past the image), as the RGBA8_SNORM texel it is stored as
-CACAO_HD uint32_t prepare_normal(const gr_cacao_constants &c, uint32_t word)
+GR_HD uint32_t prepare_normal(const gr_cacao_constants &c, uint32_t word)
 {
 	const float nx = float(word & 1023u) / 1023.0f * c.NormalsUnpackMul + c.NormalsUnpackAdd;
 	const float ny = float((word >> 10) & 1023u) / 1023.0f * c.NormalsUnpackMul + c.NormalsUnpackAdd;
@@ -332,7 +311,7 @@ CACAO_HD uint32_t prepare_normal(const gr_cacao_constants &c, uint32_t word)
 	return to_snorm8(vx / len) | (to_snorm8(vy / len) << 8) | (to_snorm8(vz / len) << 16) | (to_snorm8(1.0f) << 24);
 }
 
-CACAO_HD float pack_edges(float l, float r, float t, float b)
+GR_HD float pack_edges(float l, float r, float t, float b)
 {
 	l = rintf(saturate(l) * 3.05f);
 	r = rintf(saturate(r) * 3.05f);
@@ -341,7 +320,7 @@ CACAO_HD float pack_edges(float l, float r, float t, float b)
 	return dot4(l, r, t, b, 64.0f / 255.0f, 16.0f / 255.0f, 4.0f / 255.0f, 1.0f / 255.0f);
 }
 // FFX_CACAO_UnpackEdges / FFX_CACAO_UnpackEdgesFloat16_4 of the sampled edge channel: left, right, top, bottom
-CACAO_HD void unpack_edges(const gr_cacao_constants &c, float packed_value, float e[4])
+GR_HD void unpack_edges(const gr_cacao_constants &c, float packed_value, float e[4])
 {
 	const uint32_t packed = uint32_t(packed_value * 255.5f);
 	e[0] = saturate(third((packed >> 6) & 3u) + c.InvSharpness);
@@ -406,17 +385,17 @@ inline PerPass per_pass_of(const gr_cacao_constants constants[4])
 	return p;
 }
 
-CACAO_HD float depth_texel(const Images &im, uint32_t pass, int mip, int x, int y)
+GR_HD float depth_texel(const Images &im, uint32_t pass, int mip, int x, int y)
 {
 	return half_to_float(reinterpret_cast<const uint16_t *>(im.depth[pass][mip])[size_t(y) * im.mip_w[mip] + x]);
 }
 // g_ViewspaceDepthTapSampler: nearest texel of the nearest mip, clamped
-CACAO_HD int nearest_mip(float lod)
+GR_HD int nearest_mip(float lod)
 {
 	const float t = ceilf(lod + 0.5f) - 1.0f;
 	return t > 0.0f ? (t < 3.0f ? int(t) : 3) : 0;
 }
-CACAO_HD float depth_tap(const Images &im, uint32_t pass, float u, float v, float lod)
+GR_HD float depth_tap(const Images &im, uint32_t pass, float u, float v, float lod)
 {
 	const int mip = nearest_mip(lod);
 	const int w = im.mip_w[mip], h = im.mip_h[mip];
@@ -424,7 +403,7 @@ CACAO_HD float depth_tap(const Images &im, uint32_t pass, float u, float v, floa
 	return depth_texel(im, pass, mip, x, y);
 }
 // g_DeinterleavedNormals[int3(coord, pass)]: zero outside the image
-CACAO_HD void normal_texel(const Images &im, uint32_t pass, int x, int y, float n[3])
+GR_HD void normal_texel(const Images &im, uint32_t pass, int x, int y, float n[3])
 {
 	uint32_t word = 0;
 	const bool inside = uint32_t(x) < uint32_t(im.half_w) && uint32_t(y) < uint32_t(im.half_h);
@@ -435,7 +414,7 @@ CACAO_HD void normal_texel(const Images &im, uint32_t pass, int x, int y, float 
 	n[2] = inside ? snorm8((word >> 16) & 0xffu) : 0.0f;
 }
 
-CACAO_HD float pixel_obscurance(const gr_cacao_constants &c, const float n[3], float dx, float dy, float dz, float falloff_mul_sq)
+GR_HD float pixel_obscurance(const gr_cacao_constants &c, const float n[3], float dx, float dy, float dz, float falloff_mul_sq)
 {
 	const float length_sq = dx * dx + dy * dy + dz * dz;
 	const float n_dot_d = (n[0] * dx + n[1] * dy + n[2] * dz) / sqrtf(length_sq);
@@ -449,7 +428,7 @@ struct TapState
 };
 // One depth sample of a tap pair: FFX_CACAO_SSAOTapInner (weight_mod >= 0) and one turn of FFX_CACAO_SSAOAddHits, which overwrites the
 // pattern's weight with the haloing term alone (weight_mod < 0 says so).
-CACAO_HD void tap_sample(const gr_cacao_constants &c, const Images &im, uint32_t pass, TapState &s, float u, float v, float lod, const float centre[3],
+GR_HD void tap_sample(const gr_cacao_constants &c, const Images &im, uint32_t pass, TapState &s, float u, float v, float lod, const float centre[3],
                          const float n[3], float falloff_mul_sq, float weight_mod)
 {
 	const float z = depth_tap(im, pass, u, v, lod);
@@ -470,7 +449,7 @@ CACAO_HD void tap_sample(const gr_cacao_constants &c, const Images &im, uint32_t
 // before the RG8 store.  lod_flag (host builds of the tests only, may be null): set when a tap's lod + 0.5 lies within 2^-10 of 1, 2
 // or 3, where the last bit of log2 selects the mip.
 template <int QUALITY, bool BASE>
-CACAO_HD void generate_texel(const gr_cacao_constants &c, const PerPass &pp, const Images &im, uint32_t pass, int X, int Y, float out[2], bool *lod_flag = nullptr)
+GR_HD void generate_texel(const gr_cacao_constants &c, const PerPass &pp, const Images &im, uint32_t pass, int X, int Y, float out[2], bool *lod_flag = nullptr)
 {
 	const float svx = float(X), svy = float(Y);
 	const float inv_w = c.DeinterleavedDepthBufferInverseDimensions[0], inv_h = c.DeinterleavedDepthBufferInverseDimensions[1];
@@ -611,7 +590,7 @@ CACAO_HD void generate_texel(const gr_cacao_constants &c, const PerPass &pp, con
 }
 
 // ---- importance map -----------------------------------------------------------------------------------------------------------------
-CACAO_HD float importance_texel(const gr_cacao_constants &c, const Images &im, int X, int Y)
+GR_HD float importance_texel(const gr_cacao_constants &c, const Images &im, int X, int Y)
 {
 	const float u = (float(2 * X) + 0.5f) * c.SSAOBufferInverseDimensions[0], v = (float(2 * Y) + 0.5f) * c.SSAOBufferInverseDimensions[1];
 	int ix, iy;
@@ -640,7 +619,7 @@ CACAO_HD float importance_texel(const gr_cacao_constants &c, const Images &im, i
 }
 
 // PostprocessImportanceMapA (B = false) and B: the four taps half a texel and one and a half texels off the centre
-template <bool B> CACAO_HD float importance_postprocess_texel(const gr_cacao_constants &c, const Images &im, int X, int Y)
+template <bool B> GR_HD float importance_postprocess_texel(const gr_cacao_constants &c, const Images &im, int X, int Y)
 {
 	const uint8_t *map = im.importance[B ? 1 : 0];
 	const int w = im.imp_w, h = im.imp_h;
@@ -670,7 +649,7 @@ template <bool B> CACAO_HD float importance_postprocess_texel(const gr_cacao_con
 
 // ---- blur -----------------------------------------------------------------------------------------------------------------------------
 // FFX_CACAO_CalcBlurredSampleF16_4 for one of its four lanes
-CACAO_HD float blurred_sample(const float e[4], float centre, float left, float right, float top, float bottom)
+GR_HD float blurred_sample(const float e[4], float centre, float left, float right, float top, float bottom)
 {
 	float sum = centre * 0.5f, weight = 0.5f;
 	sum += left * e[0];
@@ -685,7 +664,7 @@ CACAO_HD float blurred_sample(const float e[4], float centre, float left, float 
 }
 
 // ---- apply ------------------------------------------------------------------------------------------------------------------------------
-CACAO_HD uint32_t apply_texel(const gr_cacao_constants &c, const Images &im, uint32_t from_pong, int X, int Y)
+GR_HD uint32_t apply_texel(const gr_cacao_constants &c, const Images &im, uint32_t from_pong, int X, int Y)
 {
 	const int hx = X / 2, hy = Y / 2, mx = X % 2, my = Y % 2;
 	const int ic = mx + my * 2, ih = (1 - mx) + my * 2, iv = mx + (1 - my) * 2, id = (1 - mx) + (1 - my) * 2;
@@ -753,7 +732,7 @@ __global__ __launch_bounds__(GROUP *GROUP) void k_cacao_prepare_depths(PrepareDe
 	const auto store = [&a](uint32_t mip, uint32_t layer, uint32_t x, uint32_t y, float value) {
 		const uint32_t w = mip_extent(a.ws.half_w, mip), h = mip_extent(a.ws.half_h, mip);
 		if (x < w && y < h)
-			reinterpret_cast<uint16_t *>(a.workspace + a.ws.depth_mip[mip] + uint64_t(layer) * w * h * 2u)[size_t(y) * w + x] = uint16_t(float_to_half(value));
+			reinterpret_cast<uint16_t *>(a.workspace + a.ws.depth_mip[mip] + uint64_t(layer) * w * h * 2u)[size_t(y) * w + x] = uint16_t(float_to_half_pinned(value));
 	};
 	for (uint32_t l = 0; l < 4; l++)
 		store(0, l, tx, ty, d[l]);
@@ -902,21 +881,21 @@ __global__ __launch_bounds__(BLUR_GROUP *BLUR_GROUP) void k_cacao_blur(BlurLaunc
 
 	// the apron no lane stores: read by the outermost lanes, whose results the shrinking tile discards
 	if (tid_x == 0)
-		CACAO_UNROLL
+		GR_UNROLL
 		for (int y = 0; y < BLUR_TILE_H; y++)
 			s_front[buffer_y + y][0] = s_back[buffer_y + y][0] = s_front[buffer_y + y][BLUR_ARRAY_W - 1] = s_back[buffer_y + y][BLUR_ARRAY_W - 1] = 0u;
 	if (tid_y == 0)
-		CACAO_UNROLL
+		GR_UNROLL
 		for (int x = 0; x < 2; x++)
 			s_front[0][buffer_x + x] = s_back[0][buffer_x + x] = s_front[BLUR_ARRAY_H - 1][buffer_x + x] = s_back[BLUR_ARRAY_H - 1][buffer_x + x] = 0u;
 
 	float edges[BLUR_TILE_H][BLUR_TILE_W][4];
 	uint32_t edge_bytes[BLUR_TILE_H][BLUR_TILE_W];
-	CACAO_UNROLL
+	GR_UNROLL
 	for (int y = 0; y < BLUR_TILE_H; y++)
 	{
 		float ssao[BLUR_TILE_W];
-		CACAO_UNROLL
+		GR_UNROLL
 		for (int x = 0; x < BLUR_TILE_W; x++)
 		{
 			// g_PointMirrorSampler at a texel centre: linear, mirrored
@@ -926,8 +905,8 @@ __global__ __launch_bounds__(BLUR_GROUP *BLUR_GROUP) void k_cacao_blur(BlurLaunc
 			unpack_edges(a.c, packed, edges[y][x]);
 			edge_bytes[y][x] = to_unorm8(packed);
 		}
-		s_front[buffer_y + y][buffer_x] = float_to_half(ssao[0]) | (float_to_half(ssao[1]) << 16);
-		s_front[buffer_y + y][buffer_x + 1] = float_to_half(ssao[2]) | (float_to_half(ssao[3]) << 16);
+		s_front[buffer_y + y][buffer_x] = float_to_half_pinned(ssao[0]) | (float_to_half_pinned(ssao[1]) << 16);
+		s_front[buffer_y + y][buffer_x + 1] = float_to_half_pinned(ssao[2]) | (float_to_half_pinned(ssao[3]) << 16);
 	}
 	__syncthreads();
 
@@ -935,7 +914,7 @@ __global__ __launch_bounds__(BLUR_GROUP *BLUR_GROUP) void k_cacao_blur(BlurLaunc
 	{
 		uint32_t(*src)[BLUR_ARRAY_W + 1] = (i & 1) ? s_back : s_front;
 		uint32_t(*dst)[BLUR_ARRAY_W + 1] = (i & 1) ? s_front : s_back;
-		CACAO_UNROLL
+		GR_UNROLL
 		for (int y = 0; y < BLUR_TILE_H; y++)
 		{
 			const int cx = buffer_x, cy = buffer_y + y;
@@ -946,18 +925,18 @@ __global__ __launch_bounds__(BLUR_GROUP *BLUR_GROUP) void k_cacao_blur(BlurLaunc
 			const float left[4] = {half_to_float(src[cy][cx - 1] >> 16), centre[0], centre[1], centre[2]};
 			const float right[4] = {centre[1], centre[2], centre[3], half_to_float(src[cy][cx + 2] & 0xffffu)};
 			float r[4];
-			CACAO_UNROLL
+			GR_UNROLL
 			for (int k = 0; k < 4; k++)
 				r[k] = blurred_sample(edges[y][k], centre[k], left[k], right[k], top[k], bottom[k]);
-			dst[cy][cx] = float_to_half(r[0]) | (float_to_half(r[1]) << 16);
-			dst[cy][cx + 1] = float_to_half(r[2]) | (float_to_half(r[3]) << 16);
+			dst[cy][cx] = float_to_half_pinned(r[0]) | (float_to_half_pinned(r[1]) << 16);
+			dst[cy][cx + 1] = float_to_half_pinned(r[2]) | (float_to_half_pinned(r[3]) << 16);
 		}
 		__syncthreads();
 	}
 
 	uint32_t(*result)[BLUR_ARRAY_W + 1] = (n & 1) ? s_back : s_front;
 	uint8_t *out = a.out[pass];
-	CACAO_UNROLL
+	GR_UNROLL
 	for (int y = 0; y < BLUR_TILE_H; y++)
 	{
 		const int output_y = BLUR_TILE_H * tid_y + y;
@@ -965,7 +944,7 @@ __global__ __launch_bounds__(BLUR_GROUP *BLUR_GROUP) void k_cacao_blur(BlurLaunc
 			continue;
 		const uint32_t r0 = result[buffer_y + y][buffer_x], r1 = result[buffer_y + y][buffer_x + 1];
 		const float value[4] = {half_to_float(r0 & 0xffffu), half_to_float(r0 >> 16), half_to_float(r1 & 0xffffu), half_to_float(r1 >> 16)};
-		CACAO_UNROLL
+		GR_UNROLL
 		for (int x = 0; x < BLUR_TILE_W; x++)
 		{
 			const int output_x = BLUR_TILE_W * tid_x + x, px = image_x + x, py = image_y + y;

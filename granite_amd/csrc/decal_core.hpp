@@ -27,27 +27,22 @@
 #pragma once
 #include <cmath>
 #include <cstdint>
-
-#if defined(__HIPCC__)
-#define GR_DECAL_FN __host__ __device__ inline __attribute__((always_inline))
-#else
-#define GR_DECAL_FN inline
-#endif
+#include "core_base.hpp"
 
 namespace gr_decal
 {
 constexpr uint32_t FORMAT_RGBA8_UNORM = 37u, FORMAT_RGBA8_SRGB = 43u; // GR_FORMAT_R8G8B8A8_UNORM / _SRGB (VkFormat values)
 
 struct Vec2 { float x, y; };
-struct Vec3 { float x, y, z; };
+using Vec3 = gr_core::f3;
 struct Vec4 { float x, y, z, w; };
 
 // GLSL min / max as glsl_cpu.hpp has them (fminf / fmaxf): the other operand where one is NaN.
-GR_DECAL_FN float min_f(float a, float b) { return fminf(a, b); }
-GR_DECAL_FN float max_f(float a, float b) { return fmaxf(a, b); }
+GR_HD float min_f(float a, float b) { return fminf(a, b); }
+GR_HD float max_f(float a, float b) { return fmaxf(a, b); }
 
 // column-major mat4 x vec4, summed column by column
-GR_DECAL_FN Vec4 mul_mat4(const float *m, float x, float y, float z, float w)
+GR_HD Vec4 mul_mat4(const float *m, float x, float y, float z, float w)
 {
 	Vec4 r = {m[0] * x, m[1] * x, m[2] * x, m[3] * x};
 	r = {r.x + m[4] * y, r.y + m[5] * y, r.z + m[6] * y, r.w + m[7] * y};
@@ -62,17 +57,17 @@ struct ScreenBB
 	Vec4 bb = {1.0f, 1.0f, -1.0f, -1.0f};
 	float lo_w = 1.0f, hi_w = -1.0f;
 };
-GR_DECAL_FN void update_bb(ScreenBB &s, const Vec4 &clip)
+GR_HD void update_bb(ScreenBB &s, const Vec4 &clip)
 {
 	s.lo_w = min_f(s.lo_w, clip.w);
 	s.hi_w = max_f(s.hi_w, clip.w);
 	const float px = clip.x / clip.w, py = clip.y / clip.w;
 	s.bb = {min_f(s.bb.x, px), min_f(s.bb.y, py), max_f(s.bb.z, px), max_f(s.bb.w, py)};
 }
-GR_DECAL_FN Vec4 add4(const Vec4 &a, const float *col) { return {a.x + col[0], a.y + col[1], a.z + col[2], a.w + col[3]}; }
+GR_HD Vec4 add4(const Vec4 &a, const float *col) { return {a.x + col[0], a.y + col[1], a.z + col[2], a.w + col[3]}; }
 
 // compute_decal_screen_bb (:37-67): the unit box's eight corners, built from corner0 and the columns
-GR_DECAL_FN Vec4 compute_decal_screen_bb(const float *mvp)
+GR_HD Vec4 compute_decal_screen_bb(const float *mvp)
 {
 	ScreenBB s;
 	const Vec4 corner0 = mul_mat4(mvp, -0.5f, -0.5f, -0.5f, 1.0f);
@@ -95,17 +90,17 @@ GR_DECAL_FN Vec4 compute_decal_screen_bb(const float *mvp)
 }
 
 // test_decal (:28-31), strict on both sides
-GR_DECAL_FN bool test_decal(float u, float v, float stride_u, float stride_v, const Vec4 &bb)
+GR_HD bool test_decal(float u, float v, float stride_u, float stride_v, const Vec4 &bb)
 {
 	return u + stride_u > bb.x && v + stride_v > bb.y && u < bb.z && v < bb.w;
 }
 
 // 2.0 * vec2(cell) * inv_resolution - 1.0 for one axis (:80,98)
-GR_DECAL_FN float cell_uv(uint32_t cell, float inv_resolution) { return 2.0f * float(cell) * inv_resolution - 1.0f; }
+GR_HD float cell_uv(uint32_t cell, float inv_resolution) { return 2.0f * float(cell) * inv_resolution - 1.0f; }
 
 // ---- volumetric_decal.h ------------------------------------------------------------------------------------------------------------------
 // clustering.vert:10-13 / clustering.frag:37-39: clip = inv_view_projection * (ndc.xy, depth, 1), pos = clip.xyz / clip.w
-GR_DECAL_FN Vec3 world_position(const float *inv_vp, uint32_t x, uint32_t y, float inv_width, float inv_height, float depth)
+GR_HD Vec3 world_position(const float *inv_vp, uint32_t x, uint32_t y, float inv_width, float inv_height, float depth)
 {
 	const float ndc_x = 2.0f * (float(x) + 0.5f) * inv_width - 1.0f;
 	const float ndc_y = 2.0f * (float(y) + 0.5f) * inv_height - 1.0f;
@@ -114,14 +109,14 @@ GR_DECAL_FN Vec3 world_position(const float *inv_vp, uint32_t x, uint32_t y, flo
 }
 
 // ivec2(gl_FragCoord.xy * inv_resolution * xy_scale), clamped to the grid, for one axis (:26-27)
-GR_DECAL_FN int cluster_cell(uint32_t p, float inv_resolution, float xy_scale, int resolution)
+GR_HD int cluster_cell(uint32_t p, float inv_resolution, float xy_scale, int resolution)
 {
 	const int c = int((float(p) + 0.5f) * inv_resolution * xy_scale); // >= 0 and far below 2^31 for every image the launcher takes
 	return c < resolution - 1 ? c : resolution - 1;
 }
 
 // int(dot(pos - camera_base, camera_front) * z_scale) clamped to [0, z_max_index] (:31-33)
-GR_DECAL_FN int z_slice(const Vec3 &pos, const float *camera_base, const float *camera_front, float z_scale, int z_max_index)
+GR_HD int z_slice(const Vec3 &pos, const float *camera_base, const float *camera_front, float z_scale, int z_max_index)
 {
 	const float dx = pos.x - camera_base[0], dy = pos.y - camera_base[1], dz = pos.z - camera_base[2];
 	const float z = (dx * camera_front[0] + dy * camera_front[1] + dz * camera_front[2]) * z_scale;
@@ -133,7 +128,7 @@ GR_DECAL_FN int z_slice(const Vec3 &pos, const float *camera_base, const float *
 }
 
 // cluster_mask_range (clusterer_bindless_buffers.h:17-27)
-GR_DECAL_FN uint32_t cluster_mask_range(uint32_t mask, uint32_t range_x, uint32_t range_y, uint32_t start_index)
+GR_HD uint32_t cluster_mask_range(uint32_t mask, uint32_t range_x, uint32_t range_y, uint32_t start_index)
 {
 	auto clamp_u = [](uint32_t v, uint32_t lo, uint32_t hi) { v = v > lo ? v : lo; return v < hi ? v : hi; };
 	range_x = clamp_u(range_x, start_index, start_index + 32u);
@@ -144,12 +139,12 @@ GR_DECAL_FN uint32_t cluster_mask_range(uint32_t mask, uint32_t range_x, uint32_
 }
 
 // uvw = (dot(row0, (pos, 1)), dot(row1, ..), dot(row2, ..)) (:50-56); rows = 12 floats of a mat_affine
-GR_DECAL_FN Vec3 decal_uvw(const float *rows, const Vec3 &pos)
+GR_HD Vec3 decal_uvw(const float *rows, const Vec3 &pos)
 {
 	auto row_dot = [&](const float *r) { return r[0] * pos.x + r[1] * pos.y + r[2] * pos.z + r[3] * 1.0f; };
 	return {row_dot(rows), row_dot(rows + 4), row_dot(rows + 8)};
 }
-GR_DECAL_FN bool uvw_in_range(const Vec3 &uvw) { return fabsf(uvw.x) < 0.5f && fabsf(uvw.y) < 0.5f && fabsf(uvw.z) < 0.5f; }
+GR_HD bool uvw_in_range(const Vec3 &uvw) { return fabsf(uvw.x) < 0.5f && fabsf(uvw.y) < 0.5f && fabsf(uvw.z) < 0.5f; }
 
 // ---- the texture fetch --------------------------------------------------------------------------------------------------------------------
 struct Texture // gr_decal_texture
@@ -159,7 +154,7 @@ struct Texture // gr_decal_texture
 };
 static_assert(sizeof(Texture) == 24, "gr_decal_texture");
 
-GR_DECAL_FN float log2_rho(float rho)
+GR_HD float log2_rho(float rho)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
 	return __builtin_amdgcn_logf(rho);
@@ -169,7 +164,7 @@ GR_DECAL_FN float log2_rho(float rho)
 }
 
 // lambda from the quad's differences (zero for an axis that does not count)
-GR_DECAL_FN float texture_lod(float dudx, float dvdx, float dudy, float dvdy, uint32_t width, uint32_t height, uint32_t num_levels)
+GR_HD float texture_lod(float dudx, float dvdx, float dudy, float dvdy, uint32_t width, uint32_t height, uint32_t num_levels)
 {
 	const float w = float(width), h = float(height);
 	const float ax = dudx * w, ay = dvdx * h, bx = dudy * w, by = dvdy * h;
@@ -182,13 +177,13 @@ GR_DECAL_FN float texture_lod(float dudx, float dvdx, float dudy, float dvdy, ui
 	return lambda > 0.0f ? (lambda < top ? lambda : top) : 0.0f;
 }
 
-GR_DECAL_FN int wrap_repeat(int i, int n)
+GR_HD int wrap_repeat(int i, int n)
 {
 	i %= n;
 	return i < 0 ? i + n : i;
 }
 
-GR_DECAL_FN Vec4 decode_texel(uint32_t texel, bool srgb, const float *srgb_table)
+GR_HD Vec4 decode_texel(uint32_t texel, bool srgb, const float *srgb_table)
 {
 	const uint32_t r = texel & 255u, g = (texel >> 8) & 255u, b = (texel >> 16) & 255u, a = texel >> 24;
 	if (srgb)
@@ -196,14 +191,14 @@ GR_DECAL_FN Vec4 decode_texel(uint32_t texel, bool srgb, const float *srgb_table
 	return {float(r) / 255.0f, float(g) / 255.0f, float(b) / 255.0f, float(a) / 255.0f};
 }
 
-GR_DECAL_FN Vec4 mix4(const Vec4 &a, const Vec4 &b, float t)
+GR_HD Vec4 mix4(const Vec4 &a, const Vec4 &b, float t)
 {
 	const float s = 1.0f - t;
 	return {a.x * s + b.x * t, a.y * s + b.y * t, a.z * s + b.z * t, a.w * s + b.w * t};
 }
 
 // one bilinear fetch at `level`; `offset` = texels before that level
-GR_DECAL_FN Vec4 sample_level(const Texture &t, uint32_t level, float u, float v, const float *srgb_table)
+GR_HD Vec4 sample_level(const Texture &t, uint32_t level, float u, float v, const float *srgb_table)
 {
 	uint32_t offset = 0u;
 	for (uint32_t l = 0; l < level; l++)
@@ -225,7 +220,7 @@ GR_DECAL_FN Vec4 sample_level(const Texture &t, uint32_t level, float u, float v
 	return mix4(mix4(t00, t10, a), mix4(t01, t11, a), b);
 }
 
-GR_DECAL_FN Vec4 sample_texture(const Texture &t, float u, float v, float lambda, const float *srgb_table)
+GR_HD Vec4 sample_texture(const Texture &t, float u, float v, float lambda, const float *srgb_table)
 {
 	const float base = floorf(lambda);
 	const uint32_t l0 = uint32_t(base), l1 = l0 + 1u < t.num_levels ? l0 + 1u : t.num_levels - 1u;
@@ -240,7 +235,7 @@ GR_DECAL_FN Vec4 sample_texture(const Texture &t, float u, float v, float lambda
 }
 
 // base_color = mix(base_color, decal_color, decal_color.a), rgb only: the G-buffer's alpha is never changed
-GR_DECAL_FN Vec3 blend_decal(const Vec3 &base, const Vec4 &decal)
+GR_HD Vec3 blend_decal(const Vec3 &base, const Vec4 &decal)
 {
 	const float s = 1.0f - decal.w;
 	return {base.x * s + decal.x * decal.w, base.y * s + decal.y * decal.w, base.z * s + decal.z * decal.w};

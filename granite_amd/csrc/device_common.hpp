@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/granite_hip.h"
+#include "core_base.hpp"
 #include "packed_float.hpp"
 
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
@@ -35,17 +36,14 @@ static inline DevImageRW to_dev_rw(const gr_image *img)
 	return {static_cast<uint8_t *>(img->ptr), int(img->width), int(img->height), img->pitch_bytes};
 }
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+// The scalar helpers of core_base.hpp under the names the kernels have always called them by.
+using gr_core::linear_axis;
+using gr_core::SAMPLER_SNAP;
+using gr_core::unorm8_to_float;
 
-// UNORM8 -> float: v / 255 for an integer v in [0, 255], bit-identical to the IEEE quotient for all 256 inputs
-// (tests/test_oracle_kat.py) at two VALU operations instead of a full division: 1 / 255 split into its fp32 rounding and
-// the remainder, v * hi + fl(v * lo) with one rounding at the end.
-__device__ __forceinline__ float unorm8_to_float(uint32_t v)
-{
-	const float f = float(v);
-	const float hi = 0x1.010102p-8f, lo = -0x1.fdfdfep-33f;
-	return fmaf(f, hi, f * lo);
-}
+// The device-only clamp: same value as gr_core::clampi, kept in this form because the ternary form changes the code of every kernel that
+// samples through it.
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 // RGBA16F texel fetch: one 8-byte load, hardware cvt to fp32.
 __device__ __forceinline__ float4 load_rgba16f(const DevImage &img, int x, int y)
@@ -131,19 +129,8 @@ __device__ __forceinline__ float4 fma4(float4 a, float s, float4 c)
 // source of texels: fetch(x, y) takes coordinates already clamped to the image and returns the
 // four channels as fp32 (sample_linear_rgba16f is this with a global-memory fetch; the fused pyramid kernels fetch a staged
 // tile from LDS).  One definition, so that every path weighs and sums in the same order.
-// Sub-texel resolution of the sampler (the oracle's model, oracle_common.h / aa_core.hpp): f = unnormalised coordinate - 0.5;
+// Sub-texel resolution of the sampler (the oracle's model, oracle_common.h; core_base.hpp: linear_axis): f = unnormalised coordinate - 0.5;
 // a coordinate within 2^-8 of a texel centre reads that texel alone (weight 0 for its neighbour).
-constexpr float SAMPLER_SNAP = 1.0f / 256.0f;
-__device__ __forceinline__ void linear_axis(float f, int &i0, float &weight)
-{
-	const float fl = floorf(f + SAMPLER_SNAP);
-	float a = f - fl;
-	if (a < SAMPLER_SNAP)
-		a = 0.0f;
-	i0 = int(fl);
-	weight = a;
-}
-
 template <typename Fetch>
 __device__ __forceinline__ float4 sample_linear_with(Fetch fetch, int w, int h, float u, float v)
 {

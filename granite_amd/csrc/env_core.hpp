@@ -14,19 +14,21 @@
 //     as the nearest texel of the face that direction selects;
 //   - trilinear: lod clamped to [0, levels - 1], linear_axis(lod) gives floor(lod) and the weight of the next level.
 #pragma once
-#include <math.h>
-#include <stdint.h>
-#include <string.h>
-
-#if defined(__HIPCC__)
-#define ENV_HD __host__ __device__ __forceinline__
-#else
-#define ENV_HD inline
-#endif
+#include "core_base.hpp"
 
 namespace gr_env
 {
-constexpr float SAMPLER_SNAP = 1.0f / 256.0f;
+using gr_core::clampi;
+using gr_core::cross3;
+using gr_core::dot3;
+using gr_core::f3;
+using gr_core::float_to_half;
+using gr_core::half_to_float;
+using gr_core::linear_axis;
+using gr_core::make3;
+using gr_core::normalize3;
+using gr_core::wrapi;
+
 constexpr float SHADER_PI = 3.1415628f; // as the two IBL shaders spell it
 constexpr uint32_t SPECULAR_SAMPLES = 1024u;
 constexpr float DIFFUSE_DELTA = 0.025f;
@@ -39,100 +41,22 @@ struct uint2
 	uint32_t x, y;
 };
 #endif
-struct f3
-{
-	float x, y, z;
-};
-ENV_HD f3 make3(float x, float y, float z) { return {x, y, z}; }
-ENV_HD f3 operator+(f3 a, f3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-ENV_HD f3 operator*(f3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
-ENV_HD float dot3(f3 a, f3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-ENV_HD f3 cross3(f3 a, f3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-ENV_HD f3 normalize3(f3 a)
-{
-	const float inv = 1.0f / sqrtf(dot3(a, a));
-	return a * inv;
-}
-
-ENV_HD int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// f = unnormalised coordinate - 0.5: index of the first texel and weight of the second (oracle_common.h: linear_axis).
-ENV_HD void linear_axis(float f, int &i0, float &weight)
-{
-	const float fl = floorf(f + SAMPLER_SNAP);
-	float a = f - fl;
-	if (a < SAMPLER_SNAP)
-		a = 0.0f;
-	i0 = int(fl);
-	weight = a;
-}
-
-// ---- fp16 ------------------------------------------------------------------------------------------------------------------
-ENV_HD float half_to_float(uint32_t h)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-	return float(__builtin_bit_cast(_Float16, uint16_t(h)));
-#else
-	const uint32_t s = (h & 0x8000u) << 16, e = (h >> 10) & 0x1fu, m = h & 0x3ffu;
-	uint32_t bits;
-	if (e == 0)
-	{
-		const float v = float(m) * 5.9604644775390625e-08f; // m * 2^-24
-		memcpy(&bits, &v, 4);
-		bits |= s;
-	}
-	else if (e == 31)
-		bits = s | 0x7f800000u | (m << 13);
-	else
-		bits = s | ((e + 112u) << 23) | (m << 13);
-	float f;
-	memcpy(&f, &bits, 4);
-	return f;
-#endif
-}
-
-// round to nearest even, as v_cvt_f16_f32 and the oracle's float_to_half_rne
-ENV_HD uint32_t float_to_half(float f)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-	return uint32_t(__builtin_bit_cast(uint16_t, _Float16(f)));
-#else
-	uint32_t u;
-	memcpy(&u, &f, 4);
-	const uint32_t s = (u >> 16) & 0x8000u, a = u & 0x7fffffffu;
-	if (a >= 0x7f800000u)
-		return s | 0x7c00u | (a > 0x7f800000u ? (0x200u | ((a >> 13) & 0x3ffu)) : 0u);
-	if (a >= 0x477ff000u)
-		return s | 0x7c00u;
-	if (a < 0x38800000u)
-	{
-		if (a < 0x33000000u)
-			return s;
-		const uint32_t e = a >> 23, m = (a & 0x7fffffu) | 0x800000u, shift = 126u - e; // 14 .. 24
-		const uint32_t q = m >> shift, rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1u);
-		return s | (q + ((rem > half || (rem == half && (q & 1u))) ? 1u : 0u));
-	}
-	const uint32_t r = a - 0x38000000u; // rebias 127 -> 15
-	const uint32_t q = r >> 13, rem = r & 0x1fffu;
-	return s | (q + ((rem > 0x1000u || (rem == 0x1000u && (q & 1u))) ? 1u : 0u));
-#endif
-}
 
 // ---- layout ----------------------------------------------------------------------------------------------------------------
-ENV_HD uint32_t level_size(uint32_t size, uint32_t level)
+GR_HD uint32_t level_size(uint32_t size, uint32_t level)
 {
 	const uint32_t n = level < 32u ? size >> level : 0u;
 	return n ? n : 1u;
 }
 // log2(size) + 1: the levels of a full chain
-ENV_HD uint32_t full_chain_levels(uint32_t size)
+GR_HD uint32_t full_chain_levels(uint32_t size)
 {
 	uint32_t levels = 0;
 	for (; size; size >>= 1)
 		levels++;
 	return levels;
 }
-ENV_HD uint64_t chain_offset(uint32_t size, uint32_t level, uint32_t face)
+GR_HD uint64_t chain_offset(uint32_t size, uint32_t level, uint32_t face)
 {
 	uint64_t at = 0;
 	for (uint32_t l = 0; l < level; l++)
@@ -157,18 +81,18 @@ struct CubeLevel
 	int n;
 	uint32_t face_texels;
 };
-ENV_HD CubeLevel cube_level(const Cube &c, uint32_t level)
+GR_HD CubeLevel cube_level(const Cube &c, uint32_t level)
 {
 	const uint32_t n = level_size(c.size, level);
 	return {reinterpret_cast<const uint2 *>(c.base + chain_offset(c.size, level, 0)), int(n), n * n};
 }
-ENV_HD f3 unpack_rgb(uint2 t) { return {half_to_float(t.x & 0xffffu), half_to_float(t.x >> 16), half_to_float(t.y & 0xffffu)}; }
-ENV_HD f3 load_texel(const CubeLevel &l, int face, int x, int y) { return unpack_rgb(l.texels[uint32_t(face) * l.face_texels + uint32_t(y * l.n + x)]); }
-ENV_HD uint2 pack_rgba(f3 c, float a) { return {float_to_half(c.x) | (float_to_half(c.y) << 16), float_to_half(c.z) | (float_to_half(a) << 16)}; }
+GR_HD f3 unpack_rgb(uint2 t) { return {half_to_float(t.x & 0xffffu), half_to_float(t.x >> 16), half_to_float(t.y & 0xffffu)}; }
+GR_HD f3 load_texel(const CubeLevel &l, int face, int x, int y) { return unpack_rgb(l.texels[uint32_t(face) * l.face_texels + uint32_t(y * l.n + x)]); }
+GR_HD uint2 pack_rgba(f3 c, float a) { return {float_to_half(c.x) | (float_to_half(c.y) << 16), float_to_half(c.z) | (float_to_half(a) << 16)}; }
 
 // ---- cube addressing ---------------------------------------------------------------------------------------------------------
 // Vulkan's table: major axis -> face, (sc, tc, |ma|).  Ties: Z over Y over X.
-ENV_HD int select_face(f3 d, float &sc, float &tc, float &ma)
+GR_HD int select_face(f3 d, float &sc, float &tc, float &ma)
 {
 	const float ax = fabsf(d.x), ay = fabsf(d.y), az = fabsf(d.z);
 	if (az >= ax && az >= ay)
@@ -191,7 +115,7 @@ ENV_HD int select_face(f3 d, float &sc, float &tc, float &ma)
 	return d.x < 0.0f ? 1 : 0;
 }
 // The table read backwards: the direction through (sc, tc) on the plane |ma| = 1 of `face`.
-ENV_HD f3 face_direction(int face, float sc, float tc)
+GR_HD f3 face_direction(int face, float sc, float tc)
 {
 	switch (face)
 	{
@@ -205,14 +129,14 @@ ENV_HD f3 face_direction(int face, float sc, float tc)
 }
 // The direction the rasteriser gives texel (x, y) of `face` in an n x n viewport: inv = inverse(proj * look) of
 // compute_cube_render_transform(0, face, 0.1, 100) (column major), applied to (ndc, 1, 1) as skybox.vert does; not normalised.
-ENV_HD f3 texel_direction(const float *inv, int n, int x, int y)
+GR_HD f3 texel_direction(const float *inv, int n, int x, int y)
 {
 	const float px = (float(x) + 0.5f) / float(n) * 2.0f - 1.0f, py = (float(y) + 0.5f) / float(n) * 2.0f - 1.0f;
 	return {inv[0] * px + inv[4] * py + inv[8] + inv[12], inv[1] * px + inv[5] * py + inv[9] + inv[13], inv[2] * px + inv[6] * py + inv[10] + inv[14]};
 }
 
 // A texel of the footprint: on the face it is read as it is, off the face through the direction of its centre.
-ENV_HD f3 footprint_texel(const CubeLevel &l, int face, int x, int y)
+GR_HD f3 footprint_texel(const CubeLevel &l, int face, int x, int y)
 {
 	if (uint32_t(x) < uint32_t(l.n) && uint32_t(y) < uint32_t(l.n))
 		return load_texel(l, face, x, y);
@@ -228,7 +152,7 @@ ENV_HD f3 footprint_texel(const CubeLevel &l, int face, int x, int y)
 	return load_texel(l, other, ox, oy);
 }
 
-ENV_HD f3 sample_level(const CubeLevel &l, int face, float s, float t)
+GR_HD f3 sample_level(const CubeLevel &l, int face, float s, float t)
 {
 	int ix, iy;
 	float a, b;
@@ -253,7 +177,7 @@ struct LodPair
 	uint32_t level0, level1;
 	float weight; // of level1; 0 reads level0 alone
 };
-ENV_HD LodPair trilinear_levels(float lod, uint32_t levels)
+GR_HD LodPair trilinear_levels(float lod, uint32_t levels)
 {
 	const float top = float(levels - 1u);
 	lod = lod < 0.0f ? 0.0f : (lod > top ? top : lod);
@@ -267,7 +191,7 @@ ENV_HD LodPair trilinear_levels(float lod, uint32_t levels)
 	return p;
 }
 // LinearWrap (mipmap mode nearest): the level nearest to lod, Vulkan's ceil(lod + 0.5) - 1.
-ENV_HD uint32_t nearest_level(float lod, uint32_t levels)
+GR_HD uint32_t nearest_level(float lod, uint32_t levels)
 {
 	const float top = float(levels - 1u);
 	lod = lod < 0.0f ? 0.0f : (lod > top ? top : lod);
@@ -275,7 +199,7 @@ ENV_HD uint32_t nearest_level(float lod, uint32_t levels)
 	return uint32_t(clampi(l, 0, int(levels) - 1));
 }
 
-ENV_HD f3 sample_cube(const CubeLevel &l0, const CubeLevel &l1, float weight1, f3 dir)
+GR_HD f3 sample_cube(const CubeLevel &l0, const CubeLevel &l1, float weight1, f3 dir)
 {
 	float sc, tc, ma;
 	const int face = select_face(dir, sc, tc, ma);
@@ -294,16 +218,11 @@ struct Equirect
 	int w, h;
 	uint32_t pitch;
 };
-ENV_HD int wrapi(int v, int n)
-{
-	v %= n;
-	return v < 0 ? v + n : v;
-}
-ENV_HD f3 equirect_texel(const Equirect &e, int x, int y)
+GR_HD f3 equirect_texel(const Equirect &e, int x, int y)
 {
 	return unpack_rgb(*reinterpret_cast<const uint2 *>(e.ptr + size_t(wrapi(y, e.h)) * e.pitch + size_t(wrapi(x, e.w)) * 8u));
 }
-ENV_HD f3 latlon(const Equirect &e, f3 direction)
+GR_HD f3 latlon(const Equirect &e, f3 direction)
 {
 	f3 v = normalize3(direction);
 	if (fabsf(v.x) < 0.00001f)
@@ -326,7 +245,7 @@ ENV_HD f3 latlon(const Equirect &e, f3 direction)
 }
 
 // ---- generate_mipmap: texel (x, y) of an n-texel face from the m-texel face above it, a linear-filter blit clamped to the face ---------
-ENV_HD void blit_texel(const uint2 *src, int m, int n, int x, int y, f3 &rgb, float &alpha)
+GR_HD void blit_texel(const uint2 *src, int m, int n, int x, int y, f3 &rgb, float &alpha)
 {
 	const float scale = float(m) / float(n);
 	int ix, iy;
@@ -356,14 +275,14 @@ ENV_HD void blit_texel(const uint2 *src, int m, int n, int x, int y, f3 &rgb, fl
 }
 
 // ---- ibl_specular.frag -----------------------------------------------------------------------------------------------------------
-ENV_HD float radical_inverse(uint32_t bits)
+GR_HD float radical_inverse(uint32_t bits)
 {
 	uint32_t r = 0;
 	for (int i = 0; i < 32; i++)
 		r |= ((bits >> i) & 1u) << (31 - i);
 	return float(r) * 2.3283064365386963e-10f;
 }
-ENV_HD float specular_roughness(uint32_t level, uint32_t levels)
+GR_HD float specular_roughness(uint32_t level, uint32_t levels)
 {
 	const float t = levels > 1u ? float(level) / float(levels - 1u) : 0.0f;
 	return 0.001f * (1.0f - t) + 1.0f * t; // mix(0.001, 1, t)
@@ -374,7 +293,7 @@ struct SpecularSample
 };
 // Sample i of the level: ImportanceSampleGGX and the reflection of V = N about H, in the frame (tangent, bitangent, N).  Nothing here
 // depends on the texel, so a level's 1024 entries are computed once.
-ENV_HD SpecularSample specular_sample(uint32_t i, float roughness)
+GR_HD SpecularSample specular_sample(uint32_t i, float roughness)
 {
 	const float xi_x = float(i) / float(SPECULAR_SAMPLES), xi_y = radical_inverse(i);
 	const float a = roughness * roughness;
@@ -390,7 +309,7 @@ struct Frame
 {
 	f3 tangent, bitangent, n;
 };
-ENV_HD Frame specular_frame(f3 direction)
+GR_HD Frame specular_frame(f3 direction)
 {
 	Frame f;
 	f.n = normalize3(direction);
@@ -400,7 +319,7 @@ ENV_HD Frame specular_frame(f3 direction)
 	return f;
 }
 // Samples first, first + step, ... of `table` (SPECULAR_SAMPLES entries) added to (sum, weight).
-ENV_HD void specular_accumulate(const CubeLevel &l0, const CubeLevel &l1, float weight1, const Frame &f, const SpecularSample *table, uint32_t first, uint32_t step,
+GR_HD void specular_accumulate(const CubeLevel &l0, const CubeLevel &l1, float weight1, const Frame &f, const SpecularSample *table, uint32_t first, uint32_t step,
                                 f3 &sum, float &weight)
 {
 	for (uint32_t i = first; i < SPECULAR_SAMPLES; i += step)
@@ -417,7 +336,7 @@ ENV_HD void specular_accumulate(const CubeLevel &l0, const CubeLevel &l1, float 
 
 // ---- ibl_diffuse.frag ------------------------------------------------------------------------------------------------------------
 // Entry k of the angle tables: the loop variable after k fp32 additions of sample_delta, as the shader's float loops step it.
-ENV_HD float diffuse_angle(uint32_t k)
+GR_HD float diffuse_angle(uint32_t k)
 {
 	float angle = 0.0f;
 	for (uint32_t i = 0; i < k; i++)
@@ -425,7 +344,7 @@ ENV_HD float diffuse_angle(uint32_t k)
 	return angle;
 }
 // How often `for (float a = 0; a < limit; a += sample_delta)` runs.
-ENV_HD uint32_t diffuse_steps(float limit)
+GR_HD uint32_t diffuse_steps(float limit)
 {
 	uint32_t n = 0;
 	for (float a = 0.0f; a < limit; a += DIFFUSE_DELTA)
@@ -436,7 +355,7 @@ struct SinCos
 {
 	float s, c;
 };
-ENV_HD Frame diffuse_frame(f3 direction)
+GR_HD Frame diffuse_frame(f3 direction)
 {
 	Frame f;
 	f.n = normalize3(direction);
@@ -445,7 +364,7 @@ ENV_HD Frame diffuse_frame(f3 direction)
 	return f;
 }
 // Taps first, first + step, ... of the 252 x 63 grid (phi outer, theta inner), phi[] and theta[] holding sin and cos of the angles.
-ENV_HD void diffuse_accumulate(const CubeLevel &l, const Frame &f, const SinCos *phi, const SinCos *theta, uint32_t first, uint32_t step, f3 &sum)
+GR_HD void diffuse_accumulate(const CubeLevel &l, const Frame &f, const SinCos *phi, const SinCos *theta, uint32_t first, uint32_t step, f3 &sum)
 {
 	for (uint32_t i = first; i < DIFFUSE_PHI_STEPS * DIFFUSE_THETA_STEPS; i += step)
 	{
@@ -454,7 +373,7 @@ ENV_HD void diffuse_accumulate(const CubeLevel &l, const Frame &f, const SinCos 
 		sum = sum + sample_cube(l, l, 0.0f, dir) * (t.c * t.s);
 	}
 }
-ENV_HD f3 diffuse_resolve(f3 sum) { return sum * SHADER_PI * (1.0f / float(DIFFUSE_PHI_STEPS * DIFFUSE_THETA_STEPS)); }
+GR_HD f3 diffuse_resolve(f3 sum) { return sum * SHADER_PI * (1.0f / float(DIFFUSE_PHI_STEPS * DIFFUSE_THETA_STEPS)); }
 } // namespace gr_env
 #include "host/math.hpp"
 namespace gr_env

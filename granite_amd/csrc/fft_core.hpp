@@ -10,20 +10,13 @@
 // and rounded once; every twiddle any pass needs is an entry of it.  Arithmetic and LDS are fp32 for both data types; FP16 is the
 // type of memory (user buffers, images and the scratch between passes).
 #pragma once
-#include <math.h>
-#include <stdint.h>
-#include <string.h>
-
-#if defined(__HIPCC__)
-#define FFT_HD __host__ __device__ __forceinline__
-#define FFT_UNROLL _Pragma("unroll")
-#else
-#define FFT_HD inline
-#define FFT_UNROLL
-#endif
+#include "core_base.hpp"
 
 namespace gr_fft
 {
+using gr_core::float_to_half;
+using gr_core::half_to_float;
+
 constexpr uint32_t GROUP = 512u;          // lanes of a workgroup
 constexpr uint32_t TILE_ELEMENTS = 8192u; // complex numbers a workgroup holds at most (64 KiB of fp32 pairs)
 constexpr uint32_t REGS = TILE_ELEMENTS / GROUP;
@@ -46,60 +39,15 @@ struct alignas(8) c32
 {
 	float x, y;
 };
-FFT_HD c32 operator+(c32 a, c32 b) { return {a.x + b.x, a.y + b.y}; }
-FFT_HD c32 operator-(c32 a, c32 b) { return {a.x - b.x, a.y - b.y}; }
-FFT_HD c32 cmul(c32 a, c32 b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
-FFT_HD c32 conj(c32 a) { return {a.x, -a.y}; }
+GR_HD c32 operator+(c32 a, c32 b) { return {a.x + b.x, a.y + b.y}; }
+GR_HD c32 operator-(c32 a, c32 b) { return {a.x - b.x, a.y - b.y}; }
+GR_HD c32 cmul(c32 a, c32 b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
+GR_HD c32 conj(c32 a) { return {a.x, -a.y}; }
 // a * (dir i)
-FFT_HD c32 rot(c32 a, float dir) { return {-dir * a.y, dir * a.x}; }
+GR_HD c32 rot(c32 a, float dir) { return {-dir * a.y, dir * a.x}; }
 
-// ---- fp16 <-> fp32 ----------------------------------------------------------------------------------------------------------
-FFT_HD float half_to_float(uint32_t h)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-	return float(__builtin_bit_cast(_Float16, uint16_t(h)));
-#else
-	const uint32_t s = (h & 0x8000u) << 16, e = (h >> 10) & 0x1fu, m = h & 0x3ffu;
-	uint32_t bits;
-	if (e == 0)
-	{
-		const float v = float(m) * 5.9604644775390625e-08f; // m * 2^-24
-		memcpy(&bits, &v, 4);
-		bits |= s;
-	}
-	else if (e == 31)
-		bits = s | 0x7f800000u | (m << 13);
-	else
-		bits = s | ((e + 112u) << 23) | (m << 13);
-	float f;
-	memcpy(&f, &bits, 4);
-	return f;
-#endif
-}
-// round to nearest even, overflow to infinity
-FFT_HD uint32_t float_to_half(float f)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-	return __builtin_bit_cast(uint16_t, _Float16(f));
-#else
-	uint32_t u;
-	memcpy(&u, &f, 4);
-	const uint32_t s = (u >> 16) & 0x8000u, a = u & 0x7fffffffu;
-	if (a > 0x7f800000u)
-		return s | 0x7e00u;
-	if (a >= 0x477ff000u) // rounds to 2^16 or above
-		return s | 0x7c00u;
-	if (a < 0x38800000u) // below 2^-14: a multiple of 2^-24
-	{
-		float v;
-		memcpy(&v, &a, 4);
-		return s | uint32_t(__builtin_rintf(v * 16777216.0f));
-	}
-	return s | (((a + 0xfffu + ((a >> 13) & 1u)) >> 13) - (112u << 10));
-#endif
-}
-FFT_HD c32 unpack_half2(uint32_t v) { return {half_to_float(v & 0xffffu), half_to_float(v >> 16)}; }
-FFT_HD uint32_t pack_half2(c32 v) { return float_to_half(v.x) | (float_to_half(v.y) << 16); }
+GR_HD c32 unpack_half2(uint32_t v) { return {half_to_float(v & 0xffffu), half_to_float(v >> 16)}; }
+GR_HD uint32_t pack_half2(c32 v) { return float_to_half(v.x) | (float_to_half(v.y) << 16); }
 
 // ---- plan -------------------------------------------------------------------------------------------------------------------
 struct Options
@@ -156,7 +104,7 @@ inline uint32_t log2_of(uint32_t v)
 		l++;
 	return l;
 }
-FFT_HD uint32_t lds_at(const Pass &P, uint32_t c, uint32_t t) { return c * P.lds_stride + t + (t >> 5); }
+GR_HD uint32_t lds_at(const Pass &P, uint32_t c, uint32_t t) { return c * P.lds_stride + t + (t >> 5); }
 
 inline View linear_view(uint32_t kind, uint32_t row_stride, uint32_t layer_stride)
 {
@@ -348,7 +296,7 @@ inline void build_twiddles(c32 *table, uint32_t n, float dir)
 }
 
 // ---- memory -----------------------------------------------------------------------------------------------------------------
-FFT_HD c32 view_load(const View &v, uint32_t at)
+GR_HD c32 view_load(const View &v, uint32_t at)
 {
 	switch (v.kind)
 	{
@@ -366,7 +314,7 @@ FFT_HD c32 view_load(const View &v, uint32_t at)
 	}
 }
 
-FFT_HD void view_store(const View &v, uint32_t at, c32 value)
+GR_HD void view_store(const View &v, uint32_t at, c32 value)
 {
 	switch (v.kind)
 	{
@@ -420,14 +368,14 @@ FFT_HD void view_store(const View &v, uint32_t at, c32 value)
 	}
 }
 
-FFT_HD bool view_is_image(const View &v) { return v.kind >= VIEW_IMG_C32; }
-FFT_HD uint32_t view_at(const View &v, uint32_t x, uint32_t y, uint32_t z)
+GR_HD bool view_is_image(const View &v) { return v.kind >= VIEW_IMG_C32; }
+GR_HD uint32_t view_at(const View &v, uint32_t x, uint32_t y, uint32_t z)
 {
 	if (view_is_image(v))
 		return x | (y << 16);
 	return x * v.x_stride + y * v.row_stride + z * v.layer_stride;
 }
-FFT_HD uint32_t view_dim_stride(const View &v, uint32_t dim)
+GR_HD uint32_t view_dim_stride(const View &v, uint32_t dim)
 {
 	if (view_is_image(v))
 		return dim == 0 ? 1u : 65536u;
@@ -435,7 +383,7 @@ FFT_HD uint32_t view_dim_stride(const View &v, uint32_t dim)
 }
 
 // ---- butterflies ------------------------------------------------------------------------------------------------------------
-FFT_HD void butterfly4(c32 &a0, c32 &a1, c32 &a2, c32 &a3, float dir)
+GR_HD void butterfly4(c32 &a0, c32 &a1, c32 &a2, c32 &a3, float dir)
 {
 	const c32 t0 = a0 + a2, t1 = a0 - a2, t2 = a1 + a3, t3 = rot(a1 - a3, dir);
 	a0 = t0 + t2;
@@ -443,7 +391,7 @@ FFT_HD void butterfly4(c32 &a0, c32 &a1, c32 &a2, c32 &a3, float dir)
 	a2 = t0 - t2;
 	a3 = t1 - t3;
 }
-FFT_HD void butterfly8(c32 *a, float dir)
+GR_HD void butterfly8(c32 *a, float dir)
 {
 	c32 e0 = a[0], e1 = a[2], e2 = a[4], e3 = a[6], o0 = a[1], o1 = a[3], o2 = a[5], o3 = a[7];
 	butterfly4(e0, e1, e2, e3, dir);
@@ -464,14 +412,14 @@ FFT_HD void butterfly8(c32 *a, float dir)
 
 // ---- the phases of a C2C pass; a barrier stands between each two ------------------------------------------------------------
 // LDS: columns x lds_stride complex numbers, then per column: input offset, output offset, k = j mod p.
-FFT_HD uint32_t *column_table(const Pass &P, c32 *lds) { return reinterpret_cast<uint32_t *>(lds + P.columns * P.lds_stride); }
-FFT_HD uint32_t valid_columns(const Pass &P, uint32_t group)
+GR_HD uint32_t *column_table(const Pass &P, c32 *lds) { return reinterpret_cast<uint32_t *>(lds + P.columns * P.lds_stride); }
+GR_HD uint32_t valid_columns(const Pass &P, uint32_t group)
 {
 	const uint32_t first = group * P.columns, left = P.total_columns - first;
 	return left < P.columns ? left : P.columns;
 }
 
-FFT_HD void phase_columns(const Pass &P, c32 *lds, uint32_t group, uint32_t lane)
+GR_HD void phase_columns(const Pass &P, c32 *lds, uint32_t group, uint32_t lane)
 {
 	uint32_t *table = column_table(P, lds);
 	const uint32_t valid = valid_columns(P, group);
@@ -510,7 +458,7 @@ FFT_HD void phase_columns(const Pass &P, c32 *lds, uint32_t group, uint32_t lane
 	}
 }
 
-FFT_HD void tile_element(const Pass &P, bool t_fastest, uint32_t e, uint32_t &c, uint32_t &t)
+GR_HD void tile_element(const Pass &P, bool t_fastest, uint32_t e, uint32_t &c, uint32_t &t)
 {
 	if (t_fastest)
 	{
@@ -524,7 +472,7 @@ FFT_HD void tile_element(const Pass &P, bool t_fastest, uint32_t e, uint32_t &c,
 	}
 }
 
-FFT_HD void phase_load(const Pass &P, c32 *lds, uint32_t group, uint32_t lane)
+GR_HD void phase_load(const Pass &P, c32 *lds, uint32_t group, uint32_t lane)
 {
 	const uint32_t *table = column_table(P, lds);
 	const uint32_t valid = valid_columns(P, group);
@@ -543,12 +491,12 @@ FFT_HD void phase_load(const Pass &P, c32 *lds, uint32_t group, uint32_t lane)
 }
 
 // One radix-RADIX step of the R-point transforms in LDS, cumulative local radix `local_p`: read and compute ...
-template <uint32_t RADIX> FFT_HD void phase_butterflies(const Pass &P, uint32_t local_p, const c32 *lds, c32 *regs, uint32_t lane)
+template <uint32_t RADIX> GR_HD void phase_butterflies(const Pass &P, uint32_t local_p, const c32 *lds, c32 *regs, uint32_t lane)
 {
 	constexpr uint32_t LOG2 = RADIX == 8u ? 3u : 2u, PER_LANE = REGS / RADIX;
 	const uint32_t per_column_log2 = P.log2_radix - LOG2, per_column = 1u << per_column_log2;
 	const uint32_t total = P.columns << per_column_log2, scale = P.table_n / (local_p * RADIX);
-FFT_UNROLL
+GR_UNROLL
 	for (uint32_t i = 0; i < PER_LANE; i++)
 	{
 		const uint32_t g = lane + i * GROUP;
@@ -556,7 +504,7 @@ FFT_UNROLL
 		{
 			const uint32_t c = g >> per_column_log2, b = g & (per_column - 1u), k = b & (local_p - 1u);
 			c32 a[RADIX];
-FFT_UNROLL
+GR_UNROLL
 			for (uint32_t m = 0; m < RADIX; m++)
 			{
 				a[m] = lds[lds_at(P, c, b + m * per_column)];
@@ -567,19 +515,19 @@ FFT_UNROLL
 				butterfly8(a, P.dir);
 			else
 				butterfly4(a[0], a[1], a[2], a[3], P.dir);
-FFT_UNROLL
+GR_UNROLL
 			for (uint32_t m = 0; m < RADIX; m++)
 				regs[i * RADIX + m] = a[m];
 		}
 	}
 }
 // ... and, after every lane has read, write.
-template <uint32_t RADIX> FFT_HD void phase_scatter(const Pass &P, uint32_t local_p, c32 *lds, const c32 *regs, uint32_t lane)
+template <uint32_t RADIX> GR_HD void phase_scatter(const Pass &P, uint32_t local_p, c32 *lds, const c32 *regs, uint32_t lane)
 {
 	constexpr uint32_t LOG2 = RADIX == 8u ? 3u : 2u, PER_LANE = REGS / RADIX;
 	const uint32_t per_column_log2 = P.log2_radix - LOG2, per_column = 1u << per_column_log2;
 	const uint32_t total = P.columns << per_column_log2;
-FFT_UNROLL
+GR_UNROLL
 	for (uint32_t i = 0; i < PER_LANE; i++)
 	{
 		const uint32_t g = lane + i * GROUP;
@@ -587,14 +535,14 @@ FFT_UNROLL
 		{
 			const uint32_t c = g >> per_column_log2, b = g & (per_column - 1u), k = b & (local_p - 1u);
 			const uint32_t first = ((b - k) << LOG2) + k;
-FFT_UNROLL
+GR_UNROLL
 			for (uint32_t m = 0; m < RADIX; m++)
 				lds[lds_at(P, c, first + m * local_p)] = regs[i * RADIX + m];
 		}
 	}
 }
 
-FFT_HD void phase_store(const Pass &P, const c32 *lds, uint32_t group, uint32_t lane)
+GR_HD void phase_store(const Pass &P, const c32 *lds, uint32_t group, uint32_t lane)
 {
 	const uint32_t *table = column_table(P, const_cast<c32 *>(lds));
 	const uint32_t valid = valid_columns(P, group);
@@ -613,7 +561,7 @@ FFT_HD void phase_store(const Pass &P, const c32 *lds, uint32_t group, uint32_t 
 // R2C: Z = the Nx / 2-point transform of the row read as pairs; X[k] = E[k] + W^k O[k], k in [0, Nx / 2].
 // C2R: Z'[k] = (X[k] + conj X[Nx / 2 - k]) + i W^k (X[k] - conj X[Nx / 2 - k]), k in [0, Nx / 2): twice the packed spectrum, so that the
 //      unnormalised inverse gives Nx x.
-FFT_HD void resolve_element(const Pass &P, uint32_t index)
+GR_HD void resolve_element(const Pass &P, uint32_t index)
 {
 	const uint32_t total = P.cols * P.ny * P.nz;
 	if (index >= total)

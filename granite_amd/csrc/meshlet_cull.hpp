@@ -19,15 +19,14 @@
 #pragma once
 #include <cmath>
 #include <cstdint>
-
-#if defined(__HIPCC__)
-#define GR_CULL_FN __host__ __device__ inline __attribute__((always_inline))
-#else
-#define GR_CULL_FN inline
-#endif
+#include "core_base.hpp"
 
 namespace gr_cull
 {
+using gr_core::clampi;
+using gr_core::dot3;
+using Vec3 = gr_core::f3;
+
 struct Task // MeshAssetDrawTaskInfo, inc/meshlet_render_types.h:15-22
 {
 	uint32_t aabb_instance, occluder_state_offset, node_instance, mesh_index_count, material_flags;
@@ -81,23 +80,16 @@ struct CullArgs
 	Frustum frustum;
 };
 
-struct Vec3
-{
-	float x, y, z;
-};
-
-GR_CULL_FN float dot3(const Vec3 &a, const Vec3 &b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 // dot(vec4(v, 1.0), p)
-GR_CULL_FN float dot_point(const Vec3 &v, const float p[4]) { return v.x * p[0] + v.y * p[1] + v.z * p[2] + 1.0f * p[3]; }
+GR_HD float dot_point(const Vec3 &v, const float p[4]) { return v.x * p[0] + v.y * p[1] + v.z * p[2] + 1.0f * p[3]; }
 
-GR_CULL_FN int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-GR_CULL_FN int glsl_clampi(int v, int lo, int hi) // GLSL's clamp: min(max(v, lo), hi), also where lo > hi
+GR_HD int glsl_clampi(int v, int lo, int hi) // GLSL's clamp: min(max(v, lo), hi), also where lo > hi
 {
 	const int m = v > lo ? v : lo;
 	return m < hi ? m : hi;
 }
 // GLSL findMSB(int): -1 for 0 and -1; for a negative value the highest 0 bit.
-GR_CULL_FN int find_msb(int v)
+GR_HD int find_msb(int v)
 {
 	uint32_t u = uint32_t(v < 0 ? ~v : v);
 	int r = -1;
@@ -108,14 +100,14 @@ GR_CULL_FN int find_msb(int v)
 	}
 	return r;
 }
-GR_CULL_FN int float_to_int(float v)
+GR_HD int float_to_int(float v)
 {
 	const float c = fminf(fmaxf(v, -2147483648.0f), 2147483520.0f); // fmaxf(NaN, a) = a
 	return int(c);
 }
 
 // texelFetch(uHiZDepth, (x, y), level): level `level` of the chain is max(w >> level, 1) x max(h >> level, 1) texels
-GR_CULL_FN float hiz_texel(const CullArgs &a, int x, int y, int level)
+GR_HD float hiz_texel(const CullArgs &a, int x, int y, int level)
 {
 	level = clampi(level, 0, int(a.chain_levels) - 1);
 	uint32_t offset = 0;
@@ -130,7 +122,7 @@ GR_CULL_FN float hiz_texel(const CullArgs &a, int x, int y, int level)
 }
 
 // meshlet_render.h:41-48
-GR_CULL_FN Vec3 view_transform_yz_flip(const Frustum &f, const Vec3 &p)
+GR_HD Vec3 view_transform_yz_flip(const Frustum &f, const Vec3 &p)
 {
 	float v[3];
 	for (int i = 0; i < 3; i++)
@@ -139,7 +131,7 @@ GR_CULL_FN Vec3 view_transform_yz_flip(const Frustum &f, const Vec3 &p)
 }
 
 // meshlet_render.h:51-90
-GR_CULL_FN bool hiz_cull(const CullArgs &a, float lo_x, float hi_x, float lo_y, float hi_y, float closest_z)
+GR_HD bool hiz_cull(const CullArgs &a, float lo_x, float hi_x, float lo_y, float hi_y, float closest_z)
 {
 	const Frustum &f = a.frustum;
 	const float rx0 = lo_x * f.viewport_scale_bias[0] + f.viewport_scale_bias[2], rx1 = hi_x * f.viewport_scale_bias[0] + f.viewport_scale_bias[2];
@@ -174,7 +166,7 @@ GR_CULL_FN bool hiz_cull(const CullArgs &a, float lo_x, float hi_x, float lo_y, 
 }
 
 // meshlet_render.h:93-103
-GR_CULL_FN void project_sphere_flat(float view_xy, float view_z, float radius, float &lo, float &hi)
+GR_HD void project_sphere_flat(float view_xy, float view_z, float radius, float &lo, float &hi)
 {
 	const float len = sqrtf(view_xy * view_xy + view_z * view_z);
 	const float sin_xy = radius / len;
@@ -186,7 +178,7 @@ GR_CULL_FN void project_sphere_flat(float view_xy, float view_z, float radius, f
 }
 
 // meshlet_render.h:108-135
-template <bool ORTHO> GR_CULL_FN bool cluster_cull_hiz(const CullArgs &a, const Vec3 &center, float radius)
+template <bool ORTHO> GR_HD bool cluster_cull_hiz(const CullArgs &a, const Vec3 &center, float radius)
 {
 	const Vec3 view = view_transform_yz_flip(a.frustum, center);
 	// no clipping against the near plane: a sphere close enough is accepted; ORTHO has no effective near plane
@@ -209,7 +201,7 @@ template <bool ORTHO> GR_CULL_FN bool cluster_cull_hiz(const CullArgs &a, const 
 }
 
 // meshlet_render.h:138-174
-template <int PHASE, bool ORTHO> GR_CULL_FN bool cluster_cull(const CullArgs &a, const Affine &m, const Bound &b)
+template <int PHASE, bool ORTHO> GR_HD bool cluster_cull(const CullArgs &a, const Affine &m, const Bound &b)
 {
 	const Vec3 c = {b.center_radius[0], b.center_radius[1], b.center_radius[2]};
 	const Vec3 center = {dot_point(c, m.rows[0]), dot_point(c, m.rows[1]), dot_point(c, m.rows[2])};
@@ -238,7 +230,7 @@ template <int PHASE, bool ORTHO> GR_CULL_FN bool cluster_cull(const CullArgs &a,
 }
 
 // meshlet_render.h:176-195
-template <int PHASE, bool ORTHO> GR_CULL_FN bool frustum_cull(const CullArgs &a, const AABB &box)
+template <int PHASE, bool ORTHO> GR_HD bool frustum_cull(const CullArgs &a, const AABB &box)
 {
 	for (int i = 0; i < 6; i++)
 	{
@@ -257,8 +249,8 @@ template <int PHASE, bool ORTHO> GR_CULL_FN bool frustum_cull(const CullArgs &a,
 	return true;
 }
 
-GR_CULL_FN uint32_t occluder_word(const CullArgs &a, uint32_t index) { return index < a.occluder_count ? a.occluders[index] : 0u; }
-GR_CULL_FN void set_occluder_word(const CullArgs &a, uint32_t index, uint32_t value)
+GR_HD uint32_t occluder_word(const CullArgs &a, uint32_t index) { return index < a.occluder_count ? a.occluders[index] : 0u; }
+GR_HD void set_occluder_word(const CullArgs &a, uint32_t index, uint32_t value)
 {
 	if (index < a.occluder_count)
 		a.occluders[index] = value;
@@ -266,7 +258,7 @@ GR_CULL_FN void set_occluder_word(const CullArgs &a, uint32_t index, uint32_t va
 
 // main() of meshlet_cull.comp up to its ballot, for the task at `flat_index` of the dispatch: does the task need work?  Phase 2 clears
 // the occluder word of a task that does not.
-template <int PHASE, bool ORTHO> GR_CULL_FN bool task_needs_work(const CullArgs &a, uint32_t flat_index)
+template <int PHASE, bool ORTHO> GR_HD bool task_needs_work(const CullArgs &a, uint32_t flat_index)
 {
 	if (flat_index >= a.count)
 		return false;
@@ -284,7 +276,7 @@ template <int PHASE, bool ORTHO> GR_CULL_FN bool task_needs_work(const CullArgs 
 
 // process_task() up to its first ballot, for chunk `lane` (0 .. 31) of a task that needs work: is the chunk visible now?
 // old_state: the task's occluder word as it was (phases 1 and 2).
-template <int PHASE, bool ORTHO, bool SKINNED> GR_CULL_FN bool chunk_visible(const CullArgs &a, const Task &task, uint32_t lane, uint32_t old_state, uint32_t &chunk)
+template <int PHASE, bool ORTHO, bool SKINNED> GR_HD bool chunk_visible(const CullArgs &a, const Task &task, uint32_t lane, uint32_t old_state, uint32_t &chunk)
 {
 	const uint32_t count = (task.mesh_index_count & 31u) + 1u;
 	chunk = (task.mesh_index_count & ~31u) + lane;
@@ -300,7 +292,7 @@ template <int PHASE, bool ORTHO, bool SKINNED> GR_CULL_FN bool chunk_visible(con
 }
 
 // the record of a surviving chunk, five dwords at draw_indirect_offset + 5 * slot; not written where it would end past the buffer
-GR_CULL_FN void write_draw(const CullArgs &a, uint32_t slot, uint32_t chunk, uint32_t task_index)
+GR_HD void write_draw(const CullArgs &a, uint32_t slot, uint32_t chunk, uint32_t task_index)
 {
 	const uint64_t at = uint64_t(a.draw_indirect_offset) + uint64_t(slot) * 5u;
 	if (at + 5u > a.output_dwords)

@@ -22,12 +22,7 @@
 #pragma once
 #include <cmath>
 #include <cstdint>
-
-#if defined(__HIPCC__)
-#define GR_MESHLET_FN __host__ __device__ inline __attribute__((always_inline))
-#else
-#define GR_MESHLET_FN inline
-#endif
+#include "core_base.hpp"
 
 namespace gr_meshlet
 {
@@ -65,10 +60,10 @@ struct TexturedAttr
 };
 static_assert(sizeof(Stream) == 16 && sizeof(Offsets) == 12 && sizeof(TexturedAttr) == 16, "records are the shader's");
 
-GR_MESHLET_FN uint32_t payload_word(const Payload &p, uint32_t index) { return index < p.count ? p.words[index] : 0u; }
+GR_HD uint32_t payload_word(const Payload &p, uint32_t index) { return index < p.count ? p.words[index] : 0u; }
 
 // the 64-bit window of element `index` of a stream of `components` x `bits`, and the bit at which the element starts in it
-GR_MESHLET_FN uint64_t window(const Payload &p, uint32_t offset_in_words, uint32_t index, uint32_t bits, uint32_t components, uint32_t &start_bit)
+GR_HD uint64_t window(const Payload &p, uint32_t offset_in_words, uint32_t index, uint32_t bits, uint32_t components, uint32_t &start_bit)
 {
 	const uint32_t first_bit = index * bits * components;
 	const uint32_t start_word = offset_in_words + first_bit / 32u; // wraps as the shader's uint does; the bound check follows
@@ -76,19 +71,19 @@ GR_MESHLET_FN uint64_t window(const Payload &p, uint32_t offset_in_words, uint32
 	const uint32_t word0 = payload_word(p, start_word), word1 = payload_word(p, start_word + 1u);
 	return uint64_t(word0) | (uint64_t(word1) << 32);
 }
-GR_MESHLET_FN uint32_t field(uint64_t word, uint32_t shift, uint32_t bits)
+GR_HD uint32_t field(uint64_t word, uint32_t shift, uint32_t bits)
 {
 	const uint32_t v = shift < 64u ? uint32_t(word >> shift) : 0u;
 	return bits == 0u ? 0u : (bits >= 32u ? v : v & ((1u << bits) - 1u));
 }
-GR_MESHLET_FN void decode2(const Payload &p, uint32_t offset_in_words, uint32_t index, uint32_t bits, uint32_t v[2])
+GR_HD void decode2(const Payload &p, uint32_t offset_in_words, uint32_t index, uint32_t bits, uint32_t v[2])
 {
 	uint32_t start;
 	const uint64_t word = window(p, offset_in_words, index, bits, 2u, start);
 	v[0] = field(word, start, bits);
 	v[1] = field(word, start + bits, bits);
 }
-GR_MESHLET_FN void decode3(const Payload &p, uint32_t offset_in_words, uint32_t index, uint32_t bits, uint32_t v[3])
+GR_HD void decode3(const Payload &p, uint32_t offset_in_words, uint32_t index, uint32_t bits, uint32_t v[3])
 {
 	uint32_t start;
 	const uint64_t word = window(p, offset_in_words, index, bits, 3u, start);
@@ -96,7 +91,7 @@ GR_MESHLET_FN void decode3(const Payload &p, uint32_t offset_in_words, uint32_t 
 	v[1] = field(word, start + bits, bits);
 	v[2] = field(word, start + 2u * bits, bits);
 }
-GR_MESHLET_FN void decode4(const Payload &p, uint32_t offset_in_words, uint32_t index, uint32_t bits, uint32_t v[4])
+GR_HD void decode4(const Payload &p, uint32_t offset_in_words, uint32_t index, uint32_t bits, uint32_t v[4])
 {
 	uint32_t start;
 	const uint64_t word = window(p, offset_in_words, index, bits, 4u, start);
@@ -107,9 +102,9 @@ GR_MESHLET_FN void decode4(const Payload &p, uint32_t offset_in_words, uint32_t 
 }
 
 // ---- the six stream decoders ----------------------------------------------------------------------------------------------------------
-GR_MESHLET_FN void decode_index_buffer(const Payload &p, const Stream &s, uint32_t lane, uint32_t v[3]) { decode3(p, s.offset_in_words, lane, 5u, v); }
+GR_HD void decode_index_buffer(const Payload &p, const Stream &s, uint32_t lane, uint32_t v[3]) { decode3(p, s.offset_in_words, lane, 5u, v); }
 
-GR_MESHLET_FN void decode_snorm_scaled_i16x3(const Payload &p, const Stream &s, uint32_t lane, int16_t v[3], int &exponent)
+GR_HD void decode_snorm_scaled_i16x3(const Payload &p, const Stream &s, uint32_t lane, int16_t v[3], int &exponent)
 {
 	exponent = int32_t(s.bits) >> 16;
 	uint32_t value[3];
@@ -118,7 +113,7 @@ GR_MESHLET_FN void decode_snorm_scaled_i16x3(const Payload &p, const Stream &s, 
 	v[1] = int16_t(uint16_t(value[1] + (s.base[0] >> 16)));
 	v[2] = int16_t(uint16_t(value[2] + (s.base[1] & 0xffffu)));
 }
-GR_MESHLET_FN void decode_snorm_scaled_i16x2(const Payload &p, const Stream &s, uint32_t lane, int16_t v[2], int &exponent)
+GR_HD void decode_snorm_scaled_i16x2(const Payload &p, const Stream &s, uint32_t lane, int16_t v[2], int &exponent)
 {
 	exponent = int32_t(s.bits) >> 16;
 	uint32_t value[2];
@@ -127,15 +122,15 @@ GR_MESHLET_FN void decode_snorm_scaled_i16x2(const Payload &p, const Stream &s, 
 	v[1] = int16_t(uint16_t(value[1] + (s.base[0] >> 16)));
 }
 // base + delta of a four-byte stream, each component still 32 bits wide
-GR_MESHLET_FN void decode_bytes4(const Payload &p, const Stream &s, uint32_t lane, uint32_t v[4])
+GR_HD void decode_bytes4(const Payload &p, const Stream &s, uint32_t lane, uint32_t v[4])
 {
 	decode4(p, s.offset_in_words, lane, s.bits & 0xffu, v);
 	for (int i = 0; i < 4; i++)
 		v[i] += (s.base[0] >> (8 * i)) & 0xffu;
 }
-GR_MESHLET_FN uint32_t pack_bytes4(const uint32_t v[4]) { return (v[0] & 0xffu) | ((v[1] & 0xffu) << 8) | ((v[2] & 0xffu) << 16) | ((v[3] & 0xffu) << 24); }
+GR_HD uint32_t pack_bytes4(const uint32_t v[4]) { return (v[0] & 0xffu) | ((v[1] & 0xffu) << 8) | ((v[2] & 0xffu) << 16) | ((v[3] & 0xffu) << 24); }
 // the four bytes nx, ny, tx, ty as one word, and the tangent's sign: aux 3 takes it from the low bit of ty, aux 2 is negative, else positive
-GR_MESHLET_FN uint32_t decode_normal_tangent_oct8(const Payload &p, const Stream &s, uint32_t lane, bool &t_sign)
+GR_HD uint32_t decode_normal_tangent_oct8(const Payload &p, const Stream &s, uint32_t lane, bool &t_sign)
 {
 	uint32_t v[4];
 	decode_bytes4(p, s, lane, v);
@@ -149,19 +144,19 @@ GR_MESHLET_FN uint32_t decode_normal_tangent_oct8(const Payload &p, const Stream
 		t_sign = aux == 2u;
 	return pack_bytes4(v);
 }
-GR_MESHLET_FN uint32_t decode_bone_indices(const Payload &p, const Stream &s, uint32_t lane)
+GR_HD uint32_t decode_bone_indices(const Payload &p, const Stream &s, uint32_t lane)
 {
 	uint32_t v[4];
 	decode_bytes4(p, s, lane, v);
 	return pack_bytes4(v);
 }
-GR_MESHLET_FN uint32_t decode_bone_weights(const Payload &p, const Stream &s, uint32_t lane) { return decode_bone_indices(p, s, lane); }
+GR_HD uint32_t decode_bone_weights(const Payload &p, const Stream &s, uint32_t lane) { return decode_bone_indices(p, s, lane); }
 
 // ---- attributes -----------------------------------------------------------------------------------------------------------------------
-GR_MESHLET_FN float snorm_exp_position(int16_t v, int exponent) { return ldexpf(float(v), exponent); }
-GR_MESHLET_FN float snorm_exp_uv(int16_t v, int exponent) { return 0.5f * ldexpf(float(v), exponent) + 0.5f; }
+GR_HD float snorm_exp_position(int16_t v, int exponent) { return ldexpf(float(v), exponent); }
+GR_HD float snorm_exp_uv(int16_t v, int exponent) { return 0.5f * ldexpf(float(v), exponent) + 0.5f; }
 
-GR_MESHLET_FN void oct_normal(float fx, float fy, float n[3])
+GR_HD void oct_normal(float fx, float fy, float n[3])
 {
 	n[0] = fx;
 	n[1] = fy;
@@ -174,13 +169,13 @@ GR_MESHLET_FN void oct_normal(float fx, float fy, float n[3])
 	n[1] /= len;
 	n[2] /= len;
 }
-GR_MESHLET_FN uint32_t quantize_snorm(float v, float scale, uint32_t mask) { return uint32_t(int32_t(roundf(fminf(fmaxf(v, -1.0f), 1.0f) * scale))) & mask; }
-GR_MESHLET_FN uint32_t pack_a2bgr10(float x, float y, float z, float w)
+GR_HD uint32_t quantize_snorm(float v, float scale, uint32_t mask) { return uint32_t(int32_t(roundf(fminf(fmaxf(v, -1.0f), 1.0f) * scale))) & mask; }
+GR_HD uint32_t pack_a2bgr10(float x, float y, float z, float w)
 {
 	return (quantize_snorm(w, 1.0f, 3u) << 30) | (quantize_snorm(z, 511.0f, 1023u) << 20) | (quantize_snorm(y, 511.0f, 1023u) << 10) | quantize_snorm(x, 511.0f, 1023u);
 }
 // nt: the word of decode_normal_tangent_oct8.  normal.w is 0, tangent.w is -1 for t_sign and 1 otherwise.
-GR_MESHLET_FN void oct8_normal_tangent(uint32_t nt, bool t_sign, uint32_t &normal, uint32_t &tangent)
+GR_HD void oct8_normal_tangent(uint32_t nt, bool t_sign, uint32_t &normal, uint32_t &tangent)
 {
 	float f[4], n[3], t[3];
 	for (int i = 0; i < 4; i++)
@@ -209,7 +204,7 @@ struct DecodeArgs
 	uint32_t stream_count, target_style;
 };
 
-GR_MESHLET_FN Stream load_stream(const Stream *s)
+GR_HD Stream load_stream(const Stream *s)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
 	const uint4 v = *reinterpret_cast<const uint4 *>(s); // one 16-byte load, the same address in all 32 lanes of a meshlet
@@ -218,10 +213,10 @@ GR_MESHLET_FN Stream load_stream(const Stream *s)
 	return *s;
 #endif
 }
-template <typename T> GR_MESHLET_FN void store_aligned(uint8_t *at, T v) { __builtin_memcpy(__builtin_assume_aligned(at, sizeof(T)), &v, sizeof(T)); }
+template <typename T> GR_HD void store_aligned(uint8_t *at, T v) { __builtin_memcpy(__builtin_assume_aligned(at, sizeof(T)), &v, sizeof(T)); }
 
 // INDEX_BYTES: 4 (unrolled mesh), 2 (INDEX16) or 1.  ALIGNED: `indices` is a multiple of INDEX_BYTES; otherwise bytes are stored one by one.
-template <int INDEX_BYTES, bool ALIGNED> GR_MESHLET_FN void store_index(uint8_t *at, uint32_t v)
+template <int INDEX_BYTES, bool ALIGNED> GR_HD void store_index(uint8_t *at, uint32_t v)
 {
 	if (INDEX_BYTES == 1)
 		at[0] = uint8_t(v);
@@ -234,7 +229,7 @@ template <int INDEX_BYTES, bool ALIGNED> GR_MESHLET_FN void store_index(uint8_t 
 			at[i] = uint8_t(v >> (8 * i));
 }
 
-template <int INDEX_BYTES, bool ALIGNED> GR_MESHLET_FN void decode_lane(const DecodeArgs &a, uint32_t meshlet, uint32_t lane)
+template <int INDEX_BYTES, bool ALIGNED> GR_HD void decode_lane(const DecodeArgs &a, uint32_t meshlet, uint32_t lane)
 {
 	if (meshlet >= a.meshlet_count || lane >= MAX_ELEMENTS)
 		return;

@@ -11,44 +11,28 @@
 //   - the four texels are joined as linear_combine joins them: two lerps along x, t * (1 - a) + t' * a, then one along y; a weight
 //     of exactly 0 does not read its texel;
 //   - texel indices, textureLodOffset's offset included, are taken modulo the size (Euclidean: -1 is size - 1).
-// fp16 conversion, linear_axis and the Euclidean modulo are env_core.hpp's (the project's one host + device statement of them).
+// fp16 conversion, linear_axis and the Euclidean modulo are core_base.hpp's.
 #pragma once
-#include "env_core.hpp"
-
-#if defined(__HIPCC__)
-#define OCEAN_HD __host__ __device__ __forceinline__
-#else
-#define OCEAN_HD inline
-#endif
+#include "core_base.hpp"
 
 namespace gr_ocean
 {
-using gr_env::half_to_float;
-using gr_env::linear_axis;
-using gr_env::wrapi;
+using gr_core::float_to_half_pinned;
+using gr_core::half_to_float;
+using gr_core::linear_axis;
+using gr_core::wrapi;
 
 constexpr uint32_t NUM_FREQ_BANDS = 8u;
 constexpr float GRAVITY = 9.81f;
 constexpr float LAMBDA = 1.2f;
 enum Variant : uint32_t { HEIGHT = 0, GRADIENT_NORMAL = 1, GRADIENT_DISPLACEMENT = 2, VARIANT_COUNT = 3 };
 
-// The fp16 store conversion of a value that is an fp32 result first, as the shaders' are.  On the device the value is pinned in a
-// register before it is converted: otherwise the compiler fuses a multiply and the conversion behind it into one mixed-precision
-// instruction that rounds the exact product once, to fp16, and a store differs from the shader's in its last bit now and then.
-OCEAN_HD uint32_t float_to_half(float f)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-	asm("" : "+v"(f));
-#endif
-	return gr_env::float_to_half(f);
-}
-
 struct c2
 {
 	float x, y;
 };
 // cmul of generate_fft.comp: (a.x b.x - b.y a.y, a.y b.x + b.y a.x), each product rounded before the sum
-OCEAN_HD c2 cmul(c2 a, c2 b) { return {a.x * b.x - b.y * a.y, a.y * b.x + b.y * a.x}; }
+GR_HD c2 cmul(c2 a, c2 b) { return {a.x * b.x - b.y * a.y, a.y * b.x + b.y * a.x}; }
 
 struct GenerateArgs
 {
@@ -61,13 +45,13 @@ struct GenerateArgs
 };
 
 // i > N / 2 goes negative (the Nyquist bin itself stays positive)
-OCEAN_HD float alias(uint32_t i, uint32_t n)
+GR_HD float alias(uint32_t i, uint32_t n)
 {
 	const float f = float(i);
 	return f > 0.5f * float(n) ? f - float(n) : f;
 }
 
-OCEAN_HD float band_amplitude(const GenerateArgs &g, float fx, float fy)
+GR_HD float band_amplitude(const GenerateArgs &g, float fx, float fy)
 {
 	const float bx = fx * g.freq_to_band_mod, by = fy * g.freq_to_band_mod;
 	float band = bx > by ? bx : by;
@@ -80,7 +64,7 @@ OCEAN_HD float band_amplitude(const GenerateArgs &g, float fx, float fy)
 
 // Bin (x, y) of the animated spectrum; `a` is the distribution at the bin, `b` at its mirror ((N - i) & (N - 1)).  sincosf is the
 // full-range one: w reaches thousands of radians.
-OCEAN_HD uint32_t generate_bin(const GenerateArgs &g, uint32_t x, uint32_t y, c2 a, c2 b)
+GR_HD uint32_t generate_bin(const GenerateArgs &g, uint32_t x, uint32_t y, c2 a, c2 b)
 {
 	const float fx = alias(x, g.nx), fy = alias(y, g.ny);
 	const float kx = g.mod_x * fx, ky = g.mod_y * fy;
@@ -104,7 +88,7 @@ OCEAN_HD uint32_t generate_bin(const GenerateArgs &g, uint32_t x, uint32_t y, c2
 		res.x *= amplitude;
 		res.y *= amplitude;
 	}
-	return float_to_half(res.x) | (float_to_half(res.y) << 16);
+	return float_to_half_pinned(res.x) | (float_to_half_pinned(res.y) << 16);
 }
 
 // ---- LinearWrap over a linear image of C fp16 channels a texel ---------------------------------------------------------------
@@ -118,7 +102,7 @@ template <int C> struct Texel
 {
 	float v[C];
 };
-template <int C> OCEAN_HD Texel<C> fetch_wrap(const Texture &t, int x, int y)
+template <int C> GR_HD Texel<C> fetch_wrap(const Texture &t, int x, int y)
 {
 	const uint16_t *p = reinterpret_cast<const uint16_t *>(t.ptr + size_t(wrapi(y, t.h)) * t.pitch) + size_t(wrapi(x, t.w)) * C;
 	Texel<C> r;
@@ -126,7 +110,7 @@ template <int C> OCEAN_HD Texel<C> fetch_wrap(const Texture &t, int x, int y)
 		r.v[c] = half_to_float(p[c]);
 	return r;
 }
-template <int C> OCEAN_HD Texel<C> lerp(const Texel<C> &lo, const Texel<C> &hi, float t)
+template <int C> GR_HD Texel<C> lerp(const Texel<C> &lo, const Texel<C> &hi, float t)
 {
 	Texel<C> r;
 	for (int c = 0; c < C; c++)
@@ -134,7 +118,7 @@ template <int C> OCEAN_HD Texel<C> lerp(const Texel<C> &lo, const Texel<C> &hi, 
 	return r;
 }
 // textureLodOffset(sampler, (u, v), 0, (ox, oy))
-template <int C> OCEAN_HD Texel<C> sample_wrap(const Texture &t, float u, float v, int ox, int oy)
+template <int C> GR_HD Texel<C> sample_wrap(const Texture &t, float u, float v, int ox, int oy)
 {
 	int x0, y0;
 	float a, b;
@@ -153,9 +137,9 @@ struct uint2_bits
 {
 	uint32_t x, y;
 };
-OCEAN_HD uint2_bits pack4(float x, float y, float z, float w)
+GR_HD uint2_bits pack4(float x, float y, float z, float w)
 {
-	return {float_to_half(x) | (float_to_half(y) << 16), float_to_half(z) | (float_to_half(w) << 16)};
+	return {float_to_half_pinned(x) | (float_to_half_pinned(y) << 16), float_to_half_pinned(z) | (float_to_half_pinned(w) << 16)};
 }
 
 // ---- bake_maps.comp ------------------------------------------------------------------------------------------------------------
@@ -166,7 +150,7 @@ struct BakeArgs
 };
 // Texel (x, y): what the shader stores to iHeightDisplacement and to iGradJacobian.  Both coordinate pairs advance by inv_size.xy; the
 // displacement pair only starts at half a displacement texel, as the shader has it.
-OCEAN_HD void bake_texel(const BakeArgs &a, uint32_t x, uint32_t y, uint2_bits &height_displacement, uint2_bits &grad_jacobian)
+GR_HD void bake_texel(const BakeArgs &a, uint32_t x, uint32_t y, uint2_bits &height_displacement, uint2_bits &grad_jacobian)
 {
 	const float px = float(x) * a.inv_size[0], py = float(y) * a.inv_size[1];
 	const float u = px + 0.5f * a.inv_size[0], v = py + 0.5f * a.inv_size[1];
@@ -197,12 +181,12 @@ struct MipmapArgs
 	uint32_t count_x, count_y;
 };
 // Texel (x, y) of the output, C channels: one LinearWrap tap at (2 gid + 1) * inv_resolution, times result_mod.
-template <int C> OCEAN_HD void mipmap_texel(const MipmapArgs &a, uint32_t x, uint32_t y, uint16_t *out)
+template <int C> GR_HD void mipmap_texel(const MipmapArgs &a, uint32_t x, uint32_t y, uint16_t *out)
 {
 	const float u = (2.0f * float(x) + 1.0f) * a.inv_resolution[0], v = (2.0f * float(y) + 1.0f) * a.inv_resolution[1];
 	const Texel<C> t = sample_wrap<C>(a.in, u, v, 0, 0);
 	for (int c = 0; c < C; c++)
-		out[c] = uint16_t(float_to_half(a.result_mod[c] * t.v[c]));
+		out[c] = uint16_t(float_to_half_pinned(a.result_mod[c] * t.v[c]));
 }
 
 // ---- update_lod.comp -----------------------------------------------------------------------------------------------------------
@@ -217,13 +201,13 @@ struct UpdateLodArgs
 	float base_x, base_y, size_x, size_y;
 	float lod_bias;
 };
-OCEAN_HD float square_dist(const UpdateLodArgs &a, float px, float pz)
+GR_HD float square_dist(const UpdateLodArgs &a, float px, float pz)
 {
 	const float dx = a.camera[0] - px, dy = a.camera[1] - 0.0f, dz = a.camera[2] - pz;
 	return (dx * dx + dy * dy) + dz * dz;
 }
 // Block (x, y): the texel it stores to, (id + image_offset) & (n - 1), and the R16F bits of its LOD.
-OCEAN_HD uint16_t update_lod_texel(const UpdateLodArgs &a, int x, int y, int &image_x, int &image_y)
+GR_HD uint16_t update_lod_texel(const UpdateLodArgs &a, int x, int y, int &image_x, int &image_y)
 {
 	const float x00 = a.base_x + float(x) * a.size_x, y00 = a.base_y + float(y) * a.size_y;
 	const float x10 = x00 + 1.0f * a.size_x, y10 = y00 + 0.0f * a.size_y;
@@ -239,7 +223,7 @@ OCEAN_HD uint16_t update_lod_texel(const UpdateLodArgs &a, int x, int y, int &im
 	lod = fminf(fmaxf(lod, 0.0f), a.max_lod);
 	image_x = (x + a.offset_x) & (a.n - 1);
 	image_y = (y + a.offset_y) & (a.n - 1);
-	return uint16_t(float_to_half(lod));
+	return uint16_t(float_to_half_pinned(lod));
 }
 
 // ---- cull_blocks.comp ----------------------------------------------------------------------------------------------------------
@@ -262,7 +246,7 @@ struct CullArgs
 };
 // frustum_cull: the block's box, widened by the guard band and the heightmap range, against six planes; the corner farthest along
 // a plane's normal decides, and the first plane that has it behind ends the test.
-OCEAN_HD bool box_in_frustum(const CullArgs &a, int x, int y)
+GR_HD bool box_in_frustum(const CullArgs &a, int x, int y)
 {
 	const float min_x = a.base_x + float(x) * a.size_x, min_z = a.base_y + float(y) * a.size_y;
 	const float max_x = min_x + a.size_x, max_z = min_z + a.size_y;
@@ -279,7 +263,7 @@ OCEAN_HD bool box_in_frustum(const CullArgs &a, int x, int y)
 }
 // A nearest tap at texel coordinate c of the n x n LOD image: NearestWrap (c mod n; & (n - 1) is Euclidean on two's complement) or
 // NearestClamp.  For a power-of-two n and |c| < 2^20 this is the texel that uv = (c + 0.5) / n selects.
-OCEAN_HD float lod_tap(const CullArgs &a, int cx, int cy)
+GR_HD float lod_tap(const CullArgs &a, int cx, int cy)
 {
 	if (a.wrap)
 	{
@@ -295,7 +279,7 @@ OCEAN_HD float lod_tap(const CullArgs &a, int cx, int cy)
 }
 // Block (x, y) that passed the box test: its patch and its bucket.  The bucket is the shader's int(min(inner, min of the four)), kept
 // inside 0 .. max_lod whatever the image holds (the shader indexes with it unchecked; an image of update_lod's never leaves the range).
-OCEAN_HD int cull_patch(const CullArgs &a, int x, int y, Patch &patch)
+GR_HD int cull_patch(const CullArgs &a, int x, int y, Patch &patch)
 {
 	const int cx = x + a.offset_x, cy = y + a.offset_y;
 	const float centre = lod_tap(a, cx, cy);

@@ -83,8 +83,8 @@ __global__ __launch_bounds__(GROUP) void k_sky_apply(const ApplyArgs a)
 	{
 		// r, g and b: alpha's two bytes are not stored to
 		uint8_t *texel = a.emissive + size_t(y) * a.emissive_pitch + size_t(x) * 8u;
-		*reinterpret_cast<uint32_t *>(texel) = gr_env::float_to_half(rgb.x) | (gr_env::float_to_half(rgb.y) << 16);
-		*reinterpret_cast<uint16_t *>(texel + 4) = uint16_t(gr_env::float_to_half(rgb.z));
+		*reinterpret_cast<uint32_t *>(texel) = gr_core::float_to_half(rgb.x) | (gr_core::float_to_half(rgb.y) << 16);
+		*reinterpret_cast<uint16_t *>(texel + 4) = uint16_t(gr_core::float_to_half(rgb.z));
 	}
 }
 

@@ -19,11 +19,11 @@
 #pragma once
 #include "env_core.hpp"
 
-#define SKY_HD ENV_HD
-
 namespace gr_sky
 {
-using gr_env::f3;
+using gr_core::dot3;
+using gr_core::f3;
+using gr_core::length3;
 
 constexpr float B_RAYLEIGH[3] = {5.5e-6f, 13.0e-6f, 22.4e-6f};
 constexpr float B_MIE = 21.0e-6f;
@@ -40,41 +40,40 @@ constexpr float H_ATMOSPHERE = 100000.0f;
 constexpr int APPLY_PRIMARY_STEPS = 16, APPLY_LIGHT_STEPS = 8; // skybox.frag
 constexpr int CUBE_PRIMARY_STEPS = 32, CUBE_LIGHT_STEPS = 16;  // volumetric_light_setup_sky.comp
 
-SKY_HD f3 add3(f3 a, f3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-SKY_HD f3 mul3(f3 a, f3 b) { return {a.x * b.x, a.y * b.y, a.z * b.z}; }
-SKY_HD f3 scale3(f3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
-SKY_HD float length3(f3 a) { return sqrtf(gr_env::dot3(a, a)); }
+GR_HD f3 add3(f3 a, f3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
+GR_HD f3 mul3(f3 a, f3 b) { return {a.x * b.x, a.y * b.y, a.z * b.z}; }
+GR_HD f3 scale3(f3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
 // a / length(a): three divisions
-SKY_HD f3 normalize_div(f3 a)
+GR_HD f3 normalize_div(f3 a)
 {
 	const float l = length3(a);
 	return {a.x / l, a.y / l, a.z / l};
 }
 
-SKY_HD float phase_rayleigh(float cos_theta)
+GR_HD float phase_rayleigh(float cos_theta)
 {
 	const float mumu = cos_theta * cos_theta;
 	return 3.0f / (50.2654824574f) * (1.0f + mumu);
 }
-SKY_HD float phase_mie(float cos_theta)
+GR_HD float phase_mie(float cos_theta)
 {
 	const float g = G, gg = G2, mu = cos_theta;
 	const float mumu = mu * mu;
 	return 3.0f / (25.1327412287f) * ((1.0f - gg) * (mumu + 1.0f)) / (powf(1.0f + gg - 2.0f * mu * g, 1.5f) * (2.0f + gg));
 }
-SKY_HD float density_rayleigh(float h) { return expf(-h / H_RAYLEIGH); }
-SKY_HD float density_mie(float h) { return expf(-h / H_MIE); }
-SKY_HD float density_mod_absorption(float h)
+GR_HD float density_rayleigh(float h) { return expf(-h / H_RAYLEIGH); }
+GR_HD float density_mie(float h) { return expf(-h / H_MIE); }
+GR_HD float density_mod_absorption(float h)
 {
 	const float denom = (H_ABSORPTION - h) / ABSORPTION_FALLOFF;
 	return 1.0f / (denom * denom + 1.0f);
 }
 
 // false: quadratic < 0 and both roots are 0
-SKY_HD bool trace_to_sphere(f3 pos, f3 dir, float radius, float &t0, float &t1)
+GR_HD bool trace_to_sphere(f3 pos, f3 dir, float radius, float &t0, float &t1)
 {
-	const float b = 2.0f * gr_env::dot3(pos, dir);
-	const float c = gr_env::dot3(pos, pos) - radius * radius;
+	const float b = 2.0f * dot3(pos, dir);
+	const float c = dot3(pos, pos) - radius * radius;
 	const float quadratic = b * b - 4.0f * c;
 	if (quadratic < 0.0f)
 	{
@@ -88,7 +87,7 @@ SKY_HD bool trace_to_sphere(f3 pos, f3 dir, float radius, float &t0, float &t1)
 	return true;
 }
 
-SKY_HD f3 sample_optical_depth(float h, float &depth_r, float &depth_m, float step_length)
+GR_HD f3 sample_optical_depth(float h, float &depth_r, float &depth_m, float step_length)
 {
 	depth_r = density_rayleigh(h) * step_length;
 	depth_m = density_mie(h) * step_length;
@@ -98,9 +97,9 @@ SKY_HD f3 sample_optical_depth(float h, float &depth_r, float &depth_m, float st
 	        depth_r * B_RAYLEIGH[2] + mie + depth_a * B_ABSORPTION[2]};
 }
 
-SKY_HD float sample_height(f3 sample_pos) { return fmaxf(length3(sample_pos) - E_RADIUS, 0.0f); }
+GR_HD float sample_height(f3 sample_pos) { return fmaxf(length3(sample_pos) - E_RADIUS, 0.0f); }
 
-SKY_HD f3 accumulate_optical_depth(f3 pos, f3 dir, float t, int light_steps)
+GR_HD f3 accumulate_optical_depth(f3 pos, f3 dir, float t, int light_steps)
 {
 	f3 accumulated = {0.0f, 0.0f, 0.0f};
 	const float step_length = t / float(light_steps);
@@ -115,7 +114,7 @@ SKY_HD f3 accumulate_optical_depth(f3 pos, f3 dir, float t, int light_steps)
 }
 
 // The ray's range in the atmosphere, or false where the result is 0: the part of rayleigh_mie_scatter that decides.
-SKY_HD bool scatter_range(f3 pos, f3 v, float &t_start, float &t_diff)
+GR_HD bool scatter_range(f3 pos, f3 v, float &t_start, float &t_diff)
 {
 	float atmos0, atmos1, earth0, earth1;
 	trace_to_sphere(pos, v, E_RADIUS + H_ATMOSPHERE, atmos0, atmos1);
@@ -127,7 +126,7 @@ SKY_HD bool scatter_range(f3 pos, f3 v, float &t_start, float &t_diff)
 	return t_diff > 0.0f && !intersects_earth;
 }
 
-SKY_HD f3 rayleigh_mie_scatter(f3 v, f3 l, float camera_height, int primary_steps, int light_steps)
+GR_HD f3 rayleigh_mie_scatter(f3 v, f3 l, float camera_height, int primary_steps, int light_steps)
 {
 	camera_height = fmaxf(camera_height, 0.0f);
 	const f3 pos = {0.0f, E_RADIUS + camera_height, 0.0f};
@@ -154,7 +153,7 @@ SKY_HD f3 rayleigh_mie_scatter(f3 v, f3 l, float camera_height, int primary_step
 		inscatter_mie = add3(inscatter_mie, scale3(transmittance, depth_m));
 	}
 
-	const float cos_theta = gr_env::dot3(v, l);
+	const float cos_theta = dot3(v, l);
 	const float pr = phase_rayleigh(cos_theta);
 	inscatter_rayleigh = mul3(inscatter_rayleigh, f3{pr * B_RAYLEIGH[0], pr * B_RAYLEIGH[1], pr * B_RAYLEIGH[2]});
 	inscatter_mie = scale3(inscatter_mie, phase_mie(cos_theta) * B_MIE);
@@ -162,14 +161,14 @@ SKY_HD f3 rayleigh_mie_scatter(f3 v, f3 l, float camera_height, int primary_step
 }
 
 // ---- the pixel's direction ------------------------------------------------------------------------------------------------------
-SKY_HD f3 pixel_direction(const float *inv, uint32_t width, uint32_t height, uint32_t x, uint32_t y)
+GR_HD f3 pixel_direction(const float *inv, uint32_t width, uint32_t height, uint32_t x, uint32_t y)
 {
 	const float px = 2.0f * (float(x) + 0.5f) / float(width) - 1.0f, py = 2.0f * (float(y) + 0.5f) / float(height) - 1.0f;
 	return {inv[0] * px + inv[4] * py + inv[8] + inv[12], inv[1] * px + inv[5] * py + inv[9] + inv[13], inv[2] * px + inv[6] * py + inv[10] + inv[14]};
 }
 
 // skybox.frag without HAVE_EMISSIVE
-SKY_HD f3 sky_procedural(f3 direction, const float *color, const float *sun_direction, float camera_height)
+GR_HD f3 sky_procedural(f3 direction, const float *color, const float *sun_direction, float camera_height)
 {
 	const f3 s = rayleigh_mie_scatter(normalize_div(direction), f3{sun_direction[0], sun_direction[1], sun_direction[2]}, camera_height, APPLY_PRIMARY_STEPS,
 	                                  APPLY_LIGHT_STEPS);
@@ -178,7 +177,7 @@ SKY_HD f3 sky_procedural(f3 direction, const float *color, const float *sun_dire
 
 // ---- the textured variant ---------------------------------------------------------------------------------------------------------
 // (sc, tc) / |ma| of `d` by the row of the Vulkan table that belongs to `face`, whichever axis of d is the longest.
-SKY_HD void project_on_face(int face, f3 d, float &u, float &v)
+GR_HD void project_on_face(int face, f3 d, float &u, float &v)
 {
 	float sc, tc, ma;
 	switch (face)
@@ -194,7 +193,7 @@ SKY_HD void project_on_face(int face, f3 d, float &u, float &v)
 	v = tc / ma;
 }
 
-SKY_HD float cube_lambda(const float *inv, uint32_t width, uint32_t height, uint32_t x, uint32_t y, int face, uint32_t size, uint32_t levels)
+GR_HD float cube_lambda(const float *inv, uint32_t width, uint32_t height, uint32_t x, uint32_t y, int face, uint32_t size, uint32_t levels)
 {
 	const uint32_t x0 = x & ~1u, x1 = x | 1u, y0 = y & ~1u, y1 = y | 1u;
 	float len_dx = 0.0f, len_dy = 0.0f;
@@ -223,7 +222,7 @@ SKY_HD float cube_lambda(const float *inv, uint32_t width, uint32_t height, uint
 }
 
 // skybox.frag with HAVE_EMISSIVE: texture(uSkybox, vDirection).rgb * color
-SKY_HD f3 sky_textured(const gr_env::Cube &cube, const float *inv, uint32_t width, uint32_t height, uint32_t x, uint32_t y, const float *color)
+GR_HD f3 sky_textured(const gr_env::Cube &cube, const float *inv, uint32_t width, uint32_t height, uint32_t x, uint32_t y, const float *color)
 {
 	const f3 d = pixel_direction(inv, width, height, x, y);
 	float sc, tc, ma;
@@ -238,7 +237,7 @@ SKY_HD f3 sky_textured(const gr_env::Cube &cube, const float *inv, uint32_t widt
 }
 
 // ---- volumetric_light_setup_sky.comp ------------------------------------------------------------------------------------------------
-SKY_HD f3 sky_cube_texel(uint32_t face, uint32_t x, uint32_t y, float inv_resolution, const float *sun_color, const float *sun_direction, float camera_y)
+GR_HD f3 sky_cube_texel(uint32_t face, uint32_t x, uint32_t y, float inv_resolution, const float *sun_color, const float *sun_direction, float camera_y)
 {
 	// inc/cube_coordinates.h: base_dirs, pos_du, pos_dv
 	const float base[6][3] = {{1.0f, 0.0f, 0.0f}, {-1.0f, 0.0f, 0.0f}, {0.0f, 1.0f, 0.0f}, {0.0f, -1.0f, 0.0f}, {0.0f, 0.0f, 1.0f}, {0.0f, 0.0f, -1.0f}};

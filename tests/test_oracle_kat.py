@@ -342,7 +342,7 @@ def test_oracle_reproduces_committed_fixtures():
 
 
 def test_unorm8_decode_without_a_division_is_exact():
-    """device_common.hpp unorm8_to_float: fma(v, hi, fl(v * lo)) with hi = fl(1/255), lo = fl(1/255 - hi) equals the IEEE
+    """core_base.hpp unorm8_to_float: fma(v, hi, fl(v * lo)) with hi = fl(1/255), lo = fl(1/255 - hi) equals the IEEE
     quotient v / 255 for every byte (exact rational arithmetic, one rounding per operation, ties to even), so kernels may
     use it where the oracle divides."""
     from fractions import Fraction

@@ -141,7 +141,7 @@ EXPORTED_SYMBOLS = [
     "gra_get_render_parameters", "gra_set_lights", "gra_upload_gbuffer", "gra_render_frames", "gra_sync",
     "gra_get_resource", "gra_read_resource", "gra_get_backbuffer", "gra_read_backbuffer", "gra_get_cluster_state",
     "gra_dump_graph", "gra_collect_timestamps", "gra_get_kernel_context", "gra_get_stream", "gra_get_taa_reprojection",
-    "gra_set_smaa_luts", "gra_get_host_stats", "gra_get_output_gather_stats", "gra_get_prefetched_refreshes", "gra_get_launch_graph_replays", "gra_get_allocated_bytes", "gra_gtx_probe", "gra_gtx_read", "gra_gtx_write", "gra_gtx_decode", "gra_environment_bake", "gra_fft_transform",
+    "gra_set_smaa_luts", "gra_get_host_stats", "gra_get_output_gather_stats", "gra_get_prefetched_refreshes", "gra_get_launch_graph_replays", "gra_get_allocated_bytes", "gra_gtx_probe", "gra_gtx_read", "gra_gtx_write", "gra_gtx_decode", "gra_gtx_encode", "gra_string_to_format", "gra_gtx_encode_layout", "gra_environment_bake", "gra_fft_transform",
     "gra_upload_gbuffer_gtx", "gra_save_resource_gtx", "gra_get_render_size", "gra_upload_ambient_occlusion", "gra_upload_aa_bench_images", "gra_compute_rec709_to_display", "gra_set_exchange_callback", "gra_get_strip_plan", "gra_get_strip_plan_aa", "gra_get_strip_plan_taa_history",
     "gra_comm_create_unique_id", "gra_comm_init", "gra_comm_info", "gra_comm_init_output", "gra_install_ssr_tables", "gra_reset_timestamps", "gra_set_directional_light", "gra_set_fog", "gra_generate_mipmaps", "gra_write_resource", "gra_get_frame_state", "gra_set_frame_state",
     "gra_video_begin", "gra_video_frame_layout", "gra_video_read_frame", "gra_video_end",
@@ -208,6 +208,9 @@ def load_library() -> C.CDLL:
         "gra_gtx_read": (C.c_int, [C.c_char_p, vp, C.c_uint64, vp, C.c_size_t]),
         "gra_gtx_write": (C.c_int, [C.c_char_p, vp, vp, vp, C.c_size_t]),
         "gra_gtx_decode": (C.c_int, [vp, C.c_char_p, C.c_char_p]),
+        "gra_gtx_encode": (C.c_int, [vp, C.c_char_p, C.c_char_p, C.c_uint32, C.c_int]),
+        "gra_string_to_format": (C.c_uint32, [C.c_char_p]),
+        "gra_gtx_encode_layout": (C.c_int, [vp, C.c_uint32, C.c_int, vp, vp, C.c_uint32, vp, C.c_size_t]),
         "gra_environment_bake": (C.c_int, [vp, C.c_char_p, C.c_float] + [C.c_char_p] * 3),
         "gra_fft_transform": (C.c_int, [vp, P(FftRequest)]),
         "gra_meshlet_describe": (C.c_int, [C.c_char_p, P(MeshletInfo), vp, C.c_size_t]),
@@ -256,6 +259,11 @@ def load_library() -> C.CDLL:
         fn.restype, fn.argtypes = res, args
     _lib = lib
     return lib
+
+
+def string_to_format(name: str) -> int:
+    """Granite::string_to_format for the names this build encodes (bc4_unorm, bc5_unorm, r8_unorm, rg8_unorm, rgba8_unorm); 0 otherwise."""
+    return int(load_library().gra_string_to_format(str(name).encode()))
 
 
 def _ptr(a):
@@ -432,6 +440,15 @@ class Application:
     def decode_gtx(self, src: str, dst: str):
         """Decode the block-compressed .gtx `src` (BC1-BC7 or ASTC LDR) on the device, every level and layer, into the uncompressed .gtx `dst`."""
         self._check(self.lib.gra_gtx_decode(self.handle, str(src).encode(), str(dst).encode()))
+
+    def encode_gtx(self, src: str, dst: str, format, mipgen: bool = False):
+        """Compress the .gtx `src` (R8 / RG8 / RGBA8) on the device into the .gtx `dst`: `format` is a name Granite::string_to_format
+        takes here (bc4_unorm, bc5_unorm, r8_unorm, rg8_unorm, rgba8_unorm) or its VkFormat number; mipgen=True makes the full mip chain
+        from level 0 first."""
+        number = string_to_format(format) if isinstance(format, str) else int(format)
+        if not number:
+            raise ValueError(f"{format!r} is not a format this build encodes")
+        self._check(self.lib.gra_gtx_encode(self.handle, str(src).encode(), str(dst).encode(), number, int(bool(mipgen))))
 
     def bake_environment(self, equirect: str, cube: Optional[str] = None, reflection: Optional[str] = None, irradiance: Optional[str] = None,
                          cube_scale: float = 1.0):

@@ -688,6 +688,9 @@ def load_library() -> C.CDLL:
         "gr_texture_block_dim": (C.c_int, [C.c_uint32, P(C.c_uint32), P(C.c_uint32)]),
         "gr_texture_block_info": (C.c_int, [C.c_uint32, P(C.c_uint32), P(C.c_uint32)]),
         "gr_texture_decode": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint32, P(Image)]),
+        "gr_texture_encode_supported": (C.c_int, [C.c_uint32, C.c_uint32]),
+        "gr_texture_encode": (C.c_int, [vp, vp, C.c_uint32, P(Image), vp, C.c_uint32]),
+        "gr_texture_generate_mipmap": (C.c_int, [vp, vp, P(Image), P(Image)]),
         "gr_cube_chain_bytes": (C.c_uint64, [C.c_uint32, C.c_uint32]),
         "gr_cube_chain_offset": (C.c_uint64, [C.c_uint32, C.c_uint32, C.c_uint32]),
         "gr_env_equirect_to_cube": (C.c_int, [vp, vp, P(Image), vp, C.c_uint32, C.c_uint32]),
@@ -747,6 +750,7 @@ EXPORTED_SYMBOLS = [
     "gr_hiz", "gr_mip_chain_offset", "gr_mip_chain_size", "gr_fsr_upscale", "gr_fsr_sharpen", "gr_fill_byte", "gr_fill_u32", "gr_pq10_encode", "gr_get_device_info", "gr_spd_downsample", "gr_debug_mix", "gr_pack_b10g11r11",
     "gr_video_scale", "gr_video_scale_plan", "gr_video_scaler_weights", "gr_video_yuv_to_rgb", "gr_video_yuv_plan",
     "gr_texture_decoded_format", "gr_texture_block_bytes", "gr_texture_block_dim", "gr_texture_block_info", "gr_texture_decode",
+    "gr_texture_encode_supported", "gr_texture_encode", "gr_texture_generate_mipmap",
     "gr_cube_chain_bytes", "gr_cube_chain_offset", "gr_env_equirect_to_cube", "gr_env_specular", "gr_env_diffuse",
     "gr_fft_describe", "gr_fft_plan_create", "gr_fft_plan_destroy", "gr_fft_plan_iterations", "gr_fft_execute", "gr_fft_execute_iteration",
     "gr_ocean_generate_fft", "gr_ocean_bake_maps", "gr_ocean_mipmap", "gr_ocean_update_lod", "gr_ocean_init_counter_buffer", "gr_ocean_cull_blocks",
@@ -1112,6 +1116,17 @@ class Context:
         texels a block as texture_block_info gives them) into `out` (DeviceImage or Image) of the decoded format."""
         desc = out.desc if isinstance(out, DeviceImage) else out
         self.check(self.lib.gr_texture_decode(self.handle, stream, int(block_format), blocks, int(block_row_pitch), C.byref(desc)))
+
+    def texture_encode(self, block_format: int, image, blocks, block_row_pitch: int, stream=None):
+        """gr_texture_encode: one level of one layer of R8 / RG8 / RGBA8 texels (`image`: DeviceImage or Image) to BC4 / BC5 blocks at the
+        device pointer `blocks`, ceil(w / 4) blocks a row, rows `block_row_pitch` bytes apart."""
+        desc = image.desc if isinstance(image, DeviceImage) else image
+        self.check(self.lib.gr_texture_encode(self.handle, stream, int(block_format), C.byref(desc), blocks, int(block_row_pitch)))
+
+    def texture_generate_mipmap(self, src, dst, stream=None):
+        """gr_texture_generate_mipmap: `dst` (max(src >> 1, 1) texels an axis, same UNORM8 format) from `src`; DeviceImage or Image each."""
+        s, d = (i.desc if isinstance(i, DeviceImage) else i for i in (src, dst))
+        self.check(self.lib.gr_texture_generate_mipmap(self.handle, stream, C.byref(s), C.byref(d)))
 
     @staticmethod
     def texture_block_info(block_format: int):

@@ -5,6 +5,7 @@
 #include "../post/spd.hpp"
 #include "../gtx.hpp"
 #include "../texture_decoder.hpp"
+#include "../texture_compression.hpp"
 #include "../utils/image_utils.hpp"
 #include "../fft/fft.hpp"
 #include "../ocean.hpp"
@@ -369,6 +370,60 @@ int gra_gtx_decode(gra_app *app, const char *src_path, const char *dst_path)
 		if (!device.get_context())
 			throw std::logic_error("gra_gtx_decode: the application has no device");
 		gtx_save(decode_compressed_image(device.get_context(), nullptr, gtx_load(src_path)), dst_path);
+	});
+}
+
+int gra_gtx_encode(gra_app *app, const char *src_path, const char *dst_path, uint32_t format, int generate_mipmaps_)
+{
+	return guarded(app, [&]() {
+		if (!src_path || !dst_path)
+			throw std::logic_error("gra_gtx_encode: null path");
+		auto &device = app->app->get_device();
+		if (!device.get_context())
+			throw std::logic_error("gra_gtx_encode: the application has no device");
+		GtxImage image = gtx_load(src_path);
+		if (generate_mipmaps_)
+			image = generate_mipmaps(device.get_context(), nullptr, image);
+		CompressorArguments args;
+		args.format = VkFormat(format);
+		gtx_save(compress_texture(device.get_context(), nullptr, args, image), dst_path);
+	});
+}
+
+uint32_t gra_string_to_format(const char *name)
+{
+	return name ? uint32_t(string_to_format(name)) : 0u;
+}
+
+int gra_gtx_encode_layout(const gra_gtx_info *input, uint32_t format, int generate_mipmaps_, gra_gtx_info *output, uint64_t *level_offsets,
+                          uint32_t level_capacity, char *error, size_t error_size)
+{
+	return guarded_message(error, error_size, [&]() {
+		if (!input || !output)
+			throw std::logic_error("gra_gtx_encode_layout: null argument");
+		GtxImage img;
+		img.type = input->type;
+		img.format = VkFormat(input->format);
+		img.width = input->width;
+		img.height = input->height;
+		img.depth = input->depth;
+		img.layers = input->layers;
+		img.levels = input->levels;
+		img.flags = input->flags;
+		if (!img.width || !img.height || img.depth != 1 || !img.layers || !img.levels || img.levels > 16 || img.width > 65536u || img.height > 65536u ||
+		    img.layers > 65536u)
+			throw std::logic_error("gra_gtx_encode_layout: empty, 3-D or implausible dimensions");
+		if (!vk_format_payload_block_size(VkFormat(format)))
+			throw std::logic_error("gra_gtx_encode_layout: format " + std::to_string(format) + " is not one the executor handles");
+		if (generate_mipmaps_)
+		{
+			img.levels = num_miplevels(img.width, img.height);
+			img.flags &= ~2u;
+		}
+		const GtxImage out = compressed_layout(img, VkFormat(format));
+		fill_gtx_info(output, out);
+		for (uint32_t l = 0; level_offsets && l < level_capacity && l < out.levels; l++)
+			level_offsets[l] = out.level_offset(l);
 	});
 }
 

@@ -121,3 +121,13 @@ def write(path: str, fmt: int, levels: List[np.ndarray], flags: int = 0, layers:
     err = C.create_string_buffer(512)
     if _lib().gra_gtx_write(path.encode(), C.byref(info), payload.ctypes.data, err, len(err)) < 0:
         raise GtxError(err.value.decode())
+
+
+def encode_layout(info: GtxInfo, fmt: int, mipgen: bool = False):
+    """(GtxInfo, [level offsets]) of what Application.encode_gtx writes for an image described by `info` (gra_gtx_encode_layout; no device)."""
+    out = GtxInfo()
+    offsets = (C.c_uint64 * 32)()
+    err = C.create_string_buffer(512)
+    if _lib().gra_gtx_encode_layout(C.byref(info), int(fmt), int(bool(mipgen)), C.byref(out), offsets, len(offsets), err, len(err)) < 0:
+        raise GtxError(err.value.decode())
+    return out, [int(o) for o in offsets[:out.levels]]

@@ -232,6 +232,20 @@ int gra_upload_gbuffer_gtx(gra_app *app, const char *emissive, const char *albed
  * (Granite::decode_compressed_image, one gr_texture_decode each), and writes an uncompressed .gtx of the decoded format with the
  * same extents, layers, levels and flags. */
 int gra_gtx_decode(gra_app *app, const char *src_path, const char *dst_path);
+/* What tools/gtx_convert.cpp does for the formats this build encodes, on the application's device.  The .gtx `src_path` (R8_UNORM,
+ * R8G8_UNORM, R8G8B8A8_UNORM; R8G8B8A8_SRGB for a block target without generate_mipmaps; no 3-D) gets, with generate_mipmaps != 0, a full
+ * mip chain made from its level 0 (Granite::generate_mipmaps; a chain it has is made again), then every level and layer is compressed to
+ * `format` (Granite::compress_texture): VK_FORMAT_BC4_UNORM_BLOCK (139), VK_FORMAT_BC5_UNORM_BLOCK (141, not from R8_UNORM), or the
+ * input's own format for a copy.  `dst_path` keeps the extents, layers and flags (less the mipgen-on-load bit where mips were made). */
+int gra_gtx_encode(gra_app *app, const char *src_path, const char *dst_path, uint32_t format, int generate_mipmaps);
+/* Needs no device.  Granite::string_to_format for the names gra_gtx_encode handles (bc4_unorm, bc5_unorm, r8_unorm, rg8_unorm,
+ * rgba8_unorm); 0 (VK_FORMAT_UNDEFINED) for every other name and for NULL. */
+uint32_t gra_string_to_format(const char *name);
+/* Needs no device.  The layout gra_gtx_encode gives an image described by `input` (payload_size is not read): *output is its header for
+ * `format`, with generate_mipmaps != 0 for the full chain, and level_offsets[l], l < level_capacity and l < output->levels, the payload
+ * offset of level l.  level_offsets may be NULL. */
+int gra_gtx_encode_layout(const gra_gtx_info *input, uint32_t format, int generate_mipmaps, gra_gtx_info *output, uint64_t *level_offsets,
+                          uint32_t level_capacity, char *error, size_t error_size);
 /* Environment baking on the application's device, what tools/convert_equirect_to_environment.cpp does: the 2-D R16G16B16A16_SFLOAT
  * .gtx `equirect_gtx` becomes a cube of unsigned(cube_scale * max(width / 3, height / 2)) texels with a full mip chain
  * (Granite::convert_equirect_to_cube), from which the 128-texel, 8-level GGX reflection cube (convert_cube_to_ibl_specular) and the

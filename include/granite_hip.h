@@ -57,7 +57,8 @@ typedef enum gr_format
 	GR_FORMAT_B10G11R11_UFLOAT_PACK32 = 122, /* HDR targets with renderTargetFp16 = false (scene_viewer_application.cpp:881-883), TAA colour (temporal.cpp:211-213) */
 	GR_FORMAT_D16_UNORM = 124,
 	GR_FORMAT_D32_SFLOAT = 126,
-	/* Block-compressed inputs of gr_texture_decode only; no other entry point takes them.  140 and 142 (BC4 / BC5 SNORM) are absent. */
+	/* Block-compressed inputs of gr_texture_decode (BC4 / BC5 UNORM are also what gr_texture_encode writes); no other entry point takes
+	 * them.  140 and 142 (BC4 / BC5 SNORM) are absent. */
 	GR_FORMAT_BC1_RGB_UNORM_BLOCK = 131,
 	GR_FORMAT_BC1_RGB_SRGB_BLOCK = 132,
 	GR_FORMAT_BC1_RGBA_UNORM_BLOCK = 133,
@@ -868,6 +869,33 @@ int gr_texture_block_info(uint32_t block_format, uint32_t *block_bytes, uint32_t
  * whose endpoint mode is an HDR one; a void extent stores the top bytes of its colour whether or not its HDR flag is set. */
 int gr_texture_decode(gr_ctx *ctx, gr_stream stream, uint32_t block_format, const void *blocks,
                       uint32_t block_row_pitch_bytes, const gr_image *out);
+
+/* ---- Block-compressed texture encode and mip generation (scene-export/rgtc_compressor.cpp, texture_compression.cpp's
+ * enqueue_compression_block_rgtc, texture_utils.cpp's generate_mipmaps).  Integer rules for the blocks, fp32 with one rounding an operation
+ * for the mips: both give the bytes the reference's code gives on a CPU. ---- */
+
+/* Host-only. 1 where gr_texture_encode takes the pair, 0 otherwise: GR_FORMAT_BC4_UNORM_BLOCK from R8_UNORM, R8G8_UNORM, R8G8B8A8_UNORM
+ * or R8G8B8A8_SRGB; GR_FORMAT_BC5_UNORM_BLOCK from the last three.  No other block format is encoded. */
+int gr_texture_encode_supported(uint32_t block_format, uint32_t input_format);
+/* One level of one layer.  `in`: width x height texels (at most 65536 an axis) of one of the four formats above; its raw bytes are read,
+ * component 0 for BC4, components 0 and 1 for BC5, so an _SRGB image is encoded as the numbers it holds.  Any in->pitch_bytes >= the
+ * row's bytes and any byte alignment of in->ptr.
+ * `blocks`: device pointer, receives ceil(w/4) x ceil(h/4) blocks of 8 (BC4) or 16 (BC5: the red block, then the green one) bytes, rows
+ * `block_row_pitch_bytes` apart.  The pointer and the pitch must be multiples of the block size and the pitch >= ceil(w/4) blocks.
+ * Exactly those blocks are written: no byte between the end of a row of blocks and the next row.  A block that reaches past the right or
+ * bottom edge is filled with the last column / row of the image.
+ * width or height 0 returns GR_OK without launching.  Refused before a launch, with the argument and the rule in gr_last_error:
+ * a block format or input format other than the above and BC5 from R8_UNORM (GR_ERR_UNSUPPORTED_FORMAT); null pointers, an extent above
+ * 65536, a pitch that does not cover a row, a misaligned `blocks` or block pitch (GR_ERR_INVALID_ARGUMENT). */
+int gr_texture_encode(gr_ctx *ctx, gr_stream stream, uint32_t block_format, const gr_image *in, void *blocks,
+                      uint32_t block_row_pitch_bytes);
+/* One mip level of one layer: dst_level is the bilinear reduction of src_level as generate_mipmaps computes it, each destination texel
+ * filtered from four taps of the source around its own centre, stored with round-half-away-from-zero.  Both images have the same format,
+ * R8_UNORM, R8G8_UNORM or R8G8B8A8_UNORM, and dst_level is max(src >> 1, 1) texels an axis.  Any pitch that covers a row and any byte
+ * alignment.  Refused before a launch: R8G8B8A8_SRGB (its filter works in linear light, which is not built), every other format and
+ * two different formats (GR_ERR_UNSUPPORTED_FORMAT); null pointers, an empty image, a source above 65536 texels an axis, a dst_level of
+ * another extent, a pitch that does not cover a row, images that share bytes (GR_ERR_INVALID_ARGUMENT). */
+int gr_texture_generate_mipmap(gr_ctx *ctx, gr_stream stream, const gr_image *src_level, const gr_image *dst_level);
 
 /* ---- environment baking ---------------------------------------------------------------------------------------------------
  * renderer/utils/image_utils.cpp: convert_equirect_to_cube, convert_cube_to_ibl_specular, convert_cube_to_ibl_diffuse

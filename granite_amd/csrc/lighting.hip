@@ -9,27 +9,36 @@
 // HDR may be the same buffer (the reference's blend read-modify-write) or distinct ones (same values, same bytes).  The two
 // blend roundings of the reference are reproduced in registers: hdr = rne16(rne16(emissive + directional) + clustered).
 //
-// Mapping.  A wave64 owns an 8x8 pixel tile and never synchronises with another wave (wave-private LDS, no barriers);
-// four waves side by side form a 32x8 workgroup so every row of the workgroup is one 256 B HDR / 128 B G-buffer segment.
-// The light loop is wave-uniform like the reference's subgroup path (clusterer_bindless.h:49-81), in three steps per
-// 64-light chunk of the tile's light-index window:
-//   1. gather (one LIGHT per lane): lane l owns light 64*chunk + l.  Its bit is the OR of that bit over every cluster
-//      cell the tile touches, trimmed to the wave's Z-slice index window [min first, max last] - a superset of the
-//      reference's subgroupOr of per-lane trimmed masks.  What the superset adds lies outside its radius for the pixels
-//      concerned and contributes exactly 0 (point.h:38, spot.h:45); the reference's subgroup footprint cannot matter
-//      for the same reason (oracle: orc_lighting_bruteforce_clustered).
-//   2. cull + stage: each lane tests its light's sphere (1.001 r) against the tile's bounding sphere, and a spot's cone
-//      against the same sphere (most of a spot's sphere lies outside its cone); a survivor writes its record -- with per-light
-//      constants (10 / r, (1.001 r)^2, fp32 spot scale / bias) computed once per light instead of once per pixel -- into
-//      the slot of its own lane in a wave-private LDS list.  Two ballots name the survivors: point lights, and the lights
-//      walked with the cone body (spots, and point lights small enough for the 0.1 distance floor to matter).
-//   3. shade (one PIXEL per lane): the set bits of each ballot are walked in index order by a loop with a straight-line body
-//      (no light-type branch) and broadcast ds_read_b128; every BRDF operand is a VGPR.
-//      On gfx950 fp32 fma / mul / add issue at full rate only with VGPR / literal / inline operands (measured: 1.2 ns per
-//      wave-instruction per SIMD vs 1.9 ns with an SGPR operand, 2.0 ns for min / max / med3 / cmp / cvt, 3.6 ns for
-//      rcp / rsq), which is what bounds this kernel on the 4096-light config, not HBM.
-// The BRDF is algebraically the reference's; normalisations are folded (dot products on the unnormalised light vector,
-// H.V = |V+L|/2, one rcp for G*D) to cut the per-light VALU count.
+// Mapping.  A wave64 owns a tile of 8 PX x 8 pixels, PX horizontally adjacent pixels per lane: two (16x8) whenever the lane's pair of
+// texels is one naturally aligned access in every attachment (even width, even pitches in texels), else one (gr_lighting).  A wave never
+// synchronises with another wave (wave-private LDS, no barriers); four waves side by side form a workgroup, so every row of the workgroup
+// is one contiguous segment of each attachment.  k_lighting loads the tile's attachment words (load_raw) and shade_tile runs the stages:
+//   * unpack_raw, decode_gbuffer, make_surface: the words of a pixel, its G-buffer values, its world position and the material terms
+//     that are hoisted out of the light loop (Surface);
+//   * directional_quad: the directional term, the ambient fallback and the AO sample, blended into the texel (the first blend);
+//   * the slice window: the light-index window [min first, max last] of the Z slices of the tile's pixels, and for a wide window the
+//     gap trim: the indices between the foreground's ranges and the background's, which are in no pixel's range, leave the window;
+//   * tile_cells, bounding_sphere: the cluster cells the tile touches and the sphere around its lit pixels;
+//   * the gather, one LIGHT per lane.  Narrow window (one or two 64-light chunks): lane l owns light 64 * chunk + l and ORs its bit over
+//     the touched cells (or_cell_words) -- a superset of the reference's subgroupOr of per-lane trimmed masks.  What the superset adds lies
+//     outside its radius for the pixels concerned and contributes exactly 0 (point.h:38, spot.h:45); the reference's subgroup footprint
+//     cannot matter for the same reason (oracle: orc_lighting_bruteforce_clustered).  Wide window (three chunks or more): gather_wide
+//     reads the window's words once and compacts their set bits into a wave-private list, a turn takes the next 64 entries;
+//   * cull_and_stage: each lane tests its light's sphere (1.001 r) against the tile's bounding sphere, and a spot's cone against the same
+//     sphere (most of a spot's sphere lies outside its cone); a tile with a gap has two spheres, one around the pixels below the gap and one
+//     around those above, and a light is tested against the one its index belongs to (the two-sphere cull).  A survivor writes its record --
+//     with per-light constants (10 / r, (1.001 r)^2, fp32 spot scale / bias) computed once per light instead of once per pixel -- into the
+//     slot of its own lane in a wave-private LDS list.  Two ballots name the survivors: point lights, and the lights walked with the cone
+//     body (spots, and point lights small enough for the 0.1 distance floor to matter);
+//   * the two walks, PX PIXELS per lane: the set bits of each ballot are walked in index order (walk_next) by a loop with a straight-line
+//     body (shade_positional: no light-type branch) and broadcast ds_read_b128; every BRDF operand is a VGPR.
+//     On gfx950 fp32 fma / mul / add issue at full rate only with VGPR / literal / inline operands (measured: 1.2 ns per
+//     wave-instruction per SIMD vs 1.9 ns with an SGPR operand, 2.0 ns for min / max / med3 / cmp / cvt, 3.6 ns for
+//     rcp / rsq), which is what bounds this kernel on the 4096-light config, not HBM;
+//   * the three blends.  Each rounds as the attachment's store does (to fp16, or to the packed floats of B10G11R11): the
+//     directional quad's (blend_round), the clustered quad's (the sum goes straight into the halves, or the packed word, that
+//     are written out) and the fog quad's, which reads back what the second blend stored.  Then one store per lane, or none
+//     for an untouched texel in place.
 #include <cstdlib>
 #include <cstring>
 #include "ctx.hpp"
@@ -387,28 +396,20 @@ __device__ __forceinline__ void load_raw(const KernelArgs &a, int x0, int y, Raw
 	}
 }
 
-// One wave, one tile of 8 PX x 8 pixels whose attachment words are in `raw`: both quads, the fog quad, the store.
-template <int PX, bool AO, bool B10>
-__device__ __forceinline__ void shade_tile(const KernelArgs &a, const int tile_x0, const int tile_y0, const int wave, const int lane, const RawTile<PX, B10> &raw,
-                                           f32x4 *const slots, const float *s_srgb LV_STAMP_PARAM)
-{
-	const int x0 = tile_x0 + (lane & (LIGHT_TILE - 1)) * PX;
-	const int y = tile_y0 + (lane >> 3);
-	const int W = a.hdr.w, H = a.hdr.h;
-	const bool row_inside = y >= a.row_first && y < a.row_end; // row_end <= H
+// ---- The stages of a tile, in the order shade_tile runs them.  Each states what it reads and what it produces; none sees shade_tile's scope. ----
 
-	bool inside[PX], active[PX];
-	f16x4 dst[PX];
-	float depth_v[PX];
-	uint32_t alb_v[PX], nrm_v[PX], mr_v[PX];
+// The attachment words of a lane's PX pixels, one set per pixel, and the destination texel (emissive) as four halves, from either format.
+template <int PX, bool B10>
+__device__ __forceinline__ void unpack_raw(const RawTile<PX, B10> &raw, float (&depth)[PX], uint32_t (&alb)[PX], uint32_t (&nrm)[PX], uint32_t (&mr)[PX],
+                                           f16x4 (&dst)[PX])
+{
 #pragma unroll
 	for (int p = 0; p < PX; p++)
 	{
-		inside[p] = row_inside && x0 + p < W;
-		depth_v[p] = raw.depth[p];
-		alb_v[p] = raw.alb[p];
-		nrm_v[p] = raw.nrm[p];
-		mr_v[p] = PX == 2 ? (p == 0 ? raw.mr & 0xffffu : raw.mr >> 16) : raw.mr;
+		depth[p] = raw.depth[p];
+		alb[p] = raw.alb[p];
+		nrm[p] = raw.nrm[p];
+		mr[p] = PX == 2 ? (p == 0 ? raw.mr & 0xffffu : raw.mr >> 16) : raw.mr;
 		if constexpr (B10)
 		{
 			uint32_t rg, ba;
@@ -418,12 +419,265 @@ __device__ __forceinline__ void shade_tile(const KernelArgs &a, const int tile_x
 		else
 			dst[p] = __builtin_bit_cast(f16x4, make_uint2(raw.em[2 * p], raw.em[2 * p + 1]));
 	}
+}
 
-	// ---- position reconstruction (clustering.vert:10-13, clustering.frag:37-39): clip = invVP * (ndc.xy, depth, 1),
-	// pos = clip.xyz / clip.w.  Evaluated with fused multiply-adds and a Newton-refined reciprocal; a pixel that lands
-	// in the neighbouring Z slice because of the last-bit difference sees the same lights up to ones at the very edge
-	// of their radius (falloff -> 0), cf. the conservative slice ranges of clusterer.cpp:1265-1275.  The part that does not
-	// depend on depth is affine in the pixel coordinate: evaluated once per lane, stepped by clip_dx for the second pixel. ----
+// What the attachment holds after a blend's store of `v` into colour channel CHANNEL (0: red): rounded to fp16, or to the packed floats
+// of B10G11R11 (six mantissa bits, five for blue).  One channel at a time: a caller rounds each sum as it forms it, which is the order the
+// compiler's schedule of the kernel was measured with.
+template <bool B10, int CHANNEL>
+__device__ __forceinline__ float blend_round(float v)
+{
+	if constexpr (B10)
+		return round_to_ufloat<CHANNEL == 2 ? 5 : 6>(v);
+	else
+		return float(_Float16(v));
+}
+
+// ---- G-buffer decode (clustering.frag:31-35): linear base colour, the normal as stored (not renormalised), metallic, roughness ----
+__device__ __forceinline__ void decode_gbuffer(const uint32_t alb, const uint32_t nrm, const uint32_t mr, const float *s_srgb, float3_ &base, float3_ &N,
+                                               float &metallic, float &mat_roughness)
+{
+	base = f3(s_srgb[alb & 255u], s_srgb[(alb >> 8) & 255u], s_srgb[(alb >> 16) & 255u]);
+	N = f3(float(nrm & 1023u) * (2.0f / 1023.0f) - 1.0f, float((nrm >> 10) & 1023u) * (2.0f / 1023.0f) - 1.0f,
+	       float((nrm >> 20) & 1023u) * (2.0f / 1023.0f) - 1.0f);
+	metallic = float(mr & 255u) * (1.0f / 255.0f);
+	mat_roughness = float(mr >> 8) * (1.0f / 255.0f);
+}
+
+// ---- position reconstruction (clustering.vert:10-13, clustering.frag:37-39): clip = invVP * (ndc.xy, depth, 1),
+// pos = clip.xyz / clip.w.  Evaluated with fused multiply-adds and a Newton-refined reciprocal; a pixel that lands
+// in the neighbouring Z slice because of the last-bit difference sees the same lights up to ones at the very edge
+// of their radius (falloff -> 0), cf. the conservative slice ranges of clusterer.cpp:1265-1275.  The part that does not
+// depend on depth is affine in the pixel coordinate: shade_tile evaluates it once per lane (clip_base), steps it by clip_dx for the
+// second pixel and adds the depth column; make_surface takes that clip-space position and divides. ----
+//
+// One pixel (`active`: inside the render area and not on the far plane) from its clip-space position and decoded G-buffer: the world
+// position and the material terms of the light loop.
+__device__ __forceinline__ void make_surface(const KernelArgs &a, const float (&clip)[4], const bool active, const float3_ N, const float3_ base,
+                                             const float metallic, const float mat_roughness, Surface &s)
+{
+	const float clip_w = active ? clip[3] : 1.0f;
+	float inv_w = rcp(clip_w);
+	inv_w = inv_w * fmaf(-clip_w, inv_w, 2.0f);
+	const float3_ pos = f3(clip[0] * inv_w, clip[1] * inv_w, clip[2] * inv_w);
+
+	s.pos = pos;
+	s.N = N;
+	const float3_ cam = f3(a.camera_pos[0], a.camera_pos[1], a.camera_pos[2]);
+	float3_ V = cam - pos;
+	V = V * rsq(fmaxf(dot(V, V), 1e-30f));
+	s.V = V;
+	s.NdV = dot(N, V);
+	const float NoV = med3(s.NdV, 0.001f, 1.0f);
+	s.F0 = f3(fmaf(base.x - 0.04f, metallic, 0.04f), fmaf(base.y - 0.04f, metallic, 0.04f), fmaf(base.z - 0.04f, metallic, 0.04f));
+	const float roughness = fmaf(mat_roughness, 0.75f, 0.25f);
+	const float m = roughness * roughness;
+	const float m2 = m * m;
+	s.m2m1 = m2 - 1.0f;
+	const float r1 = roughness + 1.0f;
+	const float k = r1 * r1 * (1.0f / 8.0f);
+	const float omk = 1.0f - k;
+	const float Gv_over_c0 = fmaf(NoV, omk, k) * rcp(m2 * (0.25f / PI_SIC)); // m2 >= 0.0039
+	s.gA = Gv_over_c0 * omk;
+	s.gB = Gv_over_c0 * k;
+	const float kd = (1.0f - metallic) * (1.0f / PI_SIC);
+	s.D1 = f3(fmaf(-s.F0.x, base.x, base.x) * kd, fmaf(-s.F0.y, base.y, base.y) * kd, fmaf(-s.F0.z, base.z, base.z) * kd);
+}
+
+// ---- directional quad (directional.frag:41-65) on pixel (x, y): its term, the ambient fallback and the AO sample, blended into `accum` ----
+template <bool AO, bool B10>
+__device__ __forceinline__ void directional_quad(const KernelArgs &a, const Surface &s, const float3_ base, const int x, const int y, float3_ &accum)
+{
+	if (a.flags & GR_LIGHTING_DIRECTIONAL_BIT)
+	{
+		const float3_ L = f3(a.dir_direction[0], a.dir_direction[1], a.dir_direction[2]);
+		const float3_ Hv = s.V + L;
+		float3_ lit = f3(0.0f, 0.0f, 0.0f);
+		brdf_accumulate(s, dot(s.N, L), fmaxf(dot(Hv, Hv), 1e-30f), 1.0f, f3(a.dir_color[0], a.dir_color[1], a.dir_color[2]), lit);
+		// base_ambient * base_color * 0.05 (directional.frag:52-64); a scalar 0 when the fallback term is off
+		float ambient = (a.flags & GR_LIGHTING_AMBIENT_FALLBACK_BIT) ? 0.05f : 0.0f;
+		if (AO)
+			ambient *= sample_linear_r8(a.ao, (float(x) + 0.5f) * a.inv_resolution[0], (float(y) + 0.5f) * a.inv_resolution[1]);
+		lit = f3(fmaf(base.x, ambient, lit.x), fmaf(base.y, ambient, lit.y), fmaf(base.z, ambient, lit.z));
+		// blend ONE/ONE, attachment store rounds to fp16 (or to the packed floats)
+		accum = f3(blend_round<B10, 0>(accum.x + lit.x), blend_round<B10, 1>(accum.y + lit.y), blend_round<B10, 2>(accum.z + lit.z));
+	}
+}
+
+struct Cells { int cx0, cx1, cy0, cy1; }; // a rectangle of cluster cells, bounds included
+
+// clusterer_bindless.h:39-42 along one axis.
+__device__ __forceinline__ int cluster_cell(int p, float inv_res, float scale, int res)
+{
+	return clamp0_i32(int(__fmul_rn(__fmul_rn(float(p) + 0.5f, inv_res), scale)), res - 1);
+}
+
+// Cluster cells the tile touches (clusterer_bindless.h:39-42 at the tile's first and last pixel; the per-pixel formula is
+// monotonic, so every lane's cell lies in this rectangle).  There is no scalar float unit: lane 0 evaluates the formula for
+// the tile's first pixel, lane 63 for its last one (its second pixel, clamped into the image), and two v_readlane per axis
+// fetch them -- instead of four wave-uniform evaluations on the vector unit.
+template <int PX>
+__device__ __forceinline__ Cells tile_cells(const KernelArgs &a, const int x0, const int y, const int lane)
+{
+	const int my_cx = cluster_cell(min(x0 + (lane >> 5) * (PX - 1), a.hdr.w - 1), a.inv_resolution[0], a.cl_xy_scale[0], a.cl_res_x);
+	const int my_cy = cluster_cell(min(y, a.hdr.h - 1), a.inv_resolution[1], a.cl_xy_scale[1], a.cl_res_y);
+	const int cx0 = __builtin_amdgcn_readlane(my_cx, 0), cx1 = __builtin_amdgcn_readlane(my_cx, 63);
+	const int cy0 = __builtin_amdgcn_readlane(my_cy, 0), cy1 = __builtin_amdgcn_readlane(my_cy, 63);
+	return {cx0, cx1, cy0, cy1};
+}
+
+// Bounding sphere of a set of the tile's surface points (member[p]: a non-empty set): centre = its first pixel, radius = its
+// farthest pixel from that.
+template <int PX>
+__device__ __forceinline__ void bounding_sphere(const bool (&member)[PX], const Surface (&s)[PX], float3_ &centre_out, float &radius_out)
+{
+	bool any_member = false;
+#pragma unroll
+	for (int p = 0; p < PX; p++)
+		any_member = any_member || member[p];
+	const int first = __builtin_ctzll(__ballot(any_member));
+	const float3_ mine = PX == 2 && !member[0] ? s[PX - 1].pos : s[0].pos; // a lane of the ballot has one of them in the set
+	centre_out = f3(__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mine.x), first)),
+	                __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mine.y), first)),
+	                __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mine.z), first)));
+	float off2 = 0.0f;
+#pragma unroll
+	for (int p = 0; p < PX; p++)
+	{
+		const float3_ off = s[p].pos - centre_out;
+		const float mine2 = member[p] ? dot(off, off) : 0.0f;
+		off2 = p == 0 ? mine2 : fmaxf(off2, mine2);
+	}
+	// v_sqrt_f32 (1 ulp) is well inside the 1.0001 + CULL_SLACK margin
+	radius_out = __builtin_amdgcn_sqrtf(__builtin_bit_cast(float, wave_minmax_u32<true>(__builtin_bit_cast(uint32_t, off2)))) * 1.0001f + CULL_SLACK;
+}
+
+// ORs word `my_word` of the cluster bitmask, over the cells of the rectangle, into `word` (which the caller starts at 0: started here, the
+// two-pixel kernels set it with one s_mov_b64 where they have two s_mov_b32).
+__device__ __forceinline__ void or_cell_words(const KernelArgs &a, const Cells &cells, const int my_word, uint32_t &word)
+{
+	for (int cy = cells.cy0; cy <= cells.cy1; cy++)
+	{
+#pragma clang loop vectorize(disable) unroll(disable)
+		for (int cx = cells.cx0; cx <= cells.cx1; cx++)
+			word |= a.bitmask[(cy * a.cl_res_x + cx) * a.cl_num_lights_32 + my_word];
+	}
+}
+
+// ---- wide gather: lane j reads word j of the span that starts at word `span_word`, the set bits of all words go to the list in index
+// order.  Returns the number of list entries. ----
+__device__ __forceinline__ int gather_wide(const KernelArgs &a, const Cells &cells, const uint32_t win_lo, const uint32_t win_hi, const uint32_t gap_lo,
+                                           const uint32_t gap_hi, const int span_word, const int word_last, const int lane, uint16_t *const list)
+{
+	const int my_word = span_word + lane;
+	const uint32_t word_first = uint32_t(my_word) << 5u;
+	uint32_t word = 0u;
+	if (lane < a.list_words && my_word <= word_last)
+	{
+		or_cell_words(a, cells, my_word, word);
+		// the window [win.lo, win.hi] without its gap, as bits of this word
+		word &= bits_from(win_lo, word_first) & ~bits_from(win_hi + 1u, word_first) & ~(bits_from(gap_lo + 1u, word_first) & ~bits_from(gap_hi, word_first));
+	}
+	const uint32_t count = uint32_t(__builtin_popcount(word));
+	const uint32_t upto = wave_inclusive_add_u32(count);
+	const int list_count = __builtin_amdgcn_readlane(int(upto), 63);
+	uint16_t *entry = list + (upto - count);
+	for (; word != 0u; word &= word - 1u)
+		*entry++ = uint16_t(word_first + uint32_t(__builtin_ctz(word)));
+	__builtin_amdgcn_wave_barrier();
+	return list_count;
+}
+
+// ---- cull: one light per lane against the sphere around the pixels it can reach; a survivor (`keep`) stages its record.
+// `second`: walked with the cone body (spot lights, and point lights of radius < 1 / 8). ----
+__device__ __forceinline__ void cull_and_stage(const KernelArgs &a, const uint32_t light_index, const float3_ &centre, const float tile_radius, const int lane,
+                                               f32x4 *const slots, bool &keep, bool &second)
+{
+	const f32x4 *rec = reinterpret_cast<const f32x4 *>(a.lights + light_index);
+	const f32x4 c = rec[0], pq = rec[1], d = rec[2]; // colour|scale_bias, position|offset_radius, direction|inv_radius
+	const float radius = CULL_RADIUS_SCALE * rcp(d.w);
+	const float3_ to_light = f3(pq.x, pq.y, pq.z) - centre;
+	const float reach = radius + tile_radius;
+	const float dist2 = dot(to_light, to_light);
+	keep = dist2 <= reach * reach;
+	const bool is_spot = ((a.type_mask[light_index >> 5] >> (light_index & 31u)) & 1u) == 0u;
+	// unpackHalf2x16(spot_scale_bias).  The lane is copied to a scalar first: clang (ROCm 7.2) evaluates
+	// __builtin_bit_cast on a vector-component lvalue (v.w) at the address of the whole vector, i.e. as
+	// lane .x (observed: spots shaded with colour.x as scale | bias).
+	const float sb_lane = c.w;
+	const uint32_t sb_bits = __builtin_bit_cast(uint32_t, sb_lane);
+	const float spot_scale = float(__builtin_bit_cast(_Float16, uint16_t(sb_bits & 0xffffu)));
+	const float spot_bias = float(__builtin_bit_cast(_Float16, uint16_t(sb_bits >> 16)));
+	if (is_spot && keep && spot_scale > 0.0f)
+	{
+		// Cone vs the tile's bounding sphere.  spot.h:44-45: the cone factor sat(cone_angle * scale + bias) is
+		// exactly 0 for cone_angle <= -bias / scale =: cos(theta).  With v = centre - light, a = dot(v, dir) and
+		// p = distance of the centre from the axis, e = p cos(theta) - a sin(theta) = |v| sin(phi - theta) is the
+		// distance of the centre from the cone's mantle line (never more than its distance from the cone), so
+		// e > tile_radius (+ margin) puts every pixel of the tile outside the cone by an angle far above fp32
+		// rounding: the light adds exactly 0 there.  (theta >= 90 degrees, cos(theta) <= 0, never culls.)
+		const float cos_t = -spot_bias * rcp(spot_scale);
+		if (cos_t > 0.0f && cos_t < 1.0f)
+		{
+			const float sin_t = __builtin_amdgcn_sqrtf(fmaf(-cos_t, cos_t, 1.0f));
+			const float along = -dot(to_light, f3(d.x, d.y, d.z)); // dot(centre - light, direction)
+			const float off_axis = __builtin_amdgcn_sqrtf(fmaxf(fmaf(-along, along, dist2), 0.0f));
+			const float e = fmaf(off_axis, cos_t, -along * sin_t);
+			keep = e <= tile_radius * 1.001f + CULL_SLACK;
+		}
+	}
+	// inv_radius > 8: the 0.1 distance floor can reach this light's smoothstep (shade_positional)
+	second = is_spot || d.w > 8.0f;
+	// A survivor stages its record in the slot of its own lane, here, where its registers are: nothing of a light
+	// lives across the ballots of `turn` (round 4 compacted the list with mbcnt after them, which kept sixteen
+	// zero-filled registers per lane alive on every path).  The walks visit the set bits of the ballots.
+	if (keep)
+	{
+		f32x4 *dst_slot = slots + lane * (LIGHT_SLOT_BYTES / 16);
+		dst_slot[0] = f32x4{pq.x, pq.y, pq.z, radius * radius};
+		dst_slot[1] = f32x4{c.x, c.y, c.z, 10.0f * d.w};
+		if (second)
+		{
+			dst_slot[2] = is_spot ? f32x4{d.x, d.y, d.z, 0.0f} : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+			dst_slot[3] = is_spot ? f32x4{spot_scale, spot_bias, 0.0f, 0.0f} : f32x4{0.0f, 1.0f, 0.0f, 0.0f};
+		}
+	}
+}
+
+// ---- shade: PX pixels per lane, the staged lights named by `todo` broadcast from LDS in index order, the body without a light-type branch.
+// One step of a walk: the lowest set bit of `todo` is shaded and cleared (by s_bitset0_b64: one scalar instruction where `todo &= todo - 1` is
+// three on 64 bits).  The loop itself stays in `turn`: as part of this function its guard came out as s_cmp_lg / s_cbranch_scc0 where the
+// parent form has s_cmp_eq / s_cbranch_scc1. ----
+template <int PX, bool CONE>
+__device__ __forceinline__ void walk_next(uint64_t &todo, const Surface (&s)[PX], const f32x4 *const slots, float3_ (&result)[PX])
+{
+	const int bit = __builtin_ctzll(todo);
+	asm("s_bitset0_b64 %0, %1" : "+s"(todo) : "s"(bit));
+	shade_positional<PX, CONE>(s, slots + bit * (LIGHT_SLOT_BYTES / 16), result);
+}
+
+// One wave, one tile of 8 PX x 8 pixels whose attachment words are in `raw`: the stages above in order, around two uniform branches
+// (clustered or not; narrow or wide window).
+template <int PX, bool AO, bool B10>
+__device__ __forceinline__ void shade_tile(const KernelArgs &a, const int tile_x0, const int tile_y0, const int wave, const int lane, const RawTile<PX, B10> &raw,
+                                           f32x4 *const slots, const float *s_srgb LV_STAMP_PARAM)
+{
+	const int x0 = tile_x0 + (lane & (LIGHT_TILE - 1)) * PX;
+	const int y = tile_y0 + (lane >> 3);
+	const int W = a.hdr.w;
+	const bool row_inside = y >= a.row_first && y < a.row_end; // row_end <= H
+
+	bool inside[PX], active[PX];
+#pragma unroll
+	for (int p = 0; p < PX; p++)
+		inside[p] = row_inside && x0 + p < W;
+	f16x4 dst[PX];
+	float depth[PX];
+	uint32_t alb[PX], nrm[PX], mr[PX];
+	unpack_raw<PX, B10>(raw, depth, alb, nrm, mr, dst);
+	// The clip-space row of the lane's first pixel without its depth term (see make_surface).  It stays here, as do the four lines of the
+	// clip row in the loop below: moved into functions (one of which takes p, where the select is simplified before p is a constant) they
+	// gave the one-pixel kernels another schedule.
 	float clip_base[4];
 	{
 		const float ndc_x = fmaf(2.0f * (float(x0) + 0.5f), a.inv_resolution[0], -1.0f);
@@ -434,79 +688,25 @@ __device__ __forceinline__ void shade_tile(const KernelArgs &a, const int tile_x
 	}
 
 	Surface s[PX];
-	float3_ base[PX], accum[PX];
+	float3_ accum[PX];
 	bool any_active = false;
 #pragma unroll
 	for (int p = 0; p < PX; p++)
 	{
-		const int x = x0 + p;
-		const float depth = depth_v[p];
-		const uint32_t alb = alb_v[p], nrm = nrm_v[p], mr = mr_v[p];
 		// depth test NOT_EQUAL against the quad at z = 0 (renderer.cpp:1056-1057): reverse-Z far-plane pixels keep the
 		// emissive value (both draws are depth-rejected).
-		active[p] = inside[p] && depth != 0.0f;
+		active[p] = inside[p] && depth[p] != 0.0f;
 		any_active = any_active || active[p];
-
-		// ---- G-buffer decode (clustering.frag:31-35) ----
-		base[p] = f3(s_srgb[alb & 255u], s_srgb[(alb >> 8) & 255u], s_srgb[(alb >> 16) & 255u]);
-		const float3_ N = f3(float(nrm & 1023u) * (2.0f / 1023.0f) - 1.0f, float((nrm >> 10) & 1023u) * (2.0f / 1023.0f) - 1.0f,
-		                     float((nrm >> 20) & 1023u) * (2.0f / 1023.0f) - 1.0f);
-		const float metallic = float(mr & 255u) * (1.0f / 255.0f);
-		const float mat_roughness = float(mr >> 8) * (1.0f / 255.0f);
-
+		float3_ base, N;
+		float metallic, mat_roughness;
+		decode_gbuffer(alb[p], nrm[p], mr[p], s_srgb, base, N, metallic, mat_roughness);
 		float clip[4];
 #pragma unroll
 		for (int i = 0; i < 4; i++)
-			clip[i] = fmaf(depth, a.inv_vp[8 + i], p == 0 ? clip_base[i] : clip_base[i] + float(p) * a.clip_dx[i]);
-		const float clip_w = active[p] ? clip[3] : 1.0f;
-		float inv_w = rcp(clip_w);
-		inv_w = inv_w * fmaf(-clip_w, inv_w, 2.0f);
-		const float3_ pos = f3(clip[0] * inv_w, clip[1] * inv_w, clip[2] * inv_w);
-
-		s[p].pos = pos;
-		s[p].N = N;
-		const float3_ cam = f3(a.camera_pos[0], a.camera_pos[1], a.camera_pos[2]);
-		float3_ V = cam - pos;
-		V = V * rsq(fmaxf(dot(V, V), 1e-30f));
-		s[p].V = V;
-		s[p].NdV = dot(N, V);
-		const float NoV = med3(s[p].NdV, 0.001f, 1.0f);
-		s[p].F0 = f3(fmaf(base[p].x - 0.04f, metallic, 0.04f), fmaf(base[p].y - 0.04f, metallic, 0.04f),
-		             fmaf(base[p].z - 0.04f, metallic, 0.04f));
-		const float roughness = fmaf(mat_roughness, 0.75f, 0.25f);
-		const float m = roughness * roughness;
-		const float m2 = m * m;
-		s[p].m2m1 = m2 - 1.0f;
-		const float r1 = roughness + 1.0f;
-		const float k = r1 * r1 * (1.0f / 8.0f);
-		const float omk = 1.0f - k;
-		const float Gv_over_c0 = fmaf(NoV, omk, k) * rcp(m2 * (0.25f / PI_SIC)); // m2 >= 0.0039
-		s[p].gA = Gv_over_c0 * omk;
-		s[p].gB = Gv_over_c0 * k;
-		const float kd = (1.0f - metallic) * (1.0f / PI_SIC);
-		s[p].D1 = f3(fmaf(-s[p].F0.x, base[p].x, base[p].x) * kd, fmaf(-s[p].F0.y, base[p].y, base[p].y) * kd,
-		             fmaf(-s[p].F0.z, base[p].z, base[p].z) * kd);
-
+			clip[i] = fmaf(depth[p], a.inv_vp[8 + i], p == 0 ? clip_base[i] : clip_base[i] + float(p) * a.clip_dx[i]);
+		make_surface(a, clip, active[p], N, base, metallic, mat_roughness, s[p]);
 		accum[p] = f3(float(dst[p].x), float(dst[p].y), float(dst[p].z));
-
-		// ---- directional quad (directional.frag:41-65) ----
-		if (a.flags & GR_LIGHTING_DIRECTIONAL_BIT)
-		{
-			const float3_ L = f3(a.dir_direction[0], a.dir_direction[1], a.dir_direction[2]);
-			const float3_ Hv = V + L;
-			float3_ lit = f3(0.0f, 0.0f, 0.0f);
-			brdf_accumulate(s[p], dot(N, L), fmaxf(dot(Hv, Hv), 1e-30f), 1.0f, f3(a.dir_color[0], a.dir_color[1], a.dir_color[2]), lit);
-			// base_ambient * base_color * 0.05 (directional.frag:52-64); a scalar 0 when the fallback term is off
-			float ambient = (a.flags & GR_LIGHTING_AMBIENT_FALLBACK_BIT) ? 0.05f : 0.0f;
-			if (AO)
-				ambient *= sample_linear_r8(a.ao, (float(x) + 0.5f) * a.inv_resolution[0], (float(y) + 0.5f) * a.inv_resolution[1]);
-			lit = f3(fmaf(base[p].x, ambient, lit.x), fmaf(base[p].y, ambient, lit.y), fmaf(base[p].z, ambient, lit.z));
-			// blend ONE/ONE, attachment store rounds to fp16 (or to the packed floats)
-			if constexpr (B10)
-				accum[p] = f3(round_to_ufloat<6>(accum[p].x + lit.x), round_to_ufloat<6>(accum[p].y + lit.y), round_to_ufloat<5>(accum[p].z + lit.z));
-			else
-				accum[p] = f3(float(_Float16(accum[p].x + lit.x)), float(_Float16(accum[p].y + lit.y)), float(_Float16(accum[p].z + lit.z)));
-		}
+		directional_quad<AO, B10>(a, s[p], base, x0 + p, y, accum[p]);
 	}
 
 	LV_STAMP_MARK(0); // G-buffer decode, material terms and the directional quad are through
@@ -569,44 +769,10 @@ __device__ __forceinline__ void shade_tile(const KernelArgs &a, const int tile_x
 		}
 		if (win_lo <= win_hi)
 		{
-			// Cluster cells the tile touches (clusterer_bindless.h:39-42 at the tile's first and last pixel; the per-pixel formula is
-			// monotonic, so every lane's cell lies in this rectangle).  There is no scalar float unit: lane 0 evaluates the formula for
-			// the tile's first pixel, lane 63 for its last one (its second pixel, clamped into the image), and two v_readlane per axis
-			// fetch them -- instead of four wave-uniform evaluations on the vector unit.
-			auto cell = [](int p, float inv_res, float scale, int res) {
-				return clamp0_i32(int(__fmul_rn(__fmul_rn(float(p) + 0.5f, inv_res), scale)), res - 1);
-			};
-			const int my_cx = cell(min(x0 + (lane >> 5) * (PX - 1), W - 1), a.inv_resolution[0], a.cl_xy_scale[0], a.cl_res_x);
-			const int my_cy = cell(min(y, H - 1), a.inv_resolution[1], a.cl_xy_scale[1], a.cl_res_y);
-			const int cx0 = __builtin_amdgcn_readlane(my_cx, 0), cx1 = __builtin_amdgcn_readlane(my_cx, 63);
-			const int cy0 = __builtin_amdgcn_readlane(my_cy, 0), cy1 = __builtin_amdgcn_readlane(my_cy, 63);
-
-			// Bounding sphere of a set of the tile's surface points (member[p]: a non-empty set): centre = its first pixel, radius = its
-			// farthest pixel from that.
-			auto bounding_sphere = [&](const bool (&member)[PX], float3_ &centre_out, float &radius_out) __attribute__((always_inline)) {
-				bool any_member = false;
-#pragma unroll
-				for (int p = 0; p < PX; p++)
-					any_member = any_member || member[p];
-				const int first = __builtin_ctzll(__ballot(any_member));
-				const float3_ mine = PX == 2 && !member[0] ? s[PX - 1].pos : s[0].pos; // a lane of the ballot has one of them in the set
-				centre_out = f3(__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mine.x), first)),
-				                __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mine.y), first)),
-				                __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, mine.z), first)));
-				float off2 = 0.0f;
-#pragma unroll
-				for (int p = 0; p < PX; p++)
-				{
-					const float3_ off = s[p].pos - centre_out;
-					const float mine2 = member[p] ? dot(off, off) : 0.0f;
-					off2 = p == 0 ? mine2 : fmaxf(off2, mine2);
-				}
-				// v_sqrt_f32 (1 ulp) is well inside the 1.0001 + CULL_SLACK margin
-				radius_out = __builtin_amdgcn_sqrtf(__builtin_bit_cast(float, wave_minmax_u32<true>(__builtin_bit_cast(uint32_t, off2)))) * 1.0001f + CULL_SLACK;
-			};
+			const Cells cells = tile_cells<PX>(a, x0, y, lane);
 			float3_ centre;
 			float tile_radius;
-			bounding_sphere(active, centre, tile_radius); // the lit pixels of the tile
+			bounding_sphere<PX>(active, s, centre, tile_radius); // the lit pixels of the tile
 
 			LV_STAMP_MARK(1); // slice window, cells, bounding sphere
 			LV_STAMP_LAP_BEGIN();
@@ -618,86 +784,24 @@ __device__ __forceinline__ void shade_tile(const KernelArgs &a, const int tile_x
 			//     ONCE, lane j the j-th word of a span of `list_words` words, and their set bits are compacted in index order into a
 			//     wave-private list of light indices (counts by v_bcnt, their prefix sums by a DPP scan); a turn takes the next 64 of the
 			//     list -- one pair of memory round trips per 64 CANDIDATES instead of one per 64 indices.  The list lives in the
-			//     workgroup's dynamic LDS, which the launcher sizes anyway to cap the kernel's residency (gr_lighting).
+			//     workgroup's dynamic LDS, which the launcher sizes anyway to cap the kernel's residency (lds_policy).
 			const int chunk_lo = int(win_lo >> 6u), chunk_hi = int(win_hi >> 6u);
 			// One turn: up to 64 candidate lights, one per lane, culled against the tile and staged; then the walks over the survivors.
+			// (Still a lambda: as a function the one-pixel B10 kernels came out with other register moves, 14 v_mov fewer and another s_branch.)
 			auto turn = [&](const uint32_t light_index, const bool candidate, const float3_ &centre, const float tile_radius) __attribute__((always_inline)) {
-				// ---- cull: one light per lane ----
-				bool keep = false;
-				bool second = false; // walked with the cone body: spot lights, and point lights of radius < 1 / 8
-				{
-					if (candidate)
-					{
-						const f32x4 *rec = reinterpret_cast<const f32x4 *>(a.lights + light_index);
-						const f32x4 c = rec[0], pq = rec[1], d = rec[2]; // colour|scale_bias, position|offset_radius, direction|inv_radius
-						const float radius = CULL_RADIUS_SCALE * rcp(d.w);
-						const float3_ to_light = f3(pq.x, pq.y, pq.z) - centre;
-						const float reach = radius + tile_radius;
-						const float dist2 = dot(to_light, to_light);
-						keep = dist2 <= reach * reach;
-						const bool is_spot = ((a.type_mask[light_index >> 5] >> (light_index & 31u)) & 1u) == 0u;
-						// unpackHalf2x16(spot_scale_bias).  The lane is copied to a scalar first: clang (ROCm 7.2) evaluates
-						// __builtin_bit_cast on a vector-component lvalue (v.w) at the address of the whole vector, i.e. as
-						// lane .x (observed: spots shaded with colour.x as scale | bias).
-						const float sb_lane = c.w;
-						const uint32_t sb_bits = __builtin_bit_cast(uint32_t, sb_lane);
-						const float spot_scale = float(__builtin_bit_cast(_Float16, uint16_t(sb_bits & 0xffffu)));
-						const float spot_bias = float(__builtin_bit_cast(_Float16, uint16_t(sb_bits >> 16)));
-						if (is_spot && keep && spot_scale > 0.0f)
-						{
-							// Cone vs the tile's bounding sphere.  spot.h:44-45: the cone factor sat(cone_angle * scale + bias) is
-							// exactly 0 for cone_angle <= -bias / scale =: cos(theta).  With v = centre - light, a = dot(v, dir) and
-							// p = distance of the centre from the axis, e = p cos(theta) - a sin(theta) = |v| sin(phi - theta) is the
-							// distance of the centre from the cone's mantle line (never more than its distance from the cone), so
-							// e > tile_radius (+ margin) puts every pixel of the tile outside the cone by an angle far above fp32
-							// rounding: the light adds exactly 0 there.  (theta >= 90 degrees, cos(theta) <= 0, never culls.)
-							const float cos_t = -spot_bias * rcp(spot_scale);
-							if (cos_t > 0.0f && cos_t < 1.0f)
-							{
-								const float sin_t = __builtin_amdgcn_sqrtf(fmaf(-cos_t, cos_t, 1.0f));
-								const float along = -dot(to_light, f3(d.x, d.y, d.z)); // dot(centre - light, direction)
-								const float off_axis = __builtin_amdgcn_sqrtf(fmaxf(fmaf(-along, along, dist2), 0.0f));
-								const float e = fmaf(off_axis, cos_t, -along * sin_t);
-								keep = e <= tile_radius * 1.001f + CULL_SLACK;
-							}
-						}
-						// inv_radius > 8: the 0.1 distance floor can reach this light's smoothstep (shade_positional)
-						second = is_spot || d.w > 8.0f;
-						// A survivor stages its record in the slot of its own lane, here, where its registers are: nothing of a light
-						// lives across the ballots below (round 4 compacted the list with mbcnt after them, which kept sixteen
-						// zero-filled registers per lane alive on every path).  The walks visit the set bits of the ballots.
-						if (keep)
-						{
-							f32x4 *dst_slot = slots + lane * (LIGHT_SLOT_BYTES / 16);
-							dst_slot[0] = f32x4{pq.x, pq.y, pq.z, radius * radius};
-							dst_slot[1] = f32x4{c.x, c.y, c.z, 10.0f * d.w};
-							if (second)
-							{
-								dst_slot[2] = is_spot ? f32x4{d.x, d.y, d.z, 0.0f} : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-								dst_slot[3] = is_spot ? f32x4{spot_scale, spot_bias, 0.0f, 0.0f} : f32x4{0.0f, 1.0f, 0.0f, 0.0f};
-							}
-						}
-					}
-				}
+				bool keep = false, second = false;
+				if (candidate)
+					cull_and_stage(a, light_index, centre, tile_radius, lane, slots, keep, second);
 				const uint64_t kept = __ballot(keep);
 				const uint64_t seconds = __ballot(keep && second);
 				__builtin_amdgcn_wave_barrier(); // LDS is wave-private: in-order DS execution is the only ordering needed
 				LV_STAMP_LAP(2); // gather + cull
 
-				// ---- shade: PX pixels per lane, lights broadcast from LDS; each list in index order, its body without a light-type branch ----
-				// (the visited bit is cleared by s_bitset0_b64: one scalar instruction where `todo &= todo - 1` is three on 64 bits)
+				// ---- shade: each list in index order (walk_next) ----
 				for (uint64_t todo = kept & ~seconds; todo != 0ull;)
-				{
-					const int bit = __builtin_ctzll(todo);
-					asm("s_bitset0_b64 %0, %1" : "+s"(todo) : "s"(bit));
-					shade_positional<PX, false>(s, slots + bit * (LIGHT_SLOT_BYTES / 16), result);
-				}
+					walk_next<PX, false>(todo, s, slots, result);
 				for (uint64_t todo = seconds; todo != 0ull;)
-				{
-					const int bit = __builtin_ctzll(todo);
-					asm("s_bitset0_b64 %0, %1" : "+s"(todo) : "s"(bit));
-					shade_positional<PX, true>(s, slots + bit * (LIGHT_SLOT_BYTES / 16), result);
-				}
+					walk_next<PX, true>(todo, s, slots, result);
 				LV_STAMP_LAP(3); // the two walks
 				__builtin_amdgcn_wave_barrier(); // the slots are rewritten by the next turn
 			};
@@ -712,12 +816,7 @@ __device__ __forceinline__ void shade_tile(const KernelArgs &a, const int tile_x
 					if (index_in_range(light_index, win_lo, win_hi))
 					{
 						uint32_t word = 0u;
-						for (int cy = cy0; cy <= cy1; cy++)
-						{
-#pragma clang loop vectorize(disable) unroll(disable)
-							for (int cx = cx0; cx <= cx1; cx++)
-								word |= a.bitmask[(cy * a.cl_res_x + cx) * a.cl_num_lights_32 + my_word];
-						}
+						or_cell_words(a, cells, my_word, word);
 						candidate = ((word >> (uint32_t(lane) & 31u)) & 1u) != 0u;
 					}
 					turn(light_index, candidate, centre, tile_radius);
@@ -734,35 +833,14 @@ __device__ __forceinline__ void shade_tile(const KernelArgs &a, const int tile_x
 				float radius_low = tile_radius, radius_high = tile_radius;
 				if (two_groups)
 				{
-					bounding_sphere(in_low, centre_low, radius_low);
-					bounding_sphere(in_high, centre_high, radius_high);
+					bounding_sphere<PX>(in_low, s, centre_low, radius_low);
+					bounding_sphere<PX>(in_high, s, centre_high, radius_high);
 				}
 				uint16_t *const list = reinterpret_cast<uint16_t *>(lv_dynamic_lds) + wave * (a.list_words * 32);
 				const int word_last = int(win_hi >> 5u);
 				for (int span_word = int(win_lo >> 5u); span_word <= word_last; span_word += a.list_words)
 				{
-					// ---- gather: lane j reads word j of the span, the set bits of all words go to the list in index order ----
-					const int my_word = span_word + lane;
-					const uint32_t word_first = uint32_t(my_word) << 5u;
-					uint32_t word = 0u;
-					if (lane < a.list_words && my_word <= word_last)
-					{
-						for (int cy = cy0; cy <= cy1; cy++)
-						{
-#pragma clang loop vectorize(disable) unroll(disable)
-							for (int cx = cx0; cx <= cx1; cx++)
-								word |= a.bitmask[(cy * a.cl_res_x + cx) * a.cl_num_lights_32 + my_word];
-						}
-						// the window [win_lo, win_hi] without its gap, as bits of this word
-						word &= bits_from(win_lo, word_first) & ~bits_from(win_hi + 1u, word_first) & ~(bits_from(gap_lo + 1u, word_first) & ~bits_from(gap_hi, word_first));
-					}
-					const uint32_t count = uint32_t(__builtin_popcount(word));
-					const uint32_t upto = wave_inclusive_add_u32(count);
-					const int list_count = __builtin_amdgcn_readlane(int(upto), 63);
-					uint16_t *entry = list + (upto - count);
-					for (; word != 0u; word &= word - 1u)
-						*entry++ = uint16_t(word_first + uint32_t(__builtin_ctz(word)));
-					__builtin_amdgcn_wave_barrier();
+					const int list_count = gather_wide(a, cells, win_lo, win_hi, gap_lo, gap_hi, span_word, word_last, lane, list);
 					for (int next = 0; next < list_count; next += 64)
 					{
 						const bool candidate = next + lane < list_count;
@@ -933,6 +1011,104 @@ __global__ __launch_bounds__(64 * LIGHT_WAVES) LV_OCCUPANCY_ATTR void k_lighting
 	shade_tile<PX, AO, B10>(a, tile_x0, tile_y0, wave, lane, raw, s_lights[threadIdx.x >> 6], s_srgb LV_STAMP_ARG);
 }
 
+// What the kernel reads of the arguments gr_lighting has checked; the render area and list_words are the launcher's to add.
+KernelArgs fill_kernel_args(const gr_lighting_args *args, const gr_ctx *ctx, const bool clustered)
+{
+	KernelArgs k{};
+	k.albedo = to_dev(&args->albedo);
+	k.normal = to_dev(&args->normal);
+	k.pbr = to_dev(&args->pbr);
+	k.depth = to_dev(&args->depth);
+	k.emissive = to_dev(&args->emissive);
+	if (args->flags & GR_LIGHTING_AMBIENT_OCCLUSION_BIT)
+		k.ao = to_dev(&args->ambient_occlusion);
+	k.hdr = to_dev_rw(&args->hdr);
+	for (int i = 0; i < 16; i++)
+		k.inv_vp[i] = args->inv_view_projection[i];
+	for (int i = 0; i < 4; i++)
+		k.clip_dx[i] = k.inv_vp[i] * (2.0f * args->clustering.inv_resolution[0]);
+	for (int i = 0; i < 3; i++)
+	{
+		k.camera_pos[i] = args->clustering.camera_pos[i];
+		k.dir_color[i] = args->directional.color[i];
+		k.dir_direction[i] = args->directional.direction[i];
+	}
+	k.inv_resolution[0] = args->clustering.inv_resolution[0];
+	k.inv_resolution[1] = args->clustering.inv_resolution[1];
+	k.cl_xy_scale[0] = args->cluster.xy_scale[0];
+	k.cl_xy_scale[1] = args->cluster.xy_scale[1];
+	k.cl_res_x = args->cluster.resolution_xy[0];
+	k.cl_res_y = args->cluster.resolution_xy[1];
+	k.cl_num_lights = clustered ? args->cluster.num_lights : 0;
+	k.cl_num_lights_32 = args->cluster.num_lights_32;
+	k.cl_z_max_index = args->cluster.z_max_index;
+	{
+		// slice = int(dot(pos, front * zs) - dot(base, front) * zs) where the shader has dot(pos - base, front) * zs: the row is formed in
+		// double here (its entries are correctly rounded), what differs in the kernel is that the two large terms meet in the last fma instead
+		// of the subtraction coming first -- an absolute error of the slice coordinate of about |camera_base| * z_scale * 2^-23 (2e-4 of a slice
+		// at the tests' camera, 8 units from the origin with 4096 slices over 100 units; a third of a slice at 1e4 units, where fp32 world
+		// positions themselves are only good to 1e-3 units).  A pixel that changes slice by it sees lights at the edge of their range appear
+		// or vanish, with falloff -> 0 there (see make_surface).
+		const float *front = args->cluster.camera_front, *camera = args->cluster.camera_base;
+		const double z_scale = args->cluster.z_scale;
+		for (int i = 0; i < 3; i++)
+			k.cl_z_row[i] = float(double(front[i]) * z_scale);
+		k.cl_z_row[3] = float(-(double(camera[0]) * front[0] + double(camera[1]) * front[1] + double(camera[2]) * front[2]) * z_scale);
+	}
+	if (clustered)
+	{
+		const uint8_t *t = static_cast<const uint8_t *>(args->transforms);
+		k.lights = reinterpret_cast<const gr_light_info *>(t + GR_TRANSFORMS_OFFSET_LIGHTS);
+		k.type_mask = reinterpret_cast<const uint32_t *>(t + GR_TRANSFORMS_OFFSET_TYPE_MASK);
+		k.bitmask = args->bitmask;
+		k.range = reinterpret_cast<const uint2 *>(args->range);
+	}
+	k.srgb_lut = ctx->srgb_decode_lut;
+	k.flags = args->flags & (GR_LIGHTING_DIRECTIONAL_BIT | GR_LIGHTING_CLUSTERED_BIT | GR_LIGHTING_AMBIENT_FALLBACK_BIT | GR_LIGHTING_AMBIENT_OCCLUSION_BIT); // the shading bits; scheduling hints stay on the host
+	for (int i = 0; i < 3; i++)
+		k.fog_color[i] = args->fog_color[i];
+	k.fog_falloff = args->fog_falloff > 0.0f ? args->fog_falloff : 0.0f;
+	return k;
+}
+
+// The workgroup's dynamic LDS for `px` pixels a lane: the pad that caps residency, and the span of the wide-window lists that live in it.
+struct LdsPolicy
+{
+	size_t pad_lds;
+	int list_words;
+};
+LdsPolicy lds_policy(const int px, const uint32_t flags)
+{
+	// Residency cap.  The kernel is bound by the vector pipe; at full occupancy it owns every wave slot of the chip for the whole launch
+	// and the executor's other streams (the previous frame's bloom / tonemap, the next frame's cluster build) cannot get a single wave
+	// in.  Padding the workgroup's LDS footprint so that only `max_wgs` workgroups fit per CU leaves the remaining slots to them.  With
+	// two pixels per lane (94 VGPRs) five workgroups per CU = five waves per SIMD: round 5, after the kernel's per-wave instruction
+	// diet, 171.7 / 168.7 us alone against 175.7 / 170.8 with four, the frame 0.2005-0.2010 against 0.2069-0.2076 ms (four was
+	// the round-2 choice, when a fifth wave measured nothing: profiles/r05_lighting_instruction_diet.txt).
+	static const int max_wgs_env = []() {
+		const char *env = gr_measurement_switch("GR_LIGHTING_WGS_PER_CU");
+		const int v = env ? atoi(env) : 0;
+		return v >= 1 && v <= 8 ? v : 0;
+	}();
+	const int max_wgs = max_wgs_env ? max_wgs_env : (px == 2 ? ((flags & GR_LIGHTING_SHARE_REGISTERS_BIT) ? 4 : 5) : 7);
+	const size_t static_lds = sizeof(f32x4) * LIGHT_WAVES * 64 * (LIGHT_SLOT_BYTES / 16) + 256 * sizeof(float);
+	// 8 KiB of the CU's 160 KiB stay free: back-of-frame kernels that use a little LDS (luminance, the fused pyramid tail)
+	// must be able to start beside resident lighting workgroups instead of waiting for one to retire.
+	const size_t per_wg = ((160u - 8u) * 1024u / unsigned(max_wgs * 4 / LIGHT_WAVES)) & ~size_t(1023); // max_wgs counts four-wave workgroups
+	LdsPolicy lds{max_wgs >= 8 || per_wg <= static_lds ? 0 : per_wg - static_lds, 0};
+	// measurement switch: the pad in KiB whatever the cap asks for (with 96 registers the two-pixel kernel cannot exceed five waves per SIMD anyway)
+	static const int pad_kib = []() { const char *env = gr_measurement_switch("GR_LIGHTING_PAD_KIB"); return env ? atoi(env) : -1; }();
+	if (pad_kib >= 0)
+		lds.pad_lds = size_t(pad_kib) * 1024u;
+	// The pad is not idle: it holds the wide-window candidate lists (gather_wide), 32 two-byte entries per word of a span and wave.
+	// 13 KiB at five workgroups per CU: spans of 52 words = 1664 light indices.  No pad (GR_LIGHTING_WGS_PER_CU=8): the chunk loop only.
+	const size_t words = lds.pad_lds / (size_t(LIGHT_WAVES) * 32u * sizeof(uint16_t));
+	static const bool narrow_only = []() { const char *env = gr_measurement_switch("GR_LIGHTING_NARROW_ONLY"); return env && atoi(env) != 0; }();
+	if (words >= 8 && !narrow_only)
+		lds.list_words = int(words < 64 ? words : 64);
+	return lds;
+}
+
 } // namespace
 
 extern "C" {
@@ -960,69 +1136,20 @@ int gr_lighting(gr_ctx *ctx, gr_stream stream, const gr_lighting_args *args)
 		GR_CHECK_ARG(ctx, args->cluster.resolution_xy[0] > 0 && args->cluster.resolution_xy[1] > 0);
 	}
 
-	KernelArgs k{};
-	k.albedo = to_dev(&args->albedo);
-	k.normal = to_dev(&args->normal);
-	k.pbr = to_dev(&args->pbr);
-	k.depth = to_dev(&args->depth);
-	k.emissive = to_dev(&args->emissive);
-	if (args->flags & GR_LIGHTING_AMBIENT_OCCLUSION_BIT)
+	const bool ao = (args->flags & GR_LIGHTING_AMBIENT_OCCLUSION_BIT) != 0;
+	if (ao)
 	{
 		GR_CHECK_ARG(ctx, (args->flags & GR_LIGHTING_AMBIENT_FALLBACK_BIT) != 0);
 		GR_CHECK_IMAGE(ctx, &args->ambient_occlusion, GR_FORMAT_R8_UNORM);
-		k.ao = to_dev(&args->ambient_occlusion);
 	}
-	k.hdr = to_dev_rw(&args->hdr);
-	for (int i = 0; i < 16; i++)
-		k.inv_vp[i] = args->inv_view_projection[i];
-	for (int i = 0; i < 4; i++)
-		k.clip_dx[i] = k.inv_vp[i] * (2.0f * args->clustering.inv_resolution[0]);
-	for (int i = 0; i < 3; i++)
-	{
-		k.camera_pos[i] = args->clustering.camera_pos[i];
-		k.dir_color[i] = args->directional.color[i];
-		k.dir_direction[i] = args->directional.direction[i];
-	}
-	k.inv_resolution[0] = args->clustering.inv_resolution[0];
-	k.inv_resolution[1] = args->clustering.inv_resolution[1];
-	k.cl_xy_scale[0] = args->cluster.xy_scale[0];
-	k.cl_xy_scale[1] = args->cluster.xy_scale[1];
-	k.cl_res_x = args->cluster.resolution_xy[0];
-	k.cl_res_y = args->cluster.resolution_xy[1];
-	k.cl_num_lights = clustered ? args->cluster.num_lights : 0;
-	k.cl_num_lights_32 = args->cluster.num_lights_32;
-	k.cl_z_max_index = args->cluster.z_max_index;
-	{
-		// slice = int(dot(pos, front * zs) - dot(base, front) * zs) where the shader has dot(pos - base, front) * zs: the row is formed in
-		// double here (its entries are correctly rounded), what differs in the kernel is that the two large terms meet in the last fma instead
-		// of the subtraction coming first -- an absolute error of the slice coordinate of about |camera_base| * z_scale * 2^-23 (2e-4 of a slice
-		// at the tests' camera, 8 units from the origin with 4096 slices over 100 units; a third of a slice at 1e4 units, where fp32 world
-		// positions themselves are only good to 1e-3 units).  A pixel that changes slice by it sees lights at the edge of their range appear
-		// or vanish, with falloff -> 0 there (see shade_tile).
-		const float *front = args->cluster.camera_front, *camera = args->cluster.camera_base;
-		const double z_scale = args->cluster.z_scale;
-		for (int i = 0; i < 3; i++)
-			k.cl_z_row[i] = float(double(front[i]) * z_scale);
-		k.cl_z_row[3] = float(-(double(camera[0]) * front[0] + double(camera[1]) * front[1] + double(camera[2]) * front[2]) * z_scale);
-	}
-	if (clustered)
-	{
-		const uint8_t *t = static_cast<const uint8_t *>(args->transforms);
-		k.lights = reinterpret_cast<const gr_light_info *>(t + GR_TRANSFORMS_OFFSET_LIGHTS);
-		k.type_mask = reinterpret_cast<const uint32_t *>(t + GR_TRANSFORMS_OFFSET_TYPE_MASK);
-		k.bitmask = args->bitmask;
-		k.range = reinterpret_cast<const uint2 *>(args->range);
-	}
-	k.srgb_lut = ctx->srgb_decode_lut;
-	k.flags = args->flags & (GR_LIGHTING_DIRECTIONAL_BIT | GR_LIGHTING_CLUSTERED_BIT | GR_LIGHTING_AMBIENT_FALLBACK_BIT | GR_LIGHTING_AMBIENT_OCCLUSION_BIT); // the shading bits; scheduling hints stay on the host
-	for (int i = 0; i < 3; i++)
-		k.fog_color[i] = args->fog_color[i];
-	k.fog_falloff = args->fog_falloff > 0.0f ? args->fog_falloff : 0.0f;
-
 	// Render area: tiles stay aligned to multiples of 8 rows of the full target, rows outside the band are masked.
 	const RowSpan span = resolve_rows(args->rows.count ? &args->rows : nullptr, H); // {0, 0} = the whole image (granite_hip.h: gr_rows)
 	if (span.count() == 0)
 		return GR_OK;
+	// 32-bit byte offsets inside the kernel.
+	GR_CHECK_ARG(ctx, uint64_t(args->hdr.pitch_bytes) * H <= 0xffffffffull && uint64_t(args->emissive.pitch_bytes) * H <= 0xffffffffull);
+
+	KernelArgs k = fill_kernel_args(args, ctx, clustered);
 	k.row_first = int(span.first);
 	k.row_end = int(span.end);
 	k.block_row0 = int(span.first / LIGHT_TILE);
@@ -1036,66 +1163,16 @@ int gr_lighting(gr_ctx *ctx, gr_stream stream, const gr_lighting_args *args)
 	const bool pairs_aligned = (W & 1u) == 0 && is_aligned(&args->depth, 8u) && is_aligned(&args->albedo, 8u) && is_aligned(&args->normal, 8u) &&
 	                           is_aligned(&args->pbr, 4u) && is_aligned(&args->emissive, 2u * hdr_bpp) && is_aligned(&args->hdr, 2u * hdr_bpp);
 	const int px = pairs_aligned ? px_pref : 1;
-	// 32-bit byte offsets inside the kernel.
-	GR_CHECK_ARG(ctx, uint64_t(args->hdr.pitch_bytes) * H <= 0xffffffffull && uint64_t(args->emissive.pitch_bytes) * H <= 0xffffffffull);
+	const LdsPolicy lds = lds_policy(px, args->flags);
+	k.list_words = lds.list_words;
+
+	// The eight instantiations, [b10][px == 2][ao]; one launch.
+	using Kernel = void (*)(KernelArgs);
+	static const Kernel kernels[2][2][2] = {{{k_lighting<1, false, false>, k_lighting<1, true, false>}, {k_lighting<2, false, false>, k_lighting<2, true, false>}},
+	                                        {{k_lighting<1, false, true>, k_lighting<1, true, true>}, {k_lighting<2, false, true>, k_lighting<2, true, true>}}};
 	const dim3 grid(gr_div_up(W, unsigned(LIGHT_TILE * px * LIGHT_WAVES)), gr_div_up(span.end, unsigned(LIGHT_TILE)) - unsigned(k.block_row0));
-	// Residency cap.  The kernel is bound by the vector pipe; at full occupancy it owns every wave slot of the chip for the whole launch
-	// and the executor's other streams (the previous frame's bloom / tonemap, the next frame's cluster build) cannot get a single wave
-	// in.  Padding the workgroup's LDS footprint so that only `max_wgs` workgroups fit per CU leaves the remaining slots to them.  With
-	// two pixels per lane (94 VGPRs) five workgroups per CU = five waves per SIMD: round 5, after the kernel's per-wave instruction
-	// diet, 171.7 / 168.7 us alone against 175.7 / 170.8 with four, the frame 0.2005-0.2010 against 0.2069-0.2076 ms (four was
-	// the round-2 choice, when a fifth wave measured nothing: profiles/r05_lighting_instruction_diet.txt).
-	static const int max_wgs_env = []() {
-		const char *env = gr_measurement_switch("GR_LIGHTING_WGS_PER_CU");
-		const int v = env ? atoi(env) : 0;
-		return v >= 1 && v <= 8 ? v : 0;
-	}();
-	const int max_wgs = max_wgs_env ? max_wgs_env : (px == 2 ? ((args->flags & GR_LIGHTING_SHARE_REGISTERS_BIT) ? 4 : 5) : 7);
-	const size_t static_lds = sizeof(f32x4) * LIGHT_WAVES * 64 * (LIGHT_SLOT_BYTES / 16) + 256 * sizeof(float);
-	// 8 KiB of the CU's 160 KiB stay free: back-of-frame kernels that use a little LDS (luminance, the fused pyramid tail)
-	// must be able to start beside resident lighting workgroups instead of waiting for one to retire.
-	const size_t per_wg = ((160u - 8u) * 1024u / unsigned(max_wgs * 4 / LIGHT_WAVES)) & ~size_t(1023); // max_wgs counts four-wave workgroups
-	size_t pad_lds = max_wgs >= 8 || per_wg <= static_lds ? 0 : per_wg - static_lds;
-	{
-		// measurement switch: the pad in KiB whatever the cap asks for (with 96 registers the two-pixel kernel cannot exceed five waves per SIMD anyway)
-		static const int pad_kib = []() { const char *env = gr_measurement_switch("GR_LIGHTING_PAD_KIB"); return env ? atoi(env) : -1; }();
-		if (pad_kib >= 0)
-			pad_lds = size_t(pad_kib) * 1024u;
-	}
-	// The pad is not idle: it holds the wide-window candidate lists (shade_tile), 32 two-byte entries per word of a span and wave.
-	// 13 KiB at five workgroups per CU: spans of 52 words = 1664 light indices.  No pad (GR_LIGHTING_WGS_PER_CU=8): the chunk loop only.
-	{
-		const size_t words = pad_lds / (size_t(LIGHT_WAVES) * 32u * sizeof(uint16_t));
-		k.list_words = words >= 8 ? int(words < 64 ? words : 64) : 0;
-		static const bool narrow_only = []() { const char *env = gr_measurement_switch("GR_LIGHTING_NARROW_ONLY"); return env && atoi(env) != 0; }();
-		if (narrow_only)
-			k.list_words = 0;
-	}
 	gr_scoped_timing timing{ctx, gr_to_stream(stream), "lighting"};
-	const bool ao = (args->flags & GR_LIGHTING_AMBIENT_OCCLUSION_BIT) != 0;
-	const dim3 block(64 * LIGHT_WAVES);
-	const hipStream_t s = gr_to_stream(stream);
-#define GR_LAUNCH_LIGHTING(PX_, AO_, B10_) hipLaunchKernelGGL((k_lighting<PX_, AO_, B10_>), grid, block, pad_lds, s, k)
-	if (b10)
-	{
-		if (px == 2 && ao)
-			GR_LAUNCH_LIGHTING(2, true, true);
-		else if (px == 2)
-			GR_LAUNCH_LIGHTING(2, false, true);
-		else if (ao)
-			GR_LAUNCH_LIGHTING(1, true, true);
-		else
-			GR_LAUNCH_LIGHTING(1, false, true);
-	}
-	else if (px == 2 && ao)
-		GR_LAUNCH_LIGHTING(2, true, false);
-	else if (px == 2)
-		GR_LAUNCH_LIGHTING(2, false, false);
-	else if (ao)
-		GR_LAUNCH_LIGHTING(1, true, false);
-	else
-		GR_LAUNCH_LIGHTING(1, false, false);
-#undef GR_LAUNCH_LIGHTING
+	hipLaunchKernelGGL(kernels[b10][px == 2][ao], grid, dim3(64 * LIGHT_WAVES), lds.pad_lds, gr_to_stream(stream), k);
 	GR_CHECK_LAUNCH(ctx);
 	return GR_OK;
 }

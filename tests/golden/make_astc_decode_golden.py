@@ -16,47 +16,39 @@ block of an error class does.
 """
 import ctypes as C
 import os
-import shutil
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = os.environ.get("REF", "/root/reference")
-SHADER = os.path.join(REF, "assets", "shaders", "decode", "astc.comp")
-TABLES = os.path.join(REF, "vulkan", "texture", "texture_decoder.cpp")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle", "ref_build")]
 import astc_cases  # noqa: E402
 import astc_ref  # noqa: E402
+import shader_runner as sr  # noqa: E402
+
+SHADER = os.path.join(sr.SHADERS, "decode", "astc.comp")
+TABLES = os.path.join(sr.REF, "vulkan", "texture", "texture_decoder.cpp")
 
 
 def build(tmp):
     gen = os.path.join(tmp, "gen")
-    os.makedirs(gen)
-    rb = os.path.join(ROOT, "oracle", "ref_build")
-    subprocess.check_call([sys.executable, os.path.join(rb, "gen_swizzles.py"), gen])
-    subprocess.check_call([sys.executable, os.path.join(rb, "glsl2cpp.py"), SHADER, os.path.join(gen, "astc.inc")])
+    sr.respell(gen, [SHADER])
     lines = open(TABLES).read().split("\n")
     first = next(i for i, l in enumerate(lines) if l.startswith("struct ASTCQuantizationMode"))
     start = next(i for i, l in enumerate(lines) if l.startswith("void ASTCLutHolder::init_trits_quints"))
     last = next(i for i in range(start, len(lines)) if lines[i] == "}")
     open(os.path.join(gen, "astc_tables.inc"), "w").write("\n".join(lines[first:last + 1]) + "\n")
-    lib = os.path.join(tmp, "libastc_decode_runner.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++20", "-fPIC", "-ffp-contract=off", "-w", "-I" + rb, "-I" + tmp, "-DSPEC_DECODE_8BIT=true", "-shared",
-                           "-o", lib, os.path.join(HERE, "astc_decode_runner.cpp")])
-    return lib
+    objs = sr.compile_runner(tmp, os.path.join(HERE, "astc_decode_runner.cpp"), [("runner", ["-DSPEC_DECODE_8BIT=true"])])
+    return sr.link(os.path.join(tmp, "libastc_decode_runner.so"), objs)
 
 
 def generate(path):
     for needed in (SHADER, TABLES):
         if not os.path.isfile(needed):
             raise FileNotFoundError(needed)
-    tmp = tempfile.mkdtemp(prefix="astc_golden_")
     record = {}
-    try:
+    with sr.scratch("astc_golden_") as tmp:
         lib = C.CDLL(build(tmp))
         sizes = (C.c_int(), C.c_int())
         lib.ref_astc_table_sizes(C.byref(sizes[0]), C.byref(sizes[1]))
@@ -80,8 +72,6 @@ def generate(path):
             record[f"{name}/format"] = np.array([fmt, w, h], np.int32)
             record[f"{name}/blocks"] = blocks
             record[f"{name}/out"] = out
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
     np.savez_compressed(path, **record)
     print(f"{path}: {os.path.getsize(path)} bytes, {sum(k.endswith('/out') for k in record)} cases")
 

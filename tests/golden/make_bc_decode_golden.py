@@ -15,20 +15,18 @@ Prints, per case, the share of samples tests/bc_ref.py flags as ties and how man
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = os.environ.get("REF", "/root/reference")
-SHADERS = os.path.join(REF, "assets", "shaders", "decode")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle", "ref_build")]
 import bc_cases  # noqa: E402
 import bc_ref  # noqa: E402
+import shader_runner as sr  # noqa: E402
+
+SHADERS = os.path.join(sr.SHADERS, "decode")
 
 # (shader, spec0, spec1, defines): dispatch_kernel_s3tc / _rgtc / _bc7 / _bc6 (texture_decoder.cpp)
 VARIANTS = [(0, 0, 1, ["-DSPEC_USE_ALPHA=false", "-DSPEC_BC_VERSION=1"]), (0, 1, 1, ["-DSPEC_USE_ALPHA=true", "-DSPEC_BC_VERSION=1"]),
@@ -40,34 +38,19 @@ DISPATCH = {131: (0, 0, 1), 133: (0, 1, 1), 135: (0, 1, 2), 137: (0, 1, 3), 139:
 
 
 def build(tmp):
-    gen = os.path.join(tmp, "gen")
-    os.makedirs(gen)
-    rb = os.path.join(ROOT, "oracle", "ref_build")
-    subprocess.check_call([sys.executable, os.path.join(rb, "gen_swizzles.py"), gen])
-    for name in ("s3tc", "rgtc", "bc7", "bc6"):
-        inc = os.path.join(gen, name + ".inc")
-        subprocess.check_call([sys.executable, os.path.join(rb, "glsl2cpp.py"), os.path.join(SHADERS, name + ".comp"), inc])
-        text = open(inc).read()
-        open(inc, "w").write(re.sub(r"= ivec2\[\]\((.*?)\);", lambda m: "= {" + m.group(1) + "};", text, flags=re.S))
-    flags = ["-O2", "-std=c++20", "-fPIC", "-ffp-contract=off", "-w", "-I" + rb, "-I" + tmp]
-    runner = os.path.join(HERE, "bc_decode_runner.cpp")
-    objs = []
-    for shader, spec0, spec1, defines in VARIANTS:
-        objs.append(os.path.join(tmp, f"runner_{shader}_{spec0}_{spec1}.o"))
-        subprocess.check_call(["g++", *flags, f"-DBC_SHADER={shader}", f"-DBC_SPEC0={spec0}", f"-DBC_SPEC1={spec1}", *defines, "-c", runner, "-o", objs[-1]])
-    objs.append(os.path.join(tmp, "runner_entry.o"))
-    subprocess.check_call(["g++", *flags, "-DBC_ENTRY", "-c", runner, "-o", objs[-1]])
-    lib = os.path.join(tmp, "libbc_decode_runner.so")
-    subprocess.check_call(["g++", "-shared", "-o", lib, *objs])
-    return lib
+    sr.respell(os.path.join(tmp, "gen"), [f"decode/{name}.comp" for name in ("s3tc", "rgtc", "bc7", "bc6")],
+               patch=lambda text: re.sub(r"= ivec2\[\]\((.*?)\);", lambda m: "= {" + m.group(1) + "};", text, flags=re.S))
+    variants = [(f"runner_{shader}_{spec0}_{spec1}", [f"-DBC_SHADER={shader}", f"-DBC_SPEC0={spec0}", f"-DBC_SPEC1={spec1}", *defines])
+                for shader, spec0, spec1, defines in VARIANTS]
+    objs = sr.compile_runner(tmp, os.path.join(HERE, "bc_decode_runner.cpp"), [*variants, ("runner_entry", ["-DBC_ENTRY"])])
+    return sr.link(os.path.join(tmp, "libbc_decode_runner.so"), objs)
 
 
 def generate(path):
     if not os.path.isdir(SHADERS):
         raise FileNotFoundError(SHADERS)
-    tmp = tempfile.mkdtemp(prefix="bc_golden_")
     record = {}
-    try:
+    with sr.scratch("bc_golden_") as tmp:
         lib = C.CDLL(build(tmp))
         lib.ref_bc_decode.restype = C.c_int
         for name, (fmt, w, h, blocks) in sorted(bc_cases.cases().items()):
@@ -82,8 +65,6 @@ def generate(path):
             record[f"{name}/format"] = np.array([fmt, w, h], np.int32)
             record[f"{name}/blocks"] = blocks
             record[f"{name}/out"] = out
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
     np.savez_compressed(path, **record)
     print(f"{path}: {os.path.getsize(path)} bytes, {len(record) // 3} cases")
 

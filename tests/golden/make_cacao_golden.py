@@ -12,30 +12,26 @@ While recording it also runs tests/cacao_ref.py's float32 chain on every case an
 """
 import ctypes as C
 import os
-import shutil
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = os.environ.get("REF", "/root/reference")
-CACAO = os.path.join(REF, "renderer", "post", "ffx-cacao")
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path[:0] = [os.path.join(ROOT, "tests"), ROOT, os.path.join(ROOT, "oracle", "ref_build")]
 import cacao_cases as cc  # noqa: E402
 import cacao_ref as cr  # noqa: E402
+import shader_runner as sr  # noqa: E402
+
+CACAO = os.path.join(sr.REF, "renderer", "post", "ffx-cacao")
 
 FLAG_SHARE_LIMIT = 0.005
 
 
 def build(tmp):
-    lib = os.path.join(tmp, "libcacao_runner.so")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-w", "-I" + os.path.join(CACAO, "inc"), "-o", lib,
-                           os.path.join(CACAO, "src", "ffx_cacao.cpp"), os.path.join(HERE, "cacao_constants_runner.cpp")])
-    return lib
+    objs = sr.compile_objects(tmp, ["-O1", "-std=c++17", "-fPIC", "-ffp-contract=off", "-w", "-I" + os.path.join(CACAO, "inc")],
+                              [("ffx_cacao", os.path.join(CACAO, "src", "ffx_cacao.cpp"), []), ("runner", os.path.join(HERE, "cacao_constants_runner.cpp"), [])])
+    return sr.link(os.path.join(tmp, "libcacao_runner.so"), objs)
 
 
 def ptr(a):
@@ -45,9 +41,8 @@ def ptr(a):
 def generate(path):
     if not os.path.isdir(CACAO):
         raise FileNotFoundError(CACAO)
-    tmp = tempfile.mkdtemp(prefix="cacao_golden_")
     record = {}
-    try:
+    with sr.scratch("cacao_golden_") as tmp:
         lib = C.CDLL(build(tmp))
         assert [lib.cacao_runner_sizes(i) for i in range(3)] == [68, 384, 64]
         for w, h in cc.SIZES:
@@ -62,8 +57,6 @@ def generate(path):
                         record[k + "/settings"], record[k + "/constants"] = words, constants
                         record[k + "/proj"], record[k + "/view"] = proj, view
                         record[f"{w}x{h}/sizes"] = sizes
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
     np.savez_compressed(path, **record)
     print(f"{path}: {os.path.getsize(path)} bytes, {len(record)} arrays")
 

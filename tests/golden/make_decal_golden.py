@@ -39,52 +39,40 @@ branch the cases are there for is taken at least once."""
 import ctypes as C
 import io
 import os
-import shutil
-import subprocess
 import sys
-import tempfile
 import zipfile
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = os.environ.get("REF", "/root/reference")
-LIGHTS = os.path.join(REF, "assets", "shaders", "lights")
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path[:0] = [os.path.join(ROOT, "tests"), ROOT, os.path.join(ROOT, "oracle", "ref_build")]
 import decal_cases as dc  # noqa: E402
 import decal_ref as ref  # noqa: E402
+import shader_runner as sr  # noqa: E402
+
+LIGHTS = os.path.join(sr.SHADERS, "lights")
 
 
-def build(tmp):
-    gen = os.path.join(tmp, "gen")
-    os.makedirs(gen)
-    rb = os.path.join(ROOT, "oracle", "ref_build")
-    subprocess.check_call([sys.executable, os.path.join(rb, "gen_swizzles.py"), gen])
-    subprocess.check_call([sys.executable, os.path.join(rb, "glsl2cpp.py"), os.path.join(LIGHTS, "clusterer_bindless_binning_decal.comp"),
-                           os.path.join(gen, "clusterer_bindless_binning_decal.inc")])
-    inc = os.path.join(gen, "volumetric_decal.inc")
-    subprocess.check_call([sys.executable, os.path.join(rb, "glsl2cpp.py"), os.path.join(LIGHTS, "volumetric_decal.h"), inc])
-    text = open(inc).read()
+def patch_decal_header(text):
     assert "BINDING_GLOBAL_GEOMETRY_SAMPLER)" not in text
     for old, new, count in ((".world_to_texture[", ".world_to_texture.rows[", 3), ("texture2D TexDecals[];", "texture2D *TexDecals;", 1)):
         assert text.count(old) == count, old
         text = text.replace(old, new)
-    open(inc, "w").write(text)
-    lib = os.path.join(tmp, "libdecal_runner.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++20", "-fPIC", "-pthread", "-ffp-contract=off", "-fno-strict-aliasing", "-w", "-I" + rb, "-I" + tmp, "-shared",
-                           "-o", lib, os.path.join(HERE, "decal_runner.cpp")])
-    return lib
+    return text
+
+
+def build(tmp):
+    sr.respell(os.path.join(tmp, "gen"), ["lights/clusterer_bindless_binning_decal.comp", "lights/volumetric_decal.h"],
+               patch={"lights/volumetric_decal.h": patch_decal_header})
+    objs = sr.compile_runner(tmp, os.path.join(HERE, "decal_runner.cpp"), [("decal_runner", [])], extra=["-pthread", "-fno-strict-aliasing"])
+    return sr.link(os.path.join(tmp, "libdecal_runner.so"), objs, extra=["-pthread"])
 
 
 def build_host(tmp):
-    lib = os.path.join(tmp, "libdecal_host_runner.so")
-    math = os.path.join(REF, "math")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-msse4.1", "-w", "-I" + math, "-I" + os.path.join(math, "muglm"),
-                           "-I" + os.path.join(REF, "util"), "-shared", "-o", lib, os.path.join(HERE, "decal_host_runner.cpp"),
-                           os.path.join(math, "muglm", "muglm.cpp"), os.path.join(math, "aabb.cpp")])
-    return lib
+    objs = sr.reference_math_objects(tmp, [("decal_host_runner", os.path.join(HERE, "decal_host_runner.cpp"), []), ("muglm", sr.MUGLM, []),
+                                           ("aabb", os.path.join(sr.MATH, "aabb.cpp"), [])], extra=["-I" + os.path.join(sr.MATH, "muglm")])
+    return sr.link(os.path.join(tmp, "libdecal_host_runner.so"), objs)
 
 
 def run_host(host, case, cam):
@@ -176,9 +164,8 @@ def generate(path):
         if not os.path.isfile(os.path.join(LIGHTS, shader)):
             raise FileNotFoundError(os.path.join(LIGHTS, shader))
     shaders = C.CDLL(os.path.join(ROOT, "oracle", "_ref", "libref_shaders.so"))
-    tmp = tempfile.mkdtemp(prefix="decal_golden_")
     record = {}
-    try:
+    with sr.scratch("decal_golden_") as tmp:
         lib = C.CDLL(build(tmp))
         host = C.CDLL(build_host(tmp))
         seen = {"full_screen": 0, "behind": 0, "empty_cells": 0, "two_chunks": 0, "three_chunks": 0, "no_decals": 0, "border_cells_out": 0, "sub_cell": 0}
@@ -256,8 +243,6 @@ def generate(path):
             key = (t["width"], t["height"], t["num_levels"], t["format"])
             assert texture_blends.get(key, 0) > 0, f"no decal blends texture {key}"
         print("texture coverage: " + ", ".join(f"{k[0]}x{k[1]} levels {k[2]} format {k[3]}: {v} blends" for k, v in sorted(texture_blends.items())))
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
     write_npz(path, record)
     stored = np.load(path)
     for name in dc.APPLY_CASES:  # what a test will read is what was recorded

@@ -21,41 +21,27 @@ evaluation's own error, which tests/test_gpu_env_bake.py's bound is derived from
 """
 import ctypes as C
 import os
-import shutil
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = os.environ.get("REF", "/root/reference")
-SHADERS = os.path.join(REF, "assets", "shaders")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle", "ref_build")]
 import env_ref  # noqa: E402
+import shader_runner as sr  # noqa: E402
+from shader_runner import SHADERS  # noqa: E402
 
 SEED = 20260117
 
 
 def build(tmp):
-    gen = os.path.join(tmp, "gen")
-    os.makedirs(gen)
-    rb = os.path.join(ROOT, "oracle", "ref_build")
-    subprocess.check_call([sys.executable, os.path.join(rb, "gen_swizzles.py"), gen])
-    for name in ("skybox_latlon", "util/ibl_specular", "util/ibl_diffuse"):
-        subprocess.check_call([sys.executable, os.path.join(rb, "glsl2cpp.py"), os.path.join(SHADERS, name + ".frag"),
-                               os.path.join(gen, os.path.basename(name) + ".inc")])
+    sr.respell(os.path.join(tmp, "gen"), ["skybox_latlon.frag", "util/ibl_specular.frag", "util/ibl_diffuse.frag"])
     runner = os.path.join(HERE, "env_bake_runner.cpp")
-    objs = [os.path.join(tmp, n) for n in ("shaders.o", "matrices.o", "transforms.o", "muglm.o")]
-    subprocess.check_call(["g++", "-O2", "-std=c++20", "-fPIC", "-ffp-contract=off", "-w", "-I" + rb, "-I" + tmp, "-c", runner, "-o", objs[0]])
-    math = ["-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-msse4.1", "-w", "-I" + os.path.join(REF, "math"), "-I" + os.path.join(REF, "util")]
-    subprocess.check_call(["g++", *math, "-DENV_MATRICES", "-c", runner, "-o", objs[1]])
-    subprocess.check_call(["g++", *math, "-c", os.path.join(REF, "math", "transforms.cpp"), "-o", objs[2]])
-    subprocess.check_call(["g++", *math, "-c", os.path.join(REF, "math", "muglm", "muglm.cpp"), "-o", objs[3]])
-    lib = os.path.join(tmp, "libenv_bake_runner.so")
-    subprocess.check_call(["g++", "-shared", "-o", lib, *objs])
-    return lib
+    objs = sr.compile_runner(tmp, runner, [("shaders", [])])
+    objs += sr.reference_math_objects(tmp, [("matrices", runner, ["-DENV_MATRICES"]), ("transforms", os.path.join(sr.MATH, "transforms.cpp"), []),
+                                            ("muglm", sr.MUGLM, [])])
+    return sr.link(os.path.join(tmp, "libenv_bake_runner.so"), objs)
 
 
 def hdr(rng, shape):
@@ -75,10 +61,9 @@ def ptr(a):
 def generate(path):
     if not os.path.isdir(SHADERS):
         raise FileNotFoundError(SHADERS)
-    tmp = tempfile.mkdtemp(prefix="env_golden_")
     rng = np.random.default_rng(SEED)
     record = {}
-    try:
+    with sr.scratch("env_golden_") as tmp:
         lib = C.CDLL(build(tmp), mode=os.RTLD_LAZY)
         matrices = np.zeros((6, 16), np.float32)
         lib.ref_env_matrices(ptr(matrices))
@@ -113,8 +98,6 @@ def generate(path):
             lib.ref_env_diffuse(ptr(matrices), ptr(src), src_size, src_levels, ptr(out), out_size)
             record[name + "/src"], record[name + "/params"], record[name + "/out"] = src, np.array([src_size, src_levels, out_size], np.int32), out
             env_ref.report(name, out, env_ref.pack_chain([env_ref.diffuse(matrices, env_ref.unpack_chain(src, src_size, src_levels), out_size)]))
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
     np.savez_compressed(path, **record)
     print(f"{path}: {os.path.getsize(path)} bytes")
 

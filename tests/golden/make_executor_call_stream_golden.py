@@ -22,6 +22,8 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "executor_call_stream_parent.json")
 STUB = os.path.join(ROOT, "tests", "hip_stub", "libhip_stub.so")
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import host_program  # noqa: E402
 
 APP_WORKER = r'''
 import json, sys
@@ -109,11 +111,7 @@ def split_cases(stderr):
 def build_tools(lib_dir, scratch):
     if not os.path.exists(STUB) or os.path.getmtime(STUB) < os.path.getmtime(os.path.join(os.path.dirname(STUB), "hip_stub.cpp")):
         subprocess.check_call(["make", "-s", "-C", os.path.dirname(STUB)])
-    lib = os.path.join(ROOT, "granite_amd", lib_dir)
-    exe = os.path.join(scratch, "graph_cases")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", os.path.join(ROOT, "tests", "cpp", "graph_cases.cpp"),
-                           "-o", exe, "-L" + lib, "-lgranite_host", "-lgranite_hip", "-Wl,-rpath," + lib, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64"])
-    return exe
+    return host_program.build_program(scratch, "graph_cases", "graph_cases.cpp", extra=host_program.product(lib_dir))
 
 
 def record(name, exe, lib_dir="lib"):

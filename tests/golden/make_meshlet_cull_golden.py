@@ -24,54 +24,43 @@ under SKINNED, and is exempt there)."""
 import ctypes as C
 import io
 import os
-import shutil
-import subprocess
 import sys
-import tempfile
 import zipfile
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = os.environ.get("REF", "/root/reference")
-SHADER = os.path.join(REF, "assets", "shaders", "meshlet_cull.comp")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle", "ref_build")]
 import meshlet_cull_cases as mc  # noqa: E402
 import meshlet_cull_ref as ref  # noqa: E402
+import shader_runner as sr  # noqa: E402
+
+SHADER = os.path.join(sr.SHADERS, "meshlet_cull.comp")
 
 
 def fn_name(phase, flags):
     return f"ref_meshlet_cull_{mc.set_name(phase, flags)}"
 
 
-def build(tmp):
-    gen = os.path.join(tmp, "gen")
-    os.makedirs(gen)
-    rb = os.path.join(ROOT, "oracle", "ref_build")
-    subprocess.check_call([sys.executable, os.path.join(rb, "gen_swizzles.py"), gen])
-    inc = os.path.join(gen, "meshlet_cull.inc")
-    subprocess.check_call([sys.executable, os.path.join(rb, "glsl2cpp.py"), SHADER, inc])
-    text = open(inc).read()
+def rename_the_shadowed_aabb(text):
     for old, new in (("AABB aabb = aabb.data[", "AABB task_aabb = aabb.data["), ("frustum_cull(aabb.lo, aabb.hi)", "frustum_cull(task_aabb.lo, task_aabb.hi)")):
         assert text.count(old) == 1, old
         text = text.replace(old, new)
-    open(inc, "w").write(text)
-    flags = ["-O2", "-std=c++20", "-fPIC", "-pthread", "-ffp-contract=off", "-fno-strict-aliasing", "-w", "-I" + rb, "-I" + tmp]
-    runner = os.path.join(HERE, "meshlet_cull_runner.cpp")
-    jobs = []
+    return text
+
+
+def build(tmp):
+    sr.respell(os.path.join(tmp, "gen"), [SHADER], patch=rename_the_shadowed_aabb)
+    variants = []
     for phase, f in mc.sets():
         name = fn_name(phase, f)
         spec = [f"-DCULL_FN={name}", f"-DMESHLET_RENDER_PHASE={phase}", f"-DSPEC_ORTHO={'true' if f & ref.ORTHO else 'false'}",
                 f"-DSPEC_SKINNED={'true' if f & ref.SKINNED else 'false'}", f"-DSPEC_FORCE_VISIBLE={'true' if f & ref.FORCE_VISIBLE else 'false'}"]
-        jobs.append(["g++", *flags, *spec, "-c", runner, "-o", os.path.join(tmp, name + ".o")])
-    assert len(jobs) == 16
-    with ThreadPoolExecutor(4) as pool:
-        list(pool.map(subprocess.check_call, jobs))
-    lib = os.path.join(tmp, "libmeshlet_cull_runner.so")
-    subprocess.check_call(["g++", "-shared", "-pthread", "-o", lib, *[j[-1] for j in jobs]])
-    return lib
+        variants.append((name, spec))
+    assert len(variants) == 16
+    objs = sr.compile_runner(tmp, os.path.join(HERE, "meshlet_cull_runner.cpp"), variants, extra=["-pthread", "-fno-strict-aliasing"], jobs=4)
+    return sr.link(os.path.join(tmp, "libmeshlet_cull_runner.so"), objs, extra=["-pthread"])
 
 
 class CullRun(C.Structure):
@@ -129,14 +118,13 @@ DIRECTED_COVERAGE = {  # what a directed case is there for: each of these is non
 def generate(path):
     if not os.path.isfile(SHADER):
         raise FileNotFoundError(SHADER)
-    tmp = tempfile.mkdtemp(prefix="meshlet_cull_golden_")
     record = {}
     chain_table = mc.chains()
     for key, (flat, w, h, levels) in chain_table.items():
         record[f"chain/{key}"] = flat
         record[f"chain/{key}/shape"] = np.array([w, h, levels], np.int32)
     total = ref.Info()
-    try:
+    with sr.scratch("meshlet_cull_golden_") as tmp:
         lib = C.CDLL(build(tmp))
         for name in mc.CASE_NAMES:
             differ, compared = 0, 0
@@ -176,8 +164,6 @@ def generate(path):
         for cause in REJECTS + ACCEPTS:
             assert total[cause] > 0, f"nothing hit {cause}"
         print("coverage: " + ", ".join(f"{k} {total[k]}" for k in REJECTS + ACCEPTS))
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
     write_npz(path, record)
     stored = np.load(path)
     for name in mc.CASE_NAMES:  # what a test will read is what was recorded

@@ -20,21 +20,18 @@ once -- asserted identical in every set that writes them, and untouched guard in
 Prints, per class, how many elements tests/meshlet_ref.py decodes differently, and asserts that this is zero."""
 import ctypes as C
 import os
-import shutil
-import subprocess
 import sys
-import tempfile
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = os.environ.get("REF", "/root/reference")
-SHADER = os.path.join(REF, "assets", "shaders", "decode", "meshlet_decode.comp")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle", "ref_build")]
 import meshlet_cases as mc  # noqa: E402
 import meshlet_ref as mr  # noqa: E402
+import shader_runner as sr  # noqa: E402
+
+SHADER = os.path.join(sr.SHADERS, "decode", "meshlet_decode.comp")
 
 
 def fn_name(style, target, flags):
@@ -42,26 +39,17 @@ def fn_name(style, target, flags):
 
 
 def build(tmp):
-    gen = os.path.join(tmp, "gen")
-    os.makedirs(gen)
-    rb = os.path.join(ROOT, "oracle", "ref_build")
-    subprocess.check_call([sys.executable, os.path.join(rb, "gen_swizzles.py"), gen])
-    subprocess.check_call([sys.executable, os.path.join(rb, "glsl2cpp.py"), SHADER, os.path.join(gen, "meshlet_decode.inc")])
-    flags = ["-O2", "-std=c++20", "-fPIC", "-ffp-contract=off", "-w", "-I" + rb, "-I" + tmp]
-    runner = os.path.join(HERE, "meshlet_decode_runner.cpp")
-    jobs = []
+    sr.respell(os.path.join(tmp, "gen"), [SHADER])
+    variants = []
     for style in (0, 1, 2):
         for target, f in mc.sets_of(style):
             name = fn_name(style, target, f)
             spec = [f"-DMESHLET_FN={name}", f"-DSPEC_NUM_U32_STREAMS={mc.STREAMS_OF_STYLE[style]}", f"-DSPEC_TARGET_MESH_STYLE={target}",
                     f"-DSPEC_UNROLLED_MESH={'true' if f & mr.UNROLLED_MESH else 'false'}", f"-DSPEC_INDEX16={'true' if f & mr.INDEX_16 else 'false'}"]
-            jobs.append(["g++", *flags, *spec, "-c", runner, "-o", os.path.join(tmp, name + ".o")])
-    assert len(jobs) == 18
-    with ThreadPoolExecutor(4) as pool:
-        list(pool.map(subprocess.check_call, jobs))
-    lib = os.path.join(tmp, "libmeshlet_decode_runner.so")
-    subprocess.check_call(["g++", "-shared", "-o", lib, *[j[-1] for j in jobs]])
-    return lib
+            variants.append((name, spec))
+    assert len(variants) == 18
+    objs = sr.compile_runner(tmp, os.path.join(HERE, "meshlet_decode_runner.cpp"), variants, jobs=4)
+    return sr.link(os.path.join(tmp, "libmeshlet_decode_runner.so"), objs)
 
 
 def ptr(a):
@@ -83,9 +71,8 @@ def run_shader(lib, mesh, offs, primitive_offset, vertex_offset, target, flags, 
 def generate(path):
     if not os.path.isfile(SHADER):
         raise FileNotFoundError(SHADER)
-    tmp = tempfile.mkdtemp(prefix="meshlet_golden_")
     record = {}
-    try:
+    with sr.scratch("meshlet_golden_") as tmp:
         lib = C.CDLL(build(tmp))
         for name, (data, primitive_offset, vertex_offset, runtime_style) in sorted(mc.cases().items()):
             mesh = mr.parse(data)
@@ -113,8 +100,6 @@ def generate(path):
             record[f"{name}/runtime_style"] = np.array(runtime_style, np.uint32)
             for slot, value in kept.items():
                 record[f"{name}/{slot}"] = value
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
     np.savez_compressed(path, **record)
     print(f"{path}: {os.path.getsize(path)} bytes, {sum(k.endswith('/file') for k in record)} cases")
 

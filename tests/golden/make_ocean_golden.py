@@ -14,19 +14,17 @@ restatements of bake_maps and mipmap give the shaders' bytes.
 """
 import ctypes as C
 import os
-import shutil
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = os.environ.get("REF", "/root/reference")
-SHADERS = os.path.join(REF, "assets", "shaders", "ocean")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle", "ref_build")]
 import ocean_ref as ocr  # noqa: E402
+import shader_runner as sr  # noqa: E402
+
+SHADERS = os.path.join(sr.SHADERS, "ocean")
 
 VARIANT_DEFINES = {ocr.HEIGHT: [], ocr.GRADIENT_NORMAL: ["-DGRADIENT_NORMAL"], ocr.GRADIENT_DISPLACEMENT: ["-DGRADIENT_DISPLACEMENT"]}
 MIPMAP_DEFINES = {1: "-DMIPMAP_R16F", 2: "-DMIPMAP_RG16F", 4: "-DMIPMAP_RGBA16F"}
@@ -38,14 +36,7 @@ MOD_NORMAL = np.float32(2.0) * np.float32(np.pi) / (np.float32(128.0) / np.float
 
 
 def build(tmp):
-    gen = os.path.join(tmp, "gen")
-    os.makedirs(gen)
-    rb = os.path.join(ROOT, "oracle", "ref_build")
-    subprocess.check_call([sys.executable, os.path.join(rb, "gen_swizzles.py"), gen])
-    for name in ("generate_fft", "bake_maps", "mipmap"):
-        subprocess.check_call([sys.executable, os.path.join(rb, "glsl2cpp.py"), os.path.join(SHADERS, name + ".comp"), os.path.join(gen, name + ".inc")])
-    flags = ["-O2", "-std=c++20", "-fPIC", "-ffp-contract=off", "-w", "-I" + rb, "-I" + tmp]
-    runner = os.path.join(HERE, "ocean_runner.cpp")
+    sr.respell(os.path.join(tmp, "gen"), [f"ocean/{name}.comp" for name in ("generate_fft", "bake_maps", "mipmap")])
     sets = []
     for variant, defines in VARIANT_DEFINES.items():
         for bands in (0, 1):
@@ -54,13 +45,8 @@ def build(tmp):
         sets.append((f"ref_ocean_bake_{vertex}", ["-DOCEAN_BAKE", f"-DVERTEX_TEXTURE={vertex}"]))
     for channels, define in MIPMAP_DEFINES.items():
         sets.append((f"ref_ocean_mipmap_{channels}", ["-DOCEAN_MIPMAP", define]))
-    objs = []
-    for fn, defines in sets:
-        objs.append(os.path.join(tmp, fn + ".o"))
-        subprocess.check_call(["g++", *flags, f"-DOCEAN_FN={fn}", *defines, "-c", runner, "-o", objs[-1]])
-    lib = os.path.join(tmp, "libocean_runner.so")
-    subprocess.check_call(["g++", "-shared", "-o", lib, *objs])
-    return lib
+    objs = sr.compile_runner(tmp, os.path.join(HERE, "ocean_runner.cpp"), [(fn, [f"-DOCEAN_FN={fn}", *defines]) for fn, defines in sets])
+    return sr.link(os.path.join(tmp, "libocean_runner.so"), objs)
 
 
 def ptr(a):
@@ -130,9 +116,8 @@ def mipmap_cases():
 def generate(path):
     if not os.path.isdir(SHADERS):
         raise FileNotFoundError(SHADERS)
-    tmp = tempfile.mkdtemp(prefix="ocean_golden_")
     record = {}
-    try:
+    with sr.scratch("ocean_golden_") as tmp:
         lib = C.CDLL(build(tmp))
         dist = distribution()
         record["generate/distribution"] = dist  # a case of N.x x N.y reads rows 0 .. N.y - 1, columns 0 .. N.x - 1 of it
@@ -184,8 +169,6 @@ def generate(path):
             record[name + "/spec"] = np.array([w, h, channels], np.int32)
             record[name + "/out"] = out
             print(f"{name:56s} ocean_ref fp32 gives the shader's bytes")
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
     np.savez_compressed(path, **record)
     print(f"{path}: {os.path.getsize(path)} bytes")
 

@@ -23,19 +23,17 @@ The camera is nudged, a fraction of a unit at a time, until (c) holds (one texel
 turn satisfies it (the bound is then 10 to 20 units, more than a block is wide), and that combination is not recorded."""
 import ctypes as C
 import os
-import shutil
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = os.environ.get("REF", "/root/reference")
-SHADERS = os.path.join(REF, "assets", "shaders", "ocean")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle", "ref_build")]
 import ocean_lod_ref as olr  # noqa: E402
+import shader_runner as sr  # noqa: E402
+
+SHADERS = os.path.join(sr.SHADERS, "ocean")
 
 BLOCK = 16.0  # world units per block, as the default 1024 / 64
 LOD_BIAS = -3.5   # the default, for the default grid
@@ -46,22 +44,11 @@ COUNTS16 = np.array([8 * 17 + i for i in range(8)] + [0xdead0000 + i for i in ra
 
 
 def build(tmp):
-    gen = os.path.join(tmp, "gen")
-    os.makedirs(gen)
-    rb = os.path.join(ROOT, "oracle", "ref_build")
-    subprocess.check_call([sys.executable, os.path.join(rb, "gen_swizzles.py"), gen])
-    for name in ("update_lod", "init_counter_buffer", "cull_blocks"):
-        subprocess.check_call([sys.executable, os.path.join(rb, "glsl2cpp.py"), os.path.join(SHADERS, name + ".comp"), os.path.join(gen, name + ".inc")])
-    flags = ["-O2", "-std=c++20", "-fPIC", "-ffp-contract=off", "-w", "-I" + rb, "-I" + tmp]
-    runner = os.path.join(HERE, "ocean_lod_runner.cpp")
-    objs = []
-    for fn, defines in (("ref_ocean_update_lod", ["-DOCEAN_UPDATE_LOD"]), ("ref_ocean_init_counters", ["-DOCEAN_INIT_COUNTERS", "-DNUM_COUNTERS=8"]),
-                        ("ref_ocean_cull", ["-DOCEAN_CULL"])):
-        objs.append(os.path.join(tmp, fn + ".o"))
-        subprocess.check_call(["g++", *flags, f"-DOCEAN_FN={fn}", *defines, "-c", runner, "-o", objs[-1]])
-    lib = os.path.join(tmp, "libocean_lod_runner.so")
-    subprocess.check_call(["g++", "-shared", "-o", lib, *objs])
-    return lib
+    sr.respell(os.path.join(tmp, "gen"), [f"ocean/{name}.comp" for name in ("update_lod", "init_counter_buffer", "cull_blocks")])
+    sets = (("ref_ocean_update_lod", ["-DOCEAN_UPDATE_LOD"]), ("ref_ocean_init_counters", ["-DOCEAN_INIT_COUNTERS", "-DNUM_COUNTERS=8"]),
+            ("ref_ocean_cull", ["-DOCEAN_CULL"]))
+    objs = sr.compile_runner(tmp, os.path.join(HERE, "ocean_lod_runner.cpp"), [(fn, [f"-DOCEAN_FN={fn}", *defines]) for fn, defines in sets])
+    return sr.link(os.path.join(tmp, "libocean_lod_runner.so"), objs)
 
 
 def ptr(a):
@@ -136,9 +123,8 @@ def cases():
 def generate(path):
     if not os.path.isdir(SHADERS):
         raise FileNotFoundError(SHADERS)
-    tmp = tempfile.mkdtemp(prefix="ocean_lod_golden_")
     record = {"init/counts16": COUNTS16}
-    try:
+    with sr.scratch("ocean_lod_golden_") as tmp:
         lib = C.CDLL(build(tmp))
         draws0 = np.full((8, 8), 0xcdcdcdcd, np.uint32)
         lib.ref_ocean_init_counters(ptr(COUNTS16), ptr(draws0))
@@ -195,8 +181,6 @@ def generate(path):
             record[name + "/draws"] = draws
             record[name + "/patches"] = np.concatenate(got)  # each bucket's first instance_count entries, sorted, bucket after bucket
         print(f"largest share of near-tie texels: {worst_mask:.3%}")
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
     np.savez_compressed(path, **record)
     print(f"{path}: {os.path.getsize(path)} bytes")
 

@@ -17,22 +17,21 @@ import ctypes as C
 import io
 import math
 import os
-import shutil
-import subprocess
+import pathlib
 import sys
-import tempfile
 import zipfile
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = os.environ.get("REF", "/root/reference")
-SHADERS = os.path.join(REF, "assets", "shaders")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle", "ref_build")]
 import env_ref  # noqa: E402
+import host_program  # noqa: E402
+import shader_runner as sr  # noqa: E402
 import sky_cases as sc  # noqa: E402
 import sky_ref  # noqa: E402
+from shader_runner import SHADERS  # noqa: E402
 
 
 def braced_vec3_arrays(text):
@@ -51,29 +50,12 @@ def braced_vec3_arrays(text):
 
 
 def build(tmp):
-    gen = os.path.join(tmp, "gen")
-    os.makedirs(gen)
-    rb = os.path.join(ROOT, "oracle", "ref_build")
-    subprocess.check_call([sys.executable, os.path.join(rb, "gen_swizzles.py"), gen])
-    for name in ("skybox.frag", "lights/volumetric_light_setup_sky.comp"):
-        inc = os.path.join(gen, os.path.splitext(os.path.basename(name))[0] + ".inc")
-        subprocess.check_call([sys.executable, os.path.join(rb, "glsl2cpp.py"), os.path.join(SHADERS, name), inc])
-        with open(inc) as f:
-            text = f.read()
-        with open(inc, "w") as f:
-            f.write(braced_vec3_arrays(text))
+    sr.respell(os.path.join(tmp, "gen"), ["skybox.frag", "lights/volumetric_light_setup_sky.comp"], patch=braced_vec3_arrays)
     runner = os.path.join(HERE, "sky_runner.cpp")
-    objs = [os.path.join(tmp, n) for n in ("shaders.o", "matrices.o", "transforms.o", "muglm.o")]
-    subprocess.check_call(["g++", "-O2", "-std=c++20", "-fPIC", "-ffp-contract=off", "-w", "-I" + rb, "-I" + tmp, "-c", runner, "-o", objs[0]])
-    maths = ["-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-msse4.1", "-w", "-I" + os.path.join(REF, "math"), "-I" + os.path.join(REF, "util")]
-    subprocess.check_call(["g++", *maths, "-DSKY_MATRICES", "-c", runner, "-o", objs[1]])
-    subprocess.check_call(["g++", *maths, "-c", os.path.join(REF, "math", "transforms.cpp"), "-o", objs[2]])
-    subprocess.check_call(["g++", *maths, "-c", os.path.join(REF, "math", "muglm", "muglm.cpp"), "-o", objs[3]])
-    lib = os.path.join(tmp, "libsky_runner.so")
-    subprocess.check_call(["g++", "-shared", "-o", lib, *objs])
-    host = os.path.join(tmp, "sky_core_host")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-ffp-contract=off", "-o", host, os.path.join(ROOT, "tests", "cpp", "sky_core_host.cpp")])
-    return lib, host
+    objs = sr.compile_runner(tmp, runner, [("shaders", [])])
+    objs += sr.reference_math_objects(tmp, [("matrices", runner, ["-DSKY_MATRICES"]), ("transforms", os.path.join(sr.MATH, "transforms.cpp"), []),
+                                            ("muglm", sr.MUGLM, [])])
+    return sr.link(os.path.join(tmp, "libsky_runner.so"), objs), host_program.build_program(tmp, "sky_core_host", "sky_core_host.cpp", exact=True)
 
 
 def ptr(a):
@@ -100,10 +82,7 @@ def hdr_cube(rng, size, levels):
 
 
 def run_host(host, tmp, data):
-    path = os.path.join(tmp, "case.bin")
-    with open(path, "wb") as f:
-        f.write(data)
-    return subprocess.run([host, path], capture_output=True, check=True).stdout
+    return host_program.run_program(host, input_bytes=data, tmp_path=pathlib.Path(tmp))
 
 
 def save(path, record):
@@ -126,10 +105,9 @@ def bright_share(out):
 def generate(path):
     if not os.path.isdir(SHADERS):
         raise FileNotFoundError(SHADERS)
-    tmp = tempfile.mkdtemp(prefix="sky_golden_")
     rng = np.random.default_rng(sc.SEED)
     record = {}
-    try:
+    with sr.scratch("sky_golden_") as tmp:
         lib_path, host = build(tmp)
         lib = C.CDLL(lib_path, mode=os.RTLD_LAZY)
         lib.ref_sky_camera.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]
@@ -213,8 +191,6 @@ def generate(path):
             assert (out[..., :3] == 0.0).any() and (out[..., :3] != 0.0).any(), f"{name}: the -Y face sees the earth"
             print(f"{name:26s} zero texels {int((out[..., :3] == 0.0).all(axis=-1).sum()):4d} max {out[..., :3].max():9.3f} bright {bright_share(out[..., :3]):.3f}  "
                   f"sky_ref {sky_ref.ulp_distance(ref, out).max():.3f}  host {sky_ref.ulp_distance(host_rgba, out).max():.3f} fp16 ulps beyond 1e-4")
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
     save(path, record)
     print(f"{path}: {os.path.getsize(path)} bytes")
 

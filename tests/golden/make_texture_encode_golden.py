@@ -20,20 +20,18 @@ fixture, by tests/test_texture_encode_ref_cpu.py.
 BC5 from RG8 -- the scale tools/texture_encode_time.py's device times are read against."""
 import ctypes as C
 import os
-import shutil
-import subprocess
 import sys
-import tempfile
 import time
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = os.environ.get("REF", "/root/reference")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle", "ref_build")]
+import shader_runner as sr  # noqa: E402
 import texture_encode_cases as tc  # noqa: E402
 import texture_encode_ref as ref  # noqa: E402
+from shader_runner import REF  # noqa: E402
 
 
 def build(tmp):
@@ -43,14 +41,9 @@ def build(tmp):
         f.write(source[begin:end])
     flags = ["-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-w", "-I" + tmp, "-I" + os.path.join(REF, "math"), "-I" + os.path.join(REF, "util"),
              "-I" + os.path.join(REF, "scene-export")]
-    objs = []
-    for name, path in (("runner", os.path.join(HERE, "texture_encode_runner.cpp")), ("rgtc", os.path.join(REF, "scene-export", "rgtc_compressor.cpp")),
-                       ("muglm", os.path.join(REF, "math", "muglm", "muglm.cpp"))):
-        objs.append(os.path.join(tmp, name + ".o"))
-        subprocess.check_call(["g++", *flags, "-c", path, "-o", objs[-1]])
-    lib = os.path.join(tmp, "libtexture_encode_runner.so")
-    subprocess.check_call(["g++", "-shared", "-o", lib, *objs])
-    return C.CDLL(lib, mode=os.RTLD_LAZY)
+    objs = sr.compile_objects(tmp, flags, [("runner", os.path.join(HERE, "texture_encode_runner.cpp"), []),
+                                           ("rgtc", os.path.join(REF, "scene-export", "rgtc_compressor.cpp"), []), ("muglm", sr.MUGLM, [])])
+    return C.CDLL(sr.link(os.path.join(tmp, "libtexture_encode_runner.so"), objs), mode=os.RTLD_LAZY)
 
 
 def ptr(a):
@@ -89,9 +82,8 @@ def check_conditions(infos):
 
 
 def generate(path):
-    tmp = tempfile.mkdtemp(prefix="texture_encode_golden_")
     record = {}
-    try:
+    with sr.scratch("texture_encode_golden_") as tmp:
         lib = build(tmp)
         infos = []
         for name, image in tc.make_encode_inputs().items():
@@ -133,17 +125,14 @@ def generate(path):
         for level in range(tc.GTX_LEVELS):
             blocks = compress(lib, tc.chain_level(payload, fmt, w, h, 1, tc.GTX_LEVELS, level)[0], tc.BC5)
             record[f"gtx/{level}/blocks"], record[f"gtx/{level}/decoded"] = blocks, decompress(lib, blocks)
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
     np.savez_compressed(path, **record)
     print(f"{path}: {os.path.getsize(path)} bytes")
 
 
 def measure(path):
-    tmp = tempfile.mkdtemp(prefix="texture_encode_golden_")
     lines = ["# The reference's RGTC compressor (scene-export/rgtc_compressor.cpp, g++ -O2), one thread of the recording machine's CPU, 4096 x 4096 texels,",
              "# best of 3 runs.  Written by tests/golden/make_texture_encode_golden.py --time.", "# family  target  ms"]
-    try:
+    with sr.scratch("texture_encode_golden_") as tmp:
         lib = build(tmp)
         for family in ("uniform", "gradient", "masks"):
             rng = np.random.default_rng(tc.SEED + 7)
@@ -157,8 +146,6 @@ def measure(path):
                     best = min(best, time.perf_counter() - start)
                 lines.append(f"{family:9s} {target:13s} {best * 1e3:9.1f}")
                 print(lines[-1])
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
     with open(path, "w") as f:
         f.write("\n".join(lines) + "\n")
 

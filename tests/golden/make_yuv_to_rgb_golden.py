@@ -12,19 +12,17 @@ demands 99 %.
 """
 import ctypes as C
 import os
-import shutil
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-REF = os.environ.get("REF", "/root/reference")
-SHADER = os.path.join(REF, "assets", "shaders", "util", "yuv_to_rgb.comp")
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle", "ref_build")]
+import shader_runner as sr  # noqa: E402
 import yuv_ref as yr  # noqa: E402
+
+SHADER = os.path.join(sr.SHADERS, "util", "yuv_to_rgb.comp")
 
 # (pq, num_planes, nv21)
 VARIANTS = [(0, 1, 0), (0, 2, 0), (0, 2, 1), (0, 3, 0), (1, 1, 0), (1, 2, 0), (1, 2, 1), (1, 3, 0)]
@@ -67,22 +65,10 @@ def make_planes(size, n, sub, seed):
 
 
 def build(tmp):
-    gen = os.path.join(tmp, "gen")
-    os.makedirs(gen)
-    rb = os.path.join(ROOT, "oracle", "ref_build")
-    subprocess.check_call([sys.executable, os.path.join(rb, "gen_swizzles.py"), gen])
-    subprocess.check_call([sys.executable, os.path.join(rb, "glsl2cpp.py"), SHADER, os.path.join(gen, "yuv_to_rgb.inc")])
-    flags = ["-O2", "-std=c++20", "-fPIC", "-ffp-contract=off", "-w", "-I" + rb, "-I" + tmp]
-    runner = os.path.join(HERE, "yuv_to_rgb_runner.cpp")
-    objs = []
-    for pq, n, nv21 in VARIANTS:
-        objs.append(os.path.join(tmp, f"runner_{pq}_{n}_{nv21}.o"))
-        subprocess.check_call(["g++", *flags, f"-DSPEC_PQ={pq}", f"-DSPEC_NUM_PLANES={n}", f"-DSPEC_NV21={nv21}", "-c", runner, "-o", objs[-1]])
-    objs.append(os.path.join(tmp, "runner_entry.o"))
-    subprocess.check_call(["g++", *flags, "-DYUV_ENTRY", "-c", runner, "-o", objs[-1]])
-    lib = os.path.join(tmp, "libyuv_to_rgb_runner.so")
-    subprocess.check_call(["g++", "-shared", "-o", lib, *objs])
-    return lib
+    sr.respell(os.path.join(tmp, "gen"), [SHADER])
+    variants = [(f"runner_{pq}_{n}_{nv21}", [f"-DSPEC_PQ={pq}", f"-DSPEC_NUM_PLANES={n}", f"-DSPEC_NV21={nv21}"]) for pq, n, nv21 in VARIANTS]
+    objs = sr.compile_runner(tmp, os.path.join(HERE, "yuv_to_rgb_runner.cpp"), [*variants, ("runner_entry", ["-DYUV_ENTRY"])])
+    return sr.link(os.path.join(tmp, "libyuv_to_rgb_runner.so"), objs)
 
 
 def ubo_floats(p):
@@ -93,9 +79,8 @@ def ubo_floats(p):
 def generate(path):
     if not os.path.exists(SHADER):
         raise FileNotFoundError(SHADER)
-    tmp = tempfile.mkdtemp(prefix="yuv_golden_")
     record = {}
-    try:
+    with sr.scratch("yuv_golden_") as tmp:
         lib = C.CDLL(build(tmp))
         lib.ref_yuv_to_rgb.restype = C.c_int
         for seed, (name, (size, n, sub, nv21, inf)) in enumerate(sorted(cases().items())):
@@ -124,8 +109,6 @@ def generate(path):
             record[f"{name}/spec"] = np.array([p["spec_pq"], p["spec_num_planes"], p["spec_nv21"]], np.int32)
             record[f"{name}/info"] = np.array([inf[k] for k in ("bit_depth", "msb_aligned", "full_range", "matrix", "chroma_location", "pq", "nv21")], np.int32)
             record[f"{name}/out"] = out
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
     np.savez_compressed(path, **record)
     print(f"{path}: {os.path.getsize(path)} bytes, {len(cases())} cases")
 

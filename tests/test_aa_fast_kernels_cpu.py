@@ -4,25 +4,21 @@ for bit: what is checked here is the kernels' tiling, halo staging, clamping at 
 arithmetic of aa_core.hpp; what a GPU run adds is the compiler and the hardware."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from granite_amd import synth
+from host_program import CPP, build_library
 from oracle import oracle as orc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PRESET_THRESHOLD = (0.15, 0.1, 0.1, 0.05)  # SMAA.hlsl:304-324
 
 
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("aa_fast_host") / "libaa_fast_host.so")
-    subprocess.check_call(["g++", "-O1", "-std=c++20", "-pthread", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                           "-I" + os.path.join(ROOT, "tests", "cpp", "emu_include"),
-                           os.path.join(ROOT, "tests", "cpp", "aa_fast_host.cpp"), "-o", so])
-    lib = C.CDLL(so)
+    lib = C.CDLL(build_library(tmp_path_factory.mktemp("aa_fast_host"), "libaa_fast_host.so", "aa_fast_host.cpp", std="c++20", exact=True,
+                               extra=["-pthread", "-Wno-unknown-pragmas", "-I" + os.path.join(CPP, "emu_include")]))
     lib.aah_centre_taps_exact.argtypes = [C.c_int, C.c_float]
     lib.aah_centre_taps_exact.restype = C.c_int
     return lib

@@ -4,39 +4,20 @@ executed on the CPU (tests/golden/astc_decode_shader_v1.npz), byte for byte; its
 shader's buffers, entry for entry; and the same program built with -fsanitize=address,undefined -fno-sanitize-recover run on the golden
 blocks and on 4096 uniformly random 16-byte blocks per footprint class: the decoder is total, any 16 bytes decode without undefined
 behaviour and to what tests/astc_ref.py gives."""
-import os
-import subprocess
-
 import numpy as np
-import pytest
 
 import astc_cases
 import astc_ref
+from host_program import program_fixtures, run_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCE = os.path.join(ROOT, "tests", "cpp", "astc_decode_host.cpp")
 CASES = astc_cases.golden()
-
-
-@pytest.fixture(scope="module")
-def plain(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("astc_decode") / "astc_decode_host"
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-o", str(exe), SOURCE])
-    return str(exe)
-
-
-@pytest.fixture(scope="module")
-def sanitized(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("astc_decode_san") / "astc_decode_host"
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", str(exe), SOURCE])
-    return str(exe)
+plain, sanitized = program_fixtures("astc_decode_host.cpp")
 
 
 def run(exe, tmp_path, bw, bh, w, h, blocks):
     src, dst = str(tmp_path / "blocks.bin"), str(tmp_path / "out.bin")
     np.ascontiguousarray(blocks, np.uint8).tofile(src)
-    r = subprocess.run([exe, "decode", str(bw), str(bh), str(w), str(h), src, dst], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
+    run_program(exe, "decode", bw, bh, w, h, src, dst)
     return np.fromfile(dst, np.uint8).reshape(h, w, 4)
 
 
@@ -66,7 +47,7 @@ def test_host_build_equals_the_executed_shader(plain, tmp_path):
 def test_compile_time_tables_equal_the_recorded_ones(plain, tmp_path):
     recorded = astc_cases.golden_tables()
     path = str(tmp_path / "tables.bin")
-    subprocess.check_call([plain, "tables", path])
+    run_program(plain, "tables", path)
     raw, at = np.fromfile(path, np.uint8), 0
     for key, dtype, shape in (("endpoint_quantiser", np.uint16, (9, 128, 4)), ("endpoint_unquant", np.uint8, (1192,)), ("weight_quantiser", np.uint8, (16, 4)),
                               ("weight_unquant", np.uint8, (142,)), ("trits_quints", np.uint16, (384,))):
@@ -75,7 +56,7 @@ def test_compile_time_tables_equal_the_recorded_ones(plain, tmp_path):
         at += nbytes
     assert at == raw.size
     for bw, bh in astc_cases.FULL:  # the partition index is computed, not looked up: the table it would have been read from
-        subprocess.check_call([plain, "partition", str(bw), str(bh), path])
+        run_program(plain, "partition", bw, bh, path)
         assert np.array_equal(np.fromfile(path, np.uint8).reshape(32 * bh, 32 * bw), recorded[f"partition_{bw}x{bh}"]), (bw, bh)
 
 

@@ -9,29 +9,25 @@ BC7 and BC6H must equal the shader's output on every sample.  BC1-BC5 must equal
 a case's samples, except in the cases that force tie sums, whose differences must lie on tie samples only.  Tie shares the maker
 printed: bc1_rgb_random 0.22 %, bc1_rgba_random 0.19 %, bc1_rgb_tie_sums 18.97 %, bc1_rgba_tie_sums 21.39 %, every other case 0 %;
 bc_ref differed from the shaders on no sample of any case, tie or not."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import bc_cases
 import bc_ref
+from host_program import build_program, run_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KIND = {131: 0, 132: 0, 133: 1, 134: 1, 135: 2, 136: 2, 137: 3, 138: 3, 139: 4, 141: 5, 143: 6, 144: 7, 145: 8, 146: 8}
 CASES = bc_cases.golden()
 
 
 @pytest.fixture(scope="module")
 def host_decoder(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("bc_decode") / "bc_decode_host"
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-o", str(exe), os.path.join(ROOT, "tests", "cpp", "bc_decode_host.cpp")])
+    exe = build_program(tmp_path_factory.mktemp("bc_decode"), "bc_decode_host", "bc_decode_host.cpp")
 
     def run(fmt, blocks, w, h, lanes, tmp):
         src, dst = tmp / "blocks.bin", tmp / "out.bin"
         np.ascontiguousarray(blocks).tofile(src)
-        subprocess.check_call([str(exe), str(KIND[fmt]), str(lanes), str(w), str(h), str(src), str(dst)])
+        run_program(exe, KIND[fmt], lanes, w, h, src, dst)
         return np.fromfile(dst, np.uint8)
     return run
 

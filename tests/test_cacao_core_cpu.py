@@ -3,7 +3,6 @@ the kernel text the device build compiles -- and held to tests/cacao_ref.py stag
 with the bounds of tests/cacao_chain.py.  The same cases run on the device in tests/test_gpu_cacao.py.  The stand-alone program of the same
 file is run once under AddressSanitizer and UndefinedBehaviorSanitizer: the blur's LDS indexing and the guarded stores are what it is for."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
@@ -12,10 +11,9 @@ import pytest
 import cacao_cases as cc
 import cacao_chain as chain
 import cacao_ref as cr
+from host_program import build_library, build_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCE = os.path.join(ROOT, "tests", "cpp", "cacao_core_host.cpp")
-FLAGS = ["-std=c++20", "-Wall", "-Werror", "-Wno-unused-function", "-ffp-contract=off", "-pthread"]
+EXTRA = ["-Wno-unused-function", "-pthread"]
 
 
 def ptr(a):
@@ -65,9 +63,7 @@ class HostBackend:
 
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
-    lib = tmp_path_factory.mktemp("cacao_core") / "libcacao_core_host.so"
-    subprocess.check_call(["g++", "-O1", *FLAGS, "-shared", "-fPIC", "-o", str(lib), SOURCE])
-    return C.CDLL(str(lib))
+    return C.CDLL(build_library(tmp_path_factory.mktemp("cacao_core"), "libcacao_core_host.so", "cacao_core_host.cpp", std="c++20", exact=True, extra=EXTRA))
 
 
 @pytest.mark.parametrize("quality", cc.QUALITIES, ids=lambda q: f"q{q}")
@@ -135,9 +131,8 @@ def test_unorm8_load_is_the_quotient(host):
 
 def test_stand_alone_program_under_sanitizers(tmp_path):
     """the whole pass at 61 x 45, 16 x 16 and 130 x 98 on exactly sized heap blocks, -fsanitize=address,undefined"""
-    exe = tmp_path / "cacao_core_host_asan"
-    subprocess.check_call(["g++", "-O1", "-g", *FLAGS, "-DCACAO_HOST_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-                           "-o", str(exe), SOURCE])
-    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600)
+    exe = build_program(tmp_path, "cacao_core_host_asan", "cacao_core_host.cpp", sanitized=True, std="c++20", exact=True,
+                        extra=[*EXTRA, "-DCACAO_HOST_MAIN"])
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert run.returncode == 0, run.stdout + run.stderr
     assert "cacao_core_host: done" in run.stdout and "runtime error" not in run.stderr

@@ -7,14 +7,9 @@ non-NaN code; a NaN code must give a NaN of the same sign (numpy builds differ i
 the payload as it is).  The program is built plainly and with -fsanitize=address,undefined and run directly (its own main; nothing is
 preloaded).  On the device both functions are the hardware conversion, which the GPU tests of env bake, ocean, CACAO, FFT, sky, AA and
 post run."""
-import os
-import subprocess
-
 import numpy as np
-import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCE = os.path.join(ROOT, "tests", "cpp", "core_base_host.cpp")
+from host_program import program_fixtures, run_program
 
 
 def half_bits(values):
@@ -48,31 +43,15 @@ def inputs():
 EXACT, NANS = inputs()
 
 
-def build(tmp, name, flags):
-    exe = tmp / name
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-ffp-contract=off", *flags, "-o", str(exe), SOURCE])
-    return str(exe)
-
-
-@pytest.fixture(scope="module")
-def plain(tmp_path_factory):
-    return build(tmp_path_factory.mktemp("core_base"), "core_base_host", [])
-
-
-@pytest.fixture(scope="module")
-def sanitized(tmp_path_factory):
-    return build(tmp_path_factory.mktemp("core_base_san"), "core_base_host_san", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+plain, sanitized = program_fixtures("core_base_host.cpp", exact=True)
 
 
 def check(exe, tmp_path):
-    case = tmp_path / "inputs.bin"
-    case.write_bytes(np.concatenate([EXACT, NANS]).tobytes())
-    r = subprocess.run([exe, str(case)], capture_output=True)
-    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    out = run_program(exe, input_bytes=np.concatenate([EXACT, NANS]).tobytes(), tmp_path=tmp_path)
     count = EXACT.size + NANS.size
-    assert len(r.stdout) == 2 * count + 4 * 65536
-    halves = np.frombuffer(r.stdout, np.uint16, count)
-    floats = np.frombuffer(r.stdout, np.uint32, 65536, offset=2 * count)
+    assert len(out) == 2 * count + 4 * 65536
+    halves = np.frombuffer(out, np.uint16, count)
+    floats = np.frombuffer(out, np.uint32, 65536, offset=2 * count)
 
     want = half_bits(EXACT.view(np.float32))
     wrong = np.flatnonzero(halves[:EXACT.size] != want)

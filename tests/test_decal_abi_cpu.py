@@ -12,8 +12,8 @@ import sys
 import pytest
 
 from granite_amd import app as gapp, capi
+from host_program import ROOT, c_layout
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "granite_hip.h")).read()
 STUB = os.path.join(ROOT, "tests", "hip_stub", "libhip_stub.so")
 INVALID = -1
@@ -56,23 +56,12 @@ def test_the_header_asserts_the_new_structures():
 @pytest.mark.parametrize("c_name, ct", [("gr_decal_texture", capi.DecalTexture), ("gr_decal_apply_args", capi.DecalApplyArgs)])
 def test_the_structures_are_the_same_in_c_and_in_ctypes(tmp_path, c_name, ct):
     fields = [name for name, _ in ct._fields_]
-    src = tmp_path / "layout.c"
-    src.write_text('#include "granite_hip.h"\n#include <stdio.h>\n#include <stddef.h>\nint main(void) {\n' + f'  printf("%zu\\n", sizeof({c_name}));\n' +
-                   "".join(f'  printf("%zu\\n", offsetof({c_name}, {f}));\n' for f in fields) + "  return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    got = [int(v) for v in subprocess.check_output([str(exe)], text=True).split()]
-    assert got == [C.sizeof(ct)] + [getattr(ct, f).offset for f in fields]
+    assert c_layout(tmp_path, c_name, fields) == [C.sizeof(ct)] + [getattr(ct, f).offset for f in fields]
 
 
 def test_the_application_structures_are_the_same_in_c_and_in_ctypes(tmp_path):
     from granite_amd import synth
-    src = tmp_path / "layout.c"
-    src.write_text('#include "granite_app.h"\n#include <stdio.h>\n#include <stddef.h>\nint main(void) {\n  printf("%zu %zu %zu %zu\\n", sizeof(gra_config), '
-                   'offsetof(gra_config, volumetric_decals), sizeof(gra_decal_desc), offsetof(gra_decal_desc, texture));\n  return 0;\n}\n')
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    got = [int(v) for v in subprocess.check_output([str(exe)], text=True).split()]
+    got = c_layout(tmp_path, "gra_config", ["volumetric_decals"], "granite_app.h") + c_layout(tmp_path, "gra_decal_desc", ["texture"], "granite_app.h")
     assert got == [C.sizeof(gapp.Config), gapp.Config.volumetric_decals.offset, synth.DECAL_DESC_DTYPE.itemsize, synth.DECAL_DESC_DTYPE.fields["texture"][1]]
 
 

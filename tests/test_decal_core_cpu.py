@@ -3,34 +3,15 @@ tiles as the kernels of decal.hip do) and held to the reference's decal shaders 
 binning masks word for word on every case, every word written exactly once; the apply as float colour before the 8-bit store, bit for bit.
 The program is built plainly and with -fsanitize=address,undefined and run directly (its own main; nothing is preloaded).  The same cases
 run on the device in tests/test_gpu_decals.py."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import decal_cases as dc
 import decal_ref as ref
+from host_program import program_fixtures, run_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCE = os.path.join(ROOT, "tests", "cpp", "decal_core_host.cpp")
 GOLDEN = dc.load_golden()
-
-
-def build(tmp, name, flags):
-    exe = tmp / name
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-ffp-contract=off", *flags, "-o", str(exe), SOURCE])
-    return str(exe)
-
-
-@pytest.fixture(scope="module")
-def plain(tmp_path_factory):
-    return build(tmp_path_factory.mktemp("decal_core"), "decal_core_host", [])
-
-
-@pytest.fixture(scope="module")
-def sanitized(tmp_path_factory):
-    return build(tmp_path_factory.mktemp("decal_core_san"), "decal_core_host_san", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+plain, sanitized = program_fixtures("decal_core_host.cpp", exact=True)
 
 
 def counted(a):
@@ -54,9 +35,7 @@ def apply_bytes(case):
 
 
 def run(exe, tmp_path, data):
-    case = tmp_path / "case.bin"
-    case.write_bytes(data)
-    return subprocess.run([exe, str(case)], capture_output=True, check=True).stdout
+    return run_program(exe, input_bytes=data, tmp_path=tmp_path)
 
 
 def check_binning(exe, tmp_path, name):

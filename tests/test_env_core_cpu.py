@@ -4,15 +4,14 @@ tests/test_gpu_env_bake.py for why that is the bound), with a texel's taps on on
 per-face matrices of host/math.* against the reference's; and the seamless edge rule probed at face edges and at a corner."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import env_ref
+from host_program import ROOT, build_library
 from util import assert_rgba16f_close
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = np.load(os.path.join(ROOT, "tests", "golden", "env_bake_shader_v1.npz"))
 
 
@@ -22,10 +21,7 @@ def ptr(a):
 
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
-    lib = tmp_path_factory.mktemp("env_core") / "libenv_core_host.so"
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-ffp-contract=off", "-shared", "-fPIC", "-o", str(lib),
-                           os.path.join(ROOT, "tests", "cpp", "env_core_host.cpp")])
-    lib = C.CDLL(str(lib))
+    lib = C.CDLL(build_library(tmp_path_factory.mktemp("env_core"), "libenv_core_host.so", "env_core_host.cpp", exact=True))
     lib.env_host_chain_offset.restype = C.c_uint64
     return lib
 

@@ -2,26 +2,21 @@
 lane by lane as the kernels of fft.hip do, held to numpy's float64 DFT under the bounds of tests/fft_ref.py (1e-10 of the power in fp32,
 5e-4 in fp16, per output row), plus exact probes and the image store's clipping."""
 import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import fft_ref
 from fft_ref import Case, ptr
 from granite_amd import capi
+from host_program import build_library
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = fft_ref.shape_cases()
 
 
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
-    lib = tmp_path_factory.mktemp("fft_core") / "libfft_core_host.so"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-shared", "-fPIC", "-o", str(lib),
-                           os.path.join(ROOT, "tests", "cpp", "fft_core_host.cpp")])
-    return C.CDLL(str(lib))
+    # -O2: the cases run every pass lane by lane, and the suite's time is this library's speed
+    return C.CDLL(build_library(tmp_path_factory.mktemp("fft_core"), "libfft_core_host.so", "fft_core_host.cpp", extra=["-O2"]))
 
 
 def executor(host):

@@ -5,23 +5,17 @@ that ran before a producer, a recycled allocation still in use, or a wrong copy 
 (Sensitivity, measured once: with the executor's cross-stream waits switched off -- GRANITE_UNSAFE_NO_CROSS_SYNC=1 -- 33 of the
 40 graphs produce different frames.)"""
 import json
-import os
-import subprocess
 
 import pytest
 
+from host_program import PRODUCT, build_program, run_program
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "granite_amd", "lib")
 
 
 def test_pipelined_execution_of_random_graphs_equals_serial_execution(tmp_path):
-    exe = str(tmp_path / "graph_cases")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "graph_cases.cpp"), "-o", exe, "-L" + LIB, "-lgranite_host",
-                           "-lgranite_hip", "-Wl,-rpath," + LIB, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64"])
-    out = subprocess.check_output([exe, "--execute", "40"], text=True, timeout=300)
-    cases = list(map(json.loads, out.strip().splitlines()))
+    exe = build_program(tmp_path, "graph_cases", "graph_cases.cpp", extra=PRODUCT)
+    cases = list(map(json.loads, run_program(exe, "--execute", 40, timeout=300).splitlines()))
     assert len(cases) == 40
     seen = set()
     for c in cases:

@@ -2,27 +2,16 @@
 place_mesh_chunks, build_task_infos and build_mdi_culling_pass in a C++ program (tests/cpp/meshlet_cull_pass.cpp) linked against the
 built libraries, one scene per CullingPhase; the program's tasks, bounds and draws and the device's output and occluder words are held
 to tests/meshlet_cull_ref.py.  A second MDICall with indirect_count_max = 0 and offsets no launch would accept must be skipped."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import meshlet_cases as files
 import meshlet_cull_cases as mc
 import meshlet_cull_ref as ref
+from host_program import PRODUCT, program_fixtures, run_program
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "granite_amd", "lib")
-
-
-@pytest.fixture(scope="module")
-def program(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("meshlet_cull_pass") / "meshlet_cull_pass")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", os.path.join(ROOT, "tests", "cpp", "meshlet_cull_pass.cpp"),
-                           "-o", exe, "-L" + LIB, "-lgranite_host", "-lgranite_hip", "-Wl,-rpath," + LIB, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64"])
-    return exe
+program = program_fixtures("meshlet_cull_pass.cpp", extra=PRODUCT).plain
 
 
 def mesh_file(seed, meshlets, cam, rng):
@@ -66,8 +55,7 @@ def test_files_through_the_host_helpers_equal_the_restatement(program, tmp_path,
         blob += np.array([len(data)], np.uint32).tobytes() + data + b"\0" * (-len(data) % 4)
     src, dst = tmp_path / "scene.bin", tmp_path / "out.bin"
     src.write_bytes(blob)
-    r = subprocess.run([program, str(src), str(dst)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr[-2000:]
+    run_program(program, src, dst, timeout=120)
     raw = np.fromfile(dst, np.uint32)
     n_tasks, n_chunks, n_out = (int(v) for v in raw[:3])
     at = 3

@@ -12,7 +12,8 @@ import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from host_program import PRODUCT, ROOT, build_program
+
 STUB = os.path.join(ROOT, "tests", "hip_stub", "libhip_stub.so")
 
 WORKER = r'''
@@ -152,12 +153,7 @@ def test_staging_slot_is_not_reused_before_the_stream_that_read_it_is_through(tm
     And an idle stream costs no call at all: once its last record has been waited for, nothing names its events again."""
     if not os.path.exists(STUB) or os.path.getmtime(STUB) < os.path.getmtime(os.path.join(os.path.dirname(STUB), "hip_stub.cpp")):
         subprocess.check_call(["make", "-s", "-C", os.path.dirname(STUB)])
-    csrc = os.path.join(ROOT, "granite_amd", "csrc")
-    lib = os.path.join(ROOT, "granite_amd", "lib")
-    exe = str(tmp_path / "staging_fences")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-I" + csrc, "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "staging_fences.cpp"), "-o", exe, "-L" + lib, "-lgranite_host", "-lgranite_hip",
-                           "-Wl,-rpath," + lib, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64", "-pthread"])
+    exe = build_program(tmp_path, "staging_fences", "staging_fences.cpp", extra=[*PRODUCT, "-I" + os.path.join(ROOT, "granite_amd", "csrc"), "-pthread"])
     env = dict(os.environ, LD_PRELOAD=STUB, HIP_STUB_TRACE="1", HIP_STUB_EVENTS_PENDING="1")
     r = subprocess.run([exe], env=env, capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr[-3000:]

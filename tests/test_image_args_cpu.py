@@ -5,23 +5,17 @@ preloaded).  The program checks the texel-size table against host/vk_subset.hpp,
 capi.FORMAT_BPP here."""
 import json
 import os
-import subprocess
 
 import pytest
 
 from granite_amd import capi
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCE = os.path.join(ROOT, "tests", "cpp", "image_args_host.cpp")
+from host_program import ROOT, build_program, run_program
 
 
-@pytest.mark.parametrize("flags", [[], ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]], ids=["plain", "sanitized"])
-def test_contract_on_the_host(tmp_path, flags):
-    exe = tmp_path / "image_args_host"
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", *flags, "-o", str(exe), SOURCE])
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr[-3000:]
-    table = {int(fmt): size for fmt, size in json.loads(r.stdout).items()}
+@pytest.mark.parametrize("sanitized", [False, True], ids=["plain", "sanitized"])
+def test_contract_on_the_host(tmp_path, sanitized):
+    exe = build_program(tmp_path, "image_args_host", "image_args_host.cpp", sanitized=sanitized)
+    table = {int(fmt): size for fmt, size in json.loads(run_program(exe, timeout=120)).items()}
     assert table == capi.FORMAT_BPP
     assert not set(table) & set(capi.BLOCK_FORMATS)
 

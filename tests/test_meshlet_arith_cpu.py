@@ -10,17 +10,10 @@ import pytest
 
 import meshlet_cases as mc
 import meshlet_ref as mr
+from host_program import ROOT, program_fixtures, run_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCES = [os.path.join(ROOT, "tests", "cpp", "meshlet_host.cpp"), os.path.join(ROOT, "granite_amd", "csrc", "host", "mesh", "meshlet.cpp")]
-
-
-@pytest.fixture(scope="module")
-def program(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("meshlet_host") / "meshlet_host"
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", "-o", str(exe), *SOURCES])
-    return str(exe)
+program = program_fixtures(["meshlet_host.cpp", os.path.join(ROOT, "granite_amd", "csrc", "host", "mesh", "meshlet.cpp")],
+                           extra=["-D__HIP_PLATFORM_AMD__"]).sanitized
 
 
 @pytest.mark.parametrize("count", [0, 1, 8, 9, 17])
@@ -32,8 +25,7 @@ def test_offsets_and_indirect_records_equal_the_restatement(program, tmp_path, c
     for runtime_style in (mr.MDI, mr.MESHLET):
         for flags in (0, mr.UNROLLED_MESH, mr.INDEX_16):
             for po, vo in ((0, 0), (11, 5)):
-                r = subprocess.run([program, str(src), str(runtime_style), str(flags), str(po), str(vo), str(dst)], capture_output=True, text=True, timeout=60)
-                assert r.returncode == 0, r.stderr[-2000:]
+                run_program(program, src, runtime_style, flags, po, vo, dst, timeout=60)
                 raw = np.fromfile(dst, np.uint32)
                 assert np.array_equal(raw[:count * 3].reshape(-1, 3), mr.offsets(counts, runtime_style, flags)), (runtime_style, flags)
                 assert np.array_equal(raw[count * 3:], mr.indirect(counts, runtime_style, po, vo).reshape(-1)), (runtime_style, flags, po, vo)

@@ -5,7 +5,6 @@ restatement GPU tests use beyond the stored cases -- equals the executed shader 
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,8 +12,8 @@ import pytest
 import meshlet_cull_cases as mc
 import meshlet_cull_ref as ref
 from granite_amd import capi
+from host_program import ROOT, c_layout
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "granite_hip.h")).read()
 
 
@@ -56,13 +55,7 @@ def test_the_library_exports_the_entry_point():
 
 def test_the_argument_block_is_the_same_in_c_and_in_ctypes(tmp_path):
     fields = [name for name, _ in capi.MeshletCullArgs._fields_]
-    src = tmp_path / "layout.c"
-    src.write_text('#include "granite_hip.h"\n#include <stdio.h>\n#include <stddef.h>\nint main(void) {\n  printf("%zu\\n", sizeof(gr_meshlet_cull_args));\n' +
-                   "".join(f'  printf("%zu\\n", offsetof(gr_meshlet_cull_args, {f}));\n' for f in fields) + "  return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    got = [int(v) for v in subprocess.check_output([str(exe)], text=True).split()]
-    assert got == [C.sizeof(capi.MeshletCullArgs)] + [getattr(capi.MeshletCullArgs, f).offset for f in fields]
+    assert c_layout(tmp_path, "gr_meshlet_cull_args", fields) == [C.sizeof(capi.MeshletCullArgs)] + [getattr(capi.MeshletCullArgs, f).offset for f in fields]
 
 
 def test_the_host_records_are_the_kernels():

@@ -4,34 +4,15 @@ program, -ffp-contract=off, walking tasks as k_meshlet_cull does) and held to th
 (task_index, first_index), each task's records contiguous and in lane order, occluder words exact, every other dword untouched.
 The program is built plainly and with -fsanitize=address,undefined and run directly (its own main; nothing is preloaded).  The same
 cases run on the device in tests/test_gpu_meshlet_cull.py."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import meshlet_cull_cases as mc
 import meshlet_cull_ref as ref
+from host_program import program_fixtures, run_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCE = os.path.join(ROOT, "tests", "cpp", "meshlet_cull_core_host.cpp")
 GOLDEN = mc.load_golden()
-
-
-def build(tmp, name, flags):
-    exe = tmp / name
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-ffp-contract=off", *flags, "-o", str(exe), SOURCE])
-    return str(exe)
-
-
-@pytest.fixture(scope="module")
-def plain(tmp_path_factory):
-    return build(tmp_path_factory.mktemp("meshlet_cull_core"), "meshlet_cull_core_host", [])
-
-
-@pytest.fixture(scope="module")
-def sanitized(tmp_path_factory):
-    return build(tmp_path_factory.mktemp("meshlet_cull_core_san"), "meshlet_cull_core_host_san", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+plain, sanitized = program_fixtures("meshlet_cull_core_host.cpp", exact=True)
 
 
 def case_bytes(scene, phase, flags):
@@ -43,9 +24,7 @@ def case_bytes(scene, phase, flags):
 
 
 def run(exe, tmp_path, scene, phase, flags):
-    case = tmp_path / "case.bin"
-    case.write_bytes(case_bytes(scene, phase, flags))
-    raw = subprocess.run([exe, str(case)], capture_output=True, check=True).stdout
+    raw = run_program(exe, input_bytes=case_bytes(scene, phase, flags), tmp_path=tmp_path)
     words = np.frombuffer(raw, np.uint32)
     assert len(words) == len(scene["output"]) + len(scene["occluders"])
     return words[:len(scene["output"])], words[len(scene["output"]):]

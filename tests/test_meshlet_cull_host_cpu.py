@@ -15,19 +15,11 @@ import meshlet_cases as files
 import meshlet_cull_cases as mc
 import meshlet_cull_ref as ref
 import meshlet_ref as mr
+from host_program import ROOT, program_fixtures, run_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "granite_amd", "csrc", "host")
-SOURCES = [os.path.join(ROOT, "tests", "cpp", "meshlet_cull_host.cpp"), os.path.join(HOST, "mesh", "meshlet_cull.cpp"), os.path.join(HOST, "mesh", "meshlet.cpp"),
-           os.path.join(HOST, "math.cpp")]
-
-
-@pytest.fixture(scope="module")
-def program(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("meshlet_cull_host") / "meshlet_cull_host"
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", "-o", str(exe), *SOURCES])
-    return str(exe)
+program = program_fixtures(["meshlet_cull_host.cpp", os.path.join(HOST, "mesh", "meshlet_cull.cpp"), os.path.join(HOST, "mesh", "meshlet.cpp"),
+                            os.path.join(HOST, "math.cpp")], extra=["-D__HIP_PLATFORM_AMD__"]).sanitized
 
 
 def camera_words(cam, viewport, cw, hiz, extra=()):
@@ -59,13 +51,13 @@ def test_fill_meshlet_culling_ubo(program, tmp_path, ortho):
                               ((0, 0, 101, 61), False, (64, 32, 5, 0))):
         src, dst = tmp_path / "in.bin", tmp_path / "out.bin"
         src.write_bytes(camera_words(cam, viewport, cw, hiz).tobytes())
-        subprocess.run([program, "ubo", str(src), str(dst)], check=True, timeout=60)
+        run_program(program, "ubo", str(src), str(dst), timeout=60)
         got = np.fromfile(dst, np.uint32)
         assert got.shape == (56,)
         assert np.array_equal(got, expected_ubo(cam, viewport, cw, hiz)), (viewport, cw, hiz)
     # the same block the golden scenes carry
     src.write_bytes(camera_words(cam, (0, 0, 100, 60), False, (64, 32, 5, 1)).tobytes())
-    subprocess.run([program, "ubo", str(src), str(dst)], check=True, timeout=60)
+    run_program(program, "ubo", str(src), str(dst), timeout=60)
     assert np.array_equal(np.fromfile(dst, np.uint32), cam.frustum(mc.chains()["a"]))
 
 
@@ -76,7 +68,7 @@ def test_fill_meshlet_culling_ubo_by_hand(program, tmp_path):
     cam.projection[0, 0], cam.projection[1, 1], cam.projection[0, 3], cam.projection[1, 3], cam.projection[3, 2] = 1.5, -2.0, 0.25, -0.5, -1.0
     src, dst = tmp_path / "in.bin", tmp_path / "out.bin"
     src.write_bytes(camera_words(cam, (10, 20, 1920, 1080), True, (960, 576, 9, 1)).tobytes())
-    subprocess.run([program, "ubo", str(src), str(dst)], check=True, timeout=60)
+    run_program(program, "ubo", str(src), str(dst), timeout=60)
     got = ref.frustum_fields(np.fromfile(dst, np.uint32))
     assert list(got["viewport"]) == [969.5, 559.5, 960.0, 540.0]
     assert list(got["scale_bias"]) == [1440.0, 1080.0, 1200.0, 270.0]
@@ -86,7 +78,7 @@ def test_fill_meshlet_culling_ubo_by_hand(program, tmp_path):
 @pytest.mark.parametrize("count", [0, 1, 32, 33, 96])
 def test_build_task_infos(program, tmp_path, count):
     dst = tmp_path / "tasks.bin"
-    subprocess.run([program, "tasks", "7", "9", "0x123456", "40", "64", str(count), str(dst)], check=True, timeout=60)
+    run_program(program, "tasks", "7", "9", "0x123456", "40", "64", str(count), str(dst), timeout=60)
     got = np.fromfile(dst, np.uint32).reshape(-1, 5)
     want = [[7, 40 + t, 9, 64 + j + (min(count - j, 32) - 1), 0x123456] for t, j in enumerate(range(0, count, 32))]
     assert got.tolist() == want
@@ -108,7 +100,7 @@ def test_place_mesh_chunks(program, tmp_path):
         paths.append(str(path))
         metas.append((np.array(counts, np.int64), mr.parse(path.read_bytes())))
     dst = tmp_path / "place.bin"
-    subprocess.run([program, "place", str(dst), "11", "5", *paths], check=True, timeout=60)
+    run_program(program, "place", str(dst), "11", "5", *paths, timeout=60)
     raw = np.fromfile(dst, np.uint32)
     ranges = raw[:6].reshape(3, 2)
     assert ranges.tolist() == [[0, 1], [32, 2], [64, 5]]
@@ -135,7 +127,7 @@ def test_build_mdi_culling_pass_arguments(program, tmp_path, ortho):
         for force, skinned in ((0, 0), (1, 1), (0, 1)):
             src, dst = tmp_path / "in.bin", tmp_path / "out.bin"
             src.write_bytes(camera_words(cam, (0, 0, 0, 0), False, (128, 32, 6, 1), extra=(phase_enum, force, 200, 40, 8, 4096, 77, 5, 50, skinned)).tobytes())
-            subprocess.run([program, "describe", str(src), str(dst)], check=True, timeout=60)
+            run_program(program, "describe", str(src), str(dst), timeout=60)
             got = np.fromfile(dst, np.uint32)
             flags = (ref.ORTHO if ortho else 0) | (ref.SKINNED if skinned else 0) | (ref.FORCE_VISIBLE if force else 0)
             assert got[:6].tolist() == [phase, flags, 5, 50, 2, 1024]

@@ -5,33 +5,14 @@ which walks groups, meshlets and lanes as the kernel launches them) against the 
 255, offsets past the end and about to wrap, capacities short of what the counts ask for, the payload allocated at exactly
 payload_size_words words.  With the kernel's own clamps the sanitizers stay silent, nothing outside the output arrays changes, and the
 outputs are what tests/meshlet_ref.py gives.  This program is the only place malformed device data is exercised."""
-import os
-import subprocess
-
 import numpy as np
-import pytest
 
 import meshlet_cases as mc
 import meshlet_ref as mr
+from host_program import program_fixtures, run_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCE = os.path.join(ROOT, "tests", "cpp", "meshlet_decode_host.cpp")
 CASES = mc.golden()
-
-
-@pytest.fixture(scope="module")
-def plain(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("meshlet_decode") / "meshlet_decode_host"
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-ffp-contract=off", "-o", str(exe), SOURCE])
-    return str(exe)
-
-
-@pytest.fixture(scope="module")
-def sanitized(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("meshlet_decode_san") / "meshlet_decode_host"
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-o", str(exe), SOURCE])
-    return str(exe)
+plain, sanitized = program_fixtures("meshlet_decode_host.cpp", exact=True)
 
 
 def run(exe, tmp_path, streams, payload, offs, primitive_offset, vertex_offset, target, flags, caps, base_offset=0):
@@ -40,8 +21,7 @@ def run(exe, tmp_path, streams, payload, offs, primitive_offset, vertex_offset, 
     with open(src, "wb") as f:
         for part in (head, streams, payload, offs):
             f.write(np.ascontiguousarray(part, np.uint32).tobytes())
-    r = subprocess.run([exe, src, dst, str(base_offset)], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.returncode, r.stderr[-3000:])
+    run_program(exe, src, dst, base_offset)
     raw, out, at = np.fromfile(dst, np.uint8), {}, 0
     for key, size in (("indices", caps[0] * 3 * mr.index_bytes(flags)), ("positions", caps[1] * 12), ("attributes", caps[1] * 16), ("skin", caps[1] * 8)):
         out[key] = raw[at:at + size]

@@ -3,16 +3,13 @@ ocean shaders executed on the CPU (tests/golden/ocean_shader_v1.npz): generate w
 reference (a tolerance: sin / cos differ between math libraries), bake_maps and mipmap bit for bit.  The same cases run on the device in
 tests/test_gpu_ocean.py."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import ocean_ref as ocr
+from host_program import build_library
 from ocean_cases import BAKE, GENERATE, GOLDEN, MIPMAP, generate_inputs, hermitian_defect
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def ptr(a):
@@ -21,10 +18,7 @@ def ptr(a):
 
 @pytest.fixture(scope="module")
 def host(tmp_path_factory):
-    lib = tmp_path_factory.mktemp("ocean_core") / "libocean_core_host.so"
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-ffp-contract=off", "-shared", "-fPIC", "-o", str(lib),
-                           os.path.join(ROOT, "tests", "cpp", "ocean_core_host.cpp")])
-    return C.CDLL(str(lib))
+    return C.CDLL(build_library(tmp_path_factory.mktemp("ocean_core"), "libocean_core_host.so", "ocean_core_host.cpp", exact=True))
 
 
 @pytest.mark.parametrize("name", GENERATE)

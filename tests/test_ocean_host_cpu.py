@@ -6,38 +6,22 @@ order, and each entry must be that draw times a float64 amplitude * sqrt(phillip
 largest magnitude.  The bound is derived: the chain is about ten fp32 operations, and its worst conditioning is exp(-1 / (kL)^2) at the
 lowest bin, where an argument near 100 turns 1e-7 relative into 1e-5; the absolute term covers fp32 denormals."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCES = [os.path.join(ROOT, "tests", "cpp", "ocean_host.cpp"), os.path.join(ROOT, "granite_amd", "csrc", "host", "ocean_distribution.cpp")]
+from host_program import ROOT, program_fixtures, run_program
+
+plain, sanitized = program_fixtures(["ocean_host.cpp", os.path.join(ROOT, "granite_amd", "csrc", "host", "ocean_distribution.cpp")])
 # fft_resolution, displacement_downsample, grid_count, grid_resolution, ocean_size, wind, heightmap
 CONFIGS = {"small": (128, 1, 4, 32, 128.0, (4.0, 2.0), 1), "default_grid": (128, 1, 64, 128, 1024.0, (4.0, 2.0), 1),
            "plane": (64, 0, 64, 128, 1024.0, (-3.0, 0.5), 0)}
 NORMAL_MOD, AMPLITUDE, G = 7.3, 0.2, 9.81
 
 
-def build(tmp, name, flags):
-    exe = tmp / name
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", *flags, "-o", str(exe), *SOURCES])
-    return str(exe)
-
-
-@pytest.fixture(scope="module")
-def plain(tmp_path_factory):
-    return build(tmp_path_factory.mktemp("ocean_host"), "ocean_host", [])
-
-
-@pytest.fixture(scope="module")
-def sanitized(tmp_path_factory):
-    return build(tmp_path_factory.mktemp("ocean_host_san"), "ocean_host_san", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
-
-
 def run_dist(exe, config):
     n, shift, count, resolution, size, wind, heightmap = config
-    raw = subprocess.check_output([exe, "dist", str(n), str(shift), str(count), str(resolution), repr(size), repr(wind[0]), repr(wind[1]), str(heightmap)])
+    raw = run_program(exe, "dist", n, shift, count, resolution, repr(size), repr(wind[0]), repr(wind[1]), heightmap)
     data = np.frombuffer(raw, np.float32)
     m = n >> shift
     assert data.size == 8 + 2 * (n * n + m * m + n * n)
@@ -71,7 +55,7 @@ def test_distributions(plain, name):
     assert np.allclose(header[:4], [world, world, world / NORMAL_MOD, world / NORMAL_MOD], rtol=1e-6)
     assert np.allclose(header[4:6], np.asarray(wind) / np.hypot(*wind), rtol=1e-6) and np.isclose(header[6], (wind[0] ** 2 + wind[1] ** 2) / G, rtol=1e-6)
     assert np.isclose(header[7], amplitude, rtol=1e-6)
-    draws = np.frombuffer(subprocess.check_output([plain, "draws", str(2 * n * n)]), np.float32)
+    draws = np.frombuffer(run_program(plain, "draws", 2 * n * n), np.float32)
     for got, w, a in ((height, world, amplitude), (normal, world / NORMAL_MOD, amplitude * NORMAL_MOD)):
         want = expected(draws, n, w, a, wind)
         error = np.abs(got.astype(np.float64) - want)
@@ -92,11 +76,11 @@ def test_distributions(plain, name):
 
 
 def test_refusals(plain):
-    assert subprocess.run([plain, "refusals"]).returncode == 0
+    run_program(plain, "refusals")
 
 
 def test_under_address_and_undefined_behaviour_sanitizers(sanitized, plain):
-    assert subprocess.run([sanitized, "refusals"]).returncode == 0
+    run_program(sanitized, "refusals")
     for name in ("small", "plane"):
         a, b = run_dist(sanitized, CONFIGS[name]), run_dist(plain, CONFIGS[name])
         for x, y in zip(a, b):

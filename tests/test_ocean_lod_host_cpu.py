@@ -3,41 +3,25 @@ tests/cpp/ocean_lod_host.cpp, built plainly and once with -fsanitize=address,und
 the push blocks set_camera leads to equal tests/ocean_lod_ref.pass_pushes -- and with it the golden's, which were derived the same way --
 bit for bit, OceanDrawInfo holds the reference's values, the meshes equal the numpy restatement byte for byte, and what must be refused is."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import ocean_lod_ref as olr
+from host_program import ROOT, program_fixtures, run_program
 from ocean_lod_cases import CASES, GOLDEN, spec
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "granite_amd", "csrc", "host")
-SOURCES = [os.path.join(ROOT, "tests", "cpp", "ocean_lod_host.cpp"), os.path.join(HOST, "ocean_lod.cpp"), os.path.join(HOST, "ocean_distribution.cpp")]
-
-
-def build(tmp, name, flags):
-    exe = tmp / name
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__", *flags, "-o", str(exe), *SOURCES])
-    return str(exe)
-
-
-@pytest.fixture(scope="module")
-def plain(tmp_path_factory):
-    return build(tmp_path_factory.mktemp("ocean_lod_host"), "ocean_lod_host", [])
-
-
-@pytest.fixture(scope="module")
-def sanitized(tmp_path_factory):
-    return build(tmp_path_factory.mktemp("ocean_lod_host_san"), "ocean_lod_host_san", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+plain, sanitized = program_fixtures(["ocean_lod_host.cpp", os.path.join(HOST, "ocean_lod.cpp"), os.path.join(HOST, "ocean_distribution.cpp")],
+                                    extra=["-D__HIP_PLATFORM_AMD__"])
 
 
 def state(exe, fft, gc, gr, size, bias, heightmap, fixed, center, camera, planes=None):
-    args = [exe, "state", str(fft), str(gc), str(gr), repr(float(size)), repr(float(bias)), str(int(heightmap)), str(int(fixed)),
+    args = ["state", str(fft), str(gc), str(gr), repr(float(size)), repr(float(bias)), str(int(heightmap)), str(int(fixed)),
             *[repr(float(np.float32(v))) for v in center], *[repr(float(np.float32(v))) for v in camera]]
     if planes is not None:
         args += [repr(float(v)) for v in np.asarray(planes, np.float32).reshape(24)]
-    raw = subprocess.run(args, capture_output=True, check=True).stdout
+    raw = run_program(exe, *args)
     out, at = {}, 0
 
     def take(count, dtype):
@@ -101,11 +85,11 @@ def test_without_a_heightmap_the_plane_grid_and_border_are_built(plain):
 
 
 def test_refusals(plain):
-    assert subprocess.run([plain, "refusals"]).returncode == 0
+    run_program(plain, "refusals")
 
 
 def test_under_address_and_undefined_behaviour_sanitizers(sanitized):
-    assert subprocess.run([sanitized, "refusals"]).returncode == 0
+    run_program(sanitized, "refusals")
     for name in ("lod_g16_negative_perspective_moving", "lod_g4_origin_perspective_fixed", "lod_g64_default_origin_all_moving"):
         check_case(sanitized, name)
     state(sanitized, 128, 64, 128, 1024.0, -3.5, 0, 0, (0, 0, 0), (0, 0, 0))

@@ -3,23 +3,17 @@
 read-modify-write aliasing with InputRelative sizes, and the std::logic_error contract of bake()/validation
 (render_graph.cpp:562-622,2842-2846,3001-3012)."""
 import json
-import os
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "granite_amd", "lib")
+from host_program import PRODUCT, program_fixtures, run_program
+
+program = program_fixtures("graph_cases.cpp", extra=PRODUCT).plain
 
 
 @pytest.fixture(scope="module")
-def cases(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("graph_cases") / "graph_cases")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
-                           os.path.join(ROOT, "tests", "cpp", "graph_cases.cpp"), "-o", exe, "-L" + LIB, "-lgranite_host",
-                           "-lgranite_hip", "-Wl,-rpath," + LIB, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64"])
-    out = subprocess.check_output([exe], text=True)
-    return {c["case"]: c for c in map(json.loads, out.strip().splitlines())}
+def cases(program):
+    return {c["case"]: c for c in map(json.loads, run_program(program).splitlines())}
 
 
 def test_sandbox_topology_bakes_in_declaration_order(cases):
@@ -87,13 +81,8 @@ def test_validation_errors_are_logic_errors_with_the_reference_messages(cases):
 
 # ---- random graphs: invariants of bake() ------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def random_graphs(cases, tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("graph_cases_random") / "graph_cases")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
-                           os.path.join(ROOT, "tests", "cpp", "graph_cases.cpp"), "-o", exe, "-L" + LIB, "-lgranite_host",
-                           "-lgranite_hip", "-Wl,-rpath," + LIB, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib", "-lamdhip64"])
-    out = subprocess.check_output([exe, "--random", "60"], text=True)
-    return list(map(json.loads, out.strip().splitlines()))
+def random_graphs(cases, program):
+    return list(map(json.loads, run_program(program, "--random", 60).splitlines()))
 
 
 def _live_passes(declared):

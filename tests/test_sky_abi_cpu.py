@@ -4,13 +4,12 @@ device (tests/test_gpu_sky.py): they return before a launch."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import pytest
 
 from granite_amd import capi
+from host_program import ROOT, c_layout
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = open(os.path.join(ROOT, "include", "granite_hip.h")).read()
 
 
@@ -33,13 +32,7 @@ def test_the_header_asserts_the_new_structures():
 @pytest.mark.parametrize("c_name, ct", [("gr_sky_args", capi.SkyArgs), ("gr_sky_cube_params", capi.SkyCubeParams)])
 def test_the_structures_are_the_same_in_c_and_in_ctypes(tmp_path, c_name, ct):
     fields = [name for name, _ in ct._fields_]
-    src = tmp_path / "layout.c"
-    src.write_text('#include "granite_hip.h"\n#include <stdio.h>\n#include <stddef.h>\nint main(void) {\n' + f'  printf("%zu\\n", sizeof({c_name}));\n' +
-                   "".join(f'  printf("%zu\\n", offsetof({c_name}, {f}));\n' for f in fields) + "  return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    got = [int(v) for v in subprocess.check_output([str(exe)], text=True).split()]
-    assert got == [C.sizeof(ct)] + [getattr(ct, f).offset for f in fields]
+    assert c_layout(tmp_path, c_name, fields) == [C.sizeof(ct)] + [getattr(ct, f).offset for f in fields]
 
 
 def test_the_kernel_file_is_built_without_contraction():

@@ -7,15 +7,14 @@ for bit, what the reference's own math library gave for the golden's cameras (te
 and the Skybox without a cube pushes the directional light's colour and direction and camera_position.y."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import sky_cases as sc
 from granite_amd import app as gapp, capi
+from host_program import ROOT, c_layout
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = sc.load_golden()
 
 
@@ -34,13 +33,7 @@ def test_the_config_field_and_the_symbols():
 
 
 def test_gra_config_and_gra_config_ext_are_the_same_in_c_and_in_ctypes(tmp_path):
-    src = tmp_path / "layout.c"
-    src.write_text('#include "granite_app.h"\n#include <stdio.h>\n#include <stddef.h>\nint main(void) {\n  printf("%zu %zu %zu %zu %zu\\n", sizeof(gra_config), '
-                   'offsetof(gra_config, volumetric_decals), sizeof(gra_config_ext), offsetof(gra_config_ext, struct_size), offsetof(gra_config_ext, sky));\n'
-                   '  return 0;\n}\n')
-    exe = tmp_path / "layout"
-    subprocess.check_call(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
-    got = [int(v) for v in subprocess.check_output([str(exe)], text=True).split()]
+    got = c_layout(tmp_path, "gra_config", ["volumetric_decals"], "granite_app.h") + c_layout(tmp_path, "gra_config_ext", ["struct_size", "sky"], "granite_app.h")
     assert got == [C.sizeof(gapp.Config), gapp.Config.volumetric_decals.offset, C.sizeof(gapp.ConfigExt), gapp.ConfigExt.struct_size.offset,
                    gapp.ConfigExt.sky.offset]
     assert gapp.Config.volumetric_decals.offset + 4 == C.sizeof(gapp.Config), "volumetric_decals is still the last member"

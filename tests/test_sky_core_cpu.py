@@ -5,42 +5,19 @@ cube colours bit for bit (the runner and the header state one sampler and LOD mo
 pow are involved (measured: 0 on every case -- both sides call the same libm).  The program is built plainly and with
 -fsanitize=address,undefined and run directly (its own main; nothing is preloaded), on the golden's inputs and on hostile ones.  The same
 cases run on the device in tests/test_gpu_sky.py."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import sky_cases as sc
 import sky_ref
+from host_program import program_fixtures, run_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCE = os.path.join(ROOT, "tests", "cpp", "sky_core_host.cpp")
 GOLDEN = sc.load_golden()
-
-
-def build(tmp, name, flags):
-    exe = tmp / name
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-ffp-contract=off", *flags, "-o", str(exe), SOURCE])
-    return str(exe)
-
-
-@pytest.fixture(scope="module")
-def plain(tmp_path_factory):
-    return build(tmp_path_factory.mktemp("sky_core"), "sky_core_host", [])
-
-
-@pytest.fixture(scope="module")
-def sanitized(tmp_path_factory):
-    return build(tmp_path_factory.mktemp("sky_core_san"), "sky_core_host_san", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+plain, sanitized = program_fixtures("sky_core_host.cpp", exact=True)
 
 
 def run(exe, tmp_path, data):
-    case = tmp_path / "case.bin"
-    case.write_bytes(data)
-    r = subprocess.run([exe, str(case)], capture_output=True)
-    assert r.returncode == 0, r.stderr.decode()[-3000:]
-    return r.stdout
+    return run_program(exe, input_bytes=data, tmp_path=tmp_path)
 
 
 def check_apply(exe, tmp_path, name):

@@ -3,40 +3,20 @@
 reference's own compressor and mip filter (tests/golden/texture_encode_v1.npz), byte for byte.  The program is built plainly and with
 -fsanitize=address,undefined and run directly (its own main; nothing is preloaded).  The same cases run on the device in
 tests/test_gpu_texture_encode.py."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import texture_encode_cases as tc
+from host_program import program_fixtures, run_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCE = os.path.join(ROOT, "tests", "cpp", "texture_encode_core_host.cpp")
 GOLDEN = tc.load_golden()
 ENCODE = [(name, fmt) for name, case in tc.ENCODE_CASES.items() for fmt in case[3]]
-
-
-def build(tmp, name, flags):
-    exe = tmp / name
-    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-ffp-contract=off", *flags, "-o", str(exe), SOURCE])
-    return str(exe)
-
-
-@pytest.fixture(scope="module")
-def plain(tmp_path_factory):
-    return build(tmp_path_factory.mktemp("texture_encode_core"), "texture_encode_core_host", [])
-
-
-@pytest.fixture(scope="module")
-def sanitized(tmp_path_factory):
-    return build(tmp_path_factory.mktemp("texture_encode_core_san"), "texture_encode_core_host_san", ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"])
+plain, sanitized = program_fixtures("texture_encode_core_host.cpp", exact=True)
 
 
 def run(exe, tmp_path, words, data):
-    case = tmp_path / "case.bin"
-    case.write_bytes(np.asarray(words, np.uint32).tobytes() + np.ascontiguousarray(data).tobytes())
-    return np.frombuffer(subprocess.run([exe, str(case)], capture_output=True, check=True).stdout, np.uint8)
+    case = np.asarray(words, np.uint32).tobytes() + np.ascontiguousarray(data).tobytes()
+    return np.frombuffer(run_program(exe, input_bytes=case, tmp_path=tmp_path), np.uint8)
 
 
 def check_encode(exe, tmp_path, name, fmt, pad=0):

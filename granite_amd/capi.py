@@ -1317,11 +1317,14 @@ class Context:
         return chain, counter, {"chain_w": cw, "chain_h": ch, "levels": levels}
 
     def ssr_trace(self, chain: DeviceBuffer, layout: dict, pbr: DeviceImage, normal: DeviceImage, light: DeviceImage, dither: DeviceBuffer,
-                  frame: int, view_projection, inv_view_projection, camera_position, stream=None) -> dict:
-        """classify + build_indirect + trace_primary.  Returns the output / ray-length / confidence images and the ray buffers."""
+                  frame: int, view_projection, inv_view_projection, camera_position, stream=None, images: Optional[dict] = None) -> dict:
+        """classify + build_indirect + trace_primary.  Returns the output / ray-length / confidence images and the ray buffers.
+        images: the caller's own "output" (RGBA16F), "ray_length" (R16F) and "confidence" (R8) images, any of them; else fresh tight ones."""
         w, h = light.width, light.height
-        out = {"output": DeviceImage(self, w, h, FORMAT_R16G16B16A16_SFLOAT), "ray_length": DeviceImage(self, w, h, FORMAT_R16_SFLOAT),
-               "confidence": DeviceImage(self, w, h, FORMAT_R8_UNORM), "ray_list": DeviceBuffer(self, w * h * 4),
+        images = images or {}
+        out = {"output": images.get("output") or DeviceImage(self, w, h, FORMAT_R16G16B16A16_SFLOAT),
+               "ray_length": images.get("ray_length") or DeviceImage(self, w, h, FORMAT_R16_SFLOAT),
+               "confidence": images.get("confidence") or DeviceImage(self, w, h, FORMAT_R8_UNORM), "ray_list": DeviceBuffer(self, w * h * 4),
                "ray_counter": DeviceBuffer(self, 4096), "scratch": DeviceBuffer(self, self.lib.gr_ssr_scratch_bytes(w, h))}
         a = SsrArgs()
         a.depth_chain, a.chain_width, a.chain_height, a.chain_levels = chain.ptr, layout["chain_w"], layout["chain_h"], layout["levels"]

@@ -529,6 +529,9 @@ int gr_fxaa_rows(gr_ctx *ctx, gr_stream stream, const gr_image *in, const gr_ima
 	GR_CHECK_ARG(ctx, push);
 	GR_CHECK_IMAGE(ctx, in, GR_RGBA8_FORMATS);
 	GR_CHECK_IMAGE(ctx, out, GR_RGBA8_FORMATS, in->width, in->height);
+	// 32-bit byte offsets inside the kernels
+	GR_CHECK_IMAGE_OFFSETS(ctx, in);
+	GR_CHECK_IMAGE_OFFSETS(ctx, out);
 	GR_CHECK_ARG(ctx, !gr_images_overlap(in, out));
 	const RowSpan span = resolve_rows(rows, in->height);
 	if (span.count() == 0)
@@ -597,6 +600,9 @@ int gr_smaa_edge_detection_rows(gr_ctx *ctx, gr_stream stream, const gr_image *c
 	GR_CHECK_ARG(ctx, quality >= 0 && quality <= 3);
 	GR_CHECK_IMAGE(ctx, color, GR_RGBA8_FORMATS);
 	GR_CHECK_IMAGE(ctx, edges, GR_FORMAT_R8G8_UNORM, color->width, color->height);
+	// 32-bit byte offsets inside the kernels
+	GR_CHECK_IMAGE_OFFSETS(ctx, color);
+	GR_CHECK_IMAGE_OFFSETS(ctx, edges);
 	const RowSpan span = resolve_rows(rows, color->height);
 	if (span.count() == 0)
 		return GR_OK;
@@ -627,6 +633,9 @@ int gr_smaa_blend_weight_rows(gr_ctx *ctx, gr_stream stream, const gr_image *edg
 	GR_CHECK_ARG(ctx, quality >= 0 && quality <= 3);
 	GR_CHECK_IMAGE(ctx, edges, GR_FORMAT_R8G8_UNORM);
 	GR_CHECK_IMAGE(ctx, weights, GR_FORMAT_R8G8B8A8_UNORM, edges->width, edges->height);
+	// 32-bit byte offsets inside the kernels
+	GR_CHECK_IMAGE_OFFSETS(ctx, edges);
+	GR_CHECK_IMAGE_OFFSETS(ctx, weights);
 	if (!ctx->smaa_area || !ctx->smaa_search)
 		return ctx->fail(GR_ERR_INVALID_ARGUMENT, "gr_smaa_blend_weight: SMAA lookup tables not set (gr_smaa_set_luts)");
 	SmaaWeightsArgs S;
@@ -686,6 +695,10 @@ int gr_smaa_neighbor_blend_rows(gr_ctx *ctx, gr_stream stream, const gr_image *c
 	GR_CHECK_IMAGE(ctx, color, GR_RGBA8_FORMATS);
 	GR_CHECK_IMAGE(ctx, weights, GR_FORMAT_R8G8B8A8_UNORM, color->width, color->height);
 	GR_CHECK_IMAGE(ctx, out, GR_RGBA8_FORMATS, color->width, color->height);
+	// 32-bit byte offsets inside the kernels
+	GR_CHECK_IMAGE_OFFSETS(ctx, color);
+	GR_CHECK_IMAGE_OFFSETS(ctx, weights);
+	GR_CHECK_IMAGE_OFFSETS(ctx, out);
 	GR_CHECK_ARG(ctx, !gr_images_overlap(out, color));
 	const RowSpan span = resolve_rows(rows, color->height);
 	if (span.count() == 0)
@@ -740,6 +753,14 @@ int gr_taa_resolve_band(gr_ctx *ctx, gr_stream stream, const gr_image *current, 
 	GR_CHECK_IMAGE(ctx, out_history, GR_FORMAT_R16G16B16A16_SFLOAT, w, h);
 	if (history)
 		GR_CHECK_IMAGE(ctx, history, GR_FORMAT_R16G16B16A16_SFLOAT, w, h);
+	// 32-bit byte offsets inside the kernels
+	GR_CHECK_IMAGE_OFFSETS(ctx, current);
+	GR_CHECK_IMAGE_OFFSETS(ctx, depth);
+	GR_CHECK_IMAGE_OFFSETS(ctx, mv);
+	GR_CHECK_IMAGE_OFFSETS(ctx, out_color);
+	GR_CHECK_IMAGE_OFFSETS(ctx, out_history);
+	if (history)
+		GR_CHECK_IMAGE_OFFSETS(ctx, history);
 	GR_CHECK_ARG(ctx, !history || !gr_images_overlap(history, out_history));
 	const bool current_b10 = current->format == GR_FORMAT_B10G11R11_UFLOAT_PACK32, color_b10 = out_color->format == GR_FORMAT_B10G11R11_UFLOAT_PACK32;
 	const RowSpan span = resolve_rows(rows, h);
@@ -797,6 +818,9 @@ int gr_blit(gr_ctx *ctx, gr_stream stream, const gr_image *in, const gr_image *o
 	constexpr gr_format_set supported{GR_FORMAT_R16G16B16A16_SFLOAT, GR_FORMAT_R8G8B8A8_SRGB, GR_FORMAT_R8G8B8A8_UNORM};
 	GR_CHECK_IMAGE(ctx, in, supported);
 	GR_CHECK_IMAGE(ctx, out, supported);
+	// 32-bit byte offsets of the RGBA8 texels inside the kernel
+	GR_CHECK_IMAGE_OFFSETS(ctx, in);
+	GR_CHECK_IMAGE_OFFSETS(ctx, out);
 	GR_CHECK_ARG(ctx, !gr_images_overlap(in, out));
 	BlitArgs a = {};
 	a.in = to_dev(in);

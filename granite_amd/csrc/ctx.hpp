@@ -179,7 +179,15 @@ struct gr_scoped_timing
 			return (ctx)->fail(GR_ERR_INVALID_ARGUMENT, "%s: invalid argument: %s%s", __func__, &#img[#img[0] == '&'], rule__); \
 	} while (0)
 
-#define GR_CHECK_HIP(ctx, expr)                                                                        \
+// ... and, behind it, against gr_image_offset_rule where the launcher's kernels form byte offsets in 32 bits.
+#define GR_CHECK_IMAGE_OFFSETS(ctx, img)                                                                       \
+	do                                                                                                         \
+	{                                                                                                          \
+		if (const char *rule__ = gr_image_offset_rule(img))                                                    \
+			return (ctx)->fail(GR_ERR_INVALID_ARGUMENT, "%s: invalid argument: %s%s", __func__, &#img[#img[0] == '&'], rule__); \
+	} while (0)
+
+#define GR_CHECK_HIP(ctx, expr)                                                                       \
 	do                                                                                                 \
 	{                                                                                                  \
 		hipError_t err__ = (expr);                                                                     \

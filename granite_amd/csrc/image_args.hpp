@@ -75,6 +75,13 @@ static inline const char *gr_image_rule(const gr_image *img, gr_format_set forma
 	return nullptr;
 }
 
+// A limit of single launchers (lighting.hip, aa.hip), asked after gr_image_rule: their kernels form `y * pitch_bytes + x * texel` in 32 bits, so
+// the image's last byte has to lie within 4 GiB of ptr.  An attachment viewed out of a larger allocation counts with the pitch it is viewed at.
+static inline const char *gr_image_offset_rule(const gr_image *img)
+{
+	return uint64_t(img->pitch_bytes) * img->height > 0xffffffffull ? " pitch_bytes * height is above 4 GiB - 1: this launcher's kernels form byte offsets in 32 bits" : nullptr;
+}
+
 // Two byte ranges share at least one byte.  An empty range shares none.
 static inline bool gr_images_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
 {

@@ -1146,8 +1146,14 @@ int gr_lighting(gr_ctx *ctx, gr_stream stream, const gr_lighting_args *args)
 	const RowSpan span = resolve_rows(args->rows.count ? &args->rows : nullptr, H); // {0, 0} = the whole image (granite_hip.h: gr_rows)
 	if (span.count() == 0)
 		return GR_OK;
-	// 32-bit byte offsets inside the kernel.
-	GR_CHECK_ARG(ctx, uint64_t(args->hdr.pitch_bytes) * H <= 0xffffffffull && uint64_t(args->emissive.pitch_bytes) * H <= 0xffffffffull);
+	// 32-bit byte offsets inside the kernel (load_raw, the store of shade_tile), for each of the six attachments at its own pitch.  (The
+	// ambient-occlusion image is addressed in 64 bits.)
+	GR_CHECK_IMAGE_OFFSETS(ctx, &args->hdr);
+	GR_CHECK_IMAGE_OFFSETS(ctx, &args->emissive);
+	GR_CHECK_IMAGE_OFFSETS(ctx, &args->albedo);
+	GR_CHECK_IMAGE_OFFSETS(ctx, &args->normal);
+	GR_CHECK_IMAGE_OFFSETS(ctx, &args->pbr);
+	GR_CHECK_IMAGE_OFFSETS(ctx, &args->depth);
 
 	KernelArgs k = fill_kernel_args(args, ctx, clustered);
 	k.row_first = int(span.first);

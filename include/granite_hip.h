@@ -111,7 +111,12 @@ typedef enum gr_format
  * and gr_texture_decode address bytes and take any alignment).  A broken rule is GR_ERR_INVALID_ARGUMENT, with the argument and the rule in
  * gr_last_error(); a wrong format alone is GR_ERR_UNSUPPORTED_FORMAT from gr_tonemap, gr_fft_execute, gr_env_equirect_to_cube and
  * gr_texture_decode.  Where an entry point refuses an output that is its input, it refuses any shared byte of [ptr, ptr + pitch_bytes *
- * height).  Limits of a single kernel (a largest extent, 16-byte alignment for a faster path) are documented at its entry point. */
+ * height).  Limits of a single kernel (a largest extent, 16-byte alignment for a faster path) are documented at its entry point.
+ * A pitch wider than the row and a pointer into a larger allocation are taken by every launcher (rows padded to 256 bytes, views
+ * into an atlas); where a kernel's form is chosen by alignment they may select the slower one (tests/test_gpu_image_layouts.py holds every
+ * form to the same reference).  gr_lighting, gr_blit
+ * and the anti-aliasing launchers (FXAA, SMAA, TAA) form byte offsets in 32 bits and refuse, in the same way, an image argument with
+ * pitch_bytes * height above 2^32 - 1; the other launchers form them in 64 bits and have no such limit. */
 typedef struct gr_image
 {
 	void *ptr;            /* device pointer */
@@ -531,6 +536,9 @@ typedef struct gr_lighting_args
 	float fog_color[3];
 	float fog_falloff;
 } gr_lighting_args;
+/* Two pixels per lane where the width is even and pitch and ptr of every attachment are multiples of two texels, else one pixel per lane.
+ * The kernel forms byte offsets in 32 bits: each of hdr, emissive, albedo, normal, pbr and depth with
+ * pitch_bytes * height above 2^32 - 1 is refused with GR_ERR_INVALID_ARGUMENT and its name (ambient_occlusion has no such limit). */
 int gr_lighting(gr_ctx *ctx, gr_stream stream, const gr_lighting_args *args);
 
 /* 24-bit transport form of an RGBA8 target whose alpha byte is 255 everywhere (a tonemapped frame): the row-band executor
@@ -543,10 +551,14 @@ int gr_unpack_rgb8_rows(gr_ctx *ctx, gr_stream stream, const void *packed, const
 /* builtin://shaders/blit.frag over a full-screen quad (FragColor = textureLod(uTex, vUV, 0)): the copy between targets of
  * different size / format that Granite's tools record (tools/aa_bench.cpp:97-105 into the HDR target with LinearClamp,
  * :138-147 into the swapchain with NearestClamp).  in / out: R16G16B16A16_SFLOAT, R8G8B8A8_UNORM or R8G8B8A8_SRGB (decoded on
- * the fetch / encoded by the store, as the image views would); linear != 0 = StockSampler::LinearClamp, else NearestClamp. */
+ * the fetch / encoded by the store, as the image views would); linear != 0 = StockSampler::LinearClamp, else NearestClamp.
+ * 32-bit byte offsets: `in` or `out` with pitch_bytes * height above 2^32 - 1 is refused (GR_ERR_INVALID_ARGUMENT, by name). */
 int gr_blit(gr_ctx *ctx, gr_stream stream, const gr_image *in, const gr_image *out, int linear);
 
-/* ---- anti-aliasing (renderer/post/{fxaa,smaa,temporal}.cpp) ------------------------------------------------------------ */
+/* ---- anti-aliasing (renderer/post/{fxaa,smaa,temporal}.cpp) ------------------------------------------------------------
+ * The kernels of every launcher of this section (gr_fxaa, gr_smaa_edge_detection, gr_smaa_blend_weight, gr_smaa_neighbor_blend,
+ * gr_taa_resolve and their *_rows / *_band forms) form byte offsets in 32 bits: any image argument with pitch_bytes * height above
+ * 2^32 - 1 is refused with GR_ERR_INVALID_ARGUMENT and its name, before anything is launched. */
 
 /* setup_fxaa_postprocess (fxaa.cpp:28-55) + fxaa.frag.  `in` is read through its UNORM alias (cmd.set_unorm_texture):
  * the stored bytes of the tonemapped R8G8B8A8_SRGB image.  out: R8G8B8A8_SRGB or _UNORM (same bytes either way: the
@@ -573,7 +585,8 @@ int gr_smaa_edge_detection(gr_ctx *ctx, gr_stream stream, const gr_image *color,
 /* smaa-weights pass: SMAABlendingWeightCalculationPS, SMAA_SUBPIXEL_MODE 0.  weights: R8G8B8A8_UNORM.  The reference's
  * D16 "smaa-mask" depth-EQUAL test is equivalent to "edge texel != 0", which is what the kernel tests. */
 int gr_smaa_blend_weight(gr_ctx *ctx, gr_stream stream, const gr_image *edges, const gr_image *weights, const gr_push_smaa *push, int quality);
-/* smaa-blend pass: SMAANeighborhoodBlendingPS. */
+/* smaa-blend pass: SMAANeighborhoodBlendingPS.  Four pixels per lane where the width is a multiple of 4 and pitch and ptr of all three
+ * images are multiples of 16 bytes, else one. */
 int gr_smaa_neighbor_blend(gr_ctx *ctx, gr_stream stream, const gr_image *color, const gr_image *weights, const gr_image *out,
                            const gr_push_smaa *push);
 int gr_smaa_edge_detection_rows(gr_ctx *ctx, gr_stream stream, const gr_image *color, const gr_image *edges, const gr_push_smaa *push,

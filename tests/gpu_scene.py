@@ -116,21 +116,25 @@ class Scene:
             gr.check(lib.gr_free_host(h, ptr))
         return {"transforms": transforms, "spots": spots, "setup": setup, "bitmask": bitmask, "range": ranges, "zr": zr, "zr_buf": zr_buf}
 
-    def lighting_args(self, gr, dev, flags, alias_emissive=True):
+    def lighting_args(self, gr, dev, flags, alias_emissive=True, make_image=None):
+        """make_image(width, height, format, role, name) builds each attachment (tests/layout_images.py: Factory; role "in", "out" or
+        "rmw"); by default a tight capi.DeviceImage."""
         w, h = self.w, self.h
+        if make_image is None:
+            make_image = lambda iw, ih, fmt, role, name: capi.DeviceImage(gr, iw, ih, fmt)
         imgs = {
-            "albedo": capi.DeviceImage(gr, w, h, capi.FORMAT_R8G8B8A8_SRGB).upload(self.gbuf["albedo"]),
-            "normal": capi.DeviceImage(gr, w, h, capi.FORMAT_A2B10G10R10_UNORM_PACK32).upload(self.gbuf["normal"]),
-            "pbr": capi.DeviceImage(gr, w, h, capi.FORMAT_R8G8_UNORM).upload(self.gbuf["pbr"]),
-            "depth": capi.DeviceImage(gr, w, h, capi.FORMAT_D32_SFLOAT).upload(self.gbuf["depth"]),
-            "hdr": capi.DeviceImage(gr, w, h, capi.FORMAT_R16G16B16A16_SFLOAT).upload(self.gbuf["emissive"]),
+            "albedo": make_image(w, h, capi.FORMAT_R8G8B8A8_SRGB, "in", "albedo").upload(self.gbuf["albedo"]),
+            "normal": make_image(w, h, capi.FORMAT_A2B10G10R10_UNORM_PACK32, "in", "normal").upload(self.gbuf["normal"]),
+            "pbr": make_image(w, h, capi.FORMAT_R8G8_UNORM, "in", "pbr").upload(self.gbuf["pbr"]),
+            "depth": make_image(w, h, capi.FORMAT_D32_SFLOAT, "in", "depth").upload(self.gbuf["depth"]),
+            "hdr": make_image(w, h, capi.FORMAT_R16G16B16A16_SFLOAT, "rmw" if alias_emissive else "out", "hdr").upload(self.gbuf["emissive"]),
         }
         a = capi.LightingArgs()
         a.albedo, a.normal, a.pbr, a.depth, a.hdr = (imgs[k].desc for k in ("albedo", "normal", "pbr", "depth", "hdr"))
         if alias_emissive:
             a.emissive = imgs["hdr"].desc  # reference semantics: blend read-modify-write on one attachment
         else:
-            imgs["emissive"] = capi.DeviceImage(gr, w, h, capi.FORMAT_R16G16B16A16_SFLOAT).upload(self.gbuf["emissive"])
+            imgs["emissive"] = make_image(w, h, capi.FORMAT_R16G16B16A16_SFLOAT, "in", "emissive").upload(self.gbuf["emissive"])
             imgs["hdr"].upload(np.full_like(self.gbuf["emissive"], 0x7e00))  # NaN-fill: every pixel must be written
             a.emissive = imgs["emissive"].desc
         a.inv_view_projection[:] = self.rp[80:96]

@@ -53,6 +53,12 @@ def install_ssr_tables():
         raise capi.GraniteHipError("gra_install_ssr_tables failed")
 
 
+class DirectionalShadows(C.Structure):
+    """gra_directional_shadows: the directional light's shadow map and its transforms (Application.set_directional_shadows)."""
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_uint32), ("layers", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("format", C.c_uint32), ("texels", C.c_void_p), ("transforms", (C.c_float * 16) * 4), ("cascade_log_bias", C.c_float), ("pad0", C.c_uint32)]
+
+
 class FrameState(C.Structure):
     """gra_frame_state: the host-side state a frame inherits (checkpoint / replay)."""
     _fields_ = [("frames", C.c_uint64), ("elapsed", C.c_double), ("swapchain_index", C.c_uint32), ("jitter_phase", C.c_uint32),
@@ -149,7 +155,7 @@ EXPORTED_SYMBOLS = [
     "gra_ocean_default_config", "gra_ocean_create", "gra_ocean_update", "gra_ocean_describe", "gra_ocean_read", "gra_ocean_distribution",
     "gra_ocean_parameters", "gra_ocean_destroy", "gra_ocean_set_camera", "gra_ocean_draw_info", "gra_ocean_mesh_describe", "gra_ocean_mesh_read",
     "gra_meshlet_describe", "gra_meshlet_decode", "gra_set_decal_texture", "gra_set_decals", "gra_get_decal_state",
-    "gra_set_sky_cube", "gra_set_sky_cube_gtx", "gra_get_sky_state", "gra_create_ext",
+    "gra_set_sky_cube", "gra_set_sky_cube_gtx", "gra_get_sky_state", "gra_create_ext", "gra_set_directional_shadows",
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -221,6 +227,7 @@ def load_library() -> C.CDLL:
         "gra_generate_mipmaps": (C.c_int, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]),
         "gra_set_directional_light": (C.c_int, [vp, vp, vp]),
         "gra_set_fog": (C.c_int, [vp, vp, C.c_float]),
+        "gra_set_directional_shadows": (C.c_int, [vp, P(DirectionalShadows)]),
         "gra_write_resource": (C.c_int, [vp, C.c_char_p, vp, C.c_uint64]),
         "gra_get_frame_state": (C.c_int, [vp, P(FrameState)]),
         "gra_set_frame_state": (C.c_int, [vp, P(FrameState)]),
@@ -686,6 +693,30 @@ class Application:
     def set_directional(self, direction, color):
         d, c = np.asarray(direction, np.float32), np.asarray(color, np.float32)
         self._check(self.lib.gra_set_directional_light(self.handle, d.ctypes.data, c.ctypes.data))
+
+    def set_directional_shadows(self, maps, mode: int = 0, transforms=None, cascade_log_bias: float = 0.0):
+        """LightingParameters::shadows / ::shadow: the directional light's shadow map, (layers, height, width) uint16 (D16_UNORM) or float32
+        (D32_SFLOAT), or (layers, height, width, 2) float32 moments with capi.SHADOW_VSM; layers 1 or 4.  `transforms`: (4, 16) column-major
+        world -> (u, v, z).  A depth map with SHADOW_VSM runs the VSM chain on upload.  maps=None switches shadows off."""
+        if maps is None or not mode:
+            self._check(self.lib.gra_set_directional_shadows(self.handle, None))
+            return
+        maps = np.ascontiguousarray(maps)
+        if maps.ndim == 4 and maps.shape[3] == 2 and maps.dtype == np.float32:
+            fmt = capi.FORMAT_R32G32_SFLOAT
+        elif maps.ndim == 3 and maps.dtype in (np.uint16, np.float32):
+            fmt = capi.FORMAT_D16_UNORM if maps.dtype == np.uint16 else capi.FORMAT_D32_SFLOAT
+        else:
+            raise ValueError("maps: (layers, height, width) uint16 or float32, or (layers, height, width, 2) float32")
+        desc = DirectionalShadows()
+        desc.struct_size = C.sizeof(DirectionalShadows)
+        desc.mode, desc.layers, desc.height, desc.width, desc.format = int(mode), maps.shape[0], maps.shape[1], maps.shape[2], fmt
+        desc.texels = maps.ctypes.data
+        flat = np.ascontiguousarray(transforms, np.float32).reshape(4, 16)
+        for i in range(4):
+            desc.transforms[i][:] = [float(v) for v in flat[i]]
+        desc.cascade_log_bias = float(cascade_log_bias)
+        self._check(self.lib.gra_set_directional_shadows(self.handle, C.byref(desc)))
 
     def set_fog(self, color, falloff: float):
         """LightingParameters::fog: render_light's fog quad (renderer.cpp:1179-1196) when falloff > 0."""

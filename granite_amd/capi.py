@@ -527,6 +527,21 @@ class LightingArgs(C.Structure):
                 ("fog_color", C.c_float * 3), ("fog_falloff", C.c_float)]
 
 
+SHADOW_PCF, SHADOW_PCF_WIDE, SHADOW_VSM = 1, 2, 3
+SHADOW_NUM_CASCADES = 4
+
+
+class DirectionalLightArgs(C.Structure):
+    """gr_directional_light_args: the shadowed directional quad; layers 1 (transforms[0] alone) or 4 (SHADOW_CASCADES)."""
+    _fields_ = [("albedo", Image), ("normal", Image), ("pbr", Image), ("depth", Image), ("emissive", Image), ("hdr", Image),
+                ("inv_view_projection", C.c_float * 16), ("directional", PushDirectional), ("flags", C.c_uint32), ("mode", C.c_uint32),
+                ("layers", C.c_uint32), ("pad0", C.c_uint32), ("ambient_occlusion", Image), ("shadow_maps", Image * SHADOW_NUM_CASCADES),
+                ("transforms", (C.c_float * 16) * SHADOW_NUM_CASCADES)]
+
+
+assert C.sizeof(DirectionalLightArgs) == 696
+
+
 class Rows(C.Structure):
     """gr_rows: render area of one launch, output rows [first, first + count).  Passed by pointer: None (NULL) = the whole image,
     count == 0 = NO rows (the launcher returns GR_OK without launching: an empty band must not touch the image).  The one embedded
@@ -714,6 +729,9 @@ def load_library() -> C.CDLL:
         "gr_decal_apply": (C.c_int, [vp, vp, P(DecalApplyArgs)]),
         "gr_sky_apply": (C.c_int, [vp, vp, P(SkyArgs)]),
         "gr_sky_cube": (C.c_int, [vp, vp, vp, C.c_uint32, P(SkyCubeParams)]),
+        "gr_directional_light": (C.c_int, [vp, vp, P(DirectionalLightArgs)]),
+        "gr_vsm_moments": (C.c_int, [vp, vp, P(Image), P(Image)]),
+        "gr_vsm_blur": (C.c_int, [vp, vp, P(Image), P(Image), C.c_int]),
         "gr_cacao_reference_settings": (None, [P(CacaoSettings)]),
         "gr_cacao_update_buffer_sizes": (C.c_int, [C.c_uint32, C.c_uint32, P(CacaoBufferSizes)]),
         "gr_cacao_update_constants": (C.c_int, [vp, P(CacaoConstants), P(CacaoSettings), P(CacaoBufferSizes), P(C.c_float), P(C.c_float)]),
@@ -755,6 +773,7 @@ EXPORTED_SYMBOLS = [
     "gr_fft_describe", "gr_fft_plan_create", "gr_fft_plan_destroy", "gr_fft_plan_iterations", "gr_fft_execute", "gr_fft_execute_iteration",
     "gr_ocean_generate_fft", "gr_ocean_bake_maps", "gr_ocean_mipmap", "gr_ocean_update_lod", "gr_ocean_init_counter_buffer", "gr_ocean_cull_blocks",
     "gr_meshlet_decode", "gr_meshlet_cull", "gr_cluster_binning_decal", "gr_decal_apply", "gr_sky_apply", "gr_sky_cube",
+    "gr_directional_light", "gr_vsm_moments", "gr_vsm_blur",
     "gr_cacao_reference_settings", "gr_cacao_update_buffer_sizes", "gr_cacao_update_constants", "gr_cacao_workspace_bytes", "gr_cacao_workspace_describe",
     "gr_cacao_prepare_depths", "gr_cacao_prepare_normals", "gr_cacao_generate_base", "gr_cacao_importance_generate",
     "gr_cacao_importance_postprocess_a", "gr_cacao_importance_postprocess_b", "gr_cacao_generate", "gr_cacao_blur", "gr_cacao_apply",
@@ -1174,6 +1193,19 @@ class Context:
         assert out.nbytes >= self.lib.gr_cube_chain_bytes(size, 1) or not (0 < size <= 16384), (out.nbytes, size)
         params = SkyCubeParams((C.c_float * 3)(*[float(v) for v in sun_color]), float(camera_y), (C.c_float * 3)(*[float(v) for v in sun_direction]), 0.0)
         self.check(self.lib.gr_sky_cube(self.handle, stream, out.ptr, int(size), C.byref(params)))
+
+    # ---- directional-light shadows ---------------------------------------------------------------------------------------------------
+    def directional_light(self, args: DirectionalLightArgs, stream=None):
+        """gr_directional_light: hdr = rne16(emissive + the shadowed directional light [+ the ambient fallback]) where depth != 0."""
+        self.check(self.lib.gr_directional_light(self.handle, stream, C.byref(args)))
+
+    def vsm_moments(self, depth, moments, stream=None):
+        """gr_vsm_moments: (z, z * z) of a D16_UNORM or D32_SFLOAT map into an R32G32_SFLOAT image of its size."""
+        self.check(self.lib.gr_vsm_moments(self.handle, stream, depth.desc, moments.desc))
+
+    def vsm_blur(self, src, out, up: bool, stream=None):
+        """gr_vsm_blur: the nine-tap down (taps at +-1.75 texels of src) or up (+-0.875) blur of one layer of moments."""
+        self.check(self.lib.gr_vsm_blur(self.handle, stream, src.desc, out.desc, int(bool(up))))
 
     # ---- FFT: a plan owns its scratch and twiddles and may be in flight on one stream at a time ---------------------------------
     def fft_plan(self, options: FftOptions):

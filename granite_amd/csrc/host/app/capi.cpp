@@ -1368,6 +1368,11 @@ int gra_set_directional_light(gra_app *app, const float direction[3], const floa
 	return 0;
 }
 
+int gra_set_directional_shadows(gra_app *app, const gra_directional_shadows *desc)
+{
+	return guarded(app, [&]() { app->app->set_directional_shadows(desc); });
+}
+
 int gra_set_fog(gra_app *app, const float color[3], float falloff)
 {
 	if (!app)

@@ -5,6 +5,7 @@
 #include "../timeline_trace.hpp"
 #include <hip/hip_runtime_api.h>
 #include "../gtx.hpp"
+#include "../lights/shadow.hpp"
 #include "../post/spd.hpp"
 #include "../post/ssao.hpp"
 #include "../post/ssr.hpp"
@@ -1089,6 +1090,81 @@ void ImageSpaceApplication::set_fog(const float color[3], float falloff)
 {
 	lighting.fog.color = vec3(color[0], color[1], color[2]);
 	lighting.fog.falloff = falloff;
+}
+
+void ImageSpaceApplication::set_directional_shadows(const gra_directional_shadows *desc)
+{
+	const char *fn = "gra_set_directional_shadows: ";
+	if (!config.enable_lighting)
+		throw std::logic_error(std::string(fn) + "this application was created without lighting (enable_lighting).");
+	if (config.aa_bench)
+		throw std::logic_error(std::string(fn) + "the aa_bench graph has no lighting pass.");
+	if (config.strip_count > 1)
+		throw std::logic_error(std::string(fn) + "strip_count > 1: the shadowed directional light does not render row bands.");
+	if (config.hdr_packed_float)
+		throw std::logic_error(std::string(fn) + "hdr_packed_float: the shadowed directional light is built for R16G16B16A16_SFLOAT targets only.");
+	auto &device = get_device();
+	if (!desc || desc->mode == 0)
+	{
+		device.wait_idle(); // a frame in flight may still read the layers
+		lighting.shadows = {};
+		lighting.shadow = {};
+		for (auto &layer : shadow_layers)
+			layer.reset();
+		return;
+	}
+	if (desc->struct_size != sizeof(gra_directional_shadows))
+		throw std::logic_error(std::string(fn) + "struct_size is not sizeof(gra_directional_shadows).");
+	if (desc->mode != GR_SHADOW_PCF && desc->mode != GR_SHADOW_PCF_WIDE && desc->mode != GR_SHADOW_VSM)
+		throw std::logic_error(std::string(fn) + "mode must be 0, GR_SHADOW_PCF (1), GR_SHADOW_PCF_WIDE (2) or GR_SHADOW_VSM (3).");
+	if (desc->layers != 1 && desc->layers != NumShadowCascades)
+		throw std::logic_error(std::string(fn) + "layers must be 1 or 4.");
+	const bool depth_format = desc->format == GR_FORMAT_D16_UNORM || desc->format == GR_FORMAT_D32_SFLOAT;
+	if (!depth_format && !(desc->mode == GR_SHADOW_VSM && desc->format == GR_FORMAT_R32G32_SFLOAT))
+		throw std::logic_error(std::string(fn) + "format does not fit the mode: D16_UNORM or D32_SFLOAT, with GR_SHADOW_VSM also R32G32_SFLOAT.");
+	if (!desc->width || !desc->height || desc->width > GR_SHADOW_MAX_EXTENT || desc->height > GR_SHADOW_MAX_EXTENT)
+		throw std::logic_error(std::string(fn) + "width and height must be 1 .. 16384.");
+	if (!desc->texels)
+		throw std::logic_error(std::string(fn) + "null texels.");
+
+	device.wait_idle(); // a frame in flight may still read the layers these replace
+	gr_ctx *ctx = device.get_context();
+	auto check = [&](int status) {
+		if (status < 0)
+			throw std::runtime_error(gr_last_error(ctx));
+	};
+	const bool run_chain = desc->mode == GR_SHADOW_VSM && depth_format;
+	HIP::ImageHandle uploaded[NumShadowCascades], raw[NumShadowCascades], half[NumShadowCascades], result[NumShadowCascades];
+	VsmChainLayer chain[NumShadowCascades] = {};
+	for (unsigned i = 0; i < desc->layers; i++)
+	{
+		uploaded[i] = device.create_image(desc->width, desc->height, VkFormat(desc->format), "directional-shadow-" + std::to_string(i));
+		const size_t bytes = uploaded[i]->get_size_bytes();
+		check(gr_upload(ctx, nullptr, uploaded[i]->get_device_pointer(), static_cast<const uint8_t *>(desc->texels) + i * bytes, bytes));
+		result[i] = uploaded[i];
+		if (run_chain)
+		{
+			// "shadow-raw", "shadow-down" and "shadow" of the viewer's graph (host/lights/shadow.hpp)
+			raw[i] = device.create_image(desc->width, desc->height, VK_FORMAT_R32G32_SFLOAT, "shadow-raw-" + std::to_string(i));
+			half[i] = device.create_image(vsm_half_size(desc->width), vsm_half_size(desc->height), VK_FORMAT_R32G32_SFLOAT, "shadow-down-" + std::to_string(i));
+			result[i] = device.create_image(desc->width, desc->height, VK_FORMAT_R32G32_SFLOAT, "shadow-" + std::to_string(i));
+			chain[i] = {uploaded[i].get(), raw[i].get(), half[i].get(), result[i].get()};
+		}
+	}
+	if (run_chain)
+		setup_vsm_chain(ctx, nullptr, chain, desc->layers);
+	check(gr_sync(ctx, nullptr));
+
+	lighting.shadows = {};
+	lighting.shadows.mode = desc->mode;
+	lighting.shadows.num_layers = desc->layers;
+	for (unsigned i = 0; i < NumShadowCascades; i++)
+	{
+		shadow_layers[i] = i < desc->layers ? result[i] : HIP::ImageHandle();
+		lighting.shadows.layers[i] = shadow_layers[i].get();
+		memcpy(lighting.shadow.transforms[i].data(), desc->transforms[i], sizeof(desc->transforms[i]));
+	}
+	lighting.shadow.cascade_log_bias = desc->cascade_log_bias;
 }
 
 // A fresh application has no physical resources before its first frame: bake and allocate them now, so that inherited state can be

@@ -63,6 +63,8 @@ public:
 	// DirectionalLightComponent of the scene (read_lights, scene_viewer_application.cpp:58-77); direction need not be normalised.
 	void set_directional_light(const float direction[3], const float color[3]);
 	void set_fog(const float color[3], float falloff);
+	// gra_set_directional_shadows: nullptr or mode 0 switches shadows off
+	void set_directional_shadows(const gra_directional_shadows *desc);
 	// checkpoint / replay (include/granite_app.h: gra_write_resource, gra_frame_state)
 	void prepare_resources_for_write();
 	void get_frame_state(gra_frame_state &state) const;
@@ -170,6 +172,8 @@ private:
 	// The scene's background (ext.sky): the atmosphere lit by the directional light, or the cube of set_sky_cube.
 	Skybox skybox;
 	HIP::ImageHandle src_emissive, src_albedo, src_normal, src_pbr, src_depth, src_mv, src_ao;
+	// the directional light's shadow map as the lighting pass reads it (lighting.shadows points at these), one image per layer
+	HIP::ImageHandle shadow_layers[NumShadowCascades];
 	// scene_viewer_application.cpp:881-883: renderTargetFp16 ? R16G16B16A16_SFLOAT : B10G11R11_UFLOAT_PACK32
 	VkFormat hdr_target_format() const { return config.hdr_packed_float ? VK_FORMAT_B10G11R11_UFLOAT_PACK32 : VK_FORMAT_R16G16B16A16_SFLOAT; }
 	vec3 camera_motion = vec3(0.0f); // eye translation per frame (world units)

@@ -51,10 +51,31 @@ struct FogParameters
 	float falloff = 0.0f;
 };
 
+constexpr unsigned NumShadowCascades = 4;
+
+// LightingParameters::shadow (renderer/lights/lights.hpp): world -> (u, v, z) of each cascade, and the bias of log2(view_z).
+struct ShadowParameters
+{
+	mat4 transforms[NumShadowCascades];
+	float cascade_log_bias = 0.0f;
+};
+
+// LightingParameters::shadows: the directional light's shadow map.  The reference binds one (array) image view and chooses the lookup by
+// shader defines; here the view's layers, their count (1, or NumShadowCascades for SHADOW_CASCADES) and the lookup (GR_SHADOW_*; 0 = no
+// shadows, which is render_light's unshadowed path).
+struct DirectionalShadows
+{
+	const HIP::ImageView *layers[NumShadowCascades] = {};
+	unsigned num_layers = 0;
+	uint32_t mode = 0;
+};
+
 struct LightingParameters
 {
 	FogParameters fog;
 	DirectionalParameters directional;
+	ShadowParameters shadow;
+	DirectionalShadows shadows;
 	LightClusterer *cluster = nullptr;
 	// LightingParameters::ambient_occlusion (renderer/lights/lights.hpp): the SSAO result the deferred lighting pass
 	// samples, or null.  Set every frame from the graph's physical resource (scene_viewer_application.cpp:1571).

@@ -96,6 +96,30 @@ void DeferredLightRenderer::render_light(HIP::CommandBuffer &cmd, const RenderCo
 		args.rows.first = att.rows->first;
 		args.rows.count = att.rows->count;
 	}
+	if (light->shadows.mode != 0)
+	{
+		// SHADOWS (renderer.cpp:1015-1105): the directional quad is a launch of its own, and the lighting kernel draws the rest in place
+		// on what it left -- rne16(rne16(emissive + directional) + clustered), the reference's two blends.
+		if (args.rows.count != 0)
+			throw std::logic_error("render_light: the shadowed directional light does not render row bands.");
+		gr_directional_light_args shadowed = {};
+		shadowed.albedo = args.albedo, shadowed.normal = args.normal, shadowed.pbr = args.pbr, shadowed.depth = args.depth;
+		shadowed.emissive = args.emissive, shadowed.hdr = args.hdr;
+		memcpy(shadowed.inv_view_projection, args.inv_view_projection, sizeof(shadowed.inv_view_projection));
+		shadowed.directional = args.directional;
+		shadowed.directional.cascade_log_bias = light->shadow.cascade_log_bias;
+		shadowed.flags = args.flags & (GR_LIGHTING_AMBIENT_FALLBACK_BIT | GR_LIGHTING_AMBIENT_OCCLUSION_BIT);
+		shadowed.ambient_occlusion = args.ambient_occlusion;
+		shadowed.mode = light->shadows.mode;
+		shadowed.layers = light->shadows.num_layers;
+		for (unsigned i = 0; i < light->shadows.num_layers && i < NumShadowCascades; i++)
+			shadowed.shadow_maps[i] = light->shadows.layers[i]->get_view();
+		for (unsigned i = 0; i < NumShadowCascades; i++)
+			memcpy(shadowed.transforms[i], light->shadow.transforms[i].data(), sizeof(shadowed.transforms[i]));
+		cmd.check(gr_directional_light(cmd.get_context(), cmd.get_stream(), &shadowed), "directional_light");
+		args.flags &= ~(GR_LIGHTING_DIRECTIONAL_BIT | GR_LIGHTING_AMBIENT_FALLBACK_BIT | GR_LIGHTING_AMBIENT_OCCLUSION_BIT);
+		args.emissive = args.hdr;
+	}
 	cmd.check(gr_lighting(cmd.get_context(), cmd.get_stream(), &args), "lighting");
 }
 

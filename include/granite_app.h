@@ -479,6 +479,32 @@ int gra_set_directional_light(gra_app *app, const float direction[3], const floa
 /* LightingParameters::fog (renderer/lights/lights.hpp; the scene's "fog" entry in Granite): with falloff > 0 render_light ends with
  * the fog quad (renderer.cpp:1179-1196).  falloff = 0 switches it off again. */
 int gra_set_fog(gra_app *app, const float color[3], float falloff);
+/* The directional light's shadow map (LightingParameters::shadows and ::shadow).  There is no rasteriser here: the caller uploads the
+ * map as it uploads the G-buffer, and the lighting pass then draws the shadowed directional quad (gr_directional_light) followed by the
+ * clustered lights in place.  Runtime state, not a member of gra_config: NULL, or mode 0, switches shadows off again, and the frames that
+ * follow are those of an application that never had them.
+ *   mode      GR_SHADOW_PCF (1), GR_SHADOW_PCF_WIDE (2) or GR_SHADOW_VSM (3)
+ *   layers    1, or 4 for cascades; `texels` holds them one after another, each width x height, tightly packed
+ *   format    GR_FORMAT_D16_UNORM or GR_FORMAT_D32_SFLOAT; with GR_SHADOW_VSM also GR_FORMAT_R32G32_SFLOAT (finished moments).  A depth
+ *             format with GR_SHADOW_VSM runs the VSM chain on upload: moments, the down blur to half size, the up blur
+ *   transforms, cascade_log_bias   world -> (u, v, z) per layer, column-major, and the bias of log2(view_z)
+ * Refused with a message, nothing launched and the state unchanged: an application without lighting, aa_bench, strip_count > 1,
+ * hdr_packed_float, layers other than 1 or 4, a format that does not fit the mode, a width or height of 0 or above 16384, a
+ * struct_size other than sizeof(gra_directional_shadows), null texels. */
+typedef struct gra_directional_shadows
+{
+	uint32_t struct_size;
+	uint32_t mode;
+	uint32_t layers;
+	uint32_t width;
+	uint32_t height;
+	uint32_t format;
+	const void *texels;
+	float transforms[4][16];
+	float cascade_log_bias;
+	uint32_t pad0;
+} gra_directional_shadows;
+int gra_set_directional_shadows(gra_app *app, const gra_directional_shadows *desc);
 /* T(.5,.5,0) S(.5,.5,1) VP_prev inv(VP_cur) as pushed to the last taa-resolve (temporal.cpp:239-243). */
 int gra_get_taa_reprojection(gra_app *app, float *reproj16);
 /* SMAA AreaTex (160x560 RG8) / SearchTex (64x16 R8) payloads, host pointers; needed before a frame with an SMAA pass. */

@@ -1361,6 +1361,59 @@ typedef struct gr_sky_cube_params
 } gr_sky_cube_params;
 int gr_sky_cube(gr_ctx *ctx, gr_stream stream, void *out_chain, uint32_t size, const gr_sky_cube_params *params);
 
+/* ---- directional-light shadows (lights/directional.frag with SHADOWS, lights/lighting_resources.h, pcf.h, vsm.h) ---------------------------
+ * The shadowed directional quad as a launch of its own, the way DeferredLightRenderer::render_light draws it: per pixel with depth != 0
+ * hdr = rne16(emissive + compute_lighting(.., shadow_term) [+ the ambient fallback]); far-plane pixels and alpha are copied through.
+ * Followed by gr_lighting with GR_LIGHTING_CLUSTERED_BIT alone and emissive = hdr it gives the reference's own rounding sequence,
+ * rne16(rne16(emissive + directional) + clustered).  Nothing rasterises here: the shadow maps are inputs, as the G-buffer is.
+ * Arithmetic and the LinearShadow sampler model (compare GREATER_OR_EQUAL, linear, clamp to edge): granite_amd/csrc/shadow_core.hpp,
+ * DESIGN.md 7.17.
+ *   mode      GR_SHADOW_PCF: one LinearShadow fetch; GR_SHADOW_PCF_WIDE: SHADOW_MAP_PCF_KERNEL_WIDE, the 6 x 6 windowed kernel of nine
+ *             gathers; both take D16_UNORM or D32_SFLOAT maps.  GR_SHADOW_VSM: R32G32_SFLOAT moments through LinearClamp and vsm().
+ *   layers    4: SHADOW_CASCADES, cascade = log2(view_z) + directional.cascade_log_bias; 1: the plain variant, transforms[0] alone.
+ *   flags     GR_LIGHTING_AMBIENT_FALLBACK_BIT, GR_LIGHTING_AMBIENT_OCCLUSION_BIT (needs the fallback bit); no other bit.
+ * Every layer has the size, the format and the pitch rules of the first; a map is at most 16384 texels each way.
+ * Refused with GR_ERR_INVALID_ARGUMENT before anything is launched: an image that breaks the gr_image contract -- hdr that is not
+ * R16G16B16A16_SFLOAT (a B10G11R11_UFLOAT_PACK32 target is refused by name: its blend rounds differently and is not built), emissive, albedo,
+ * normal, pbr or depth of another format or size, shadow_maps[i] of a format that does not fit the mode or unlike shadow_maps[0] -- a mode
+ * other than the three, layers other than 1 or 4, a flag this entry point does not take, hdr sharing bytes with emissive other than by an
+ * equal pointer or with any input.  The kernel forms byte offsets into the six frame attachments in 32 bits: each with pitch_bytes * height
+ * above 2^32 - 1 is refused likewise (shadow maps and ambient_occlusion have no such limit). */
+#define GR_SHADOW_PCF 1u
+#define GR_SHADOW_PCF_WIDE 2u
+#define GR_SHADOW_VSM 3u
+#define GR_SHADOW_NUM_CASCADES 4
+#define GR_SHADOW_MAX_EXTENT 16384u
+typedef struct gr_directional_light_args
+{
+	gr_image albedo;   /* R8G8B8A8_SRGB */
+	gr_image normal;   /* A2B10G10R10_UNORM_PACK32 */
+	gr_image pbr;      /* R8G8_UNORM (metallic, roughness) */
+	gr_image depth;    /* D32_SFLOAT, reverse-Z */
+	gr_image emissive; /* R16G16B16A16_SFLOAT: the blend destination's contents before the draw */
+	gr_image hdr;      /* R16G16B16A16_SFLOAT result; may be `emissive` (same ptr) */
+	float inv_view_projection[16];
+	gr_push_directional directional;
+	uint32_t flags;
+	uint32_t mode;   /* GR_SHADOW_* */
+	uint32_t layers; /* 1 or 4 */
+	uint32_t pad0;
+	gr_image ambient_occlusion; /* R8_UNORM, any size; read only with GR_LIGHTING_AMBIENT_OCCLUSION_BIT */
+	gr_image shadow_maps[GR_SHADOW_NUM_CASCADES];
+	float transforms[GR_SHADOW_NUM_CASCADES][16]; /* DirectionalLightUBO::transforms, column-major: world -> (u, v, z) of a layer */
+} gr_directional_light_args;
+int gr_directional_light(gr_ctx *ctx, gr_stream stream, const gr_directional_light_args *args);
+
+/* lights/resolve_vsm.frag: moments = (z, z * z) of a D16_UNORM or D32_SFLOAT map into an R32G32_SFLOAT image of the same size.  The
+ * reference's own 4x MSAA average in front of it has no counterpart: nothing is rasterised here.
+ * Refused with GR_ERR_INVALID_ARGUMENT: an image that breaks the gr_image contract or shares bytes with the other. */
+int gr_vsm_moments(gr_ctx *ctx, gr_stream stream, const gr_image *depth, const gr_image *moments);
+
+/* post/vsm_down_blur.frag (up = 0: taps at +-1.75 texels of `in`) and post/vsm_up_blur.frag (up != 0: +-0.875): nine LinearClamp taps around
+ * the output pixel's centre, weights 0.25 / 0.125 / 0.0625, R32G32_SFLOAT to R32G32_SFLOAT of any size; one call per layer.
+ * Refused with GR_ERR_INVALID_ARGUMENT: an image that breaks the gr_image contract or shares bytes with the other. */
+int gr_vsm_blur(gr_ctx *ctx, gr_stream stream, const gr_image *in, const gr_image *out, int up);
+
 /* ---- SSAO: FidelityFX CACAO as the reference runs it (renderer/post/ssao.cpp, renderer/post/ffx-cacao) -----------------------------------
  * One configuration and its non-adaptive sibling: native resolution, normals from the G-buffer, quality HIGHEST (adaptive, shader level 3)
  * or HIGH (shader level 2), 0 .. 8 blur passes.  One entry point per shader of FFX_CACAO_GraniteDraw (ffx_cacao_impl.cpp:767-1026); the
@@ -1688,6 +1741,14 @@ GR_ASSERT_OFFSET(gr_sky_args, cube, 144);
 GR_ASSERT_SIZE(gr_sky_cube_params, 32); /* volumetric_light_setup_sky.comp's UBO */
 GR_ASSERT_OFFSET(gr_sky_cube_params, camera_y, 12);
 GR_ASSERT_OFFSET(gr_sky_cube_params, sun_direction, 16);
+GR_ASSERT_SIZE(gr_directional_light_args, 696);
+GR_ASSERT_OFFSET(gr_directional_light_args, inv_view_projection, 144);
+GR_ASSERT_OFFSET(gr_directional_light_args, directional, 208);
+GR_ASSERT_OFFSET(gr_directional_light_args, flags, 304);
+GR_ASSERT_OFFSET(gr_directional_light_args, layers, 312);
+GR_ASSERT_OFFSET(gr_directional_light_args, ambient_occlusion, 320);
+GR_ASSERT_OFFSET(gr_directional_light_args, shadow_maps, 344);
+GR_ASSERT_OFFSET(gr_directional_light_args, transforms, 440);
 GR_STATIC_ASSERT(GR_TRANSFORMS_OFFSET_SHADOW ==GR_MAX_LIGHTS_BINDLESS * 48u, "ClustererBindlessTransforms: lights[4096] of 48 B");
 GR_STATIC_ASSERT(GR_TRANSFORMS_OFFSET_MODEL + GR_MAX_LIGHTS_BINDLESS * 48u == GR_TRANSFORMS_OFFSET_TYPE_MASK, "ClustererBindlessTransforms: model[4096] of 48 B");
 GR_STATIC_ASSERT(GR_TRANSFORMS_OFFSET_TYPE_MASK + GR_MAX_LIGHTS_BINDLESS / 8u == GR_TRANSFORMS_OFFSET_DECALS, "ClustererBindlessTransforms: type_mask[128]");
